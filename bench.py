@@ -2,7 +2,7 @@
 """
 bench.py -- GAP/DR outer iterations per second + achieved HBM GB/s of the CG SpMV (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4|C2|C3|C5|...]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4|C2|C3|C5|...] [--full] [--dump-outputs DIR]
 
 A "step" is ONE outer iteration of the solver (solverwrapper.jl:23-29: affine projection by warm-started CG over
 the KKT operator -> cone projection -> relaxations) on a synthetic problem already resident in HBM.  The metric is
@@ -16,13 +16,18 @@ cone-sharded across 1/2/4/8 MI355X via RCCL" -- the configuration the metric (".
 north-star targets (1e6-variable problem, >=3.5x at 8 GPUs on the block-PSD workload) are quoted on; it fits one
 GPU.  N > 1 is STRONG scaling of that one problem by default: rank g owns blocks [512 g/N, 512 (g+1)/N) and only scalars
 cross GPUs (peer mailboxes over xGMI, or an in-stream RCCL all-reduce); `--scaling weak` gives every rank 512 blocks of a
-512 N-block problem instead, and an N > 1 run in the default mode also times that weak-scaling problem and reports it under
-`weak_scaling` in the same line.  `--workload C2` runs configs[1] (dense 5000x10000 LP) on one GPU.
+512 N-block problem instead, and an N > 1 run in the default mode with `--full` also times that weak-scaling problem and reports it
+under `weak_scaling` in the same line.  `--workload C2` runs configs[1] (dense 5000x10000 LP) on one GPU.
 
 Prints ONE JSON line (rank 0) with the contract fields plus `roofline` for the kernel with the largest measured share of the
 step (HIP events on the solver's stream around sampled launches of the KKT sweep, the batched PSD projection and the CG
-vector updates), `roofline_psd`, `time_shares` and, at N = 1, `cpu_baseline` (the C port of the oracle restatement timed on
-one host core and on all of them, for a bounded sample of steady-state outer iterations from the GPU's state).
+vector updates), `roofline_psd` and `time_shares`.  A plain run does only that: set-up, warm-up, the timed steps, the line.
+`--full` adds the measurements beside the headline, each a run of its own behind the timed region: at N = 1 `cpu_baseline`
+(the C port of the oracle restatement timed on one host core and on all of them, for a bounded sample of steady-state outer
+iterations from the GPU's state), the other CG recurrences, C4 as SURVEY 8(d) writes it (`raw_instance`, `value_as_specified`)
+and DR(direct=true) (`direct_true`); at N > 1 `weak_scaling` and `direct_true`.
+`--dump-outputs DIR` writes the iterate the last timed step left, for comparing two builds output for output (the inputs
+are seeded: the same arguments give the same problem).
 """
 from __future__ import annotations
 
@@ -134,6 +139,12 @@ def main():
     ap.add_argument("--c4-scale", type=float, default=None,
                     help="C4: divide the random symmetric constraint matrices by this instead of 32 (1 = the raw, badly conditioned "
                          "instance: ~4x the CG iterations per outer iteration; not the headline configuration)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline: the CPU baseline, the raw C4 instance, DR(direct=true), the other "
+                         "CG recurrences at N = 1 and the weak-scaling and direct=true lines at N > 1 (each --no-* flag above still skips its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the iterate the last timed step left (what fos_get_iterate hands a caller) to DIR/iterate.npy "
+                         "(DIR/iterate_rank<k>.npy per rank at N > 1), float64, at most 64 MB in all")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -193,8 +204,17 @@ def main():
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         return int(flag.item()) == 1
 
-    def run_case(weak):
-        """Build the (shard of the) problem, warm up to the steady state, time exactly --steps outer iterations."""
+    def dump_iterate(dump_dir, z):
+        """The iterate after the last timed step, float64; beyond this rank's share of 64 MB, every k-th element (a fixed sample)."""
+        cap = (64 << 20) // (8 * world)
+        if z.size > cap:
+            z = z[::-(-z.size // cap)]
+        os.makedirs(dump_dir, exist_ok=True)
+        np.save(os.path.join(dump_dir, "iterate.npy" if world == 1 else "iterate_rank%d.npy" % rank), np.ascontiguousarray(z, dtype=np.float64))
+
+    def run_case(weak, dump_dir=None):
+        """Build the (shard of the) problem, warm up to the steady state, time exactly --steps outer iterations (and, given
+        `dump_dir`, write the iterate they left)."""
         reduction = "in-stream RCCL all-reduce"
         transport = "rccl"
         peer_reason = None             # why the transports in front of the chosen one were passed over (None: the first was taken, or there is one rank)
@@ -418,6 +438,8 @@ def main():
         t2 = time.perf_counter()
         it += done
         elapsed = t2 - t1
+        if dump_dir:
+            dump_iterate(dump_dir, dev.get_iterate())
         per_rank_ms = None
         if dist is not None:
             mine_t = torch.tensor([elapsed], dtype=torch.float64, device=tdev)
@@ -723,7 +745,7 @@ def main():
     weak_main = args.scaling == "weak"
     for _attempt in range(6):
         try:
-            out, dev, prob, alg, it = run_case(weak_main)
+            out, dev, prob, alg, it = run_case(weak_main, args.dump_outputs)
             break
         except PeerTransportFailed as exc:
             # the self test passed but the first real exchanges did not: the same job, in this process, over the next transport in the order
@@ -743,7 +765,7 @@ def main():
                 "the self test passed, but an exchange of the warm-up timed out on the %s mailboxes (FOS_ECOMM)" % failed
     else:
         raise SystemExit("every transport failed during the warm-up")
-    if world == 1 and dist is None and not args.direct and not args.no_recurrence_extras and out["config"]["cg_variant"] in ("reference", "resident") \
+    if args.full and world == 1 and dist is None and not args.direct and not args.no_recurrence_extras and out["config"]["cg_variant"] in ("reference", "resident") \
             and not os.environ.get("FOS_BENCH_SHARD"):
         # the same job on the other recurrences -- same handle, same state, `--steps` more outer iterations each: the merged-reduction recurrence
         # with a launch group per iteration (what sharded handles without mailboxes run: a scaling ratio can divide like by like) and, where the
@@ -775,7 +797,7 @@ def main():
                 out[key] = {"failed": repr(exc)}
             finally:
                 dev.set_cg_variant(None)
-    if world > 1 and not weak_main and not args.no_weak_extra and args.workload == "C4":
+    if args.full and world > 1 and not weak_main and not args.no_weak_extra and args.workload == "C4":
         # the same job once more with 512 blocks PER RANK: weak scaling, reported beside the strong-scaling headline
         dev.close()
         # (an extra line: whatever goes wrong here -- the warm-up's collective vote, a time-out of the mailboxes, an out-of-memory -- costs this
@@ -794,7 +816,7 @@ def main():
             out["weak_scaling"]["config"] = {k: wout["config"][k] for k in ("workload", "local_m", "local_n", "local_nnz", "cg_iters_per_step", "parallelism")}
             rk = wout["roofline_kkt"] if isinstance(wout["roofline_kkt"], dict) else wout["roofline"]
             out["weak_scaling"]["roofline_kkt"] = {k: rk.get(k) for k in ("achieved", "frac", "avg_kernel_ms", "all_ranks")}
-    if world > 1 and dist is not None and args.workload == "C4" and not args.direct and not args.no_direct_extra and not weak_main \
+    if args.full and world > 1 and dist is not None and args.workload == "C4" and not args.direct and not args.no_direct_extra and not weak_main \
             and out["config"].get("transport") in ("peer", "host"):
         # the same sharded job under DR(direct = true): the block form's diagonal blocks are local to a rank, its three scalar sums per projection ride
         # the same mailboxes (which time out instead of hanging: a failure here costs the extra line, not the headline)
@@ -914,11 +936,11 @@ def main():
                 "gpu_cg_iters_same_step": dev.cgiter(),
             }
             return cpu
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(dev, prob, alg, it)
     # ---- the C4 instance as SURVEY 8(d) writes it (A_j as drawn, not divided by 32): same size, same code path, twice the CG
     #      iterations per outer iteration -- timed here so that the driver's line carries it beside the headline
-    if world == 1 and args.workload == "C4" and args.c4_scale is None and not args.small and not args.no_raw_instance:
+    if args.full and world == 1 and args.workload == "C4" and args.c4_scale is None and not args.small and not args.no_raw_instance:
         args.c4_scale = 1.0
         try:
             rout, rdev, rprob, ralg, rit = run_case(False)
@@ -953,7 +975,7 @@ def main():
         finally:
             args.c4_scale = None
     # ---- the same C4 with DR(direct = true) (HSDE.jl:12-15): the exact projection in the block form, three sweeps instead of ~17 CG iterations
-    if world == 1 and dist is None and args.workload == "C4" and not args.direct and not args.small and not args.no_direct_extra and args.c4_scale is None \
+    if args.full and world == 1 and dist is None and args.workload == "C4" and not args.direct and not args.small and not args.no_direct_extra and args.c4_scale is None \
             and not os.environ.get("FOS_BENCH_SHARD"):
         args.direct = True
         try:

@@ -8,7 +8,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/r03final
 mkdir -p $OUT
 run() { tag=$1; shift; envs=""; while [ "$1" != "--" ]; do envs="$envs $1"; shift; done; shift
-  env $envs python3 bench.py "$@" 2> $OUT/bench_$tag.err | tail -1 > $OUT/bench_$tag.json; }
+  env $envs python3 bench.py --full "$@" 2> $OUT/bench_$tag.err | tail -1 > $OUT/bench_$tag.json; }
 run c4 A=1 --
 run c2 A=1 -- --workload C2
 run c3 A=1 -- --workload C3

@@ -10,7 +10,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/r06final
 mkdir -p $OUT
 run() { tag=$1; shift; envs=""; while [ "$1" != "--" ]; do envs="$envs $1"; shift; done; shift
-  env $envs python3 bench.py "$@" 2> $OUT/bench_$tag.err | tail -1 > $OUT/bench_$tag.json; }
+  env $envs python3 bench.py --full "$@" 2> $OUT/bench_$tag.err | tail -1 > $OUT/bench_$tag.json; }
 run c4 A=1 --
 run c2 A=1 -- --workload C2
 run c3 A=1 -- --workload C3
@@ -40,7 +40,7 @@ run c5_shard1of2_dist1rank FOS_FORCE_DIST=1 FOS_BENCH_SHARD=0/2 -- --workload C5
 run c5_shard1of8_dist1rank FOS_FORCE_DIST=1 FOS_BENCH_SHARD=0/8 -- --workload C5 --no-cpu-baseline
 # two ranks of the full C4 on the ONE GPU of the box under both kinds of mailboxes (host coordination over gloo): residuals of the single-rank run
 for tr in peer host; do
-  FOS_REDUCTION=$tr FOS_BENCH_BACKEND=gloo HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 20 --no-weak-extra 2> $OUT/bench_c4_two_ranks_one_gpu_$tr.err | tail -1 > $OUT/bench_c4_two_ranks_one_gpu_$tr.json
+  FOS_REDUCTION=$tr FOS_BENCH_BACKEND=gloo HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 20 --no-weak-extra 2> $OUT/bench_c4_two_ranks_one_gpu_$tr.err | tail -1 > $OUT/bench_c4_two_ranks_one_gpu_$tr.json
 done
 for W in c4 c2 c3 c5; do
   extra=""; [ $W != c4 ] && extra="--workload ${W^^}"

@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/tr
 rm -rf $OUT; mkdir -p $OUT
 W=${1:-C4}
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/t -- python bench.py --steps 20 --no-cpu-baseline --workload $W $2 > $OUT/t.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/t -- python bench.py --full --steps 20 --no-cpu-baseline --workload $W $2 > $OUT/t.log 2>&1
 f=$(find $OUT/t -name "*kernel_trace.csv" | head -1)
 python - "$f" <<'PY'
 import csv,sys,collections
