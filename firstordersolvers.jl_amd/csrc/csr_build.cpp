@@ -1069,7 +1069,7 @@ bool build_resident_plan(const HostBlkCsr& S, int64_t m, int64_t n, int gmax, Re
     // columns and 70 tiles per workgroup, tiles of at most 32 steps; one workgroup per CU
     auto stream_plan = [&](const char* why_not_registers) -> bool {
         const bool allow = !(getenv("FOS_RESIDENT_STREAM") && atoi(getenv("FOS_RESIDENT_STREAM")) == 0);
-        constexpr int RS_GMAX = 256, RS_NCOMP = 7, RS_NT_MAX = 10;
+        constexpr int RS_NT_MAX = 10;
         if (!allow) return no(why_not_registers);
         const int nt_cap = tmax > 32 ? 5 : RS_NT_MAX;          // (64-step tiles: 128 registers of matrix values, five tiles' r, w, x beside them)
         const int gm = std::min(gmax, RS_GMAX);
@@ -1102,6 +1102,21 @@ bool build_resident_plan(const HostBlkCsr& S, int64_t m, int64_t n, int gmax, Re
             nt = std::max(nt, per + (r - kc > 0 ? 1 : 0));
         }
         if (nt > nt_cap) return no(why_not_registers);
+        // what the kernel can index: a tile is walked in whole groups of 8 steps, each pass of 32 steps from its unit's offset in the workgroup's
+        // <= 64 columns (rs_sweep: s_gcol[64] and the wavefront's 64 column sums) -- a unit that starts late in the workgroup and ends on a ragged
+        // group would read past the column elements and add into the next wavefront's column sums
+        const int tmax_k = tmax <= 32 ? 32 : 64;
+        for (const ResWG& w : wgs)
+            for (int ti = 0; ti < w.nblk; ++ti) {
+                const BlkDesc& d = S.blk[w.blk0 + ti];
+                const int coff = d.meta[0] - w.c0;
+                for (int hf = 0; 32 * hf < tmax_k; ++hf) {
+                    const int rem = d.steps() - 32 * hf;
+                    if (rem > 0 && coff + 32 * hf + std::min(32, (rem + 7) & ~7) > 64) return no("a unit's tile walk would pass column 64 of its workgroup (streamed form)");
+                }
+            }
+        // what the LDS holds: the launch's dynamic bytes (res_stream_lds_bytes) and the kernel's static arrays within a CU's 160 KiB
+        if (res_stream_lds_bytes(tiles_max) + RS_STATIC_LDS_MAX > RES_LDS_BUDGET) return no("a workgroup's tiles exceed the LDS (streamed form)");
         out->stream = 1; out->nt = nt <= 3 ? 3 : (nt <= 5 ? 5 : (nt <= 9 ? 9 : 10));
         out->nw = RS_NCOMP; out->ncomm = 1; out->rpt = 0; out->tmax = tmax <= 32 ? 32 : 64; out->tiles_wg_max = tiles_max; out->units = nu;
         out->wg = wgs; out->G = (int)wgs.size();

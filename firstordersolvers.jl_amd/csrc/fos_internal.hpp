@@ -434,6 +434,26 @@ struct ResWG { int32_t blk0, nblk, c0, tc, T, wg0, wpu, idx; };     // 32 bytes:
 constexpr int RES_GMAX = 512;        // workgroups of a resident solve (records every workgroup adds)
 constexpr int RES_WPU_MAX = 16;      // workgroups per unit
 constexpr int RES_SLOTS = 21;        // tiles per workgroup
+// the STREAMED form's shape (resident.hip, cg_stream_kernel): workgroups (= records), workgroups a unit may be split over, compute wavefronts (+ 1 that
+// communicates), the tiles the communication wavefront walks itself
+constexpr int RS_GMAX = 256;
+constexpr int RS_WPU_MAX = 4;
+constexpr int RS_NCOMP = 7;
+constexpr int RS_NTC = 3;
+// LDS of a launch (one function for the planner and the launch): the dynamic bytes of cg_stream_kernel for a workgroup of `tiles` tiles -- the wavefronts'
+// column sums, the G records, the other workgroups' column sums, the rows' p and s -- and of cg_resident_kernel<TMAX = tmax, NSLOT = nslot>; the planner adds
+// RS_STATIC_LDS_MAX for the kernel's static arrays (2104 bytes) and refuses a plan beyond the 160 KiB of a gfx950 CU, resident_setup checks the launch
+// against the device's limit and the kernel's own static size
+constexpr size_t RES_LDS_BUDGET = 160 * 1024;
+constexpr size_t RS_STATIC_LDS_MAX = 2560;
+inline size_t res_stream_lds_bytes(int tiles) {
+    return (size_t)(RS_NCOMP + 1) * 64 * sizeof(double2) + (size_t)4 * RS_GMAX * sizeof(double) + (size_t)(RS_WPU_MAX - 1) * 64 * 2 * sizeof(double) +
+           (size_t)tiles * 128 * sizeof(double2);
+}
+inline size_t res_reg_lds_bytes(int nslot, int tmax) {
+    return (size_t)nslot * 64 * 4 * sizeof(double2) + (size_t)nslot * tmax * sizeof(double2) + (size_t)(RES_WPU_MAX - 1) * tmax * 2 * sizeof(double) +
+           (size_t)4 * RES_GMAX * sizeof(double);
+}
 struct ResPlan {                     // host
     int G = 0, nw = 0, ncomm = 0, rpt = 0, tmax = 0, tiles_wg_max = 0, units = 0;      // nw compute wavefronts + ncomm communication wavefronts per workgroup
     int stream = 0, nt = 0;          // stream: the STREAMED form (tiles re-read every iteration, whole units per workgroup); nt: tiles per compute wavefront
@@ -452,8 +472,11 @@ struct ResLaunch {
     int64_t timeout_ticks;
 };
 // x (in: the start iterate, out: the solution), r_0 = rhs - M v; fold != nullptr: the sums cross the ranks through the mailboxes
-void launch_cg_resident(const LaunchCtx& c, const ResLaunch& rl, double2* x, const double2* rhs, const double2* v, double tol, int maxit,
-                        const PeerBox* fold, uint32_t seq_base);
+// (hipSuccess, or the error of the LDS opt-in: a plan that does not fit is refused by resident_setup before it gets here)
+hipError_t launch_cg_resident(const LaunchCtx& c, const ResLaunch& rl, double2* x, const double2* rhs, const double2* v, double tol, int maxit,
+                              const PeerBox* fold, uint32_t seq_base);
+// does the kernel instance `rl` launches fit the device's LDS (its dynamic bytes + its static arrays, and the opt-in)?  false: why
+bool res_lds_fits(const ResLaunch& rl, int device, std::string* why);
 
 // single right-hand side Q apply on component `comp` of an interleaved vector
 //   Q_PLAIN : out_plain[i] = sign * (Q v)_i            (rows 0..n+m-1; tau row by q1_finalize)

@@ -609,9 +609,8 @@ __global__ __launch_bounds__(LB) void cg_resident_kernel(ResArgs a) {
 // chip then reads the matrix once + 40 B per row, where sweep + update kernels read and write the matrix + 160 B per row and pay two launches.
 // Same exchange (records of self-validating words, no grid barrier), same recurrence, same summation order rules as the register form above;
 // a unit lives in ONE workgroup, so column sums never cross workgroups.
-constexpr int RS_GMAX = 256;          // workgroups (= records) of the streamed form: one per CU
-constexpr int RS_WPU_MAX = 4;         // workgroups a unit may be split over in the streamed form (fewer units than CUs: a shard of a four-GPU run)
-constexpr int RS_NCOMP = 7;           // compute wavefronts per workgroup (+ 1 that communicates): two wavefronts per SIMD, 256 registers each
+// (RS_GMAX = 256 workgroups = records: one per CU; RS_WPU_MAX = 4 workgroups a unit may be split over -- fewer units than CUs: a shard of a four-GPU
+//  run; RS_NCOMP = 7 compute wavefronts per workgroup + 1 that communicates: two wavefronts per SIMD, 256 registers each -- fos_internal.hpp)
 
 // a tile in NATURAL column order (as stored): row sums against the workgroup's column elements at gcol (LDS, uniform addresses: broadcasts),
 // column sums ADDED to the wavefront's own array (lanes 0..7, program order inside the wavefront)
@@ -648,7 +647,7 @@ __device__ __forceinline__ void res_tile_plain(const double (&val)[TMAX], int T,
     }
 }
 
-constexpr int RS_NTC = 3;             // tiles the communication wavefront sweeps itself (it waits at barrier (A) otherwise): 66 tiles = 7 x 9 + 3
+// (RS_NTC = 3: tiles the communication wavefront sweeps itself -- it waits at barrier (A) otherwise: 66 tiles = 7 x 9 + 3)
 
 // which tiles of a workgroup wavefront w walks (w < RS_NCOMP: compute; w == RS_NCOMP: the communication wavefront, the LAST tiles)
 __host__ __device__ inline void rs_split(int nblk, int w, int& t0, int& cnt) {
@@ -1110,14 +1109,61 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
     }
 }
 
-// dynamic LDS above the default limit needs an opt-in per kernel (a table update; a failure surfaces through the launch check)
-template <class K>
-static void res_lds_optin(K kernel, size_t bytes) {
-    if (bytes > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+// The kernel instance a plan launches, with its block and its dynamic LDS (res_stream_lds_bytes / res_reg_lds_bytes, fos_internal.hpp: the planner's formula)
+struct ResKernel { const void* fn; int threads; size_t lds; };
+static ResKernel res_kernel(const ResLaunch& rl) {
+    auto k = [](auto kern, int threads, size_t lds) { return ResKernel{reinterpret_cast<const void*>(kern), threads, lds}; };
+    if (rl.stream) {
+        // (the compute wavefronts' sums land in s_red[wv]: RS_NCOMP rows, the others zeroed once)
+        const int thr = 64 * (RS_NCOMP + 1);
+        const size_t lds = res_stream_lds_bytes(rl.tiles_wg_max);
+        if (rl.tmax > 32 && rl.nt <= 3) return k(cg_stream_kernel<64, 3>, thr, lds);
+        if (rl.tmax > 32) return k(cg_stream_kernel<64, 5>, thr, lds);
+        if (rl.nt <= 3) return k(cg_stream_kernel<32, 3>, thr, lds);
+        if (rl.nt <= 5) return k(cg_stream_kernel<32, 5>, thr, lds);
+        if (rl.nt <= 9) return k(cg_stream_kernel<32, 9>, thr, lds);
+        return k(cg_stream_kernel<32, 10>, thr, lds);
+    }
+    const int thr = 64 * (rl.nw + rl.ncomm);
+    if (rl.tmax <= 32 && rl.rpt == 1) return k(cg_resident_kernel<32, 1, 768>, thr, res_reg_lds_bytes(12, 32));
+    if (rl.tmax <= 32 && rl.rpt == 2) return k(cg_resident_kernel<32, 2, 512>, thr, res_reg_lds_bytes(16, 32));
+    if (rl.tmax <= 32) return k(cg_resident_kernel<32, 3, 512>, thr, res_reg_lds_bytes(24, 32));
+    return k(cg_resident_kernel<64, 1, 512>, thr, res_reg_lds_bytes(8, 64));
 }
 
-void launch_cg_resident(const LaunchCtx& c, const ResLaunch& rl, double2* x, const double2* rhs, const double2* v, double tol, int maxit,
-                        const PeerBox* fold, uint32_t seq_base) {
+// dynamic LDS above the default limit needs an opt-in per kernel (a table update)
+static hipError_t res_lds_optin(const ResKernel& k) {
+    if (k.lds > 48 * 1024) return hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
+    return hipSuccess;
+}
+
+bool res_lds_fits(const ResLaunch& rl, int device, std::string* why) {
+    const ResKernel k = res_kernel(rl);
+    hipFuncAttributes fa{};
+    int cap = 0;
+    char buf[192];
+    if (hipFuncGetAttributes(&fa, k.fn) != hipSuccess || hipDeviceGetAttribute(&cap, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) {
+        (void)hipGetLastError();
+        *why = "the kernel's or the device's LDS size could not be read";
+        return false;
+    }
+    if (k.lds + fa.sharedSizeBytes > (size_t)cap) {
+        snprintf(buf, sizeof(buf), "a workgroup's LDS (%zu + %zu static bytes) exceeds the device's %d", k.lds, (size_t)fa.sharedSizeBytes, cap);
+        *why = buf;
+        return false;
+    }
+    const hipError_t e = res_lds_optin(k);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        snprintf(buf, sizeof(buf), "the LDS opt-in for %zu bytes failed (%s)", k.lds, hipGetErrorString(e));
+        *why = buf;
+        return false;
+    }
+    return true;
+}
+
+hipError_t launch_cg_resident(const LaunchCtx& c, const ResLaunch& rl, double2* x, const double2* rhs, const double2* v, double tol, int maxit,
+                              const PeerBox* fold, uint32_t seq_base) {
     ResArgs a{};
     a.x = x; a.rhs = rhs; a.v = v; a.cb = c.cb; a.n = (int)c.n; a.nm = (int)(c.n + c.m); a.st = c.st;
     a.blk = c.S.blk; a.val = c.S.val; a.wg = rl.wg; a.G = rl.G; a.grec = rl.grec; a.crec = rl.crec; a.tmax = rl.tmax;
@@ -1127,27 +1173,11 @@ void launch_cg_resident(const LaunchCtx& c, const ResLaunch& rl, double2* x, con
     a.ncomp = rl.nw;
     static const int res_flags = getenv("FOS_RES_FLAGS") ? atoi(getenv("FOS_RES_FLAGS")) : (2 << 8);
     a.flags = res_flags;
-    if (rl.stream) {
-        // (the compute wavefronts' sums land in s_red[wv]: RS_NCOMP rows, the others zeroed once)
-        dim3 grid(rl.G), block(64 * (RS_NCOMP + 1));
-        const size_t lds = (size_t)(RS_NCOMP + 1) * 64 * sizeof(d2) + (size_t)4 * RS_GMAX * sizeof(double) + (size_t)(RS_WPU_MAX - 1) * 64 * 2 * sizeof(double) +
-                           (size_t)rl.tiles_wg_max * 128 * sizeof(d2);
-        if (rl.tmax > 32 && rl.nt <= 3) { res_lds_optin(cg_stream_kernel<64, 3>, lds); hipLaunchKernelGGL((cg_stream_kernel<64, 3>), grid, block, lds, c.stream, a); }
-        else if (rl.tmax > 32) { res_lds_optin(cg_stream_kernel<64, 5>, lds); hipLaunchKernelGGL((cg_stream_kernel<64, 5>), grid, block, lds, c.stream, a); }
-        else if (rl.nt <= 3) { res_lds_optin(cg_stream_kernel<32, 3>, lds); hipLaunchKernelGGL((cg_stream_kernel<32, 3>), grid, block, lds, c.stream, a); }
-        else if (rl.nt <= 5) { res_lds_optin(cg_stream_kernel<32, 5>, lds); hipLaunchKernelGGL((cg_stream_kernel<32, 5>), grid, block, lds, c.stream, a); }
-        else if (rl.nt <= 9) { res_lds_optin(cg_stream_kernel<32, 9>, lds); hipLaunchKernelGGL((cg_stream_kernel<32, 9>), grid, block, lds, c.stream, a); }
-        else { res_lds_optin(cg_stream_kernel<32, 10>, lds); hipLaunchKernelGGL((cg_stream_kernel<32, 10>), grid, block, lds, c.stream, a); }
-        return;
-    }
-    dim3 grid(rl.G), block(64 * (rl.nw + rl.ncomm));
-    auto lds_bytes = [&](size_t nslot, size_t tmax) {
-        return nslot * 64 * 4 * sizeof(d2) + nslot * tmax * sizeof(d2) + (size_t)(RES_WPU_MAX - 1) * tmax * 2 * sizeof(double) + (size_t)4 * RES_GMAX * sizeof(double);
-    };
-    if (rl.tmax <= 32 && rl.rpt == 1) { const size_t lds = lds_bytes(12, 32); res_lds_optin(cg_resident_kernel<32, 1, 768>, lds); hipLaunchKernelGGL((cg_resident_kernel<32, 1, 768>), grid, block, lds, c.stream, a); }
-    else if (rl.tmax <= 32 && rl.rpt == 2) { const size_t lds = lds_bytes(16, 32); res_lds_optin(cg_resident_kernel<32, 2, 512>, lds); hipLaunchKernelGGL((cg_resident_kernel<32, 2, 512>), grid, block, lds, c.stream, a); }
-    else if (rl.tmax <= 32) { const size_t lds = lds_bytes(24, 32); res_lds_optin(cg_resident_kernel<32, 3, 512>, lds); hipLaunchKernelGGL((cg_resident_kernel<32, 3, 512>), grid, block, lds, c.stream, a); }
-    else { const size_t lds = lds_bytes(8, 64); res_lds_optin(cg_resident_kernel<64, 1, 512>, lds); hipLaunchKernelGGL((cg_resident_kernel<64, 1, 512>), grid, block, lds, c.stream, a); }
+    const ResKernel k = res_kernel(rl);
+    const hipError_t e = res_lds_optin(k);
+    if (e != hipSuccess) return e;
+    void* args[] = {&a};
+    return hipLaunchKernel(k.fn, dim3(rl.G), dim3(k.threads), args, k.lds, c.stream);
 }
 
 }  // namespace fos

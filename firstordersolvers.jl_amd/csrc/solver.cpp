@@ -243,7 +243,7 @@ struct fos_solver {
     size_t host_seg_bytes = 0;
     std::string host_seg_name;
     unsigned long long* peer_relay = nullptr;
-    uint32_t cg_epoch = 0;                     // CG solves so far: the sequence space of the folded exchanges
+    uint32_t cg_epoch = 0;                     // windows of 2048 sequence numbers used so far (cg_solve): the folded exchanges, the resident solve
     // ... or through the caller's own collective on host buffers (fos_comm_init_host: MPI.jl, gloo, ...)
     fos_allreduce_fn host_fn = nullptr;
     void* host_user = nullptr;
@@ -512,6 +512,17 @@ int resident_setup(fos_solver* h, int gmax) {
     h->res_ok = false;
     ResPlan plan;
     if (!build_resident_plan(h->hostS, h->m, h->n, gmax, &plan)) { h->res_plan = plan; h->res_all = false; return FOS_OK; }
+    {   // the kernel instance the plan launches must fit the device's LDS (the planner assumed 160 KiB and a static allowance)
+        ResLaunch rl{};
+        rl.G = plan.G; rl.nw = plan.nw; rl.ncomm = plan.ncomm; rl.rpt = plan.rpt; rl.tmax = plan.tmax; rl.stream = plan.stream; rl.nt = plan.nt;
+        rl.tiles_wg_max = plan.tiles_wg_max;
+        std::string why;
+        if (!res_lds_fits(rl, h->device, &why)) {
+            plan.why = why; plan.G = 0; plan.wg.clear();
+            h->res_plan = plan; h->res_all = false;
+            return FOS_OK;
+        }
+    }
     FOS_HIP(hipStreamSynchronize(h->stream));
     if (!h->res.grec) {
         constexpr size_t b1 = sizeof(unsigned long long) * 2 * RES_GMAX * 8, b2 = sizeof(unsigned long long) * 2 * RES_GMAX * 64 * 4;
@@ -608,8 +619,15 @@ int cg_solve(fos_solver* h, d2* x, const d2* rhs, double tol, int maxit, int64_t
     // the tau row, the slot-spread rows and the r.r records (added by the sweep of iteration 1) -- instead of five launches
     static const bool start_env = !(getenv("FOS_CG_FUSED_START") && atoi(getenv("FOS_CG_FUSED_START")) == 0);
     const bool start_fused = !merged && !h->sharded() && !c.between && start_env;
-    h->cg_epoch += 1;                        // the same on every rank: all ranks make the same calls
-    const uint32_t seq_base = (uint32_t)(h->cg_epoch * 2048u);          // + 2 j + phase  (j <= 1000)
+    // the solve's sequence numbers: seq_base + 1 .. seq_base + 2 maxit + 3 (the folded exchanges: 2 j + phase; the resident solve: maxit + 2 exchange
+    // rounds, the streamed form's early r.r rounds on top) in windows of 2048 -- as many as `maxit` can use, so that no record of this solve carries a
+    // number of the next one.  Counted from maxit alone: the same on every rank (all ranks make the same calls), whatever form a shard takes.  A window
+    // run never wraps through epoch 0 mod 2^21 (sequence number 0 is never sent), it starts there instead (no speculation: the mark's initial value).
+    const uint32_t nwin = (uint32_t)std::min<int64_t>((2 * (int64_t)std::max(maxit, 0) + 4 + 2047) / 2048, (int64_t)1 << 20);
+    uint32_t epoch = h->cg_epoch + 1u;                   // the solve's first window
+    if (const uint32_t off = epoch & 0x1FFFFFu; off != 0u && off + (nwin - 1u) > 0x1FFFFFu) epoch += 0x200000u - off;
+    h->cg_epoch = epoch + (nwin - 1u);
+    const uint32_t seq_base = (uint32_t)(epoch * 2048u);                // + 2 j + phase
     auto iter_desc = [&](int j) {
         CgIter it;
         it.j = j; it.r = h->R; it.p_prev = h->PB[(j - 1) & 1]; it.p_cur = h->PB[j & 1];
@@ -647,8 +665,9 @@ int cg_solve(fos_solver* h, d2* x, const d2* rhs, double tol, int maxit, int64_t
         // the whole solve is ONE launch (resident.hip): nothing to enqueue ahead, nothing to predict; what follows the solve is enqueued behind it
         // (gated on DevState.done, which the launch sets when it ends) and the host reads the iteration count from the mark the launch leaves
         const int pe = prof_begin(h, FOS_PROF_RESIDENT, 1, h->prof_seen[FOS_PROF_RESIDENT]++);
-        launch_cg_resident(c, h->res, x, rhs, apply_on ? apply_on : x, tol, maxit, fold ? &h->peer : nullptr, seq_base);
+        const hipError_t le = launch_cg_resident(c, h->res, x, rhs, apply_on ? apply_on : x, tol, maxit, fold ? &h->peer : nullptr, seq_base);
         prof_end(h, pe);
+        if (le != hipSuccess) { set_error("resident CG launch: %s", hipGetErrorString(le)); return FOS_EHIP; }
         if (spec) {
             LaunchCtx cg = c;
             cg.gate = &h->st->done;
@@ -3199,6 +3218,37 @@ int fos_host_resident_cg(int64_t m, int64_t n, const int64_t* colptr, const int6
     FOS_TRY(host_resident_cg(S, P, m, n, cb.data(), xv.data(), rv.data(), v0.data(), tol, (int)std::min<int64_t>(max_iters, 1 << 30), &it));
     for (int64_t i = 0; i < l; ++i) { x[i] = xv[i].x; x[l + i] = xv[i].y; }
     if (iters) *iters = it;
+    return FOS_OK;
+}
+
+int fos_host_resident_plan(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, int32_t gmax,
+                           int64_t* info8, int32_t* wg7, int64_t wg_cap, int64_t* tile5, int64_t tile_cap) {
+    if (!colptr || !info8 || m < 0 || n < 0 || gmax < 1) { set_error("bad argument"); return FOS_EINVAL; }
+    HostBlkCsr S;
+    const int cus = 256;                       // (as fos_host_resident_cg)
+    FOS_TRY(build_stacked_csr(m, n, colptr, rowval, nzval, cus * 12, &S, cus * 28, -1, false, cus * 16));
+    ResPlan P;
+    const bool ok = build_resident_plan(S, m, n, gmax, &P);
+    int64_t ntiles = 0;
+    for (const ResWG& w : P.wg) ntiles += w.nblk;
+    info8[0] = ok ? (P.stream ? 2 : 1) : 0; info8[1] = P.G; info8[2] = P.nt; info8[3] = P.tmax; info8[4] = P.nw; info8[5] = P.rpt; info8[6] = P.ncomm;
+    info8[7] = ntiles;
+    if (!ok) { set_error("FOS_CG_RESIDENT: the operator does not qualify (%s)", P.why.c_str()); return FOS_OK; }
+    if (wg7 && wg_cap >= P.G)
+        for (int q = 0; q < P.G; ++q) {
+            const ResWG& w = P.wg[q];
+            const int32_t r[7] = {w.blk0, w.nblk, w.c0, w.tc, w.wg0, w.wpu, w.idx};
+            memcpy(wg7 + 7 * (size_t)q, r, sizeof(r));
+        }
+    if (tile5 && tile_cap >= ntiles) {
+        int64_t k = 0;
+        for (const ResWG& w : P.wg)
+            for (int ti = 0; ti < w.nblk; ++ti, ++k) {
+                const BlkDesc& d = S.blk[w.blk0 + ti];
+                int64_t* t = tile5 + 5 * k;
+                t[0] = d.meta[0]; t[1] = d.meta[3]; t[2] = d.steps(); t[3] = d.nrows(); t[4] = d.row0;
+            }
+    }
     return FOS_OK;
 }
 

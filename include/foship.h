@@ -355,6 +355,13 @@ int fos_host_stacked_spmv(int64_t m, int64_t n, const int64_t* colptr, const int
  * when the operator does not qualify; with x == NULL only the plan is made.  Used by the CPU test-suite. */
 int fos_host_resident_cg(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, const double* c,
                          int32_t gmax, double* x, const double* rhs, double tol, int64_t max_iters, int64_t* iters, int64_t* stats8);
+/* Host-only export of the resident solve's plan (no GPU needed; the operator as fos_host_resident_cg builds it, FOS_RESIDENT_STREAM as set): info8 =
+ * form (0: does not qualify -- fos_last_error says why; 1: tiles in registers; 2: streamed), workgroups G, tiles per compute wavefront nt (streamed),
+ * steps per tile tmax, compute wavefronts nw, tiles per wavefront rpt (registers), communication wavefronts, tiles in the plan.  When the caps suffice:
+ * wg7 = per workgroup {first tile, tiles, first column, columns, the unit's first workgroup, its workgroups, this one's number}, tile5 = per tile of the
+ * plan in workgroup order {first column, columns, steps, rows, first row of S}.  Used by the CPU test-suite to check a plan against the kernels' limits. */
+int fos_host_resident_plan(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, int32_t gmax,
+                           int64_t* info8, int32_t* wg7, int64_t wg_cap, int64_t* tile5, int64_t tile_cap);
 /* the same with the storage choice forced: window_mode 0 = row blocks / dual tiles, 1 = window panels (any size), -1 = as
  * fos_create decides; stats16 (may be NULL) = the 12 statistics above followed by the 4 of fos_window_stats */
 int fos_host_stacked_spmv_mode(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval,

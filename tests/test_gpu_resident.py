@@ -255,10 +255,160 @@ def test_resident_forms_on_random_block_structures(pkg, seed, monkeypatch):
     tol = 1e-9
     d.set_cg_variant("resident")
     xr, itr = d.cg_kkt(x0, rhs, tol, 5000)
+    xr2, itr2 = d.cg_kkt(x0, rhs, tol, 5000)
+    assert itr2 == itr and np.array_equal(xr, xr2), (seed, st)          # (bit-reproducible: a column sum that races with another wavefront is not)
     d.set_cg_variant("merged_update")
     xm, itm = d.cg_kkt(x0, rhs, tol, 5000)
     assert abs(itr - itm) <= 2 + itm // 20, (seed, st, itr, itm)
     y = np.empty(d.N)
     M.mul(y, xr)
     assert np.linalg.norm(y - rhs) <= 3 * tol, (seed, st)
+    d.close()
+
+
+def _resident_or_refused(pkg, d, why_word):
+    """True when the operator runs resident; else the refusal says why (naming `why_word`) and the handle's default is not resident."""
+    st = d.resident_stats()
+    if st["qualifies"]:
+        d.set_cg_variant("resident")
+        return True
+    with pytest.raises(pkg.lib.FosError) as e:
+        d.set_cg_variant("resident")
+    assert why_word in str(e.value), str(e.value)
+    assert d.cg_variant_name() != "resident"
+    return False
+
+
+def _resident_vs_merged_and_oracle(pkg, d, A, b, c, rng, what):
+    """The resident solve against the launch-per-iteration kernels and the oracle (fixed iteration counts), a tolerance-limited solve that solves
+    M x = rhs, and the same solve again: bit-identical."""
+    M = orc.KKTMatrix(orc.HSDEMatrixQ(A, b, c))
+    rhs, x0 = rng.standard_normal(d.N), rng.standard_normal(d.N)
+    for k in (1, 4):
+        d.set_cg_variant("resident")
+        xr, itr = d.cg_kkt(x0, rhs, 1e-300, k)
+        d.set_cg_variant("merged_update")
+        xm, itm = d.cg_kkt(x0, rhs, 1e-300, k)
+        xo, _ = _ocg(orc.conjugategradient_merged, M, x0, rhs, 1e-300, k)
+        xref, _ = _ocg(orc.conjugategradient, M, x0, rhs, 1e-300, k)
+        env = max(1e-14, relerr(xref, xo))
+        assert itr == itm == k and relerr(xr, xm) <= 50 * env and relerr(xr, xo) <= 50 * env, (what, k, relerr(xr, xm), relerr(xr, xo), env)
+    d.set_cg_variant("resident")
+    tol = 1e-9
+    xr, itr = d.cg_kkt(x0, rhs, tol, 5000)
+    xr2, itr2 = d.cg_kkt(x0, rhs, tol, 5000)
+    assert itr2 == itr and np.array_equal(xr, xr2), what
+    y = np.empty(d.N)
+    M.mul(y, xr)
+    assert np.linalg.norm(y - rhs) <= 3 * tol, what
+
+
+# (name, block shapes, FOS_RESIDENT_GMAX): units of one streamed workgroup whose walk would end past column 64 (refused), and one that ends on it
+EDGE_STRUCTURES = [("3x21", [(100, 21)] * 3, "1"), ("6x10", [(70, 10)] * 6, "1"), ("7x9", [(70, 9)] * 7, "1"), ("30+33", [(100, 30), (100, 33)], "1"),
+                   ("32+24+8", [(100, 32), (130, 24), (70, 8)], "1")]
+
+
+@pytest.mark.parametrize("case", EDGE_STRUCTURES, ids=[c[0] for c in EDGE_STRUCTURES])
+def test_resident_streamed_units_at_column_64(pkg, case, monkeypatch):
+    """Streamed workgroups whose units reach column 64: the ones whose 8-step groups would pass it are refused with the reason, the one that ends
+    on it runs and matches the launch-per-iteration kernels and the oracle, bit-reproducibly."""
+    name, shapes, gmax = case
+    monkeypatch.setenv("FOS_RESIDENT_GMAX", gmax)
+    monkeypatch.setenv("FOS_RESIDENT_STREAM", "2")
+    rng = np.random.default_rng(zlib.crc32(name.encode()) % 1000 + 11)
+    A = block_op(rng, shapes)
+    m, n = A.shape
+    b, c = rng.standard_normal(m), rng.standard_normal(n)
+    d = pkg.HipHSDE(A, b, c, [("Free", m)], [("Free", n)])
+    runs = _resident_or_refused(pkg, d, "column 64")
+    assert runs == (name == "32+24+8"), (name, d.resident_stats())
+    if runs:
+        assert d.resident_stats()["form"] == "streamed"
+        _resident_vs_merged_and_oracle(pkg, d, A, b, c, rng, name)
+    d.close()
+
+
+@pytest.mark.parametrize("tiles", [69, 70, 73])
+def test_resident_streamed_workgroup_lds_boundary(pkg, tiles, monkeypatch):
+    """One 32-column unit of 69 .. 73 tiles on one workgroup: 69 fit the LDS and run; 70 and 73 are refused with a reason that names the LDS
+    (never a failed launch)."""
+    monkeypatch.setenv("FOS_RESIDENT_GMAX", "1")
+    rng = np.random.default_rng(tiles)
+    A = block_op(rng, [(64 * tiles, 32)])
+    m, n = A.shape
+    b, c = rng.standard_normal(m), rng.standard_normal(n)
+    d = pkg.HipHSDE(A, b, c, [("Free", m)], [("Free", n)])
+    runs = _resident_or_refused(pkg, d, "LDS")
+    assert runs == (tiles == 69), (tiles, d.resident_stats())
+    if runs:
+        st = d.resident_stats()
+        assert st["max_tiles_per_workgroup"] == 69 and st["form"] == "streamed" and st["tiles_per_wave"] == 10, st
+        M = orc.KKTMatrix(orc.HSDEMatrixQ(A, b, c))
+        rhs, x0 = rng.standard_normal(d.N), rng.standard_normal(d.N)
+        for k in (1, 4):
+            d.set_cg_variant("resident")
+            xr, itr = d.cg_kkt(x0, rhs, 1e-300, k)
+            d.set_cg_variant("merged_update")
+            xm, itm = d.cg_kkt(x0, rhs, 1e-300, k)
+            xo, _ = _ocg(orc.conjugategradient_merged, M, x0, rhs, 1e-300, k)
+            xref, _ = _ocg(orc.conjugategradient, M, x0, rhs, 1e-300, k)
+            env = max(1e-14, relerr(xref, xo))
+            assert itr == itm == k and relerr(xr, xm) <= 50 * env, (k, relerr(xr, xm), env)
+    d.close()
+
+
+def test_resident_streamed_default_dr_step_vs_oracle(pkg, oracle):
+    """An operator on which the streamed resident solve is the DEFAULT (300 units > 256 CUs: 150 workgroups of two units): one DR step from a
+    steady-state point against the oracle's, 1e-9."""
+    from test_gpu_fullsize import _same_step_vs_oracle
+    prob = _block_sdp(pkg, 300, 16, 12)
+    d = pkg.HipHSDE(prob.A, prob.b, prob.c, prob.K1, prob.K2)
+    st = d.resident_stats()
+    assert st["qualifies"] == 1 and st["form"] == "streamed" and 2 * st["workgroups"] >= 256, st
+    assert d.cg_variant_name() == "resident"
+    d.close()
+    _same_step_vs_oracle(pkg, prob, pkg.DR(), oracle.DR(), 100, 1e-9)
+
+
+@pytest.mark.parametrize("form", ["registers", "streamed"])
+def test_resident_sequence_window_across_solves(pkg, form, monkeypatch):
+    """A solve whose exchange rounds pass 2048 (maxit 2044 .. 2052 at tol 1e-300) must leave no record that the next solve could take for its own:
+    the 1-, 2- and 5-iteration solves behind it are bit-identical to the same solves on a fresh handle (and within the envelope of the
+    launch-per-iteration kernels).  Before each solve reserved windows for all its rounds this failed only when a workgroup of the next solve
+    polled before another had published -- probabilistic; with the reservation it is deterministic."""
+    if form == "streamed":
+        monkeypatch.setenv("FOS_RESIDENT_STREAM", "2")
+        monkeypatch.setenv("FOS_RESIDENT_GMAX", "16")
+        shapes = [(136, 12)] * 32                                   # 16 workgroups of two units
+    else:
+        shapes = [(136, 12)] * 8                                    # 24 workgroups of one tile
+    rng = np.random.default_rng(77)
+    A = block_op(rng, shapes)
+    m, n = A.shape
+    b, c = rng.standard_normal(m), rng.standard_normal(n)
+    rhs, x0 = rng.standard_normal(2 * (m + n + 1)), rng.standard_normal(2 * (m + n + 1))
+    M = orc.KKTMatrix(orc.HSDEMatrixQ(A, b, c))
+    fresh = pkg.HipHSDE(A, b, c, [("Free", m)], [("Free", n)])
+    st = fresh.resident_stats()
+    assert st["qualifies"] == 1 and st["workgroups"] >= 16 and st["form"] == form, st
+    ref = {}
+    for k in (1, 2, 5):
+        fresh.set_cg_variant("resident")
+        ref[k], it = fresh.cg_kkt(x0, rhs, 1e-300, k)
+        assert it == k
+        fresh.set_cg_variant("merged_update")
+        xm, _ = fresh.cg_kkt(x0, rhs, 1e-300, k)
+        xo, _ = _ocg(orc.conjugategradient_merged, M, x0, rhs, 1e-300, k)
+        xref, _ = _ocg(orc.conjugategradient, M, x0, rhs, 1e-300, k)
+        env = max(1e-14, relerr(xref, xo))
+        assert relerr(ref[k], xm) <= 50 * env, (k, relerr(ref[k], xm), env)
+    fresh.close()
+    d = pkg.HipHSDE(A, b, c, [("Free", m)], [("Free", n)])
+    d.set_cg_variant("resident")
+    for maxit in range(2044, 2053):
+        _, it = d.cg_kkt(x0, rhs, 1e-300, maxit)
+        assert it == maxit, (maxit, it)
+        for k in (1, 2, 5):
+            x, it = d.cg_kkt(x0, rhs, 1e-300, k)
+            assert it == k and np.array_equal(x, ref[k]), (form, maxit, k, relerr(x, ref[k]))
     d.close()
