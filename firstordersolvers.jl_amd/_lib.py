@@ -73,6 +73,9 @@ PROTOTYPES = {
     "fos_enable_direct": (C.c_int, [_h, _i64p, _i64p, _dp]),
     "fos_disable_direct": (C.c_int, [_h]),
     "fos_get_direct_mode": (C.c_int, [_h, _i32p]),
+    "fos_enable_direct2": (C.c_int, [_h, _i64p, _i64p, _dp, C.c_int32]),
+    "fos_get_direct_stats": (C.c_int, [_h, _dp]),
+    "fos_host_reduced_symm": (C.c_int, [C.c_int64, _dp, _dp, _dp, _i32p]),
     "fos_set_iterate": (C.c_int, [_h, _dp]),
     "fos_get_iterate": (C.c_int, [_h, _dp]),
     "fos_get_checked": (C.c_int, [_h, _dp]),

@@ -537,6 +537,40 @@ void launch_dense_symv(const LaunchCtx& c, int64_t ld, const double* G, const do
 void launch_direct_rhs(const LaunchCtx& c, const double2* W, const double2* x, double* t);
 void launch_direct_finish(const LaunchCtx& c, const double2* x, const double2* W, double2* out);
 
+// direct = true, reduced form (direct_reduced.hip): K^-1, K = I + A'A or I + A A' of order k = min(m, n), as tiles of its lower triangle stored once
+constexpr int RED_TR = 64, RED_TC = 32;          // rows (= lanes) and columns of a tile
+constexpr int RED_TILE = RED_TR * RED_TC;        // doubles per tile
+constexpr int RED_CHUNK = 16;                    // row blocks per unit (the walk of one wavefront)
+constexpr int RED_DOT_BLOCKS = 1024;             // most workgroups (= records of the two border dots) of the vector kernels
+struct RedUnit { int32_t j, i0, i1, tile0; };    // strip j (columns [32 j, 32 j + 32)), row blocks [i0, i1), first tile in the stream
+struct RedPlan {                                 // host
+    int64_t k = 0, ntiles = 0;
+    int nt = 0, ns = 0;                          // row blocks, strips
+    std::vector<RedUnit> units;
+    std::vector<int32_t> strip_u0;               // [ns + 1] units of strip j: strip_u0[j] .. strip_u0[j + 1] - 1
+};
+struct RedDev {                                  // device
+    int64_t k, kpad; int nt, nunits;
+    const RedUnit* units; const int32_t* strip_u0;
+    double* tiles;                               // [ntiles][RED_TILE]
+    double2* rowslot;                            // [ntiles][64]: T x_J of every tile
+    double* colslot;                             // [nunits][64]: T' x_I summed over a unit, (column, right-hand side) interleaved
+};
+void build_reduced_plan(int64_t k, RedPlan* P);
+void host_reduced_pack(const RedPlan& P, const double* X, std::vector<double>* tiles, int32_t* count);
+void host_reduced_symm(const RedPlan& P, const std::vector<double>& tiles, const double* pq, double* y);
+void launch_red_form_k(const LaunchCtx& c, int64_t k, int64_t ld, const int32_t* cptr, const int32_t* cidx, const double* cval, const int32_t* rptr,
+                       const int32_t* ridx, const double* rval, double* K);
+void launch_red_pack_tiles(const LaunchCtx& c, const RedDev& R, int64_t ld, const double* X);
+void launch_red_symm(const LaunchCtx& c, const RedDev& R, const double2* pq, double2* y);          // y = K^-1 (p, q), pairs interleaved, kpad of them
+void launch_red_in1(const LaunchCtx& c, int swap, const double* t, double2* vin);
+void launch_red_pair(const LaunchCtx& c, const RedDev& R, int swap, const double* t, const double* s1, double2* pq);
+void launch_red_in2(const LaunchCtx& c, int swap, const double2* yk, double2* vin);
+int  launch_red_d(const LaunchCtx& c, int swap, const double* t, const double* s2, const double2* yk, const double* hv, const double* gv, double* d, double* dots);
+void launch_red_w(const LaunchCtx& c, const double* t, const double* d, const double* pv, const double* qv, const double* dots, int nrec, const double* minv,
+                  int add, double* w);
+void launch_red_resid(const LaunchCtx& c, const double* t, const double* w, const double* z, double* r);
+
 // direct = true on a block-separable operator (I + A'A block diagonal with blocks of order <= BLKDIR_MAX): vecops.hip, solver.cpp prox_affine_direct_block
 constexpr int BLKDIR_MAX = 64;
 void launch_blkdir_prep(const LaunchCtx& c, const double2* T, const double2* phg, double2* W2, double2* W3, double* partials);

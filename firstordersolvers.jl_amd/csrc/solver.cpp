@@ -205,6 +205,19 @@ struct fos_solver {
     double* blk_ctx = nullptr;                 // [blk_n] the blocks' shares of c'x^ (blkdir_solve_kernel)
     bool blk_skip_tail = true;                 // the third apply runs without its deferred-row and tau-row kernels (FOS_BLKDIR_FULL_APPLY=1: with them)
     bool blk_ready = false;                    // blkdir_setup ran to its end (a half-finished set-up must not pass for the block form)
+    // direct = true, REDUCED form (direct_reduced.hip): K^-1, K = I + A'A (n <= m) or I + A A' (m < n), as tiles of its lower triangle stored once
+    bool direct_red = false;
+    bool red_ready = false;                    // reduced_setup ran to its end
+    int red_swap = 0;                          // 1: m < n, K = I + A A'
+    int red_refine = 1;                        // steps of iterative refinement on the matrix-free G = I - Q Q per projection (FOS_DIRECT_REDUCED_REFINE)
+    RedPlan red_plan;
+    RedDev red{};
+    d2 *red_pq = nullptr, *red_yk = nullptr;   // the two right-hand sides of the tile product and its result, interleaved (kpad pairs)
+    double *red_s = nullptr, *red_d = nullptr, *red_r = nullptr, *red_z = nullptr;   // plain l-vectors: a Q sweep's result, D^-1 t1, the refinement's residual, Q w / Q Q w
+    double *red_p = nullptr, *red_q = nullptr, *red_g = nullptr;                     // D^-1 h, D^-1 g, g = -Q0 h
+    double* red_dots = nullptr;                // [RED_DOT_BLOCKS][2] the workgroups' shares of h'd and g'd
+    double red_minv[4] = {0, 0, 0, 0};         // inverse of the 2 x 2 border system, row-major
+    double direct_setup_s = 0.0;               // wall time of the last set-up (fos_get_direct_stats)
 
     // S1 = AffinePlusLinear state (affinepluslinear.jl:58-69)
     int64_t prox_i = 1;
@@ -864,7 +877,58 @@ int prox_affine_direct_block(fos_solver* h, const d2* x, d2* out, bool from_T = 
 }
 
 // prox!(y, S1::IndAffine([Q -I], 0), x) with the result left in h->SOL        HSDE.jl:12-15 (direct = true)
+// d = D^-1 t1, D = diag(I + A'A, I + A A'), through K^-1 alone: two Q sweeps (B' t_other, then B e) around ONE pass over the stored triangle with the two
+// right-hand sides (t_own, B' t_other).  dots != nullptr: the workgroups' shares of h'd and g'd (returns how many).  Scratch: PB[0], red_s, red_pq, red_yk.
+int reduced_dinv(fos_solver* h, const LaunchCtx& c, const double* t, double* d, double* dots) {
+    launch_red_in1(c, h->red_swap, t, h->PB[0]);
+    launch_q1(c, Q_PLAIN, h->PB[0], 0, 1.0, h->red_s);                  // (the tau row is not needed: no finalize)
+    launch_red_pair(c, h->red, h->red_swap, t, h->red_s, h->red_pq);
+    launch_red_symm(c, h->red, h->red_pq, h->red_yk);                   // (K^-1 t_own, e = K^-1 B' t_other)
+    launch_red_in2(c, h->red_swap, h->red_yk, h->PB[0]);
+    launch_q1(c, Q_PLAIN, h->PB[0], 0, 1.0, h->red_s);
+    return launch_red_d(c, h->red_swap, t, h->red_s, h->red_yk, h->cb, h->red_g, d, dots);
+}
+// w = G^-1 t (add: w += G^-1 t) by the border formula of direct_reduced.hip
+void reduced_solve(fos_solver* h, const LaunchCtx& c, const double* t, double* w, int add) {
+    const int nrec = reduced_dinv(h, c, t, h->red_d, h->red_dots);
+    launch_red_w(c, t, h->red_d, h->red_p, h->red_q, h->red_dots, nrec, h->red_minv, add, w);
+}
+// out_plain = Q v for a plain l-vector v, tau row included (scratch: AP)
+int reduced_q_plain(fos_solver* h, const LaunchCtx& c, const double* v, double* out) {
+    int fr = 0;
+    launch_set_comp(c, h->AP, v, 0);
+    launch_q1(c, Q_PLAIN, h->AP, 0, 1.0, out);
+    FOS_TRY(finish_reduce(h, c, c.S.npart, 1, 0, &fr, c.S.part_off));
+    launch_q1_finalize(c, Q_PLAIN, h->AP, 0, 1.0, out, fr);
+    return FOS_OK;
+}
+int prox_affine_direct_reduced(fos_solver* h, const d2* x) {
+    RoctxRange range("fos:prox_affine_direct_reduced (Q sweeps + one pass over the lower triangle of K^-1)");
+    LaunchCtx c = h->ctx();
+    int fr = 0;
+    double *t = h->dvec[0], *w = h->dvec[1];
+    launch_q1(c, Q_VFROMU, x, 0, 1.0, h->R);                           // R = (u, Q u)
+    FOS_TRY(finish_reduce(h, c, c.S.npart, 1, 0, &fr, c.S.part_off));
+    launch_q1_finalize(c, Q_VFROMU, x, 0, 1.0, h->R, fr);
+    launch_direct_rhs(c, h->R, x, t);                                  // t = Q u - v
+    reduced_solve(h, c, t, w, 0);
+    for (int it = 0; it < h->red_refine; ++it) {                       // w += G^-1 (t - G w), G w = w - Q Q w
+        FOS_TRY(reduced_q_plain(h, c, w, h->red_z));
+        FOS_TRY(reduced_q_plain(h, c, h->red_z, h->red_z));
+        launch_red_resid(c, t, w, h->red_z, h->red_r);
+        reduced_solve(h, c, h->red_r, w, 1);
+    }
+    launch_set_comp(c, h->AP, w, 0);                                   // (w, 0)
+    launch_q1(c, Q_VFROMU, h->AP, 0, 1.0, h->R);                       // R = (w, Q w)
+    FOS_TRY(finish_reduce(h, c, c.S.npart, 1, 0, &fr, c.S.part_off));
+    launch_q1_finalize(c, Q_VFROMU, h->AP, 0, 1.0, h->R, fr);
+    launch_direct_finish(c, x, h->R, h->SOL);                          // (u + Q w, v + w)
+    h->cgiter = 0;
+    return check_launch("reduced direct affine projection");
+}
+
 int prox_affine_direct(fos_solver* h, const d2* x) {
+    if (h->direct_red) return prox_affine_direct_reduced(h, x);
     if (h->direct_blk) return prox_affine_direct_block(h, x, h->SOL);
     RoctxRange range("fos:prox_affine_direct (2 Q sweeps + dense symmetric matvec)");
     LaunchCtx c = h->ctx();
@@ -2569,8 +2633,7 @@ int fos_set_alg(fos_handle h, int alg, double alpha, double alpha1, double alpha
 //     X_0 = I / (1.25 lambda~),   X_{k+1} = 2 X_k - X_k (G X_k),        lambda~ = a power-iteration estimate of lambda_max(G),
 // whose residual I - G X_k squares every step: ceil(log2 lambda~) + 7 steps reach rounding level (verified at the end: the
 // entries of G X - I).  Only matrix products are needed: the hand-written fp64 MFMA GEMM of vecops.hip.
-int fos_enable_direct(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval) {
-    if (!h || !colptr || (!rowval && colptr[h->n] > 1)) { set_error("NULL argument"); return FOS_EINVAL; }
+static int enable_direct_auto(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval) {
     if (h->row_sharded) { set_error("direct=true is not available on row-sharded handles"); return FOS_EUNSUPPORTED; }
     if (h->Ginv || (h->blk_ginv && h->blk_ready)) { h->direct = true; h->direct_blk = h->blk_ginv != nullptr && h->blk_ready; return FOS_OK; }
     const int64_t l = h->l, nnz = colptr[h->n] - 1;
@@ -2676,16 +2739,252 @@ int fos_enable_direct(fos_handle h, const int64_t* colptr, const int64_t* rowval
     return FOS_OK;
 }
 
-int fos_disable_direct(fos_handle h) {
-    if (!h) { set_error("NULL handle"); return FOS_EINVAL; }
-    h->direct = false; h->direct_cg = false; h->direct_blk = false;
+// direct = true, reduced form: K = I + B'B of order k = min(m, n) (B = A, or A' when m < n) formed densely from the sparse A, inverted by the same Newton-Schulz
+// iteration as the dense form, repacked as the tiles of its lower triangle; then p = D^-1 h, q = D^-1 g and the 2 x 2 border system through the projection's own path.
+static void reduced_release(fos_solver* h) {
+    dev_release(h, &h->red.tiles); dev_release(h, &h->red.rowslot); dev_release(h, &h->red.colslot);
+    { RedUnit* u = const_cast<RedUnit*>(h->red.units); dev_release(h, &u); h->red.units = nullptr; }
+    { int32_t* u = const_cast<int32_t*>(h->red.strip_u0); dev_release(h, &u); h->red.strip_u0 = nullptr; }
+    dev_release(h, &h->red_pq); dev_release(h, &h->red_yk); dev_release(h, &h->red_s); dev_release(h, &h->red_d); dev_release(h, &h->red_r); dev_release(h, &h->red_z);
+    dev_release(h, &h->red_p); dev_release(h, &h->red_q); dev_release(h, &h->red_g); dev_release(h, &h->red_dots);
+    h->red_ready = false; h->direct_red = false;
+}
+static int reduced_setup(fos_solver* h, const int64_t* colptr, const int64_t* rowval, const double* nzval) {
+    const int64_t n = h->n, m = h->m, l = h->l, nnz = colptr[n] - 1;
+    if (h->row_sharded || h->sharded()) { set_error("direct=true, reduced form: not available on sharded handles"); return FOS_EUNSUPPORTED; }
+    if (nnz != h->nnz) { set_error("fos_enable_direct2: A has %lld non-zeros, the handle was created with %lld", (long long)nnz, (long long)h->nnz); return FOS_EINVAL; }
+    const int64_t k = std::min(m, n);
+    const int64_t kmax = getenv("FOS_DIRECT_REDUCED_MAX") ? atoll(getenv("FOS_DIRECT_REDUCED_MAX")) : 46000;
+    if (k < 1) { set_error("direct=true, reduced form: min(m, n) = 0, nothing to factorise"); return FOS_EUNSUPPORTED; }
+    if (k > kmax) { set_error("direct=true, reduced form: min(m, n) = %lld exceeds the largest order of the stored inverse (%lld; FOS_DIRECT_REDUCED_MAX)", (long long)k, (long long)kmax); return FOS_EUNSUPPORTED; }
+    if (nnz > INT32_MAX || m > INT32_MAX || n > INT32_MAX) { set_error("direct=true, reduced form: operator too large for 32-bit indices"); return FOS_EUNSUPPORTED; }
+    h->red_refine = getenv("FOS_DIRECT_REDUCED_REFINE") ? std::max(0, std::min(4, atoi(getenv("FOS_DIRECT_REDUCED_REFINE")))) : 1;
+    // ---- A by columns and by rows, 0-based (the rows in column order: the summation order of K's entries)
+    std::vector<int32_t> cp((size_t)n + 1), ci((size_t)nnz), rp((size_t)m + 1, 0), ri((size_t)nnz);
+    std::vector<double> rv((size_t)nnz);
+    for (int64_t j = 0; j <= n; ++j) {
+        if (colptr[j] < 1 || colptr[j] > nnz + 1 || (j > 0 && colptr[j] < colptr[j - 1])) { set_error("fos_enable_direct2: malformed colptr"); return FOS_EINVAL; }
+        cp[j] = (int32_t)(colptr[j] - 1);
+    }
+    for (int64_t e = 0; e < nnz; ++e) {
+        const int64_t r = rowval[e] - 1;
+        if (r < 0 || r >= m) { set_error("fos_enable_direct2: row index out of range"); return FOS_EINVAL; }
+        ci[e] = (int32_t)r;
+        rp[r + 1] += 1;
+    }
+    for (int64_t r = 0; r < m; ++r) rp[r + 1] += rp[r];
+    {
+        std::vector<int32_t> fill(rp.begin(), rp.end() - 1);
+        for (int64_t j = 0; j < n; ++j)
+            for (int32_t e = cp[j]; e < cp[j + 1]; ++e) { const int32_t q = fill[ci[e]]++; ri[q] = (int32_t)j; rv[q] = nzval[e]; }
+    }
+    FOS_HIP(hipSetDevice(h->device));
+    LaunchCtx c = h->ctx();
+    const int swap = m < n ? 1 : 0;
+    const int64_t L = (k + 63) / 64 * 64;
+    const size_t L2 = (size_t)L * (size_t)L;
+    reduced_release(h);
+    build_reduced_plan(k, &h->red_plan);
+    const RedPlan& P = h->red_plan;
+    int32_t *dcp = nullptr, *dci = nullptr, *drp = nullptr, *dri = nullptr;
+    double *dcv = nullptr, *drv = nullptr, *G = nullptr, *B0 = nullptr, *B1 = nullptr, *B2 = nullptr;
+    auto cleanup = [&]() { (void)hipFree(dcp); (void)hipFree(dci); (void)hipFree(drp); (void)hipFree(dri); (void)hipFree(dcv); (void)hipFree(drv);
+                           (void)hipFree(G); (void)hipFree(B0); (void)hipFree(B1); (void)hipFree(B2); };
+    auto fail = [&](int code) { cleanup(); reduced_release(h); return code; };
+    const size_t ne = (size_t)std::max<int64_t>(nnz, 1);
+    hipError_t e = hipMalloc((void**)&dcp, sizeof(int32_t) * (n + 1));
+    if (e == hipSuccess) e = hipMalloc((void**)&dci, sizeof(int32_t) * ne);
+    if (e == hipSuccess) e = hipMalloc((void**)&dcv, sizeof(double) * ne);
+    if (e == hipSuccess) e = hipMalloc((void**)&drp, sizeof(int32_t) * (m + 1));
+    if (e == hipSuccess) e = hipMalloc((void**)&dri, sizeof(int32_t) * ne);
+    if (e == hipSuccess) e = hipMalloc((void**)&drv, sizeof(double) * ne);
+    if (e == hipSuccess) e = hipMalloc((void**)&G, sizeof(double) * L2);
+    if (e == hipSuccess) e = hipMalloc((void**)&B0, sizeof(double) * L2);
+    if (e == hipSuccess) e = hipMalloc((void**)&B1, sizeof(double) * L2);
+    if (e == hipSuccess) e = hipMalloc((void**)&B2, sizeof(double) * L2);
+    if (e != hipSuccess) { set_error("direct=true, reduced form: hipMalloc of the set-up buffers (4 x %zu bytes) failed: %s", L2 * 8, hipGetErrorString(e)); return fail(FOS_ENOMEM); }
+    const size_t lpad = (size_t)((l + 63) / 64 * 64), kpad = (size_t)P.nt * RED_TR;
+    int rc = FOS_OK;
+    RedUnit* dunits = nullptr; int32_t* dstrip = nullptr;
+    if (rc == FOS_OK) rc = dev_alloc(h, &dunits, P.units.size());
+    if (rc == FOS_OK) rc = dev_alloc(h, &dstrip, P.strip_u0.size());
+    h->red.units = dunits; h->red.strip_u0 = dstrip;
+    if (rc == FOS_OK) rc = dev_alloc(h, &h->red.tiles, (size_t)P.ntiles * RED_TILE);
+    if (rc == FOS_OK) rc = dev_alloc(h, &h->red.rowslot, (size_t)P.ntiles * 64);
+    if (rc == FOS_OK) rc = dev_alloc(h, &h->red.colslot, P.units.size() * 64);
+    if (rc == FOS_OK) rc = dev_alloc(h, &h->red_pq, kpad);
+    if (rc == FOS_OK) rc = dev_alloc(h, &h->red_yk, kpad);
+    for (double** v : {&h->red_s, &h->red_d, &h->red_r, &h->red_z, &h->red_p, &h->red_q, &h->red_g})
+        if (rc == FOS_OK) rc = dev_alloc(h, v, lpad);
+    if (rc == FOS_OK) rc = dev_alloc(h, &h->red_dots, (size_t)2 * RED_DOT_BLOCKS);
+    if (rc == FOS_OK && !h->dvec[0]) rc = dev_alloc(h, &h->dvec[0], lpad);
+    if (rc == FOS_OK && !h->dvec[1]) rc = dev_alloc(h, &h->dvec[1], lpad);
+    if (rc != FOS_OK) return fail(rc);
+    h->red.k = k; h->red.kpad = (int64_t)kpad; h->red.nt = P.nt; h->red.nunits = (int)P.units.size();
+    h->red_swap = swap;
+#define DIRECT_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error("direct=true set-up (reduced form): %s -> %s", #expr, hipGetErrorString(_e)); return fail(FOS_EHIP); } } while (0)
+    DIRECT_HIP(hipMemcpyAsync(dunits, P.units.data(), sizeof(RedUnit) * P.units.size(), hipMemcpyHostToDevice, h->stream));
+    DIRECT_HIP(hipMemcpyAsync(dstrip, P.strip_u0.data(), sizeof(int32_t) * P.strip_u0.size(), hipMemcpyHostToDevice, h->stream));
+    DIRECT_HIP(hipMemcpyAsync(dcp, cp.data(), sizeof(int32_t) * (n + 1), hipMemcpyHostToDevice, h->stream));
+    DIRECT_HIP(hipMemcpyAsync(drp, rp.data(), sizeof(int32_t) * (m + 1), hipMemcpyHostToDevice, h->stream));
+    if (nnz) {
+        DIRECT_HIP(hipMemcpyAsync(dci, ci.data(), sizeof(int32_t) * nnz, hipMemcpyHostToDevice, h->stream));
+        DIRECT_HIP(hipMemcpyAsync(dcv, nzval, sizeof(double) * nnz, hipMemcpyHostToDevice, h->stream));
+        DIRECT_HIP(hipMemcpyAsync(dri, ri.data(), sizeof(int32_t) * nnz, hipMemcpyHostToDevice, h->stream));
+        DIRECT_HIP(hipMemcpyAsync(drv, rv.data(), sizeof(double) * nnz, hipMemcpyHostToDevice, h->stream));
+    }
+    DIRECT_HIP(hipMemsetAsync(G, 0, sizeof(double) * L2, h->stream));
+    DIRECT_HIP(hipMemsetAsync(B1, 0, sizeof(double) * L2, h->stream));
+    for (double* v : {h->red_s, h->red_d, h->red_r, h->red_z, h->red_p, h->red_q, h->red_g}) DIRECT_HIP(hipMemsetAsync(v, 0, sizeof(double) * lpad, h->stream));
+    // K = I + B'B: B = A (its columns: A's columns, its rows: A's rows), or B = A' (the two exchanged)
+    if (!swap) launch_red_form_k(c, k, L, dcp, dci, dcv, drp, dri, drv, G);
+    else launch_red_form_k(c, k, L, drp, dri, drv, dcp, dci, dcv, G);
+    // ---- power iteration for lambda_max(K), as in the dense form
+    LaunchCtx ck = c;
+    ck.l = k;
+    std::vector<double> v((size_t)L, 0.0), w((size_t)L, 0.0);
+    for (int64_t i = 0; i < k; ++i) v[i] = 1.0 + 0.37 * std::sin(1.7 * (double)i);
+    double lam = 1.0;
+    for (int it = 0; it < 20; ++it) {
+        double nv = 0.0;
+        for (int64_t i = 0; i < k; ++i) nv += v[i] * v[i];
+        nv = std::sqrt(nv);
+        for (int64_t i = 0; i < k; ++i) v[i] /= nv;
+        DIRECT_HIP(hipMemcpyAsync(h->dvec[0], v.data(), sizeof(double) * k, hipMemcpyHostToDevice, h->stream));
+        launch_dense_symv(ck, L, G, h->dvec[0], h->dvec[1]);
+        DIRECT_HIP(hipMemcpyAsync(w.data(), h->dvec[1], sizeof(double) * k, hipMemcpyDeviceToHost, h->stream));
+        DIRECT_HIP(hipStreamSynchronize(h->stream));
+        double nw = 0.0;
+        for (int64_t i = 0; i < k; ++i) nw += w[i] * w[i];
+        nw = std::sqrt(nw);
+        if (!(nw == nw) || nw > 1e300) { set_error("direct=true: the operator has non-finite entries"); return fail(FOS_EINVAL); }
+        lam = std::max(lam, nw);
+        v.swap(w);
+    }
+    // ---- Newton-Schulz (same schedule and convergence test as the dense form)
+    launch_dense_scale_identity(c, L, B1, 1.0 / (1.25 * lam));
+    double *X = B1, *Xn = B2;
+    const int planned = (int)std::ceil(std::log2(std::max(1.0, lam))) + 7;
+    double resid = 1.0;
+    int it = 0;
+    std::vector<double> part(256);
+    for (; it < planned + 6; ++it) {
+        launch_dense_gemm(c, (int)L, 1.0, G, X, 0.0, nullptr, B0);          // Y = K X
+        if (it >= planned) {
+            launch_dense_resid(c, L, B0, h->partials, 256);
+            DIRECT_HIP(hipMemcpyAsync(part.data(), h->partials, sizeof(double) * 256, hipMemcpyDeviceToHost, h->stream));
+            DIRECT_HIP(hipStreamSynchronize(h->stream));
+            resid = 0.0;
+            for (double r : part) resid = (r > resid || r != r) ? r : resid;
+            if (resid <= 1e-12) break;
+        }
+        launch_dense_gemm(c, (int)L, -1.0, X, B0, 2.0, X, Xn);              // X <- 2 X - X Y
+        std::swap(X, Xn);
+    }
+    if (!(resid <= 1e-12)) { set_error("direct=true, reduced form: the inverse of K did not converge (max |K X - I| = %.3e after %d steps, lambda_max ~ %.3e)", resid, it, lam); return fail(FOS_EINVAL); }
+    launch_red_pack_tiles(c, h->red, L, X);
+    DIRECT_HIP(hipStreamSynchronize(h->stream));
+    rc = check_launch("direct=true set-up (reduced form)");
+    cleanup();                                                              // the square buffers go: the handle keeps the packed triangle
+    dcp = dci = drp = dri = nullptr; dcv = drv = G = B0 = B1 = B2 = nullptr;
+    if (rc != FOS_OK) return fail(rc);
+    // ---- g = -Q0 h, p = D^-1 h, q = D^-1 g through the projection's path; the border system on the host
+    const int64_t nm = n + m;
+    double* hfull = h->dvec[0];
+    DIRECT_HIP(hipMemsetAsync(hfull, 0, sizeof(double) * lpad, h->stream));
+    DIRECT_HIP(hipMemcpyAsync(hfull, h->cb, sizeof(double) * nm, hipMemcpyDeviceToDevice, h->stream));
+    launch_set_comp(c, h->AP, hfull, 0);
+    launch_q1(c, Q_PLAIN, h->AP, 0, -1.0, h->red_g);                        // rows 0 .. n+m-1 of -Q (h, 0) = -Q0 h (the tau entry of red_g stays 0)
+    (void)reduced_dinv(h, c, hfull, h->red_p, nullptr);
+    (void)reduced_dinv(h, c, h->red_g, h->red_q, nullptr);
+    std::vector<double> hh((size_t)nm), gg((size_t)nm), pp((size_t)nm), qq((size_t)nm);
+    DIRECT_HIP(hipMemcpyAsync(hh.data(), h->cb, sizeof(double) * nm, hipMemcpyDeviceToHost, h->stream));
+    DIRECT_HIP(hipMemcpyAsync(gg.data(), h->red_g, sizeof(double) * nm, hipMemcpyDeviceToHost, h->stream));
+    DIRECT_HIP(hipMemcpyAsync(pp.data(), h->red_p, sizeof(double) * nm, hipMemcpyDeviceToHost, h->stream));
+    DIRECT_HIP(hipMemcpyAsync(qq.data(), h->red_q, sizeof(double) * nm, hipMemcpyDeviceToHost, h->stream));
+    DIRECT_HIP(hipStreamSynchronize(h->stream));
+#undef DIRECT_HIP
+    rc = check_launch("direct=true set-up (reduced form, border)");
+    if (rc != FOS_OK) return fail(rc);
+    long double hp = 0, hq = 0, gp = 0, gq = 0, h2 = 0;
+    for (int64_t i = 0; i < nm; ++i) { hp += (long double)hh[i] * pp[i]; hq += (long double)hh[i] * qq[i]; gp += (long double)gg[i] * pp[i]; gq += (long double)gg[i] * qq[i]; h2 += (long double)hh[i] * hh[i]; }
+    const long double a00 = 1.0L + hp, a01 = hq, a10 = gp, a11 = gq - (1.0L + h2);
+    const long double det = a00 * a11 - a01 * a10;
+    if (!(fabsl(det) > 0.0L) || !std::isfinite((double)det)) { set_error("direct=true, reduced form: the 2 x 2 border system is singular"); return fail(FOS_EINVAL); }
+    h->red_minv[0] = (double)(a11 / det); h->red_minv[1] = (double)(-a01 / det); h->red_minv[2] = (double)(-a10 / det); h->red_minv[3] = (double)(a00 / det);
+    h->direct_iters = it;
+    h->red_ready = true;
     return FOS_OK;
 }
 
-// which form S1 = IndAffine([Q -I], 0) runs in: 0 = off (AffinePlusLinear's CG schedule), 1 = dense inverse, 2 = block form, 3 = CG at its tolerance floor
+int fos_enable_direct2(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval, int32_t form) {
+    if (!h || !colptr || (!rowval && colptr[h->n] > 1)) { set_error("NULL argument"); return FOS_EINVAL; }
+    if (form != FOS_DIRECT_FORM_AUTO && form != FOS_DIRECT_FORM_REDUCED) { set_error("fos_enable_direct2: form must be FOS_DIRECT_FORM_AUTO or FOS_DIRECT_FORM_REDUCED"); return FOS_EINVAL; }
+    const char* mode_env = getenv("FOS_DIRECT_MODE");
+    if (form == FOS_DIRECT_FORM_AUTO && mode_env && std::string(mode_env) == "reduced") form = FOS_DIRECT_FORM_REDUCED;
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc;
+    if (form == FOS_DIRECT_FORM_REDUCED) {
+        if (!h->red_ready) {
+            FOS_TRY(reduced_setup(h, colptr, rowval, nzval));
+            h->direct_setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+        if (h->Ginv) { dev_release(h, &h->Ginv); h->Gld = 0; }            // one form's inverse at a time
+        h->direct = true; h->direct_red = true; h->direct_blk = false; h->direct_cg = false;
+        return FOS_OK;
+    }
+    const bool had = h->Ginv || (h->blk_ginv && h->blk_ready);
+    rc = enable_direct_auto(h, colptr, rowval, nzval);
+    if (rc == FOS_OK) {
+        if (h->red_ready) reduced_release(h);
+        h->direct_red = false;
+        if (!had) h->direct_setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return rc;
+}
+int fos_enable_direct(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval) {
+    return fos_enable_direct2(h, colptr, rowval, nzval, FOS_DIRECT_FORM_AUTO);
+}
+
+// form (as fos_get_direct_mode), order of the stored inverse (dense: l, reduced: min(m, n), else 0), wall seconds of the last set-up, its Newton-Schulz steps
+int fos_get_direct_stats(fos_handle h, double* out4) {
+    if (!h || !out4) { set_error("NULL argument"); return FOS_EINVAL; }
+    int32_t mode = 0;
+    FOS_TRY(fos_get_direct_mode(h, &mode));
+    out4[0] = (double)mode;
+    out4[1] = mode == 4 ? (double)h->red.k : (mode == 1 ? (double)h->l : 0.0);
+    out4[2] = h->direct_setup_s;
+    out4[3] = (mode == 1 || mode == 4) ? (double)h->direct_iters : 0.0;
+    return FOS_OK;
+}
+
+// test-only, host: the reduced form's tile packing and the tile product in the kernels' summation order, for a symmetric k x k matrix X (column-major) and k
+// operand pairs pq; y: k pairs; count (k x k, may be NULL): in how many tile slots each entry is stored
+int fos_host_reduced_symm(int64_t k, const double* X, const double* pq, double* y, int32_t* count) {
+    if (k < 1 || !X || !pq || !y) { set_error("bad argument"); return FOS_EINVAL; }
+    RedPlan P;
+    build_reduced_plan(k, &P);
+    std::vector<double> tiles;
+    if (count) std::fill(count, count + k * k, 0);
+    host_reduced_pack(P, X, &tiles, count);
+    const size_t kpad = (size_t)P.nt * RED_TR;
+    std::vector<double> pin(2 * kpad, 0.0), out(2 * kpad, 0.0);
+    std::copy(pq, pq + 2 * k, pin.begin());
+    host_reduced_symm(P, tiles, pin.data(), out.data());
+    std::copy(out.begin(), out.begin() + 2 * k, y);
+    return FOS_OK;
+}
+
+int fos_disable_direct(fos_handle h) {
+    if (!h) { set_error("NULL handle"); return FOS_EINVAL; }
+    h->direct = false; h->direct_cg = false; h->direct_blk = false; h->direct_red = false;
+    return FOS_OK;
+}
+
+// which form S1 = IndAffine([Q -I], 0) runs in: 0 = off (AffinePlusLinear's CG schedule), 1 = dense inverse, 2 = block form, 3 = CG at its tolerance floor, 4 = reduced form
 int fos_get_direct_mode(fos_handle h, int32_t* mode) {
     if (!h || !mode) { set_error("NULL argument"); return FOS_EINVAL; }
-    *mode = h->direct ? (h->direct_blk ? 2 : 1) : (h->direct_cg ? 3 : 0);
+    *mode = h->direct ? (h->direct_red ? 4 : (h->direct_blk ? 2 : 1)) : (h->direct_cg ? 3 : 0);
     return FOS_OK;
 }
 

@@ -423,24 +423,35 @@ class HipHSDE:
     def sync(self):
         _lib.check(self._lib.fos_sync(self._h))
 
-    def enable_direct(self, A):
-        """direct = true (HSDE.jl:12-15): exact affine projection through a one-time dense factorisation (fos_enable_direct)."""
+    DIRECT_FORMS = {"auto": 0, "reduced": 4}                      # FOS_DIRECT_FORM_*
+
+    def enable_direct(self, A, form="auto"):
+        """direct = true (HSDE.jl:12-15): exact affine projection through a one-time factorisation (fos_enable_direct2).  form="auto": the first of
+        block / dense / cg that applies; form="reduced": the inverse of I + A'A or I + A A' (order min(m, n) <= 46 000) as packed lower-triangle tiles."""
+        if form not in self.DIRECT_FORMS:
+            raise ValueError("direct form must be one of %s, not %r" % (sorted(self.DIRECT_FORMS), form))
         A = sp.csc_matrix(A)
         A.sort_indices()
         colptr = (A.indptr.astype(np.int64) + 1)
         rowval = (A.indices.astype(np.int64) + 1)
         nz = np.ascontiguousarray(A.data, dtype=np.float64)
         i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-        _lib.check(self._lib.fos_enable_direct(self._h, i64(colptr), i64(rowval), _lib.dptr(nz)))
+        _lib.check(self._lib.fos_enable_direct2(self._h, i64(colptr), i64(rowval), _lib.dptr(nz), self.DIRECT_FORMS[form]))
 
     def disable_direct(self):
         _lib.check(self._lib.fos_disable_direct(self._h))
 
     def direct_mode(self):
-        """'off' | 'dense' | 'block' | 'cg': the form S1 = IndAffine([Q -I], 0) runs in (fos_get_direct_mode)"""
+        """'off' | 'dense' | 'block' | 'cg' | 'reduced': the form S1 = IndAffine([Q -I], 0) runs in (fos_get_direct_mode)"""
         v = C.c_int32(0)
         _lib.check(self._lib.fos_get_direct_mode(self._h, C.byref(v)))
-        return ("off", "dense", "block", "cg")[v.value]
+        return ("off", "dense", "block", "cg", "reduced")[v.value]
+
+    def direct_stats(self):
+        """the last set-up of direct = true (fos_get_direct_stats): form, order of the stored inverse, set-up seconds, Newton-Schulz steps"""
+        out = np.zeros(4)
+        _lib.check(self._lib.fos_get_direct_stats(self._h, _lib.dptr(out)))
+        return {"form": ("off", "dense", "block", "cg", "reduced")[int(out[0])], "k": int(out[1]), "setup_s": float(out[2]), "ns_steps": int(out[3])}
 
     def set_tuning(self, spmv_workgroups=0, cg_chunk=0, fuse_p=-1):
         """fuse_p: -1 keeps the library's choice, 0 / 1 force the three- / two-launch CG iteration."""
@@ -679,7 +690,7 @@ class FOSMathProgModel:
         if "cg_variant" in self.options:                           # device-side key (the reference ignores unknown option keys):
             self.data.set_cg_variant(self.options["cg_variant"])   # which CG recurrence the affine projection runs (foship.h FOS_CG_*)
         if self.alg.direct:                                        # HSDE(model, direct=alg.direct)   HSDE.jl:12-15
-            self.data.enable_direct(A)
+            self.data.enable_direct(A, form=self.options.get("direct_form", "auto"))     # device-side key, like cg_variant
         self.init_duration = time.perf_counter_ns() - t1
         return self
 
@@ -724,7 +735,7 @@ class FOSMathProgModel:
         status = HSDEStatus(self, checki, eps, verbose, debug, out=self.out)
         # HSDE.jl:27 -- the table drops its cg column when S1 runs no CG; beyond the sizes the exact forms cover, direct = true is the same
         # projection by CG at its tolerance floor (fos_enable_direct): the column stays, the iterations are real
-        status.direct = bool(self.alg.direct) and self.data.direct_mode() in ("dense", "block")
+        status.direct = bool(self.alg.direct) and self.data.direct_mode() in ("dense", "block", "reduced")
         self.status_obj = status
         t1 = time.time()
         status.printstatusheader()

@@ -109,9 +109,9 @@ for T in (:GAP, :GAPA, :FISTA, :Dykstra, :(FirstOrderSolvers.GAPP))
             # AffinePlusLinear (5 N-vectors of CG state) and DualConeProduct, which the device path never touches.
             # m, n as DualConeProduct's constructor takes them [cones.jl:121]
             sm, sn = model.K1.ranges[end][end], model.K2.ranges[end][end]
-            dmode = Ref{Int32}(0)          # fos_get_direct_mode, read below: 1 dense inverse, 2 block form (no CG: the table drops its cg column), 3 CG at its floor
+            dmode = Ref{Int32}(0)          # fos_get_direct_mode, read below: 1 dense inverse, 2 block form, 4 reduced form (no CG: the table drops its cg column), 3 CG at its floor
             status_generator = (mo, checki, eps, verbose, debug) ->
-                HSDEStatus(sm, sn, 0, mo, :Continue, checki, eps, verbose, false, alg.direct && dmode[] in (1, 2), time_ns(), model.init_duration, debug)
+                HSDEStatus(sm, sn, 0, mo, :Continue, checki, eps, verbose, false, alg.direct && dmode[] in (1, 2, 4), time_ns(), model.init_duration, debug)
             data = HipData(model, get(model.options, :device, 0))
             set_alg!(data, alg)
             if haskey(model.options, :cg_variant)      # device-side key: which CG recurrence the affine projection runs (FOS_CG_* of foship.h)
@@ -123,8 +123,10 @@ for T in (:GAP, :GAPA, :FISTA, :Dykstra, :(FirstOrderSolvers.GAPP))
             end
             if alg.direct            # HSDE.jl:12-15: S1 = IndAffine([Q -I], 0) -> exact projection, (I + Q Q')^-1 formed once on the device
                 A = model.A
-                GC.@preserve A check(ccall((:fos_enable_direct, libfoship), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}),
-                                           data.handle, A.colptr, A.rowval, A.nzval))
+                # the option direct_form = :reduced asks for the reduced form (FOS_DIRECT_FORM_REDUCED = 4: the inverse of I + A'A or I + A A' only, min(m, n) <= 46 000)
+                form = get(model.options, :direct_form, :auto) == :reduced ? Int32(4) : Int32(0)
+                GC.@preserve A check(ccall((:fos_enable_direct2, libfoship), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Int32),
+                                           data.handle, A.colptr, A.rowval, A.nzval, form))
                 check(ccall((:fos_get_direct_mode, libfoship), Cint, (Ptr{Cvoid}, Ref{Int32}), data.handle, dmode))
             end
             return data, status_generator

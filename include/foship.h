@@ -203,10 +203,28 @@ int fos_reset_affine(fos_handle h);
  * every rank, after the transport is enabled); it takes the block form when every rank's columns group, and fails with FOS_EUNSUPPORTED on every rank otherwise
  * (no dense or CG-floor form there).  Row-sharded handles: FOS_EUNSUPPORTED.
  * fos_get_direct_mode: 0 = off, 1 = dense inverse, 2 = block form, 3 = CG at its tolerance floor (the host keeps the table's cg column then).
- * FOS_DIRECT_MODE=block|dense|cg (environment) forces a form. */
+ * FOS_DIRECT_MODE=block|dense|cg (environment) forces a form; FOS_DIRECT_MODE=reduced selects the reduced form below (mode 4). */
 int fos_enable_direct(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval);
 int fos_disable_direct(fos_handle h);
 int fos_get_direct_mode(fos_handle h, int32_t* mode);
+
+/* direct = true, REDUCED form (HSDE.jl:12-15; opt-in): I + Q Q' = [D + h h', g; g', 1 + h'h] with D = diag(I + A'A, I + A A'), h = [c; b], g = [-A'b; A c], so the
+ * exact projection needs only K^-1, K = I + A'A (n <= m) or I + A A' (m < n), of order k = min(m, n): the other block of D^-1 is I - B K^-1 B'.  K is formed
+ * densely on the device from the CSC of A, inverted by the dense form's Newton-Schulz iteration and kept as the tiles of its LOWER TRIANGLE, stored once
+ * (4 k^2 bytes; four square k x k buffers more during set-up).  A projection reads that triangle ONCE, with two right-hand sides, between Q sweeps; one step
+ * of iterative refinement on the matrix-free I - Q Q follows by default (FOS_DIRECT_REDUCED_REFINE=0..4 steps).  k <= 46000 (FOS_DIRECT_REDUCED_MAX), any l;
+ * sharded handles: FOS_EUNSUPPORTED.  No CG runs, cgiter stays 0, fos_get_direct_mode reports 4.  Bit-identical from run to run.
+ * fos_enable_direct2: form = FOS_DIRECT_FORM_AUTO is fos_enable_direct exactly; FOS_DIRECT_FORM_REDUCED asks for the reduced form (so does FOS_DIRECT_MODE=reduced
+ * through either entry).  A handle keeps one form's inverse at a time: enabling another form frees it. */
+#define FOS_DIRECT_FORM_AUTO 0
+#define FOS_DIRECT_FORM_REDUCED 4
+int fos_enable_direct2(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval, int32_t form);
+/* direct = true (HSDE.jl:12-15), what the last set-up did: out4 = form (as fos_get_direct_mode), order of the stored inverse (dense: l, reduced: min(m, n), else 0),
+ * wall seconds of the set-up, its Newton-Schulz steps */
+int fos_get_direct_stats(fos_handle h, double* out4);
+/* direct = true, reduced form (HSDE.jl:12-15), test-only and host-only (no GPU needed): the tile packing of a symmetric k x k matrix X (column-major) and the
+ * tile product y = X [p q] in the kernels' summation order; pq, y: k interleaved pairs; count (k x k, may be NULL): in how many tile slots each entry is stored */
+int fos_host_reduced_symm(int64_t k, const double* X, const double* pq, double* y, int32_t* count);
 
 /* getinitialvalue / option initx (solverwrapper.jl:10, HSDE.jl:40-47): z = 0, tau = kappa = 1 when z == NULL */
 int fos_set_iterate(fos_handle h, const double* z);
