@@ -75,6 +75,10 @@ PROTOTYPES = {
     "fos_get_direct_mode": (C.c_int, [_h, _i32p]),
     "fos_enable_direct2": (C.c_int, [_h, _i64p, _i64p, _dp, C.c_int32]),
     "fos_get_direct_stats": (C.c_int, [_h, _dp]),
+    "fos_enable_direct3": (C.c_int, [_h, _i64p, _i64p, _dp, C.c_int32, C.c_int32]),
+    "fos_get_direct_stats2": (C.c_int, [_h, _dp]),
+    "fos_dense_spd_inverse": (C.c_int, [C.c_int32, C.c_int64, _dp, _dp, C.c_int32, _dp]),
+    "fos_host_chol_inverse": (C.c_int, [C.c_int64, _dp, _dp, _i64p]),
     "fos_host_reduced_symm": (C.c_int, [C.c_int64, _dp, _dp, _dp, _i32p]),
     "fos_set_iterate": (C.c_int, [_h, _dp]),
     "fos_get_iterate": (C.c_int, [_h, _dp]),

@@ -534,6 +534,9 @@ void launch_dense_gemm(const LaunchCtx& c, int L, double alpha, const double* A,
 void launch_dense_resid(const LaunchCtx& c, int64_t L, const double* Y, double* partials, int nblocks);
 void launch_dense_scale_identity(const LaunchCtx& c, int64_t L, double* X, double s);
 void launch_dense_symv(const LaunchCtx& c, int64_t ld, const double* G, const double* t, double* w);
+// the inverse of a dense symmetric positive definite matrix through a blocked Cholesky factorisation (dense_chol.hip); the same blocking on the host (tests)
+void launch_dense_spd_inverse_chol(const LaunchCtx& c, int64_t L, const double* G, double* X, double* Lw, double* Ww, int32_t* info);
+int64_t host_chol_inverse(int64_t k, const double* K, double* X);
 void launch_direct_rhs(const LaunchCtx& c, const double2* W, const double2* x, double* t);
 void launch_direct_finish(const LaunchCtx& c, const double2* x, const double2* W, double2* out);
 

@@ -190,7 +190,12 @@ struct fos_solver {
     bool direct_cg = false;                    // direct = true on an operator too large for the dense inverse: the same projection by CG at its tolerance floor from the first call on
     double* Ginv = nullptr;                    // (I + Q Q')^-1, symmetric, column-major, leading dimension Gld (l padded to 64)
     int64_t Gld = 0;
-    int direct_iters = 0;                      // Newton-Schulz iterations the set-up took
+    int direct_iters = 0;                      // Newton-Schulz iterations the set-up took (Cholesky factor: its polish steps, 0..2)
+    int direct_factor_req = 0;                 // FOS_DIRECT_FACTOR_*: how the stored inverse (dense or reduced form) was asked to be built
+    int direct_factor = 0;                     // ... and how it was built (NEWTON after a fallback)
+    double direct_invert_s = 0.0;              // seconds of the inversion stage alone (matrix formed -> inverse accepted)
+    double direct_probe = 0.0;                 // last probe residual of the Cholesky path (0 on the Newton path)
+    bool direct_fell_back = false;             // the Cholesky path gave up and Newton-Schulz ran
     double* dvec[2] = {nullptr, nullptr};      // two plain l-vectors
     // direct = true on a BLOCK-SEPARABLE operator: I + A'A is block diagonal with blocks of order <= BLKDIR_MAX (an SDP with few variables per
     // block: C4), so the exact projection costs three KKT sweeps -- no CG, no dense l x l inverse (prox_affine_direct_block)
@@ -2628,12 +2633,155 @@ int fos_set_alg(fos_handle h, int alg, double alpha, double alpha1, double alpha
     return FOS_OK;
 }
 
+// ---- the inverse of the dense symmetric positive definite matrix of a direct form (I + Q Q' or K), shared by the dense form, the reduced form and the test entry.
+// G: L x L column-major (L % 64 == 0, padding = identity), of order c.l; B0, B1, B2: L x L work buffers; dv0, dv1: two L-vectors; partials: 256 doubles.
+// *Xout: the buffer (B1 or B2) that holds the accepted inverse.
+struct DenseInv {
+    int used = FOS_DIRECT_FACTOR_NEWTON;       // the factor that produced *Xout
+    int steps = 0;                             // Newton-Schulz steps (Newton), polish steps (Cholesky)
+    double seconds = 0.0, probe = 0.0;
+    bool fell_back = false;
+    int64_t bad_col = -1;                      // first column whose Cholesky pivot was not a positive finite number
+};
+#define INV_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error("%s set-up: %s -> %s", what, #expr, hipGetErrorString(_e)); return FOS_EHIP; } } while (0)
+// the start vector of the power iteration (which = 0) and three more of its kind for the probe
+static void direct_test_vector(int64_t k, int which, std::vector<double>& v) {
+    for (int64_t i = 0; i < k; ++i) v[i] = 1.0 + 0.37 * std::sin((1.7 + 0.6 * which) * (double)i + (double)which);
+}
+// Newton-Schulz:  X_0 = I / (1.25 lambda~),  X_{k+1} = 2 X_k - X_k (G X_k),  lambda~ a power-iteration estimate of lambda_max(G); accepted when max |G X - I| <= 1e-12
+static int dense_inverse_newton(const LaunchCtx& c, int64_t L, const double* G, double* B0, double* B1, double* B2, double* dv0, double* dv1, double* partials,
+                                const char* what, const char* gname, double** Xout, int* steps) {
+    const int64_t l = c.l;
+    // ---- power iteration for lambda_max(G) (Rayleigh quotients from below; host-side norms of an l-vector)
+    std::vector<double> v((size_t)L, 0.0), w((size_t)L, 0.0);
+    direct_test_vector(l, 0, v);
+    double lam = 1.0;
+    for (int it = 0; it < 20; ++it) {
+        double nv = 0.0;
+        for (int64_t i = 0; i < l; ++i) nv += v[i] * v[i];
+        nv = std::sqrt(nv);
+        for (int64_t i = 0; i < l; ++i) v[i] /= nv;
+        INV_HIP(hipMemcpyAsync(dv0, v.data(), sizeof(double) * l, hipMemcpyHostToDevice, c.stream));
+        launch_dense_symv(c, L, G, dv0, dv1);
+        INV_HIP(hipMemcpyAsync(w.data(), dv1, sizeof(double) * l, hipMemcpyDeviceToHost, c.stream));
+        INV_HIP(hipStreamSynchronize(c.stream));
+        double nw = 0.0;
+        for (int64_t i = 0; i < l; ++i) nw += w[i] * w[i];
+        nw = std::sqrt(nw);
+        if (!(nw == nw) || nw > 1e300) { set_error("direct=true: the operator has non-finite entries"); return FOS_EINVAL; }
+        lam = std::max(lam, nw);
+        v.swap(w);
+    }
+    // ---- Newton-Schulz
+    INV_HIP(hipMemsetAsync(B1, 0, sizeof(double) * (size_t)L * (size_t)L, c.stream));
+    launch_dense_scale_identity(c, L, B1, 1.0 / (1.25 * lam));              // X_0
+    double *X = B1, *Xn = B2;
+    const int planned = (int)std::ceil(std::log2(std::max(1.0, lam))) + 7;
+    double resid = 1.0;
+    int it = 0;
+    std::vector<double> part(256);
+    for (; it < planned + 6; ++it) {
+        launch_dense_gemm(c, (int)L, 1.0, G, X, 0.0, nullptr, B0);          // Y = G X
+        if (it >= planned) {                                                // converged?  max |Y - I|
+            launch_dense_resid(c, L, B0, partials, 256);
+            INV_HIP(hipMemcpyAsync(part.data(), partials, sizeof(double) * 256, hipMemcpyDeviceToHost, c.stream));
+            INV_HIP(hipStreamSynchronize(c.stream));
+            resid = 0.0;
+            for (double r : part) resid = (r > resid || r != r) ? r : resid;
+            if (resid <= 1e-12) break;
+        }
+        launch_dense_gemm(c, (int)L, -1.0, X, B0, 2.0, X, Xn);              // X <- 2 X - X Y
+        std::swap(X, Xn);
+    }
+    if (!(resid <= 1e-12)) { set_error("%s: the inverse of %s did not converge (max |G X - I| = %.3e after %d steps, lambda_max ~ %.3e)", what, gname, resid, it, lam); return FOS_EINVAL; }
+    *Xout = X; *steps = it;
+    return FOS_OK;
+}
+// r = max_j |G (X v_j) - v_j|_inf / |v_j|_inf over four fixed vectors: the acceptance test of the Cholesky path (two matrix-vector products each, no l^3 product)
+static int dense_inverse_probe(const LaunchCtx& c, int64_t L, const double* G, const double* X, double* dv0, double* dv1, const char* what, double* r) {
+    const int64_t l = c.l;
+    std::vector<double> v((size_t)l), w((size_t)l);
+    double worst = 0.0;
+    for (int j = 0; j < 4; ++j) {
+        direct_test_vector(l, j, v);
+        INV_HIP(hipMemcpyAsync(dv0, v.data(), sizeof(double) * l, hipMemcpyHostToDevice, c.stream));
+        launch_dense_symv(c, L, X, dv0, dv1);
+        launch_dense_symv(c, L, G, dv1, dv0);
+        INV_HIP(hipMemcpyAsync(w.data(), dv0, sizeof(double) * l, hipMemcpyDeviceToHost, c.stream));
+        INV_HIP(hipStreamSynchronize(c.stream));
+        double d = 0.0, nv = 0.0;
+        for (int64_t i = 0; i < l; ++i) { const double e = std::fabs(w[i] - v[i]); d = (e > d || e != e) ? e : d; nv = std::max(nv, std::fabs(v[i])); }
+        d /= nv;
+        worst = (d > worst || d != d) ? d : worst;
+    }
+    *r = worst;
+    return FOS_OK;
+}
+// factor = FOS_DIRECT_FACTOR_CHOLESKY: blocked Cholesky (dense_chol.hip), probe, at most two Newton-Schulz polish steps, then -- if the probe stays above 1e-12, or
+// (pivot_fallback) a pivot failed on finite entries -- the Newton-Schulz set-up as if it had been asked for.  Without pivot_fallback a bad pivot is FOS_EINVAL.
+static int dense_spd_inverse(const LaunchCtx& c, int64_t L, const double* G, double* B0, double* B1, double* B2, double* dv0, double* dv1, double* partials,
+                             const char* what, const char* gname, int factor, bool pivot_fallback, double** Xout, DenseInv* st) {
+    *st = DenseInv{};
+    INV_HIP(hipStreamSynchronize(c.stream));                               // G is formed: the clock of the inversion stage starts here
+    const auto t0 = std::chrono::steady_clock::now();
+    auto stamp = [&]() { st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
+    if (factor == FOS_DIRECT_FACTOR_CHOLESKY) {
+        const int64_t l = c.l;
+        {   // the non-finite check of the power iteration: one product with its start vector
+            std::vector<double> v((size_t)l), w((size_t)l);
+            direct_test_vector(l, 0, v);
+            INV_HIP(hipMemcpyAsync(dv0, v.data(), sizeof(double) * l, hipMemcpyHostToDevice, c.stream));
+            launch_dense_symv(c, L, G, dv0, dv1);
+            INV_HIP(hipMemcpyAsync(w.data(), dv1, sizeof(double) * l, hipMemcpyDeviceToHost, c.stream));
+            INV_HIP(hipStreamSynchronize(c.stream));
+            double nw = 0.0;
+            for (int64_t i = 0; i < l; ++i) nw += w[i] * w[i];
+            if (!(nw == nw) || std::sqrt(nw) > 1e300) { set_error("direct=true: the operator has non-finite entries"); return FOS_EINVAL; }
+        }
+        int32_t* dinfo = nullptr;
+        INV_HIP(hipMalloc((void**)&dinfo, sizeof(int32_t)));
+        int32_t info = 0;
+        launch_dense_spd_inverse_chol(c, L, G, B2, B0, B1, dinfo);          // B0: the factor, B1: its inverse, B2: G^-1
+        hipError_t e = hipMemcpyAsync(&info, dinfo, sizeof(int32_t), hipMemcpyDeviceToHost, c.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+        (void)hipFree(dinfo);
+        if (e != hipSuccess) { set_error("%s set-up: Cholesky factorisation -> %s", what, hipGetErrorString(e)); return FOS_EHIP; }
+        FOS_TRY(check_launch("direct=true set-up (Cholesky factorisation)"));
+        bool ok = info == 0;
+        if (!ok) {
+            st->bad_col = (int64_t)info - 1;
+            if (!pivot_fallback) {
+                set_error("%s: Cholesky factorisation of %s: the pivot of column %lld is not a positive finite number (the matrix is not positive definite)", what, gname, (long long)st->bad_col);
+                return FOS_EINVAL;
+            }
+        } else {
+            double *X = B2, *Xn = B1;
+            FOS_TRY(dense_inverse_probe(c, L, G, X, dv0, dv1, what, &st->probe));
+            while (!(st->probe <= 1e-12) && st->steps < 2) {
+                launch_dense_gemm(c, (int)L, 1.0, G, X, 0.0, nullptr, B0);      // Y = G X
+                launch_dense_gemm(c, (int)L, -1.0, X, B0, 2.0, X, Xn);          // X <- 2 X - X Y
+                std::swap(X, Xn);
+                st->steps += 1;
+                FOS_TRY(dense_inverse_probe(c, L, G, X, dv0, dv1, what, &st->probe));
+            }
+            ok = st->probe <= 1e-12;
+            if (ok) { st->used = FOS_DIRECT_FACTOR_CHOLESKY; *Xout = X; stamp(); return FOS_OK; }
+        }
+        st->fell_back = true;
+    }
+    st->used = FOS_DIRECT_FACTOR_NEWTON;
+    FOS_TRY(dense_inverse_newton(c, L, G, B0, B1, B2, dv0, dv1, partials, what, gname, Xout, &st->steps));
+    stamp();
+    return FOS_OK;
+}
+#undef INV_HIP
+
 // direct = true: build (I + Q Q')^-1 once.  A is handed over again (the handle keeps only its device format).
 // G = I + Q Q' = I - Q Q is symmetric positive definite with lambda_min >= 1; its inverse is formed by the Newton-Schulz iteration
 //     X_0 = I / (1.25 lambda~),   X_{k+1} = 2 X_k - X_k (G X_k),        lambda~ = a power-iteration estimate of lambda_max(G),
 // whose residual I - G X_k squares every step: ceil(log2 lambda~) + 7 steps reach rounding level (verified at the end: the
 // entries of G X - I).  Only matrix products are needed: the hand-written fp64 MFMA GEMM of vecops.hip.
-static int enable_direct_auto(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval) {
+static int enable_direct_auto(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval, int factor) {
     if (h->row_sharded) { set_error("direct=true is not available on row-sharded handles"); return FOS_EUNSUPPORTED; }
     if (h->Ginv || (h->blk_ginv && h->blk_ready)) { h->direct = true; h->direct_blk = h->blk_ginv != nullptr && h->blk_ready; return FOS_OK; }
     const int64_t l = h->l, nnz = colptr[h->n] - 1;
@@ -2686,55 +2834,18 @@ static int enable_direct_auto(fos_handle h, const int64_t* colptr, const int64_t
     launch_dense_q_fill(c, dcp, drv, dnz, B0, L);                           // B0 = Q (zero padded to L x L)
     launch_dense_scale_identity(c, L, B1, 1.0);                             // B1 = I
     launch_dense_gemm(c, (int)L, -1.0, B0, B0, 1.0, B1, G);                 // G = I - Q Q  (padding rows/columns: identity)
-    // ---- power iteration for lambda_max(G) (Rayleigh quotients from below; host-side norms of an l-vector)
-    std::vector<double> v((size_t)L, 0.0), w((size_t)L, 0.0);
-    for (int64_t i = 0; i < l; ++i) v[i] = 1.0 + 0.37 * std::sin(1.7 * (double)i);
-    double lam = 1.0;
-    for (int it = 0; it < 20; ++it) {
-        double nv = 0.0;
-        for (int64_t i = 0; i < l; ++i) nv += v[i] * v[i];
-        nv = std::sqrt(nv);
-        for (int64_t i = 0; i < l; ++i) v[i] /= nv;
-        DIRECT_HIP(hipMemcpyAsync(h->dvec[0], v.data(), sizeof(double) * l, hipMemcpyHostToDevice, h->stream));
-        launch_dense_symv(c, L, G, h->dvec[0], h->dvec[1]);
-        DIRECT_HIP(hipMemcpyAsync(w.data(), h->dvec[1], sizeof(double) * l, hipMemcpyDeviceToHost, h->stream));
-        DIRECT_HIP(hipStreamSynchronize(h->stream));
-        double nw = 0.0;
-        for (int64_t i = 0; i < l; ++i) nw += w[i] * w[i];
-        nw = std::sqrt(nw);
-        if (!(nw == nw) || nw > 1e300) { set_error("direct=true: the operator has non-finite entries"); return fail(FOS_EINVAL); }
-        lam = std::max(lam, nw);
-        v.swap(w);
-    }
-    // ---- Newton-Schulz
-    const double x0 = 1.0 / (1.25 * lam);
-    launch_dense_scale_identity(c, L, B1, x0);                              // X_0 = x0 I  (B1 was I: only its diagonal is non-zero)
-    double *X = B1, *Xn = B2;
-    const int planned = (int)std::ceil(std::log2(std::max(1.0, lam))) + 7;
-    double resid = 1.0;
-    int it = 0;
-    std::vector<double> part(256);
-    for (; it < planned + 6; ++it) {
-        launch_dense_gemm(c, (int)L, 1.0, G, X, 0.0, nullptr, B0);          // Y = G X
-        if (it >= planned) {                                                // converged?  max |Y - I|
-            launch_dense_resid(c, L, B0, h->partials, 256);
-            DIRECT_HIP(hipMemcpyAsync(part.data(), h->partials, sizeof(double) * 256, hipMemcpyDeviceToHost, h->stream));
-            DIRECT_HIP(hipStreamSynchronize(h->stream));
-            resid = 0.0;
-            for (double r : part) resid = (r > resid || r != r) ? r : resid;
-            if (resid <= 1e-12) break;
-        }
-        launch_dense_gemm(c, (int)L, -1.0, X, B0, 2.0, X, Xn);              // X <- 2 X - X Y
-        std::swap(X, Xn);
-    }
-    if (!(resid <= 1e-12)) { set_error("direct=true: the inverse of I + Q Q' did not converge (max |G X - I| = %.3e after %d steps, lambda_max ~ %.3e)", resid, it, lam); return fail(FOS_EINVAL); }
+    double* X = nullptr;
+    DenseInv inv;
+    rc = dense_spd_inverse(c, L, G, B0, B1, B2, h->dvec[0], h->dvec[1], h->partials, "direct=true", "I + Q Q'", factor, true, &X, &inv);
+    if (rc != FOS_OK) return fail(rc);
     DIRECT_HIP(hipMemcpyAsync(G, X, sizeof(double) * L2, hipMemcpyDeviceToDevice, h->stream));     // keep the inverse in the handle's buffer
     DIRECT_HIP(hipStreamSynchronize(h->stream));
 #undef DIRECT_HIP
     rc = check_launch("direct=true set-up");
     cleanup();
     if (rc != FOS_OK) return rc;
-    h->Ginv = G; h->Gld = L; h->direct_iters = it;
+    h->Ginv = G; h->Gld = L; h->direct_iters = inv.steps;
+    h->direct_factor_req = factor; h->direct_factor = inv.used; h->direct_invert_s = inv.seconds; h->direct_probe = inv.probe; h->direct_fell_back = inv.fell_back;
     h->direct = true;
     return FOS_OK;
 }
@@ -2749,7 +2860,7 @@ static void reduced_release(fos_solver* h) {
     dev_release(h, &h->red_p); dev_release(h, &h->red_q); dev_release(h, &h->red_g); dev_release(h, &h->red_dots);
     h->red_ready = false; h->direct_red = false;
 }
-static int reduced_setup(fos_solver* h, const int64_t* colptr, const int64_t* rowval, const double* nzval) {
+static int reduced_setup(fos_solver* h, const int64_t* colptr, const int64_t* rowval, const double* nzval, int factor) {
     const int64_t n = h->n, m = h->m, l = h->l, nnz = colptr[n] - 1;
     if (h->row_sharded || h->sharded()) { set_error("direct=true, reduced form: not available on sharded handles"); return FOS_EUNSUPPORTED; }
     if (nnz != h->nnz) { set_error("fos_enable_direct2: A has %lld non-zeros, the handle was created with %lld", (long long)nnz, (long long)h->nnz); return FOS_EINVAL; }
@@ -2834,54 +2945,17 @@ static int reduced_setup(fos_solver* h, const int64_t* colptr, const int64_t* ro
         DIRECT_HIP(hipMemcpyAsync(drv, rv.data(), sizeof(double) * nnz, hipMemcpyHostToDevice, h->stream));
     }
     DIRECT_HIP(hipMemsetAsync(G, 0, sizeof(double) * L2, h->stream));
-    DIRECT_HIP(hipMemsetAsync(B1, 0, sizeof(double) * L2, h->stream));
     for (double* v : {h->red_s, h->red_d, h->red_r, h->red_z, h->red_p, h->red_q, h->red_g}) DIRECT_HIP(hipMemsetAsync(v, 0, sizeof(double) * lpad, h->stream));
     // K = I + B'B: B = A (its columns: A's columns, its rows: A's rows), or B = A' (the two exchanged)
     if (!swap) launch_red_form_k(c, k, L, dcp, dci, dcv, drp, dri, drv, G);
     else launch_red_form_k(c, k, L, drp, dri, drv, dcp, dci, dcv, G);
-    // ---- power iteration for lambda_max(K), as in the dense form
+    // ---- K^-1: Newton-Schulz as in the dense form, or the blocked Cholesky factorisation
     LaunchCtx ck = c;
     ck.l = k;
-    std::vector<double> v((size_t)L, 0.0), w((size_t)L, 0.0);
-    for (int64_t i = 0; i < k; ++i) v[i] = 1.0 + 0.37 * std::sin(1.7 * (double)i);
-    double lam = 1.0;
-    for (int it = 0; it < 20; ++it) {
-        double nv = 0.0;
-        for (int64_t i = 0; i < k; ++i) nv += v[i] * v[i];
-        nv = std::sqrt(nv);
-        for (int64_t i = 0; i < k; ++i) v[i] /= nv;
-        DIRECT_HIP(hipMemcpyAsync(h->dvec[0], v.data(), sizeof(double) * k, hipMemcpyHostToDevice, h->stream));
-        launch_dense_symv(ck, L, G, h->dvec[0], h->dvec[1]);
-        DIRECT_HIP(hipMemcpyAsync(w.data(), h->dvec[1], sizeof(double) * k, hipMemcpyDeviceToHost, h->stream));
-        DIRECT_HIP(hipStreamSynchronize(h->stream));
-        double nw = 0.0;
-        for (int64_t i = 0; i < k; ++i) nw += w[i] * w[i];
-        nw = std::sqrt(nw);
-        if (!(nw == nw) || nw > 1e300) { set_error("direct=true: the operator has non-finite entries"); return fail(FOS_EINVAL); }
-        lam = std::max(lam, nw);
-        v.swap(w);
-    }
-    // ---- Newton-Schulz (same schedule and convergence test as the dense form)
-    launch_dense_scale_identity(c, L, B1, 1.0 / (1.25 * lam));
-    double *X = B1, *Xn = B2;
-    const int planned = (int)std::ceil(std::log2(std::max(1.0, lam))) + 7;
-    double resid = 1.0;
-    int it = 0;
-    std::vector<double> part(256);
-    for (; it < planned + 6; ++it) {
-        launch_dense_gemm(c, (int)L, 1.0, G, X, 0.0, nullptr, B0);          // Y = K X
-        if (it >= planned) {
-            launch_dense_resid(c, L, B0, h->partials, 256);
-            DIRECT_HIP(hipMemcpyAsync(part.data(), h->partials, sizeof(double) * 256, hipMemcpyDeviceToHost, h->stream));
-            DIRECT_HIP(hipStreamSynchronize(h->stream));
-            resid = 0.0;
-            for (double r : part) resid = (r > resid || r != r) ? r : resid;
-            if (resid <= 1e-12) break;
-        }
-        launch_dense_gemm(c, (int)L, -1.0, X, B0, 2.0, X, Xn);              // X <- 2 X - X Y
-        std::swap(X, Xn);
-    }
-    if (!(resid <= 1e-12)) { set_error("direct=true, reduced form: the inverse of K did not converge (max |K X - I| = %.3e after %d steps, lambda_max ~ %.3e)", resid, it, lam); return fail(FOS_EINVAL); }
+    double* X = nullptr;
+    DenseInv inv;
+    rc = dense_spd_inverse(ck, L, G, B0, B1, B2, h->dvec[0], h->dvec[1], h->partials, "direct=true, reduced form", "K", factor, true, &X, &inv);
+    if (rc != FOS_OK) return fail(rc);
     launch_red_pack_tiles(c, h->red, L, X);
     DIRECT_HIP(hipStreamSynchronize(h->stream));
     rc = check_launch("direct=true set-up (reduced form)");
@@ -2912,29 +2986,37 @@ static int reduced_setup(fos_solver* h, const int64_t* colptr, const int64_t* ro
     const long double det = a00 * a11 - a01 * a10;
     if (!(fabsl(det) > 0.0L) || !std::isfinite((double)det)) { set_error("direct=true, reduced form: the 2 x 2 border system is singular"); return fail(FOS_EINVAL); }
     h->red_minv[0] = (double)(a11 / det); h->red_minv[1] = (double)(-a01 / det); h->red_minv[2] = (double)(-a10 / det); h->red_minv[3] = (double)(a00 / det);
-    h->direct_iters = it;
+    h->direct_iters = inv.steps;
+    h->direct_factor_req = factor; h->direct_factor = inv.used; h->direct_invert_s = inv.seconds; h->direct_probe = inv.probe; h->direct_fell_back = inv.fell_back;
     h->red_ready = true;
     return FOS_OK;
 }
 
-int fos_enable_direct2(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval, int32_t form) {
+int fos_enable_direct3(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval, int32_t form, int32_t factor) {
     if (!h || !colptr || (!rowval && colptr[h->n] > 1)) { set_error("NULL argument"); return FOS_EINVAL; }
-    if (form != FOS_DIRECT_FORM_AUTO && form != FOS_DIRECT_FORM_REDUCED) { set_error("fos_enable_direct2: form must be FOS_DIRECT_FORM_AUTO or FOS_DIRECT_FORM_REDUCED"); return FOS_EINVAL; }
+    if (form != FOS_DIRECT_FORM_AUTO && form != FOS_DIRECT_FORM_REDUCED) { set_error("fos_enable_direct3: form must be FOS_DIRECT_FORM_AUTO or FOS_DIRECT_FORM_REDUCED"); return FOS_EINVAL; }
+    if (factor != FOS_DIRECT_FACTOR_NEWTON && factor != FOS_DIRECT_FACTOR_CHOLESKY) { set_error("fos_enable_direct3: factor must be FOS_DIRECT_FACTOR_NEWTON or FOS_DIRECT_FACTOR_CHOLESKY"); return FOS_EINVAL; }
     const char* mode_env = getenv("FOS_DIRECT_MODE");
     if (form == FOS_DIRECT_FORM_AUTO && mode_env && std::string(mode_env) == "reduced") form = FOS_DIRECT_FORM_REDUCED;
+    if (const char* fenv = getenv("FOS_DIRECT_FACTOR")) {                  // only for callers that did not choose: the old entries pass NEWTON
+        const std::string f = fenv;
+        if (f != "newton" && f != "cholesky") { set_error("FOS_DIRECT_FACTOR must be newton or cholesky, not '%s'", fenv); return FOS_EINVAL; }
+        if (factor == FOS_DIRECT_FACTOR_NEWTON && f == "cholesky") factor = FOS_DIRECT_FACTOR_CHOLESKY;
+    }
     const auto t0 = std::chrono::steady_clock::now();
     int rc;
     if (form == FOS_DIRECT_FORM_REDUCED) {
-        if (!h->red_ready) {
-            FOS_TRY(reduced_setup(h, colptr, rowval, nzval));
+        if (!h->red_ready || h->direct_factor_req != factor) {             // another factor: the set-up runs again
+            FOS_TRY(reduced_setup(h, colptr, rowval, nzval, factor));
             h->direct_setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         }
         if (h->Ginv) { dev_release(h, &h->Ginv); h->Gld = 0; }            // one form's inverse at a time
         h->direct = true; h->direct_red = true; h->direct_blk = false; h->direct_cg = false;
         return FOS_OK;
     }
+    if (h->Ginv && h->direct_factor_req != factor) { dev_release(h, &h->Ginv); h->Gld = 0; }
     const bool had = h->Ginv || (h->blk_ginv && h->blk_ready);
-    rc = enable_direct_auto(h, colptr, rowval, nzval);
+    rc = enable_direct_auto(h, colptr, rowval, nzval, factor);
     if (rc == FOS_OK) {
         if (h->red_ready) reduced_release(h);
         h->direct_red = false;
@@ -2942,8 +3024,11 @@ int fos_enable_direct2(fos_handle h, const int64_t* colptr, const int64_t* rowva
     }
     return rc;
 }
+int fos_enable_direct2(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval, int32_t form) {
+    return fos_enable_direct3(h, colptr, rowval, nzval, form, FOS_DIRECT_FACTOR_NEWTON);
+}
 int fos_enable_direct(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval) {
-    return fos_enable_direct2(h, colptr, rowval, nzval, FOS_DIRECT_FORM_AUTO);
+    return fos_enable_direct3(h, colptr, rowval, nzval, FOS_DIRECT_FORM_AUTO, FOS_DIRECT_FACTOR_NEWTON);
 }
 
 // form (as fos_get_direct_mode), order of the stored inverse (dense: l, reduced: min(m, n), else 0), wall seconds of the last set-up, its Newton-Schulz steps
@@ -2955,6 +3040,65 @@ int fos_get_direct_stats(fos_handle h, double* out4) {
     out4[1] = mode == 4 ? (double)h->red.k : (mode == 1 ? (double)h->l : 0.0);
     out4[2] = h->direct_setup_s;
     out4[3] = (mode == 1 || mode == 4) ? (double)h->direct_iters : 0.0;
+    return FOS_OK;
+}
+
+// the four values of fos_get_direct_stats, then: the factor that built the stored inverse (FOS_DIRECT_FACTOR_*), the seconds of the inversion stage alone, the
+// last probe residual of the Cholesky path, 1.0 if that path fell back to Newton-Schulz
+int fos_get_direct_stats2(fos_handle h, double* out8) {
+    if (!h || !out8) { set_error("NULL argument"); return FOS_EINVAL; }
+    FOS_TRY(fos_get_direct_stats(h, out8));
+    const bool stored = out8[0] == 1.0 || out8[0] == 4.0;
+    out8[4] = stored ? (double)h->direct_factor : 0.0;
+    out8[5] = stored ? h->direct_invert_s : 0.0;
+    out8[6] = stored ? h->direct_probe : 0.0;
+    out8[7] = stored && h->direct_fell_back ? 1.0 : 0.0;
+    return FOS_OK;
+}
+
+// test-only: X = K^-1 for a symmetric positive definite k x k host matrix (column-major) through the set-up's own path (padding, factor, probe, polish, fallback
+// for a probe that stays above the bar; a bad pivot is an error here).  info4: bad-pivot column or -1, Newton-Schulz / polish steps, probe residual, fallback flag
+int fos_dense_spd_inverse(int32_t device, int64_t k, const double* K, double* X, int32_t factor, double* info4) {
+    if (k < 1 || k > 46000 || !K || !X || !info4) { set_error("fos_dense_spd_inverse: bad argument"); return FOS_EINVAL; }
+    if (factor != FOS_DIRECT_FACTOR_NEWTON && factor != FOS_DIRECT_FACTOR_CHOLESKY) { set_error("fos_dense_spd_inverse: factor must be FOS_DIRECT_FACTOR_NEWTON or FOS_DIRECT_FACTOR_CHOLESKY"); return FOS_EINVAL; }
+    info4[0] = -1.0; info4[1] = info4[2] = info4[3] = 0.0;
+    FOS_HIP(hipSetDevice(device));
+    const int64_t L = (k + 63) / 64 * 64;
+    const size_t L2 = (size_t)L * (size_t)L;
+    std::vector<double> pad(L2, 0.0);
+    for (int64_t i = 0; i < L; ++i) pad[(size_t)i + (size_t)i * L] = 1.0;
+    for (int64_t j = 0; j < k; ++j) std::copy(K + j * k, K + j * k + k, pad.begin() + (size_t)j * L);
+    double* buf[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};       // G, B0, B1, B2, two vectors, partials
+    hipStream_t stream = nullptr;
+    auto cleanup = [&]() { for (double* b : buf) (void)hipFree(b); if (stream) (void)hipStreamDestroy(stream); };
+    hipError_t e = hipStreamCreate(&stream);
+    for (int q = 0; q < 7 && e == hipSuccess; ++q) e = hipMalloc((void**)&buf[q], sizeof(double) * (q < 4 ? L2 : (q < 6 ? (size_t)L : 256)));
+    if (e == hipSuccess) e = hipMemcpyAsync(buf[0], pad.data(), sizeof(double) * L2, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) { cleanup(); set_error("fos_dense_spd_inverse: %s", hipGetErrorString(e)); return FOS_EHIP; }
+    LaunchCtx c{};
+    c.stream = stream;
+    c.l = k;
+    double* Xd = nullptr;
+    DenseInv inv;
+    int rc = dense_spd_inverse(c, L, buf[0], buf[1], buf[2], buf[3], buf[4], buf[5], buf[6], "fos_dense_spd_inverse", "K", factor, false, &Xd, &inv);
+    info4[0] = (double)inv.bad_col; info4[1] = (double)inv.steps; info4[2] = inv.probe; info4[3] = inv.fell_back ? 1.0 : 0.0;
+    if (rc == FOS_OK) {
+        e = hipMemcpyAsync(pad.data(), Xd, sizeof(double) * L2, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) { set_error("fos_dense_spd_inverse: %s", hipGetErrorString(e)); rc = FOS_EHIP; }
+        else for (int64_t j = 0; j < k; ++j) std::copy(pad.begin() + (size_t)j * L, pad.begin() + (size_t)j * L + k, X + j * k);
+    } else {
+        (void)hipStreamSynchronize(stream);
+    }
+    cleanup();
+    return rc;
+}
+
+// test-only, host: the blocked Cholesky inverse of dense_chol.hip with the same blocking and block order on the CPU; *bad_pivot: the first bad column or -1
+int fos_host_chol_inverse(int64_t k, const double* K, double* X, int64_t* bad_pivot) {
+    if (k < 1 || !K || !X || !bad_pivot) { set_error("bad argument"); return FOS_EINVAL; }
+    *bad_pivot = host_chol_inverse(k, K, X);
+    if (*bad_pivot >= 0) { set_error("fos_host_chol_inverse: the pivot of column %lld is not a positive finite number (the matrix is not positive definite)", (long long)*bad_pivot); return FOS_EINVAL; }
     return FOS_OK;
 }
 

@@ -188,6 +188,16 @@ def _normalize_cones(cones, total, what):
     return (np.asarray(types, dtype=np.int32), np.asarray(starts, dtype=np.int64), np.asarray(lens, dtype=np.int64))
 
 
+DIRECT_FACTOR_NAMES = ("newton", "cholesky")                     # FOS_DIRECT_FACTOR_*
+
+
+def direct_factor_code(factor):
+    """FOS_DIRECT_FACTOR_* of the name of a factor of direct = true ("newton" | "cholesky"); needs no GPU"""
+    if factor not in DIRECT_FACTOR_NAMES:
+        raise ValueError("direct factor must be one of %s, not %r" % (sorted(DIRECT_FACTOR_NAMES), factor))
+    return DIRECT_FACTOR_NAMES.index(factor)
+
+
 class HipHSDE:
     """Owns one fos_handle: the device-resident S1 (AffinePlusLinear over HSDEMatrixQ), S2 (DualConeProduct),
     iterate and algorithm data.  == what init_algorithm!/get_sets_and_status build (FOSSolverInterface.jl:76-79)."""
@@ -425,18 +435,20 @@ class HipHSDE:
 
     DIRECT_FORMS = {"auto": 0, "reduced": 4}                      # FOS_DIRECT_FORM_*
 
-    def enable_direct(self, A, form="auto"):
-        """direct = true (HSDE.jl:12-15): exact affine projection through a one-time factorisation (fos_enable_direct2).  form="auto": the first of
-        block / dense / cg that applies; form="reduced": the inverse of I + A'A or I + A A' (order min(m, n) <= 46 000) as packed lower-triangle tiles."""
+    def enable_direct(self, A, form="auto", factor="newton"):
+        """direct = true (HSDE.jl:12-15): exact affine projection through a one-time factorisation (fos_enable_direct3).  form="auto": the first of
+        block / dense / cg that applies; form="reduced": the inverse of I + A'A or I + A A' (order min(m, n) <= 46 000) as packed lower-triangle tiles.
+        factor: how the stored inverse of the dense and the reduced form is built -- "newton" (Newton-Schulz) or "cholesky" (blocked Cholesky, opt-in)."""
         if form not in self.DIRECT_FORMS:
             raise ValueError("direct form must be one of %s, not %r" % (sorted(self.DIRECT_FORMS), form))
+        factor_code = direct_factor_code(factor)
         A = sp.csc_matrix(A)
         A.sort_indices()
         colptr = (A.indptr.astype(np.int64) + 1)
         rowval = (A.indices.astype(np.int64) + 1)
         nz = np.ascontiguousarray(A.data, dtype=np.float64)
         i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-        _lib.check(self._lib.fos_enable_direct2(self._h, i64(colptr), i64(rowval), _lib.dptr(nz), self.DIRECT_FORMS[form]))
+        _lib.check(self._lib.fos_enable_direct3(self._h, i64(colptr), i64(rowval), _lib.dptr(nz), self.DIRECT_FORMS[form], factor_code))
 
     def disable_direct(self):
         _lib.check(self._lib.fos_disable_direct(self._h))
@@ -448,10 +460,12 @@ class HipHSDE:
         return ("off", "dense", "block", "cg", "reduced")[v.value]
 
     def direct_stats(self):
-        """the last set-up of direct = true (fos_get_direct_stats): form, order of the stored inverse, set-up seconds, Newton-Schulz steps"""
-        out = np.zeros(4)
-        _lib.check(self._lib.fos_get_direct_stats(self._h, _lib.dptr(out)))
-        return {"form": ("off", "dense", "block", "cg", "reduced")[int(out[0])], "k": int(out[1]), "setup_s": float(out[2]), "ns_steps": int(out[3])}
+        """the last set-up of direct = true (fos_get_direct_stats2): form, order of the stored inverse, set-up seconds, Newton-Schulz steps (Cholesky factor: its
+        polish steps), the factor that built the inverse, the seconds of the inversion stage alone, the last probe residual, whether Cholesky fell back"""
+        out = np.zeros(8)
+        _lib.check(self._lib.fos_get_direct_stats2(self._h, _lib.dptr(out)))
+        return {"form": ("off", "dense", "block", "cg", "reduced")[int(out[0])], "k": int(out[1]), "setup_s": float(out[2]), "ns_steps": int(out[3]),
+                "factor": DIRECT_FACTOR_NAMES[int(out[4])], "invert_s": float(out[5]), "probe_resid": float(out[6]), "fell_back": int(out[7])}
 
     def set_tuning(self, spmv_workgroups=0, cg_chunk=0, fuse_p=-1):
         """fuse_p: -1 keeps the library's choice, 0 / 1 force the three- / two-launch CG iteration."""
@@ -690,7 +704,8 @@ class FOSMathProgModel:
         if "cg_variant" in self.options:                           # device-side key (the reference ignores unknown option keys):
             self.data.set_cg_variant(self.options["cg_variant"])   # which CG recurrence the affine projection runs (foship.h FOS_CG_*)
         if self.alg.direct:                                        # HSDE(model, direct=alg.direct)   HSDE.jl:12-15
-            self.data.enable_direct(A, form=self.options.get("direct_form", "auto"))     # device-side key, like cg_variant
+            self.data.enable_direct(A, form=self.options.get("direct_form", "auto"),     # device-side keys, like cg_variant
+                                    factor=self.options.get("direct_factor", "newton"))
         self.init_duration = time.perf_counter_ns() - t1
         return self
 

@@ -125,8 +125,16 @@ for T in (:GAP, :GAPA, :FISTA, :Dykstra, :(FirstOrderSolvers.GAPP))
                 A = model.A
                 # the option direct_form = :reduced asks for the reduced form (FOS_DIRECT_FORM_REDUCED = 4: the inverse of I + A'A or I + A A' only, min(m, n) <= 46 000)
                 form = get(model.options, :direct_form, :auto) == :reduced ? Int32(4) : Int32(0)
-                GC.@preserve A check(ccall((:fos_enable_direct2, libfoship), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Int32),
-                                           data.handle, A.colptr, A.rowval, A.nzval, form))
+                # the option direct_factor = :cholesky builds the stored inverse by a blocked Cholesky factorisation (FOS_DIRECT_FACTOR_CHOLESKY = 1) instead of Newton-Schulz (0)
+                dfac = get(model.options, :direct_factor, :newton)
+                dfac in (:newton, :cholesky) || error("direct_factor must be :newton or :cholesky, not $(repr(dfac))")
+                if dfac == :cholesky
+                    GC.@preserve A check(ccall((:fos_enable_direct3, libfoship), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Int32, Int32),
+                                               data.handle, A.colptr, A.rowval, A.nzval, form, Int32(1)))
+                else                 # no factor chosen: the older entry (the environment's FOS_DIRECT_FACTOR still applies there)
+                    GC.@preserve A check(ccall((:fos_enable_direct2, libfoship), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Int32),
+                                               data.handle, A.colptr, A.rowval, A.nzval, form))
+                end
                 check(ccall((:fos_get_direct_mode, libfoship), Cint, (Ptr{Cvoid}, Ref{Int32}), data.handle, dmode))
             end
             return data, status_generator

@@ -222,6 +222,27 @@ int fos_enable_direct2(fos_handle h, const int64_t* colptr, const int64_t* rowva
 /* direct = true (HSDE.jl:12-15), what the last set-up did: out4 = form (as fos_get_direct_mode), order of the stored inverse (dense: l, reduced: min(m, n), else 0),
  * wall seconds of the set-up, its Newton-Schulz steps */
 int fos_get_direct_stats(fos_handle h, double* out4);
+/* direct = true (HSDE.jl:12-15), HOW the stored inverse of the dense and the reduced form is built (opt-in): FOS_DIRECT_FACTOR_NEWTON is the Newton-Schulz iteration
+ * above; FOS_DIRECT_FACTOR_CHOLESKY a blocked Cholesky factorisation and inversion on the fp64 matrix cores (csrc/dense_chol.hip: G = L L' by block columns of 64,
+ * W = L^-1, X = W'W, about k^3 flops instead of ~62 k^3; no atomics, bit-identical from run to run; no more device memory than the Newton path).  The inverse is
+ * accepted when a probe with four fixed vectors, max_j |G (X v_j) - v_j|_inf / |v_j|_inf, is <= 1e-12; otherwise at most two Newton-Schulz steps polish it, and if
+ * it still misses -- or a pivot is not a positive finite number although the entries are finite -- the Newton-Schulz set-up runs instead (reported by
+ * fos_get_direct_stats2).  The block form and the CG form have no factor.  A handle keeps one inverse: asking for the other factor runs the set-up again.
+ * fos_enable_direct3: fos_enable_direct2 with the factor; fos_enable_direct2 is this with FOS_DIRECT_FACTOR_NEWTON.  FOS_DIRECT_FACTOR=cholesky|newton (environment)
+ * picks the factor for callers that pass FOS_DIRECT_FACTOR_NEWTON (the older entries), in the manner of FOS_DIRECT_MODE.
+ * fos_get_direct_stats2: out8 = the four values of fos_get_direct_stats (with the Cholesky factor its 4th value counts the polish steps, 0..2), the factor that built
+ * the inverse, the seconds of the inversion stage alone (matrix formed -> inverse accepted), the last probe residual, 1.0 if the Cholesky path fell back. */
+#define FOS_DIRECT_FACTOR_NEWTON 0
+#define FOS_DIRECT_FACTOR_CHOLESKY 1
+int fos_enable_direct3(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval, int32_t form, int32_t factor);
+int fos_get_direct_stats2(fos_handle h, double* out8);
+/* test-only: X = K^-1 for a symmetric positive definite k x k HOST matrix (column-major; X likewise) on `device` through the set-up's own path (padding to a
+ * multiple of 64, factor, probe, polish).  info4 = bad-pivot column (0-based) or -1, Newton-Schulz / polish steps, probe residual, fallback flag.  A bad pivot
+ * is FOS_EINVAL with the column in fos_last_error() (no fallback here). */
+int fos_dense_spd_inverse(int32_t device, int64_t k, const double* K, double* X, int32_t factor, double* info4);
+/* test-only and host-only (no GPU needed): the blocked Cholesky inverse with the kernels' blocking and block order on the CPU; *bad_pivot = the first column
+ * whose pivot is not a positive finite number (then FOS_EINVAL) or -1 */
+int fos_host_chol_inverse(int64_t k, const double* K, double* X, int64_t* bad_pivot);
 /* direct = true, reduced form (HSDE.jl:12-15), test-only and host-only (no GPU needed): the tile packing of a symmetric k x k matrix X (column-major) and the
  * tile product y = X [p q] in the kernels' summation order; pq, y: k interleaved pairs; count (k x k, may be NULL): in how many tile slots each entry is stored */
 int fos_host_reduced_symm(int64_t k, const double* X, const double* pq, double* y, int32_t* count);
