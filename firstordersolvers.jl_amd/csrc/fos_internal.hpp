@@ -574,7 +574,7 @@ void launch_red_w(const LaunchCtx& c, const double* t, const double* d, const do
                   int add, double* w);
 void launch_red_resid(const LaunchCtx& c, const double* t, const double* w, const double* z, double* r);
 
-// direct = true on a block-separable operator (I + A'A block diagonal with blocks of order <= BLKDIR_MAX): vecops.hip, solver.cpp prox_affine_direct_block
+// direct = true on a block-separable operator (I + A'A block diagonal with blocks of order <= BLKDIR_MAX): vecops.hip, direct.cpp prox_affine_direct_block
 constexpr int BLKDIR_MAX = 64;
 void launch_blkdir_prep(const LaunchCtx& c, const double2* T, const double2* phg, double2* W2, double2* W3, double* partials);
 void launch_blkdir_solve(const LaunchCtx& c, int nblk, const int64_t* goff, const int32_t* ioff, const int32_t* idx, const double* Ginv, const double2* R,

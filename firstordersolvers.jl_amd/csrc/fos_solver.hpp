@@ -1,0 +1,272 @@
+// struct fos_solver (the handle behind fos_handle) and the helpers that solver.cpp and direct.cpp share.  Private: not part of the ABI.
+#pragma once
+
+#include <rccl/rccl.h>
+
+#include <algorithm>
+
+#include "fos_internal.hpp"
+
+typedef double2 d2;
+
+// which form S1 = IndAffine([Q -I], 0) runs in: the values of fos_get_direct_mode
+enum DirectForm : int32_t { DIRECT_OFF = 0, DIRECT_DENSE = 1, DIRECT_BLOCK = 2, DIRECT_CG = 3, DIRECT_REDUCED = 4 };
+
+// how the stored inverse of the dense or the reduced form was built (dense_spd_inverse, direct.cpp)
+struct DenseInv {
+    int used = FOS_DIRECT_FACTOR_NEWTON;       // the factor that produced the accepted inverse (NEWTON after a fallback)
+    int steps = 0;                             // Newton-Schulz steps (Newton), polish steps (Cholesky: 0..2)
+    double seconds = 0.0, probe = 0.0;         // the inversion stage alone (matrix formed -> inverse accepted); last probe residual of the Cholesky path (0 on the Newton path)
+    bool fell_back = false;                    // the Cholesky path gave up and Newton-Schulz ran
+    int64_t bad_col = -1;                      // first column whose Cholesky pivot was not a positive finite number
+};
+
+// ------------------------------------------------------------------------------------------------ the handle
+struct fos_solver {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int64_t m = 0, n = 0, l = 0, nnz = 0;
+    int64_t l_global = 0;                      // == l unless sharded (tolerance floor uses the global size)
+
+    // operator
+    fos::HostBlkCsr hostS;                          // kept only for re-partitioning (indices freed after upload)
+    int64_t win_stats[4] = {0, 0, 0, 0};       // window panels: panels, (panel, window) segments, 64-row slices, stored entries
+    fos::DevBlkCsr S{};
+    std::vector<void*> owned;                  // every hipMalloc'd pointer
+    std::vector<void*> pooled;                 // blocks of the process-wide pool of uncached memory (uncached_acquire): released, never freed
+    double* cb = nullptr;
+    double nb = 0.0, nc = 0.0;                 // ||b||, ||c|| (global)
+    double nb_local = 0.0, nc_local = 0.0;     // this shard's ||b||, ||c||
+
+    // vectors: l double2 each
+    d2 *X = nullptr, *T1 = nullptr, *T2 = nullptr;          // iterate, tmp1, tmp2
+    d2 *SOL = nullptr, *RHS = nullptr, *R = nullptr, *AP = nullptr;                 // CG: xinit/y, rhs, r, z
+    d2 *PB[2] = {nullptr, nullptr};                         // CG direction, ping-pong: p_j lives in PB[j & 1]
+    d2 *Y = nullptr, *XOLD = nullptr;                       // FISTA y / xold ; Dykstra p / q
+    d2 *W = nullptr;                                        // scratch (Dykstra sums, test entries)
+    d2 *SOL2 = nullptr;                                     // HSDEMatrix.cgdata.xinit
+    double* plain = nullptr;                                // 2l doubles: ABI staging
+
+    // cones
+    uint8_t* ew_op = nullptr;
+    fos::ConeDesc* soc = nullptr; int nsoc = 0;
+    fos::ConeDesc* expc = nullptr; int nexp = 0;
+    fos::ConeDesc* psd = nullptr; int npsd = 0; int psd_kmax = 0, psd_kmin = 0;       // PSD cones of order <= 64 (psd.hip)
+    fos::PsdSign* psd_big = nullptr;                // ... of order > 64: projected by matrix products (psd_sign.hip)
+    double* psd_scratch = nullptr;
+    double* psd_V[2] = {nullptr, nullptr};     // warm-start eigenvector bases (ping-pong), orders <= 64
+    int psd_cur = 0, psd_have_prev = 0;
+    int* psd_stats = nullptr;                  // Jacobi sweeps of the last projection, per (cone, copy)  (fos_psd_debug)
+    int psd_phase_limit = 0;                   // diagnostic: stop the PSD kernel after a phase (wrong results!)
+    int cus = 256;                             // compute units of `device`
+    int psd_wave = -1; bool psd_narrow = false, psd_wide = false; int psd_wide_threads = 512;      // FOS_PSD_* (read at fos_create)
+    mutable bool psd_attr_set = false, psd_attr_set_r = false;
+    int32_t* psd_redo = nullptr;               // per (cone, copy): 1 = the refinement kernel left the matrix to the Jacobi kernel
+    int psd_refine = -1;                       // FOS_PSD_REFINE
+    bool psd_extrapolate = true;               // FOS_PSD_EXTRAPOLATE
+    double psd_theta = 0.0;                    // FOS_PSD_THETA
+    bool peer_same_device = false;             // a peer rank's mailbox lives on THIS device (several ranks on one GPU: tests)
+
+    // scalars
+    fos::DevState* st = nullptr;
+    fos::DevState* st_host = nullptr;               // pinned
+    // speculation past a CG solve: the kernels that follow it are enqueued (gated on fos::DevState.done) BEFORE the host learns the
+    // iteration count, which it then reads from a record the CG kernels write into pinned host memory (wait_cg_mark)
+    fos::HostMark* mark = nullptr;                  // pinned + mapped; fos::DevState.hostmark points at it
+    double* pre_sums = nullptr;                // fos::LaunchCtx::pre
+    bool pre_on = true;
+    bool speculate = true;
+    double* partials = nullptr;
+    double* reduced = nullptr;                 // 16 doubles
+    int vec_blocks = 0;
+    int cg_blocks = 0;
+    uint32_t* def_mask = nullptr;              // bit i: row i of S is finished from partial slots (dual tiles)
+    bool fuse_p = false;                       // the p update of CG rides on the next sweep (2 launches per iteration)
+    int cg_variant = -1;                       // FOS_CG_*: -1 = the handle's default (sharded: merged reduction, closing in the update)
+    // FOS_CG_RESIDENT (resident.hip): the plan (which workgroup holds which tiles), its device copy and the workgroups' record arrays
+    fos::ResPlan res_plan;
+    fos::ResLaunch res{};
+    bool res_ok = false;                       // this handle's operator qualifies (under the current workgroup budget)
+    bool res_all = false;                      // ... and so does every rank's (sharded: the vote of global_setup)
+    int res_gmax = 0;                          // the budget the plan was made for
+
+    // algorithm (gap.jl:6-21, gapa.jl:9-25, fista.jl:6-18, dykstra.jl:5-17)
+    int alg = FOS_ALG_GAP;
+    double alpha = 0.8, alpha1 = 1.8, alpha2 = 1.8, beta = 0.0;
+    double fista_t = 1.0;
+
+    // direct = true (HSDE.jl:12-15): S1 = IndAffine([Q -I], 0), an exact projection through a one-time dense factorisation (direct.cpp).
+    // direct_form says which form is ACTIVE; what is STORED (Ginv, blk_ready, red_ready) does not depend on it: a disabled handle keeps its factorisation
+    DirectForm direct_form = DIRECT_OFF;
+    bool direct_exact() const { return direct_form != DIRECT_OFF && direct_form != DIRECT_CG; }     // S1 runs no CG
+    double* Ginv = nullptr;                    // (I + Q Q')^-1, symmetric, column-major, leading dimension Gld (l padded to 64)
+    int64_t Gld = 0;
+    int direct_factor_req = 0;                 // FOS_DIRECT_FACTOR_*: how the stored inverse (dense or reduced form) was asked to be built
+    DenseInv direct_inv;                       // ... and how it was built
+    double* dvec[2] = {nullptr, nullptr};      // two plain l-vectors
+    // direct = true on a BLOCK-SEPARABLE operator: I + A'A is block diagonal with blocks of order <= BLKDIR_MAX (an SDP with few variables per
+    // block: C4), so the exact projection costs three KKT sweeps -- no CG, no dense l x l inverse (prox_affine_direct_block)
+    int blk_n = 0;                             // diagonal blocks of I + A'A
+    int64_t* blk_goff = nullptr;               // [blk_n] start of block b's inverse (s_b x s_b, column-major) in blk_ginv
+    int32_t* blk_ioff = nullptr;               // [blk_n + 1] start of block b's column list in blk_idx
+    int32_t* blk_idx = nullptr;
+    double* blk_ginv = nullptr;
+    d2 *blk_phg = nullptr, *blk_qphg = nullptr;   // (D^-1 h, D^-1 M h) and their images under Q, per row
+    double* blk_prm = nullptr;                 // the 3 x 3 inverse of the border system (9), delta = 1 + |[c; b]|^2
+    double* blk_ctx = nullptr;                 // [blk_n] the blocks' shares of c'x^ (blkdir_solve_kernel)
+    bool blk_skip_tail = true;                 // the third apply runs without its deferred-row and tau-row kernels (FOS_BLKDIR_FULL_APPLY=1: with them)
+    bool blk_ready = false;                    // blkdir_setup ran to its end (a half-finished set-up must not pass for the block form)
+    // direct = true, REDUCED form (direct_reduced.hip): K^-1, K = I + A'A (n <= m) or I + A A' (m < n), as tiles of its lower triangle stored once
+    bool red_ready = false;                    // reduced_setup ran to its end
+    int red_swap = 0;                          // 1: m < n, K = I + A A'
+    int red_refine = 1;                        // steps of iterative refinement on the matrix-free G = I - Q Q per projection (FOS_DIRECT_REDUCED_REFINE)
+    fos::RedPlan red_plan;
+    fos::RedDev red{};
+    d2 *red_pq = nullptr, *red_yk = nullptr;   // the two right-hand sides of the tile product and its result, interleaved (kpad pairs)
+    double *red_s = nullptr, *red_d = nullptr, *red_r = nullptr, *red_z = nullptr;   // plain l-vectors: a Q sweep's result, D^-1 t1, the refinement's residual, Q w / Q Q w
+    double *red_p = nullptr, *red_q = nullptr, *red_g = nullptr;                     // D^-1 h, D^-1 g, g = -Q0 h
+    double* red_dots = nullptr;                // [RED_DOT_BLOCKS][2] the workgroups' shares of h'd and g'd
+    double red_minv[4] = {0, 0, 0, 0};         // inverse of the 2 x 2 border system, row-major
+    double direct_setup_s = 0.0;               // wall time of the last set-up (fos_get_direct_stats)
+
+    // S1 = AffinePlusLinear state (affinepluslinear.jl:58-69)
+    int64_t prox_i = 1;
+    bool firstrun = true;
+    int64_t cgiter = 0;
+    int hit_max_accum = 0;
+    bool firstrun2 = true;                     // HSDEMatrix.cgdata.firstrun
+    int last_cg_pred = 0;
+    // LineSearchWrapper (wrappers/linesearch.jl): every ls_interval-th iteration is a 31-point step-length search
+    bool shift_ready = false;                  // RHS already holds SOL - [0; X.y] (written by the step's last kernel): inside fos_step only
+    bool shift_fuse = true;                    // FOS_SHIFT_FUSE=0: every projection runs its own shift pass
+    bool in_step = false;
+    int64_t ls_interval = 0;
+    bool ls_now = false;                       // the iteration in flight is a line-search iteration (between step_once and step_finish)
+    // GAPP ("projected GAP", solvers/gapproj.jl): GAP whose every gapp_iproj-th iteration is a 21-point projected search
+    int64_t gapp_iproj = 0;
+    bool gapp_now = false;
+    double gapp_log[23] = {0};                 // 21 test norms, alpha_best, iteration
+    double ls_log[34] = {0};                   // last search: ||res||, the 31 test residuals, the chosen alpha, the iteration
+    // LongstepWrapper (wrappers/longstep.jl, saveplanes.jl): the last nsave + 1 iterations of every long_interval save the two half-planes of
+    // their projections; the iterate is then projected onto the saved planes
+    fos::LongPlanes lp;                             // (fos_internal.hpp)
+    int cg_same_run = 0;                       // consecutive solves that took exactly last_cg_pred iterations
+    const d2* last_checked = nullptr;          // vector the last checkstatus was evaluated on
+
+    // sharding: scalar sums cross GPUs either by an in-stream RCCL all-reduce (comm) or through peer mailboxes (peer_on)
+    ncclComm_t comm = nullptr;
+    int nranks = 1, rank = 0;
+    unsigned long long* peer_mbox = nullptr;   // own mailbox (uncached device memory, exported through HIP IPC)
+    std::vector<void*> peer_opened;            // IPC mappings of the peers' mailboxes
+    fos::PeerBox peer{};
+    bool peer_on = false;
+    // host-pinned mailboxes (fos_peer_open_host): the mapped + registered shm segment, its name (rank 0 unlinks it), the local relay
+    void* host_seg = nullptr;
+    int host_seg_fd = -1;                      // kept open: fos_peer_selftest asks it whether the mapped segment is still linked under its name
+    size_t host_seg_bytes = 0;
+    std::string host_seg_name;
+    unsigned long long* peer_relay = nullptr;
+    uint32_t cg_epoch = 0;                     // windows of 2048 sequence numbers used so far (cg_solve): the folded exchanges, the resident solve
+    // ... or through the caller's own collective on host buffers (fos_comm_init_host: MPI.jl, gloo, ...)
+    fos_allreduce_fn host_fn = nullptr;
+    void* host_user = nullptr;
+    double* host_buf = nullptr;                // pinned, max(2n, 16) doubles
+    // row-sharded + peer mailboxes: the n-vector A'y crosses the ranks through peer-mapped memory too (fos_internal.hpp, fos::VecBox)
+    double* vec_buf = nullptr;                 // own exchange buffer: [2][nranks][2n] doubles, then [2][nranks] flags (uncached, IPC-exported)
+    std::vector<void*> vec_opened;
+    fos::VecBox vec{};
+    uint32_t vec_seq = 0;                      // exchanges enqueued so far (the same on every rank: all make the same calls)
+    int vec_nranks = 0;
+    bool sharded() const { return comm != nullptr || peer_on || host_fn != nullptr; }
+    // row sharding of a non-block-diagonal A: the first n entries (and tau, kappa) of every vector are replicated,
+    // the slots of the rows of A' are summed over the ranks (RCCL all-reduce of 2n doubles) between a sweep and its slot-list sums
+    bool row_sharded = false;
+    double* slots_rd = nullptr;
+
+    // tuning / measurement
+    int cg_chunk = 8;
+    int nwg_target = 2048;
+    bool prof = false;
+    int prof_period = 1;                       // every prof_period-th launch of a class is bracketed by events (1: all)
+    int64_t cg_total = 0;                      // CG iterations since fos_create
+    int64_t direct_sweeps = 0;                 // sweeps of the block-direct projection since fos_create (profiling ordinal)
+    struct ProfRec { hipEvent_t a, b; int cls; int j; };
+    std::vector<ProfRec> prof_recs;            // event pairs, reused
+    size_t prof_used = 0;
+    int64_t prof_seen[FOS_PROF_CLASSES] = {0, 0, 0, 0, 0};
+    int64_t prof_steps = 0, prof_steps_sampled = 0;   // outer iterations since fos_profile / of them sampled for FOS_PROF_OTHER
+    bool prof_step_on = false;                 // the outer iteration in flight brackets its FOS_PROF_OTHER groups
+    static constexpr size_t PROF_CAP = 16384;
+
+    static int sum_slots_over_ranks(void* self);      // solver.cpp (needs the RCCL table)
+    // row-sharded WITH dual tiles: the sweep fills local slot lists (S.slots = slots_rd + 2n doubles); between sweep and consumers the
+    // lists of the n rows of A' are added up (cmp_rec / cmp_idx -> cmp_local) and THAT n-vector crosses the ranks into slots_rd[0..n);
+    // the consumers' records (S.def_rec) name slot j for row j < n and the local lists, shifted by n, for the rows of A
+    fos::DefRow* cmp_rec = nullptr;
+    int32_t* cmp_idx = nullptr;
+    double* cmp_local = nullptr;
+    int cmp_lpr = 1;
+
+    fos::LaunchCtx ctx() const {
+        fos::LaunchCtx c;
+        c.stream = stream; c.S = S; c.cb = cb; c.n = n; c.m = m; c.l = l; c.st = st;
+        c.partials = partials; c.reduced = reduced; c.vec_blocks = vec_blocks; c.cg_blocks = cg_blocks;
+        c.peer = peer_on ? &peer : nullptr;
+        c.def_mask = def_mask;
+        c.pre = pre_on ? pre_sums : nullptr;
+        c.between = nullptr; c.between_arg = nullptr;
+        c.cus = cus; c.psd_wave = psd_wave; c.psd_narrow = psd_narrow; c.psd_wide = psd_wide; c.psd_wide_threads = psd_wide_threads;
+        c.psd_attr_set = &psd_attr_set; c.psd_attr_set_r = &psd_attr_set_r; c.psd_refine = psd_refine; c.psd_extrapolate = psd_extrapolate; c.psd_theta = psd_theta;
+        c.psd_refine_max_mats = (peer_same_device && nranks > 1) ? std::max(1, cus / nranks) : 0;
+        c.count_repl = (!row_sharded || rank == 0) ? 1 : 0;
+        c.n_repl = row_sharded ? n : 0;
+        if (row_sharded) { c.between = &fos_solver::sum_slots_over_ranks; c.between_arg = const_cast<fos_solver*>(this); }
+        return c;
+    }
+};
+
+// ------------------------------------------------------------------------------------------------ shared helpers (defined in solver.cpp)
+namespace fos {
+struct RoctxRange {                            // a named range for `rocprofv3 --marker-trace` (FOS_ROCTX=1)
+    bool on;
+    explicit RoctxRange(const char* name);
+    ~RoctxRange();
+};
+int allreduce(fos_solver* h, int count);
+int finish_reduce(fos_solver* h, const LaunchCtx& c, int count, int nacc, int gate, int* from_reduced, int off = 0);
+int check_launch(const char* where);
+int prof_begin(fos_solver* h, int cls, int j, int64_t ordinal);
+int prof_begin_other(fos_solver* h, int post);
+void prof_end(fos_solver* h, int idx);
+int poll_state(fos_solver* h);
+int kkt_apply_full(fos_solver* h, const LaunchCtx& c, const d2* w, d2* out, bool deferred = true, bool tau_row = true);
+// direct.cpp: prox!(y, S1::IndAffine([Q -I], 0), x) in the handle's exact form, the result left in h->SOL
+int prox_affine_direct(fos_solver* h, const d2* x);
+
+template <class T>
+int dev_alloc(fos_solver* h, T** p, size_t count) {
+    void* q = nullptr;
+    size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) { set_error("hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e)); return FOS_ENOMEM; }
+    h->owned.push_back(q);
+    *p = reinterpret_cast<T*>(q);
+    return FOS_OK;
+}
+
+template <class T>
+void dev_release(fos_solver* h, T** p) {          // frees a dev_alloc'd buffer before the handle's end
+    if (!*p) return;
+    auto it = std::find(h->owned.begin(), h->owned.end(), (void*)*p);
+    if (it != h->owned.end()) h->owned.erase(it);
+    (void)hipFree(*p);
+    *p = nullptr;
+}
+
+template <class T>
+int dev_upload(fos_solver* h, T** p, const std::vector<T>& v) {
+    FOS_TRY(dev_alloc(h, p, v.size()));
+    if (!v.empty()) FOS_HIP(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return FOS_OK;
+}
+}  // namespace fos

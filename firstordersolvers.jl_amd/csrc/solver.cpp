@@ -7,23 +7,16 @@
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
-#include <rccl/rccl.h>
 #include <functional>
 
-#include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cmath>
-#include <memory>
 #include <mutex>
-#include <thread>
 
-#include "fos_internal.hpp"
+#include "fos_solver.hpp"
 
 namespace fos {
 const char* last_error_cstr();
-
-typedef double2 d2;
 
 // ------------------------------------------------------------------------------------------------ RCCL via dlopen
 // (no link-time dependency: single-GPU users never load it; inside a torch process dlopen returns the copy torch
@@ -65,11 +58,6 @@ static bool roctx_on() {
     }
     return g_roctx.state == 1;
 }
-struct RoctxRange {
-    bool on;
-    explicit RoctxRange(const char* name) : on(roctx_on()) { if (on) g_roctx.push(name); }
-    ~RoctxRange() { if (on) g_roctx.pop(); }
-};
 
 static int rccl_load() {
     if (g_rccl.lib) return FOS_OK;
@@ -107,220 +95,9 @@ static int rccl_load() {
         }                                                                                                  \
     } while (0)
 
-}  // namespace fos
+RoctxRange::RoctxRange(const char* name) : on(roctx_on()) { if (on) g_roctx.push(name); }
+RoctxRange::~RoctxRange() { if (on) g_roctx.pop(); }
 
-using namespace fos;
-
-// ------------------------------------------------------------------------------------------------ the handle
-struct fos_solver {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int64_t m = 0, n = 0, l = 0, nnz = 0;
-    int64_t l_global = 0;                      // == l unless sharded (tolerance floor uses the global size)
-
-    // operator
-    HostBlkCsr hostS;                          // kept only for re-partitioning (indices freed after upload)
-    int64_t win_stats[4] = {0, 0, 0, 0};       // window panels: panels, (panel, window) segments, 64-row slices, stored entries
-    DevBlkCsr S{};
-    std::vector<void*> owned;                  // every hipMalloc'd pointer
-    std::vector<void*> pooled;                 // blocks of the process-wide pool of uncached memory (uncached_acquire): released, never freed
-    double* cb = nullptr;
-    double nb = 0.0, nc = 0.0;                 // ||b||, ||c|| (global)
-    double nb_local = 0.0, nc_local = 0.0;     // this shard's ||b||, ||c||
-
-    // vectors: l double2 each
-    d2 *X = nullptr, *T1 = nullptr, *T2 = nullptr;          // iterate, tmp1, tmp2
-    d2 *SOL = nullptr, *RHS = nullptr, *R = nullptr, *AP = nullptr;                 // CG: xinit/y, rhs, r, z
-    d2 *PB[2] = {nullptr, nullptr};                         // CG direction, ping-pong: p_j lives in PB[j & 1]
-    d2 *Y = nullptr, *XOLD = nullptr;                       // FISTA y / xold ; Dykstra p / q
-    d2 *W = nullptr;                                        // scratch (Dykstra sums, test entries)
-    d2 *SOL2 = nullptr;                                     // HSDEMatrix.cgdata.xinit
-    double* plain = nullptr;                                // 2l doubles: ABI staging
-
-    // cones
-    uint8_t* ew_op = nullptr;
-    ConeDesc* soc = nullptr; int nsoc = 0;
-    ConeDesc* expc = nullptr; int nexp = 0;
-    ConeDesc* psd = nullptr; int npsd = 0; int psd_kmax = 0, psd_kmin = 0;       // PSD cones of order <= 64 (psd.hip)
-    PsdSign* psd_big = nullptr;                // ... of order > 64: projected by matrix products (psd_sign.hip)
-    double* psd_scratch = nullptr;
-    double* psd_V[2] = {nullptr, nullptr};     // warm-start eigenvector bases (ping-pong), orders <= 64
-    int psd_cur = 0, psd_have_prev = 0;
-    int* psd_stats = nullptr;                  // Jacobi sweeps of the last projection, per (cone, copy)  (fos_psd_debug)
-    int psd_phase_limit = 0;                   // diagnostic: stop the PSD kernel after a phase (wrong results!)
-    int cus = 256;                             // compute units of `device`
-    int psd_wave = -1; bool psd_narrow = false, psd_wide = false; int psd_wide_threads = 512;      // FOS_PSD_* (read at fos_create)
-    mutable bool psd_attr_set = false, psd_attr_set_r = false;
-    int32_t* psd_redo = nullptr;               // per (cone, copy): 1 = the refinement kernel left the matrix to the Jacobi kernel
-    int psd_refine = -1;                       // FOS_PSD_REFINE
-    bool psd_extrapolate = true;               // FOS_PSD_EXTRAPOLATE
-    double psd_theta = 0.0;                    // FOS_PSD_THETA
-    bool peer_same_device = false;             // a peer rank's mailbox lives on THIS device (several ranks on one GPU: tests)
-
-    // scalars
-    DevState* st = nullptr;
-    DevState* st_host = nullptr;               // pinned
-    // speculation past a CG solve: the kernels that follow it are enqueued (gated on DevState.done) BEFORE the host learns the
-    // iteration count, which it then reads from a record the CG kernels write into pinned host memory (wait_cg_mark)
-    HostMark* mark = nullptr;                  // pinned + mapped; DevState.hostmark points at it
-    double* pre_sums = nullptr;                // LaunchCtx::pre
-    bool pre_on = true;
-    bool speculate = true;
-    double* partials = nullptr;
-    double* reduced = nullptr;                 // 16 doubles
-    int vec_blocks = 0;
-    int cg_blocks = 0;
-    uint32_t* def_mask = nullptr;              // bit i: row i of S is finished from partial slots (dual tiles)
-    bool fuse_p = false;                       // the p update of CG rides on the next sweep (2 launches per iteration)
-    int cg_variant = -1;                       // FOS_CG_*: -1 = the handle's default (sharded: merged reduction, closing in the update)
-    // FOS_CG_RESIDENT (resident.hip): the plan (which workgroup holds which tiles), its device copy and the workgroups' record arrays
-    ResPlan res_plan;
-    ResLaunch res{};
-    bool res_ok = false;                       // this handle's operator qualifies (under the current workgroup budget)
-    bool res_all = false;                      // ... and so does every rank's (sharded: the vote of global_setup)
-    int res_gmax = 0;                          // the budget the plan was made for
-
-    // algorithm (gap.jl:6-21, gapa.jl:9-25, fista.jl:6-18, dykstra.jl:5-17)
-    int alg = FOS_ALG_GAP;
-    double alpha = 0.8, alpha1 = 1.8, alpha2 = 1.8, beta = 0.0;
-    double fista_t = 1.0;
-
-    // direct = true (HSDE.jl:12-15): S1 = IndAffine([Q -I], 0), an exact projection through a one-time dense factorisation
-    bool direct = false;
-    bool direct_cg = false;                    // direct = true on an operator too large for the dense inverse: the same projection by CG at its tolerance floor from the first call on
-    double* Ginv = nullptr;                    // (I + Q Q')^-1, symmetric, column-major, leading dimension Gld (l padded to 64)
-    int64_t Gld = 0;
-    int direct_iters = 0;                      // Newton-Schulz iterations the set-up took (Cholesky factor: its polish steps, 0..2)
-    int direct_factor_req = 0;                 // FOS_DIRECT_FACTOR_*: how the stored inverse (dense or reduced form) was asked to be built
-    int direct_factor = 0;                     // ... and how it was built (NEWTON after a fallback)
-    double direct_invert_s = 0.0;              // seconds of the inversion stage alone (matrix formed -> inverse accepted)
-    double direct_probe = 0.0;                 // last probe residual of the Cholesky path (0 on the Newton path)
-    bool direct_fell_back = false;             // the Cholesky path gave up and Newton-Schulz ran
-    double* dvec[2] = {nullptr, nullptr};      // two plain l-vectors
-    // direct = true on a BLOCK-SEPARABLE operator: I + A'A is block diagonal with blocks of order <= BLKDIR_MAX (an SDP with few variables per
-    // block: C4), so the exact projection costs three KKT sweeps -- no CG, no dense l x l inverse (prox_affine_direct_block)
-    bool direct_blk = false;
-    int blk_n = 0;                             // diagonal blocks of I + A'A
-    int64_t* blk_goff = nullptr;               // [blk_n] start of block b's inverse (s_b x s_b, column-major) in blk_ginv
-    int32_t* blk_ioff = nullptr;               // [blk_n + 1] start of block b's column list in blk_idx
-    int32_t* blk_idx = nullptr;
-    double* blk_ginv = nullptr;
-    d2 *blk_phg = nullptr, *blk_qphg = nullptr;   // (D^-1 h, D^-1 M h) and their images under Q, per row
-    double* blk_prm = nullptr;                 // the 3 x 3 inverse of the border system (9), delta = 1 + |[c; b]|^2
-    double* blk_ctx = nullptr;                 // [blk_n] the blocks' shares of c'x^ (blkdir_solve_kernel)
-    bool blk_skip_tail = true;                 // the third apply runs without its deferred-row and tau-row kernels (FOS_BLKDIR_FULL_APPLY=1: with them)
-    bool blk_ready = false;                    // blkdir_setup ran to its end (a half-finished set-up must not pass for the block form)
-    // direct = true, REDUCED form (direct_reduced.hip): K^-1, K = I + A'A (n <= m) or I + A A' (m < n), as tiles of its lower triangle stored once
-    bool direct_red = false;
-    bool red_ready = false;                    // reduced_setup ran to its end
-    int red_swap = 0;                          // 1: m < n, K = I + A A'
-    int red_refine = 1;                        // steps of iterative refinement on the matrix-free G = I - Q Q per projection (FOS_DIRECT_REDUCED_REFINE)
-    RedPlan red_plan;
-    RedDev red{};
-    d2 *red_pq = nullptr, *red_yk = nullptr;   // the two right-hand sides of the tile product and its result, interleaved (kpad pairs)
-    double *red_s = nullptr, *red_d = nullptr, *red_r = nullptr, *red_z = nullptr;   // plain l-vectors: a Q sweep's result, D^-1 t1, the refinement's residual, Q w / Q Q w
-    double *red_p = nullptr, *red_q = nullptr, *red_g = nullptr;                     // D^-1 h, D^-1 g, g = -Q0 h
-    double* red_dots = nullptr;                // [RED_DOT_BLOCKS][2] the workgroups' shares of h'd and g'd
-    double red_minv[4] = {0, 0, 0, 0};         // inverse of the 2 x 2 border system, row-major
-    double direct_setup_s = 0.0;               // wall time of the last set-up (fos_get_direct_stats)
-
-    // S1 = AffinePlusLinear state (affinepluslinear.jl:58-69)
-    int64_t prox_i = 1;
-    bool firstrun = true;
-    int64_t cgiter = 0;
-    int hit_max_accum = 0;
-    bool firstrun2 = true;                     // HSDEMatrix.cgdata.firstrun
-    int last_cg_pred = 0;
-    // LineSearchWrapper (wrappers/linesearch.jl): every ls_interval-th iteration is a 31-point step-length search
-    bool shift_ready = false;                  // RHS already holds SOL - [0; X.y] (written by the step's last kernel): inside fos_step only
-    bool shift_fuse = true;                    // FOS_SHIFT_FUSE=0: every projection runs its own shift pass
-    bool in_step = false;
-    int64_t ls_interval = 0;
-    bool ls_now = false;                       // the iteration in flight is a line-search iteration (between step_once and step_finish)
-    // GAPP ("projected GAP", solvers/gapproj.jl): GAP whose every gapp_iproj-th iteration is a 21-point projected search
-    int64_t gapp_iproj = 0;
-    bool gapp_now = false;
-    double gapp_log[23] = {0};                 // 21 test norms, alpha_best, iteration
-    double ls_log[34] = {0};                   // last search: ||res||, the 31 test residuals, the chosen alpha, the iteration
-    // LongstepWrapper (wrappers/longstep.jl, saveplanes.jl): the last nsave + 1 iterations of every long_interval save the two half-planes of
-    // their projections; the iterate is then projected onto the saved planes
-    LongPlanes lp;                             // (fos_internal.hpp)
-    int cg_same_run = 0;                       // consecutive solves that took exactly last_cg_pred iterations
-    const d2* last_checked = nullptr;          // vector the last checkstatus was evaluated on
-
-    // sharding: scalar sums cross GPUs either by an in-stream RCCL all-reduce (comm) or through peer mailboxes (peer_on)
-    ncclComm_t comm = nullptr;
-    int nranks = 1, rank = 0;
-    unsigned long long* peer_mbox = nullptr;   // own mailbox (uncached device memory, exported through HIP IPC)
-    std::vector<void*> peer_opened;            // IPC mappings of the peers' mailboxes
-    PeerBox peer{};
-    bool peer_on = false;
-    // host-pinned mailboxes (fos_peer_open_host): the mapped + registered shm segment, its name (rank 0 unlinks it), the local relay
-    void* host_seg = nullptr;
-    int host_seg_fd = -1;                      // kept open: fos_peer_selftest asks it whether the mapped segment is still linked under its name
-    size_t host_seg_bytes = 0;
-    std::string host_seg_name;
-    unsigned long long* peer_relay = nullptr;
-    uint32_t cg_epoch = 0;                     // windows of 2048 sequence numbers used so far (cg_solve): the folded exchanges, the resident solve
-    // ... or through the caller's own collective on host buffers (fos_comm_init_host: MPI.jl, gloo, ...)
-    fos_allreduce_fn host_fn = nullptr;
-    void* host_user = nullptr;
-    double* host_buf = nullptr;                // pinned, max(2n, 16) doubles
-    // row-sharded + peer mailboxes: the n-vector A'y crosses the ranks through peer-mapped memory too (fos_internal.hpp, VecBox)
-    double* vec_buf = nullptr;                 // own exchange buffer: [2][nranks][2n] doubles, then [2][nranks] flags (uncached, IPC-exported)
-    std::vector<void*> vec_opened;
-    VecBox vec{};
-    uint32_t vec_seq = 0;                      // exchanges enqueued so far (the same on every rank: all make the same calls)
-    int vec_nranks = 0;
-    bool sharded() const { return comm != nullptr || peer_on || host_fn != nullptr; }
-    // row sharding of a non-block-diagonal A: the first n entries (and tau, kappa) of every vector are replicated,
-    // the slots of the rows of A' are summed over the ranks (RCCL all-reduce of 2n doubles) between a sweep and its slot-list sums
-    bool row_sharded = false;
-    double* slots_rd = nullptr;
-
-    // tuning / measurement
-    int cg_chunk = 8;
-    int nwg_target = 2048;
-    bool prof = false;
-    int prof_period = 1;                       // every prof_period-th launch of a class is bracketed by events (1: all)
-    int64_t cg_total = 0;                      // CG iterations since fos_create
-    int64_t direct_sweeps = 0;                 // sweeps of the block-direct projection since fos_create (profiling ordinal)
-    struct ProfRec { hipEvent_t a, b; int cls; int j; };
-    std::vector<ProfRec> prof_recs;            // event pairs, reused
-    size_t prof_used = 0;
-    int64_t prof_seen[FOS_PROF_CLASSES] = {0, 0, 0, 0, 0};
-    int64_t prof_steps = 0, prof_steps_sampled = 0;   // outer iterations since fos_profile / of them sampled for FOS_PROF_OTHER
-    bool prof_step_on = false;                 // the outer iteration in flight brackets its FOS_PROF_OTHER groups
-    static constexpr size_t PROF_CAP = 16384;
-
-    static int sum_slots_over_ranks(void* self);      // defined below (needs the RCCL table)
-    // row-sharded WITH dual tiles: the sweep fills local slot lists (S.slots = slots_rd + 2n doubles); between sweep and consumers the
-    // lists of the n rows of A' are added up (cmp_rec / cmp_idx -> cmp_local) and THAT n-vector crosses the ranks into slots_rd[0..n);
-    // the consumers' records (S.def_rec) name slot j for row j < n and the local lists, shifted by n, for the rows of A
-    DefRow* cmp_rec = nullptr;
-    int32_t* cmp_idx = nullptr;
-    double* cmp_local = nullptr;
-    int cmp_lpr = 1;
-
-    LaunchCtx ctx() const {
-        LaunchCtx c;
-        c.stream = stream; c.S = S; c.cb = cb; c.n = n; c.m = m; c.l = l; c.st = st;
-        c.partials = partials; c.reduced = reduced; c.vec_blocks = vec_blocks; c.cg_blocks = cg_blocks;
-        c.peer = peer_on ? &peer : nullptr;
-        c.def_mask = def_mask;
-        c.pre = pre_on ? pre_sums : nullptr;
-        c.between = nullptr; c.between_arg = nullptr;
-        c.cus = cus; c.psd_wave = psd_wave; c.psd_narrow = psd_narrow; c.psd_wide = psd_wide; c.psd_wide_threads = psd_wide_threads;
-        c.psd_attr_set = &psd_attr_set; c.psd_attr_set_r = &psd_attr_set_r; c.psd_refine = psd_refine; c.psd_extrapolate = psd_extrapolate; c.psd_theta = psd_theta;
-        c.psd_refine_max_mats = (peer_same_device && nranks > 1) ? std::max(1, cus / nranks) : 0;
-        c.count_repl = (!row_sharded || rank == 0) ? 1 : 0;
-        c.n_repl = row_sharded ? n : 0;
-        if (row_sharded) { c.between = &fos_solver::sum_slots_over_ranks; c.between_arg = const_cast<fos_solver*>(this); }
-        return c;
-    }
-};
-
-// row-sharded operators: slots (this rank's partial sums of A'y, 2n doubles) -> slots_rd (their sum over the ranks), in stream
 // the caller's collective: stage `count` doubles through the pinned host buffer (synchronises the stream; a slow path by design)
 static int host_allreduce(fos_solver* h, const double* src, double* dst, size_t count) {
     if (hipMemcpyAsync(h->host_buf, src, sizeof(double) * count, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return FOS_EHIP;
@@ -330,54 +107,7 @@ static int host_allreduce(fos_solver* h, const double* src, double* dst, size_t 
     return hipStreamSynchronize(h->stream) == hipSuccess ? FOS_OK : FOS_EHIP;          // the buffer is reused by the next call
 }
 
-int fos_solver::sum_slots_over_ranks(void* self) {
-    fos_solver* h = static_cast<fos_solver*>(self);
-    const double* src = h->S.slots;            // one slot per row of A' ...
-    if (h->cmp_local) {                        // ... or, with dual tiles, the rows' local slot lists added up first
-        launch_slots_compact(h->ctx(), (int)h->n, h->cmp_rec, h->cmp_idx, h->cmp_lpr, h->S.slots, h->cmp_local);
-        src = h->cmp_local;
-    }
-    if (h->host_fn) return host_allreduce(h, src, h->slots_rd, (size_t)2 * (size_t)h->n);
-    if (h->peer_on && h->vec.buf) {            // peer-mapped memory: push + sum, in stream, no library call
-        launch_vec_exchange(h->ctx(), h->vec, ++h->vec_seq, src, h->slots_rd);
-        return FOS_OK;
-    }
-    if (!h->comm) {            // no communicator yet (set-up calls before fos_comm_init, or a single process): the sum is the copy
-        return hipMemcpyAsync(h->slots_rd, src, sizeof(double) * 2 * (size_t)h->n, hipMemcpyDeviceToDevice, h->stream) == hipSuccess ? FOS_OK : FOS_EHIP;
-    }
-    return g_rccl.AllReduce(src, h->slots_rd, (size_t)2 * (size_t)h->n, ncclDouble, ncclSum, h->comm, h->stream) == ncclSuccess ? FOS_OK : FOS_ECOMM;
-}
-
-namespace {
-
-template <class T>
-int dev_alloc(fos_solver* h, T** p, size_t count) {
-    void* q = nullptr;
-    size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) { set_error("hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e)); return FOS_ENOMEM; }
-    h->owned.push_back(q);
-    *p = reinterpret_cast<T*>(q);
-    return FOS_OK;
-}
-
-template <class T>
-void dev_release(fos_solver* h, T** p) {          // frees a dev_alloc'd buffer before the handle's end
-    if (!*p) return;
-    auto it = std::find(h->owned.begin(), h->owned.end(), (void*)*p);
-    if (it != h->owned.end()) h->owned.erase(it);
-    (void)hipFree(*p);
-    *p = nullptr;
-}
-
-template <class T>
-int dev_upload(fos_solver* h, T** p, const std::vector<T>& v) {
-    FOS_TRY(dev_alloc(h, p, v.size()));
-    if (!v.empty()) FOS_HIP(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return FOS_OK;
-}
-
-int psd_order(int64_t len) {
+static int psd_order(int64_t len) {
     int64_t k = (int64_t)std::llround(std::sqrt(0.25 + 2.0 * (double)len) - 0.5);
     if (k * (k + 1) / 2 != len) return -1;
     return (int)k;
@@ -393,7 +123,7 @@ int allreduce(fos_solver* h, int count) {
 }
 
 // partials[count][nacc] --(sharded: local reduce + all-reduce)--> returns from_reduced flag for the finalize kernel
-int finish_reduce(fos_solver* h, const LaunchCtx& c, int count, int nacc, int gate, int* from_reduced, int off = 0) {
+int finish_reduce(fos_solver* h, const LaunchCtx& c, int count, int nacc, int gate, int* from_reduced, int off) {
     if (!h->sharded()) { *from_reduced = 0; return FOS_OK; }
     launch_reduce1(c, count, nacc, gate, off);
     FOS_TRY(allreduce(h, nacc));
@@ -448,6 +178,43 @@ int poll_state(fos_solver* h) {
     }
     return FOS_OK;
 }
+
+// out = [I Q'; Q -I] w, all l rows (sweep + tau-row finalize)
+// deferred = false: the slot-spread rows of `out` (rows of A' under dual tiles) are not finished; tau_row = false: nor is the tau row -- for callers that
+// need neither (the block-direct projection: single-GPU handles only)
+int kkt_apply_full(fos_solver* h, const LaunchCtx& c, const d2* w, d2* out, bool deferred, bool tau_row) {
+    launch_kkt2(c, w, out, 0, deferred || tau_row);          // (the tau-row kernel reads the records the deferred-row kernel leaves)
+    if (!tau_row) return FOS_OK;
+    int fr = 0;
+    FOS_TRY(finish_reduce(h, c, c.S.npart, 3, 0, &fr, c.S.part_off));
+    launch_kkt_finalize(c, w, out, 0, fr);
+    return FOS_OK;
+}
+
+}  // namespace fos
+
+using namespace fos;
+
+// row-sharded operators: slots (this rank's partial sums of A'y, 2n doubles) -> slots_rd (their sum over the ranks), in stream
+int fos_solver::sum_slots_over_ranks(void* self) {
+    fos_solver* h = static_cast<fos_solver*>(self);
+    const double* src = h->S.slots;            // one slot per row of A' ...
+    if (h->cmp_local) {                        // ... or, with dual tiles, the rows' local slot lists added up first
+        launch_slots_compact(h->ctx(), (int)h->n, h->cmp_rec, h->cmp_idx, h->cmp_lpr, h->S.slots, h->cmp_local);
+        src = h->cmp_local;
+    }
+    if (h->host_fn) return host_allreduce(h, src, h->slots_rd, (size_t)2 * (size_t)h->n);
+    if (h->peer_on && h->vec.buf) {            // peer-mapped memory: push + sum, in stream, no library call
+        launch_vec_exchange(h->ctx(), h->vec, ++h->vec_seq, src, h->slots_rd);
+        return FOS_OK;
+    }
+    if (!h->comm) {            // no communicator yet (set-up calls before fos_comm_init, or a single process): the sum is the copy
+        return hipMemcpyAsync(h->slots_rd, src, sizeof(double) * 2 * (size_t)h->n, hipMemcpyDeviceToDevice, h->stream) == hipSuccess ? FOS_OK : FOS_EHIP;
+    }
+    return g_rccl.AllReduce(src, h->slots_rd, (size_t)2 * (size_t)h->n, ncclDouble, ncclSum, h->comm, h->stream) == ncclSuccess ? FOS_OK : FOS_ECOMM;
+}
+
+namespace {
 
 // Has CG solve number `epoch` ended within its first batch of iterations?  No stream synchronisation and nothing in the stream:
 // the kernel that ends a solve writes HostMark.seq in pinned host memory, the marked p update of a batch that runs out before
@@ -593,18 +360,6 @@ int global_setup(fos_solver* h) {
     h->l_global = (int64_t)std::llround(loc[0]) + 1;
     h->nb = std::sqrt(loc[1]);
     h->nc = std::sqrt(loc[2]);
-    return FOS_OK;
-}
-
-// out = [I Q'; Q -I] w, all l rows (sweep + tau-row finalize)
-// deferred = false: the slot-spread rows of `out` (rows of A' under dual tiles) are not finished; tau_row = false: nor is the tau row -- for callers that
-// need neither (the block-direct projection: single-GPU handles only)
-int kkt_apply_full(fos_solver* h, const LaunchCtx& c, const d2* w, d2* out, bool deferred = true, bool tau_row = true) {
-    launch_kkt2(c, w, out, 0, deferred || tau_row);          // (the tau-row kernel reads the records the deferred-row kernel leaves)
-    if (!tau_row) return FOS_OK;
-    int fr = 0;
-    FOS_TRY(finish_reduce(h, c, c.S.npart, 3, 0, &fr, c.S.part_off));
-    launch_kkt_finalize(c, w, out, 0, fr);
     return FOS_OK;
 }
 
@@ -821,141 +576,9 @@ int cg_solve(fos_solver* h, d2* x, const d2* rhs, double tol, int maxit, int64_t
     return FOS_OK;
 }
 
-// prox!(y, S1::IndAffine([Q -I], 0), x) on a block-separable operator: the exact projection in THREE KKT sweeps.
-//   The projection of (u, v) onto {v = Q u} is (u^, Q u^) with (I - Q^2) u^ = u - Q v =: g   (Q' = -Q).  With h = [c; b], M = [0 A'; -A 0]:
-//       I - Q^2 = [ P + h h', -M h ; -(M h)', delta ],   P = blkdiag(I + A'A, I + AA'),  delta = 1 + h'h
-//               = D + W C W',   D = blkdiag(P, delta),  W = [ (h; 0), (M h; 0), e_tau ],  C = [1 0 0; 0 0 -1; 0 -1 0]
-//   so by Woodbury  u^ = D^-1 g - [ph, pg, e_tau / delta] kappa,  kappa = (C^-1 + W' D^-1 W)^-1 [ph.g, pg.g, g_tau / delta],  ph = D^-1 (h; 0), pg = D^-1 (M h; 0)
-//   (ph, pg, Q ph, Q pg and the 3 x 3 inverse are formed once).  D^-1 g: the x part is a product with the inverted diagonal blocks of I + A'A,
-//   the y part (I + AA')^-1 g2 = g2 - A q, q = (I + A'A)^-1 A' g2.  Q D^-1 g needs A'(g2 - A q) = q (no sweep) and A x^.  Sweeps, all through the
-//   dual-right-hand-side KKT apply out = (w1 - Q w2, Q w1 - w2):   (1) w = (u, v) -> g;   (2) w = (0, (0, g2, 0)) -> A' g2;   (3) w = ((q,0,0), (x^,0,0)) -> A q, A x^.
-//   `from_T`: h->R already holds g in its first part (set-up: ph, pg); zero_kappa: no border correction (set-up).  Scratch: the CG vectors.
-int prox_affine_direct_block(fos_solver* h, const d2* x, d2* out, bool from_T = false, bool zero_kappa = false) {
-    RoctxRange range("fos:prox_affine_direct_block (3 KKT sweeps + block-diagonal solve)");
-    LaunchCtx c = h->ctx();
-    const LaunchCtx& cb = c;
-    d2 *T = h->R, *W2 = h->PB[0], *Rr = h->AP, *W3 = h->PB[1], *V = h->RHS;
-    double* p1 = h->partials + (size_t)4 * PART_CAP;
-    double* p2 = h->partials + (size_t)5 * PART_CAP;
-    // Cone-sharded handles: D is block diagonal, so everything above is local to a rank -- except the scalars: the tau row of the first apply (summed over
-    // the ranks by kkt_apply_full), the two dots behind kappa and the tau row of the result (c'x^ + b'y^): three exchanges per projection instead of one per
-    // CG iteration.  The sums go through the handle's transport (reduce kernel with the mailbox exchange inside, or reduce kernel + all-reduce).
-    const bool sh = h->sharded();
-    int fr = 0;
-    // (profiling: the three sweeps -- each with the deferred-row kernel and the tau-row finalize of a stand-alone apply -- are the KKT class)
-    int pe = -1;
-    if (!from_T) { pe = prof_begin(h, FOS_PROF_KKT, 1, h->direct_sweeps++); FOS_TRY(kkt_apply_full(h, c, x, T)); prof_end(h, pe); }      // T.x = u - Q v = g
-    int po = prof_begin_other(h, 0);
-    launch_blkdir_prep(cb, T, h->blk_phg, W2, W3, p1);
-    if (sh) { LaunchCtx c2 = c; c2.partials = p1; launch_reduce1(c2, c.vec_blocks, 3, 0); FOS_TRY(allreduce(h, 3)); fr = 1; }
-    prof_end(h, po);
-    pe = prof_begin(h, FOS_PROF_KKT, 1, h->direct_sweeps++);
-    FOS_TRY(kkt_apply_full(h, c, W2, Rr, true, false));                // Rr.x = -Q (0, g2, 0): its x part is -A' g2 (rows of A': the deferred rows; the tau row is not needed)
-    prof_end(h, pe);
-    po = prof_begin_other(h, 0);
-    launch_blkdir_solve(cb, h->blk_n, h->blk_goff, h->blk_ioff, h->blk_idx, h->blk_ginv, Rr, T, W3, h->blk_ctx);
-    prof_end(h, po);
-    pe = prof_begin(h, FOS_PROF_KKT, 1, h->direct_sweeps++);
-    // V.y = -A q, V.x = A x^ on the rows of A -- rows the sweep finishes itself; with dual tiles neither the rows of A' nor the tau row (c'x^: the solve kernel's records) are needed.
-    // The tau row of THIS apply is needed by nobody, and on a sharded handle its reduce would overwrite the prep sums in c.reduced that blkdir_combine reads
-    // (from_reduced) and add an exchange that only some ranks make: never run there.  The deferred-row kernel runs where rows of A are slot-spread.
-    FOS_TRY(kkt_apply_full(h, c, W3, V, !h->blk_skip_tail, !h->blk_skip_tail && !sh));
-    prof_end(h, pe);
-    po = prof_begin_other(h, 0);
-    launch_blkdir_combine(cb, T, W3, V, h->blk_phg, h->blk_qphg, h->blk_prm, zero_kappa ? 1 : 0, out, p1, p2, fr);
-    if (sh && h->peer_on && cb.peer) {
-        // mailbox transports: the tau kernel sums the rank's record, exchanges it and forms the tau row itself (one launch instead of three)
-        launch_blkdir_tau(cb, T, h->blk_qphg, h->blk_prm, zero_kappa ? 1 : 0, out, p1, p2, h->blk_ctx, h->blk_n, 2);
-    } else {
-        if (sh) {
-            double* p3 = p1;                                           // (the prep records are spent)
-            launch_blkdir_tausum(cb, p2, h->blk_ctx, h->blk_n, p3);
-            LaunchCtx c3 = c; c3.partials = p3;
-            launch_reduce1(c3, 1, 1, 0);
-            FOS_TRY(allreduce(h, 1));
-        }
-        launch_blkdir_tau(cb, T, h->blk_qphg, h->blk_prm, zero_kappa ? 1 : 0, out, p1, p2, h->blk_ctx, h->blk_n, fr);
-    }
-    prof_end(h, po);
-    h->cgiter = 0;
-    return check_launch("block-direct affine projection");
-}
-
-// prox!(y, S1::IndAffine([Q -I], 0), x) with the result left in h->SOL        HSDE.jl:12-15 (direct = true)
-// d = D^-1 t1, D = diag(I + A'A, I + A A'), through K^-1 alone: two Q sweeps (B' t_other, then B e) around ONE pass over the stored triangle with the two
-// right-hand sides (t_own, B' t_other).  dots != nullptr: the workgroups' shares of h'd and g'd (returns how many).  Scratch: PB[0], red_s, red_pq, red_yk.
-int reduced_dinv(fos_solver* h, const LaunchCtx& c, const double* t, double* d, double* dots) {
-    launch_red_in1(c, h->red_swap, t, h->PB[0]);
-    launch_q1(c, Q_PLAIN, h->PB[0], 0, 1.0, h->red_s);                  // (the tau row is not needed: no finalize)
-    launch_red_pair(c, h->red, h->red_swap, t, h->red_s, h->red_pq);
-    launch_red_symm(c, h->red, h->red_pq, h->red_yk);                   // (K^-1 t_own, e = K^-1 B' t_other)
-    launch_red_in2(c, h->red_swap, h->red_yk, h->PB[0]);
-    launch_q1(c, Q_PLAIN, h->PB[0], 0, 1.0, h->red_s);
-    return launch_red_d(c, h->red_swap, t, h->red_s, h->red_yk, h->cb, h->red_g, d, dots);
-}
-// w = G^-1 t (add: w += G^-1 t) by the border formula of direct_reduced.hip
-void reduced_solve(fos_solver* h, const LaunchCtx& c, const double* t, double* w, int add) {
-    const int nrec = reduced_dinv(h, c, t, h->red_d, h->red_dots);
-    launch_red_w(c, t, h->red_d, h->red_p, h->red_q, h->red_dots, nrec, h->red_minv, add, w);
-}
-// out_plain = Q v for a plain l-vector v, tau row included (scratch: AP)
-int reduced_q_plain(fos_solver* h, const LaunchCtx& c, const double* v, double* out) {
-    int fr = 0;
-    launch_set_comp(c, h->AP, v, 0);
-    launch_q1(c, Q_PLAIN, h->AP, 0, 1.0, out);
-    FOS_TRY(finish_reduce(h, c, c.S.npart, 1, 0, &fr, c.S.part_off));
-    launch_q1_finalize(c, Q_PLAIN, h->AP, 0, 1.0, out, fr);
-    return FOS_OK;
-}
-int prox_affine_direct_reduced(fos_solver* h, const d2* x) {
-    RoctxRange range("fos:prox_affine_direct_reduced (Q sweeps + one pass over the lower triangle of K^-1)");
-    LaunchCtx c = h->ctx();
-    int fr = 0;
-    double *t = h->dvec[0], *w = h->dvec[1];
-    launch_q1(c, Q_VFROMU, x, 0, 1.0, h->R);                           // R = (u, Q u)
-    FOS_TRY(finish_reduce(h, c, c.S.npart, 1, 0, &fr, c.S.part_off));
-    launch_q1_finalize(c, Q_VFROMU, x, 0, 1.0, h->R, fr);
-    launch_direct_rhs(c, h->R, x, t);                                  // t = Q u - v
-    reduced_solve(h, c, t, w, 0);
-    for (int it = 0; it < h->red_refine; ++it) {                       // w += G^-1 (t - G w), G w = w - Q Q w
-        FOS_TRY(reduced_q_plain(h, c, w, h->red_z));
-        FOS_TRY(reduced_q_plain(h, c, h->red_z, h->red_z));
-        launch_red_resid(c, t, w, h->red_z, h->red_r);
-        reduced_solve(h, c, h->red_r, w, 1);
-    }
-    launch_set_comp(c, h->AP, w, 0);                                   // (w, 0)
-    launch_q1(c, Q_VFROMU, h->AP, 0, 1.0, h->R);                       // R = (w, Q w)
-    FOS_TRY(finish_reduce(h, c, c.S.npart, 1, 0, &fr, c.S.part_off));
-    launch_q1_finalize(c, Q_VFROMU, h->AP, 0, 1.0, h->R, fr);
-    launch_direct_finish(c, x, h->R, h->SOL);                          // (u + Q w, v + w)
-    h->cgiter = 0;
-    return check_launch("reduced direct affine projection");
-}
-
-int prox_affine_direct(fos_solver* h, const d2* x) {
-    if (h->direct_red) return prox_affine_direct_reduced(h, x);
-    if (h->direct_blk) return prox_affine_direct_block(h, x, h->SOL);
-    RoctxRange range("fos:prox_affine_direct (2 Q sweeps + dense symmetric matvec)");
-    LaunchCtx c = h->ctx();
-    int fr = 0;
-    // (scratch: the CG vectors R, AP -- the input may be X, Y or W)
-    launch_q1(c, Q_VFROMU, x, 0, 1.0, h->R);                           // R = (u, Q u)
-    FOS_TRY(finish_reduce(h, c, c.S.npart, 1, 0, &fr, c.S.part_off));
-    launch_q1_finalize(c, Q_VFROMU, x, 0, 1.0, h->R, fr);
-    launch_direct_rhs(c, h->R, x, h->dvec[0]);                         // t = Q u - v
-    launch_dense_symv(c, h->Gld, h->Ginv, h->dvec[0], h->dvec[1]);     // w = (I + Q Q')^-1 t
-    launch_set_comp(c, h->AP, h->dvec[1], 0);                          // (w, 0)
-    launch_q1(c, Q_VFROMU, h->AP, 0, 1.0, h->R);                       // R = (w, Q w)
-    FOS_TRY(finish_reduce(h, c, c.S.npart, 1, 0, &fr, c.S.part_off));
-    launch_q1_finalize(c, Q_VFROMU, h->AP, 0, 1.0, h->R, fr);
-    launch_direct_finish(c, x, h->R, h->SOL);                          // (u + Q w, v + w)
-    h->cgiter = 0;
-    return check_launch("direct affine projection");
-}
-
 // prox!(y, S1::AffinePlusLinear, x) with the result left in h->SOL       affinepluslinear.jl:83-126
 int prox_affine(fos_solver* h, const d2* x, const PostFn* post = nullptr, bool* post_ran = nullptr) {
-    if (h->direct) return prox_affine_direct(h, x);
+    if (h->direct_exact()) return prox_affine_direct(h, x);
     RoctxRange range("fos:prox_affine (rhs build + warm-started CG over the KKT operator)");
     LaunchCtx c = h->ctx();
     // The right-hand side [x1 - Q x2; 0] (:94-95) costs a sweep over A, and CG starts with another one for rhs - M y (:32-33).
@@ -980,10 +603,11 @@ int prox_affine(fos_solver* h, const d2* x, const PostFn* post = nullptr, bool* 
     h->shift_ready = false;                                             // (SOL changes below)
     // :108-112   tol = max(0.2^sqrt(i), size(A,2)*eps())
     const double eps = 2.220446049250313e-16;
-    double tol = std::max(h->direct_cg ? 0.0 : std::pow(0.2, std::sqrt((double)h->prox_i)), (double)h->l_global * eps);
+    const bool at_floor = h->direct_form == DIRECT_CG;                  // direct = true by CG: the tolerance floor from the first call on
+    double tol = std::max(at_floor ? 0.0 : std::pow(0.2, std::sqrt((double)h->prox_i)), (double)h->l_global * eps);
     h->prox_i += 1;                                                     // :114
     int64_t it = 0;
-    const int64_t cap = h->direct_cg ? 10000 : 1000;                   // (:115: 1000; the exact projection is given the default cap of conjugategradients.jl:31)
+    const int64_t cap = at_floor ? 10000 : 1000;                   // (:115: 1000; the exact projection is given the default cap of conjugategradients.jl:31)
     if (fused_rhs) FOS_TRY(cg_solve(h, h->SOL, x, tol, cap, &it, h->RHS, post, post_ran));
     else FOS_TRY(cg_solve(h, h->SOL, h->RHS, tol, cap, &it, nullptr, post, post_ran));          // :115-117 ; y aliases xinit (:106,:122)
     h->cgiter = it;                                                     // :121
@@ -1332,7 +956,7 @@ int step_once(fos_solver* h, int64_t i, const d2** check_on, bool will_check, bo
                     psd_fuse_possible(cg, h->npsd, h->psd_kmin, h->psd_kmax, h->psd_V[h->psd_cur], h->psd_V[1 - h->psd_cur], h->psd_have_prev, h->psd_redo,
                                       h->psd_phase_limit)) {
                     RoctxRange range("fos:relaxation + PSD projection + final pass (one launch)");
-                    const bool sh = h->in_step && h->shift_fuse && !h->direct;
+                    const bool sh = h->in_step && h->shift_fuse && !h->direct_exact();
                     PsdFuse fz{};
                     fz.sol = h->SOL; fz.xv = h->X; fz.shift = sh ? h->RHS : nullptr;
                     fz.a1 = h->alpha1; fz.alpha = h->alpha; fz.alpha2 = h->alpha2;
@@ -1416,13 +1040,13 @@ int step_finish_launch(fos_solver* h, const LaunchCtx& c) {
     switch (h->alg) {
         case FOS_ALG_GAP: {
             // (inside fos_step, CG projection: the kernel also leaves SOL - [0; X.y] in RHS for the next iteration's CG start)
-            const bool sh = h->in_step && h->shift_fuse && !h->direct;
+            const bool sh = h->in_step && h->shift_fuse && !h->direct_exact();
             launch_gap_final(c, h->X, h->T2, h->T1, h->alpha, h->alpha2, sh ? h->RHS : nullptr, h->SOL);          // gap.jl:58,78
             h->shift_ready = sh;
             return FOS_OK;
         }
         case FOS_ALG_GAPA: {
-            const bool sh = h->in_step && h->shift_fuse && !h->direct;
+            const bool sh = h->in_step && h->shift_fuse && !h->direct_exact();
             launch_gapa_final(c, h->X, h->T2, h->T1, h->alpha, sh ? h->RHS : nullptr, h->SOL);                    // gapa.jl:77,96,103
             h->shift_ready = sh;
             int fr = 0;
@@ -1513,237 +1137,6 @@ void add_cones(int64_t offset, bool is_K1, int64_t nK, const int32_t* type, cons
             else soc.push_back(cd);
         }
     }
-}
-
-// ---- direct = true, block-separable operators: the set-up.  Columns j, j' of A belong to one block when they share a row (connected components of the
-// pattern of A'A); separable = every component has at most BLKDIR_MAX columns.  Per block G_b = I + A_b' A_b is formed on the host (row-wise outer
-// products), inverted through its Cholesky factor and polished by one Newton step in extended precision; ph, pg and the 3 x 3 border system follow
-// from two runs of the device path itself.  *ok = false: not separable (nothing allocated).
-// v[0..2] <- their sums over the ranks of a sharded handle (set-up: through the handle's transport, one host round trip); no-op on one GPU
-int global_sum3(fos_solver* h, double* v) {
-    if (!h->sharded()) return FOS_OK;
-    LaunchCtx c = h->ctx();
-    FOS_HIP(hipMemcpyAsync(h->partials, v, sizeof(double) * 3, hipMemcpyHostToDevice, h->stream));
-    launch_reduce1(c, 1, 3, 0);
-    FOS_TRY(allreduce(h, 3));
-    FOS_HIP(hipMemcpyAsync(v, h->reduced, sizeof(double) * 3, hipMemcpyDeviceToHost, h->stream));
-    return poll_state(h);
-}
-
-int blkdir_setup(fos_solver* h, const int64_t* colptr, const int64_t* rowval, const double* nzval, bool* ok) {
-    *ok = false;
-    const int64_t n = h->n, m = h->m, l = h->l;
-    // (sharded handles: every rank takes part in the vote below, whatever its own operator looks like)
-    bool local_ok = !(n < 1 || n > (int64_t)INT32_MAX);
-    if (!local_ok && !h->sharded()) return FOS_OK;
-    std::vector<int32_t> parent((size_t)n);
-    for (int64_t j = 0; j < n; ++j) parent[(size_t)j] = (int32_t)j;
-    auto find = [&](int32_t a) { while (parent[(size_t)a] != a) { parent[(size_t)a] = parent[(size_t)parent[(size_t)a]]; a = parent[(size_t)a]; } return a; };
-    bool bad_index = false;
-    {
-        std::vector<int32_t> first((size_t)m, -1);
-        for (int64_t j = 0; j < n && !bad_index; ++j)
-            for (int64_t p = colptr[j] - 1; p < colptr[j + 1] - 1; ++p) {
-                const int64_t r = rowval[p] - 1;
-                if (r < 0 || r >= m) { bad_index = true; local_ok = false; break; }          // (reported behind the vote: the peers of a sharded handle are waiting in it)
-                if (first[(size_t)r] < 0) { first[(size_t)r] = (int32_t)j; continue; }
-                const int32_t a = find((int32_t)j), b = find(first[(size_t)r]);
-                if (a != b) parent[(size_t)std::max(a, b)] = std::min(a, b);       // the root of a component is its smallest column
-            }
-    }
-    std::vector<int32_t> cnt((size_t)n, 0), blkid((size_t)n, -1);
-    for (int64_t j = 0; j < n; ++j) cnt[(size_t)find((int32_t)j)] += 1;
-    int nblk = 0;
-    size_t gtotal = 0;
-    for (int64_t j = 0; j < n && local_ok; ++j)
-        if (cnt[(size_t)j] > 0) {
-            if (cnt[(size_t)j] > BLKDIR_MAX) { local_ok = false; break; }          // a block of I + A'A too large to invert densely per wavefront
-            blkid[(size_t)j] = nblk++;
-            gtotal += (size_t)cnt[(size_t)j] * (size_t)cnt[(size_t)j];
-        }
-    if (gtotal * sizeof(double) > ((size_t)1 << 31)) local_ok = false;
-    {
-        // the form is taken by ALL ranks or by none (its reductions are collective)
-        double vote[3] = {local_ok ? 1.0 : 0.0, 0.0, 0.0};
-        FOS_TRY(global_sum3(h, vote));
-        if (bad_index) { set_error("fos_enable_direct: row index out of range"); return FOS_EINVAL; }
-        if (h->sharded() ? vote[0] != (double)h->nranks : !local_ok) return FOS_OK;
-    }
-    std::vector<int32_t> ioff((size_t)nblk + 1, 0), idx((size_t)n);
-    std::vector<int64_t> goff((size_t)nblk, 0);
-    for (int64_t j = 0; j < n; ++j) if (cnt[(size_t)j] > 0) ioff[(size_t)blkid[(size_t)j] + 1] = cnt[(size_t)j];
-    for (int b = 0; b < nblk; ++b) { goff[(size_t)b] = b ? goff[(size_t)b - 1] + (int64_t)(ioff[(size_t)b] - ioff[(size_t)b - 1]) * (ioff[(size_t)b] - ioff[(size_t)b - 1]) : 0; ioff[(size_t)b + 1] += ioff[(size_t)b]; }
-    {
-        std::vector<int32_t> fill(ioff.begin(), ioff.end() - 1);
-        for (int64_t j = 0; j < n; ++j) idx[(size_t)fill[(size_t)blkid[(size_t)find((int32_t)j)]]++] = (int32_t)j;      // ascending inside a block
-    }
-    std::vector<double> ginv(gtotal, 0.0);
-    std::vector<int32_t> rowlocal((size_t)m, -1);            // (the blocks' row sets are disjoint: one shared map, no conflicts between threads)
-    std::atomic<int> next{0}, bad{0};
-    auto work = [&]() {
-        std::vector<int32_t> rcount, rstart, ecol;
-        std::vector<double> eval, G;
-        std::vector<long double> Lc, X, Y;
-        for (;;) {
-            const int b = next.fetch_add(1);
-            if (b >= nblk) break;
-            const int32_t i0 = ioff[(size_t)b], sdim = ioff[(size_t)b + 1] - i0;
-            // rows of the block, in order of first appearance; entries bucketed by row
-            int32_t nrows = 0;
-            int64_t nent = 0;
-            rcount.clear();
-            for (int32_t q = 0; q < sdim; ++q) {
-                const int64_t j = idx[(size_t)i0 + q];
-                for (int64_t p = colptr[j] - 1; p < colptr[j + 1] - 1; ++p) {
-                    const int64_t r = rowval[p] - 1;
-                    if (rowlocal[(size_t)r] < 0) { rowlocal[(size_t)r] = nrows++; rcount.push_back(0); }
-                    rcount[(size_t)rowlocal[(size_t)r]] += 1;
-                    ++nent;
-                }
-            }
-            rstart.assign((size_t)nrows + 1, 0);
-            for (int32_t r = 0; r < nrows; ++r) rstart[(size_t)r + 1] = rstart[(size_t)r] + rcount[(size_t)r];
-            ecol.resize((size_t)nent); eval.resize((size_t)nent);
-            std::fill(rcount.begin(), rcount.end(), 0);
-            for (int32_t q = 0; q < sdim; ++q) {
-                const int64_t j = idx[(size_t)i0 + q];
-                for (int64_t p = colptr[j] - 1; p < colptr[j + 1] - 1; ++p) {
-                    const int32_t r = rowlocal[(size_t)(rowval[p] - 1)];
-                    const size_t at = (size_t)rstart[(size_t)r] + (size_t)rcount[(size_t)r]++;
-                    ecol[at] = q; eval[at] = nzval[p];
-                }
-            }
-            G.assign((size_t)sdim * sdim, 0.0);
-            for (int32_t r = 0; r < nrows; ++r)
-                for (int32_t a = rstart[(size_t)r]; a < rstart[(size_t)r + 1]; ++a)
-                    for (int32_t c2 = a; c2 < rstart[(size_t)r + 1]; ++c2) G[(size_t)ecol[(size_t)a] * sdim + ecol[(size_t)c2]] += eval[(size_t)a] * eval[(size_t)c2];
-            for (int32_t a = 0; a < sdim; ++a) {
-                G[(size_t)a * sdim + a] += 1.0;
-                for (int32_t c2 = a + 1; c2 < sdim; ++c2) {          // (entries of a row arrive in ascending column order: the upper triangle was filled)
-                    const double v = G[(size_t)a * sdim + c2] + G[(size_t)c2 * sdim + a];
-                    G[(size_t)a * sdim + c2] = G[(size_t)c2 * sdim + a] = v;
-                }
-            }
-            // X = G^-1 through Cholesky (extended precision: the blocks are tiny), one Newton step X <- X + X (I - G X)
-            Lc.assign((size_t)sdim * sdim, 0.0L);
-            bool pd = true;
-            for (int32_t j = 0; j < sdim && pd; ++j) {
-                long double dj = G[(size_t)j * sdim + j];
-                for (int32_t k = 0; k < j; ++k) dj -= Lc[(size_t)j * sdim + k] * Lc[(size_t)j * sdim + k];
-                if (!(dj > 0.0L)) { pd = false; break; }
-                const long double ljj = sqrtl(dj);
-                Lc[(size_t)j * sdim + j] = ljj;
-                for (int32_t i = j + 1; i < sdim; ++i) {
-                    long double v = G[(size_t)i * sdim + j];
-                    for (int32_t k = 0; k < j; ++k) v -= Lc[(size_t)i * sdim + k] * Lc[(size_t)j * sdim + k];
-                    Lc[(size_t)i * sdim + j] = v / ljj;
-                }
-            }
-            if (!pd) { bad.store(1); continue; }
-            X.assign((size_t)sdim * sdim, 0.0L);
-            Y.assign((size_t)sdim, 0.0L);
-            for (int32_t e = 0; e < sdim; ++e) {
-                for (int32_t i = 0; i < sdim; ++i) { long double v = (i == e) ? 1.0L : 0.0L; for (int32_t k = 0; k < i; ++k) v -= Lc[(size_t)i * sdim + k] * Y[(size_t)k]; Y[(size_t)i] = v / Lc[(size_t)i * sdim + i]; }
-                for (int32_t i = sdim - 1; i >= 0; --i) { long double v = Y[(size_t)i]; for (int32_t k = i + 1; k < sdim; ++k) v -= Lc[(size_t)k * sdim + i] * X[(size_t)e * sdim + k]; X[(size_t)e * sdim + i] = v / Lc[(size_t)i * sdim + i]; }
-            }
-            double* out = ginv.data() + goff[(size_t)b];
-            for (int32_t e = 0; e < sdim; ++e)
-                for (int32_t i = 0; i < sdim; ++i) out[(size_t)e * sdim + i] = (double)((X[(size_t)e * sdim + i] + X[(size_t)i * sdim + e]) / 2);      // symmetric, column-major
-        }
-    };
-    {
-        const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-        std::vector<std::thread> pool;
-        for (unsigned t = 1; t < hw; ++t) pool.emplace_back(work);
-        work();
-        for (auto& t : pool) t.join();
-    }
-    {
-        double vote[3] = {bad.load() ? 1.0 : 0.0, 0.0, 0.0};       // (collective again: a rank that failed here must not leave its peers in the sums below)
-        FOS_TRY(global_sum3(h, vote));
-        if (bad.load()) { set_error("fos_enable_direct: I + A'A has a block that is not positive definite (non-finite entries in A?)"); return FOS_EINVAL; }
-        if (vote[0] != 0.0) { set_error("fos_enable_direct: I + A'A has a block that is not positive definite on another rank"); return FOS_EINVAL; }
-    }
-    // ---- device data
-    FOS_TRY(dev_upload(h, &h->blk_goff, goff));
-    FOS_TRY(dev_upload(h, &h->blk_ioff, ioff));
-    FOS_TRY(dev_upload(h, &h->blk_idx, idx));
-    FOS_TRY(dev_upload(h, &h->blk_ginv, ginv));
-    h->blk_n = nblk;
-    FOS_TRY(dev_alloc(h, &h->blk_phg, (size_t)l));
-    FOS_TRY(dev_alloc(h, &h->blk_qphg, (size_t)l));
-    FOS_TRY(dev_alloc(h, &h->blk_prm, 16));
-    FOS_TRY(dev_alloc(h, &h->blk_ctx, (size_t)nblk));
-    // (rows of A that the sweep does not finish itself -- rows wider than one tile chunk are slot-spread too -- need the deferred-row kernel behind the third apply)
-    h->blk_skip_tail = !(getenv("FOS_BLKDIR_FULL_APPLY") && atoi(getenv("FOS_BLKDIR_FULL_APPLY")) != 0);
-    for (int32_t r : h->hostS.def_rows) if (r >= n) { h->blk_skip_tail = false; break; }
-    FOS_HIP(hipMemset(h->blk_phg, 0, sizeof(d2) * (size_t)l));
-    FOS_HIP(hipMemset(h->blk_qphg, 0, sizeof(d2) * (size_t)l));
-    // ---- the border: h = [c; b], M h = [A'b; -A c], ph = D^-1 (h; 0), pg = D^-1 (M h; 0) by two runs of the device path without the border terms
-    std::vector<double> cbv((size_t)(n + m));
-    FOS_HIP(hipMemcpy(cbv.data(), h->cb, sizeof(double) * (size_t)(n + m), hipMemcpyDeviceToHost));
-    long double hh2 = 0.0L;
-    for (double v : cbv) hh2 += (long double)v * v;
-    {
-        double g3[3] = {(double)hh2, 0.0, 0.0};                    // |[c; b]|^2 over all ranks
-        FOS_TRY(global_sum3(h, g3));
-        hh2 = g3[0];
-    }
-    const double delta = (double)(1.0L + hh2);
-    std::vector<double> prm(16, 0.0);
-    prm[9] = delta;
-    FOS_HIP(hipMemcpy(h->blk_prm, prm.data(), sizeof(double) * 16, hipMemcpyHostToDevice));
-    std::vector<double> mh((size_t)(n + m), 0.0);
-    for (int64_t j = 0; j < n; ++j) {
-        long double acc = 0.0L;
-        for (int64_t p = colptr[j] - 1; p < colptr[j + 1] - 1; ++p) {
-            const int64_t r = rowval[p] - 1;
-            acc += (long double)nzval[p] * cbv[(size_t)(n + r)];
-            mh[(size_t)(n + r)] -= nzval[p] * cbv[(size_t)j];
-        }
-        mh[(size_t)j] = (double)acc;
-    }
-    std::vector<d2> tv((size_t)l), res((size_t)l), phg((size_t)l), qphg((size_t)l);
-    for (int pass = 0; pass < 2; ++pass) {
-        const std::vector<double>& src = pass == 0 ? cbv : mh;
-        for (int64_t i = 0; i < l - 1; ++i) tv[(size_t)i] = make_double2(src[(size_t)i], 0.0);
-        tv[(size_t)l - 1] = make_double2(0.0, 0.0);
-        FOS_HIP(hipMemcpy(h->R, tv.data(), sizeof(d2) * (size_t)l, hipMemcpyHostToDevice));
-        FOS_TRY(prox_affine_direct_block(h, nullptr, h->W, true, true));
-        FOS_HIP(hipStreamSynchronize(h->stream));
-        FOS_HIP(hipMemcpy(res.data(), h->W, sizeof(d2) * (size_t)l, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < l; ++i) {
-            if (pass == 0) { phg[(size_t)i].x = res[(size_t)i].x; qphg[(size_t)i].x = res[(size_t)i].y; }
-            else { phg[(size_t)i].y = res[(size_t)i].x; qphg[(size_t)i].y = res[(size_t)i].y; }
-        }
-    }
-    long double hph = 0, hpg = 0, gph = 0, gpg = 0;
-    for (int64_t i = 0; i < l - 1; ++i) {
-        hph += (long double)cbv[(size_t)i] * phg[(size_t)i].x; hpg += (long double)cbv[(size_t)i] * phg[(size_t)i].y;
-        gph += (long double)mh[(size_t)i] * phg[(size_t)i].x; gpg += (long double)mh[(size_t)i] * phg[(size_t)i].y;
-    }
-    {
-        double g3[3] = {(double)hph, (double)hpg, (double)gph}, g1[3] = {(double)gpg, 0.0, 0.0};       // the border's dots over all ranks
-        FOS_TRY(global_sum3(h, g3));
-        FOS_TRY(global_sum3(h, g1));
-        if (h->sharded()) { hph = g3[0]; hpg = g3[1]; gph = g3[2]; gpg = g1[0]; }
-    }
-    // S3 = C^-1 + W' D^-1 W,  C^-1 = [1 0 0; 0 0 -1; 0 -1 0]
-    long double S3[3][3] = {{1 + hph, hpg, 0}, {gph, gpg, -1}, {0, -1, 1 / (long double)delta}}, Inv[3][3];
-    const long double det = S3[0][0] * (S3[1][1] * S3[2][2] - S3[1][2] * S3[2][1]) - S3[0][1] * (S3[1][0] * S3[2][2] - S3[1][2] * S3[2][0]) +
-                            S3[0][2] * (S3[1][0] * S3[2][1] - S3[1][1] * S3[2][0]);
-    if (!(fabsl(det) > 0.0L) || !std::isfinite((double)det)) { set_error("fos_enable_direct: the 3 x 3 border system of the block form is singular"); return FOS_EINVAL; }
-    for (int a = 0; a < 3; ++a)
-        for (int bq = 0; bq < 3; ++bq) {
-            const int a1 = (a + 1) % 3, a2 = (a + 2) % 3, b1 = (bq + 1) % 3, b2 = (bq + 2) % 3;
-            Inv[bq][a] = (S3[a1][b1] * S3[a2][b2] - S3[a1][b2] * S3[a2][b1]) / det;          // adjugate, transposed
-        }
-    for (int a = 0; a < 3; ++a) for (int bq = 0; bq < 3; ++bq) prm[(size_t)(3 * a + bq)] = (double)Inv[a][bq];
-    FOS_HIP(hipMemcpy(h->blk_prm, prm.data(), sizeof(double) * 16, hipMemcpyHostToDevice));
-    FOS_HIP(hipMemcpy(h->blk_phg, phg.data(), sizeof(d2) * (size_t)l, hipMemcpyHostToDevice));
-    FOS_HIP(hipMemcpy(h->blk_qphg, qphg.data(), sizeof(d2) * (size_t)l, hipMemcpyHostToDevice));
-    *ok = true;
-    return FOS_OK;
 }
 
 }  // namespace
@@ -2630,505 +2023,6 @@ int fos_set_alg(fos_handle h, int alg, double alpha, double alpha1, double alpha
     FOS_HIP(hipMemsetAsync(h->Y, 0, sizeof(d2) * h->l, h->stream));
     FOS_HIP(hipMemsetAsync(h->XOLD, 0, sizeof(d2) * h->l, h->stream));
     FOS_HIP(hipStreamSynchronize(h->stream));
-    return FOS_OK;
-}
-
-// ---- the inverse of the dense symmetric positive definite matrix of a direct form (I + Q Q' or K), shared by the dense form, the reduced form and the test entry.
-// G: L x L column-major (L % 64 == 0, padding = identity), of order c.l; B0, B1, B2: L x L work buffers; dv0, dv1: two L-vectors; partials: 256 doubles.
-// *Xout: the buffer (B1 or B2) that holds the accepted inverse.
-struct DenseInv {
-    int used = FOS_DIRECT_FACTOR_NEWTON;       // the factor that produced *Xout
-    int steps = 0;                             // Newton-Schulz steps (Newton), polish steps (Cholesky)
-    double seconds = 0.0, probe = 0.0;
-    bool fell_back = false;
-    int64_t bad_col = -1;                      // first column whose Cholesky pivot was not a positive finite number
-};
-#define INV_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error("%s set-up: %s -> %s", what, #expr, hipGetErrorString(_e)); return FOS_EHIP; } } while (0)
-// the start vector of the power iteration (which = 0) and three more of its kind for the probe
-static void direct_test_vector(int64_t k, int which, std::vector<double>& v) {
-    for (int64_t i = 0; i < k; ++i) v[i] = 1.0 + 0.37 * std::sin((1.7 + 0.6 * which) * (double)i + (double)which);
-}
-// Newton-Schulz:  X_0 = I / (1.25 lambda~),  X_{k+1} = 2 X_k - X_k (G X_k),  lambda~ a power-iteration estimate of lambda_max(G); accepted when max |G X - I| <= 1e-12
-static int dense_inverse_newton(const LaunchCtx& c, int64_t L, const double* G, double* B0, double* B1, double* B2, double* dv0, double* dv1, double* partials,
-                                const char* what, const char* gname, double** Xout, int* steps) {
-    const int64_t l = c.l;
-    // ---- power iteration for lambda_max(G) (Rayleigh quotients from below; host-side norms of an l-vector)
-    std::vector<double> v((size_t)L, 0.0), w((size_t)L, 0.0);
-    direct_test_vector(l, 0, v);
-    double lam = 1.0;
-    for (int it = 0; it < 20; ++it) {
-        double nv = 0.0;
-        for (int64_t i = 0; i < l; ++i) nv += v[i] * v[i];
-        nv = std::sqrt(nv);
-        for (int64_t i = 0; i < l; ++i) v[i] /= nv;
-        INV_HIP(hipMemcpyAsync(dv0, v.data(), sizeof(double) * l, hipMemcpyHostToDevice, c.stream));
-        launch_dense_symv(c, L, G, dv0, dv1);
-        INV_HIP(hipMemcpyAsync(w.data(), dv1, sizeof(double) * l, hipMemcpyDeviceToHost, c.stream));
-        INV_HIP(hipStreamSynchronize(c.stream));
-        double nw = 0.0;
-        for (int64_t i = 0; i < l; ++i) nw += w[i] * w[i];
-        nw = std::sqrt(nw);
-        if (!(nw == nw) || nw > 1e300) { set_error("direct=true: the operator has non-finite entries"); return FOS_EINVAL; }
-        lam = std::max(lam, nw);
-        v.swap(w);
-    }
-    // ---- Newton-Schulz
-    INV_HIP(hipMemsetAsync(B1, 0, sizeof(double) * (size_t)L * (size_t)L, c.stream));
-    launch_dense_scale_identity(c, L, B1, 1.0 / (1.25 * lam));              // X_0
-    double *X = B1, *Xn = B2;
-    const int planned = (int)std::ceil(std::log2(std::max(1.0, lam))) + 7;
-    double resid = 1.0;
-    int it = 0;
-    std::vector<double> part(256);
-    for (; it < planned + 6; ++it) {
-        launch_dense_gemm(c, (int)L, 1.0, G, X, 0.0, nullptr, B0);          // Y = G X
-        if (it >= planned) {                                                // converged?  max |Y - I|
-            launch_dense_resid(c, L, B0, partials, 256);
-            INV_HIP(hipMemcpyAsync(part.data(), partials, sizeof(double) * 256, hipMemcpyDeviceToHost, c.stream));
-            INV_HIP(hipStreamSynchronize(c.stream));
-            resid = 0.0;
-            for (double r : part) resid = (r > resid || r != r) ? r : resid;
-            if (resid <= 1e-12) break;
-        }
-        launch_dense_gemm(c, (int)L, -1.0, X, B0, 2.0, X, Xn);              // X <- 2 X - X Y
-        std::swap(X, Xn);
-    }
-    if (!(resid <= 1e-12)) { set_error("%s: the inverse of %s did not converge (max |G X - I| = %.3e after %d steps, lambda_max ~ %.3e)", what, gname, resid, it, lam); return FOS_EINVAL; }
-    *Xout = X; *steps = it;
-    return FOS_OK;
-}
-// r = max_j |G (X v_j) - v_j|_inf / |v_j|_inf over four fixed vectors: the acceptance test of the Cholesky path (two matrix-vector products each, no l^3 product)
-static int dense_inverse_probe(const LaunchCtx& c, int64_t L, const double* G, const double* X, double* dv0, double* dv1, const char* what, double* r) {
-    const int64_t l = c.l;
-    std::vector<double> v((size_t)l), w((size_t)l);
-    double worst = 0.0;
-    for (int j = 0; j < 4; ++j) {
-        direct_test_vector(l, j, v);
-        INV_HIP(hipMemcpyAsync(dv0, v.data(), sizeof(double) * l, hipMemcpyHostToDevice, c.stream));
-        launch_dense_symv(c, L, X, dv0, dv1);
-        launch_dense_symv(c, L, G, dv1, dv0);
-        INV_HIP(hipMemcpyAsync(w.data(), dv0, sizeof(double) * l, hipMemcpyDeviceToHost, c.stream));
-        INV_HIP(hipStreamSynchronize(c.stream));
-        double d = 0.0, nv = 0.0;
-        for (int64_t i = 0; i < l; ++i) { const double e = std::fabs(w[i] - v[i]); d = (e > d || e != e) ? e : d; nv = std::max(nv, std::fabs(v[i])); }
-        d /= nv;
-        worst = (d > worst || d != d) ? d : worst;
-    }
-    *r = worst;
-    return FOS_OK;
-}
-// factor = FOS_DIRECT_FACTOR_CHOLESKY: blocked Cholesky (dense_chol.hip), probe, at most two Newton-Schulz polish steps, then -- if the probe stays above 1e-12, or
-// (pivot_fallback) a pivot failed on finite entries -- the Newton-Schulz set-up as if it had been asked for.  Without pivot_fallback a bad pivot is FOS_EINVAL.
-static int dense_spd_inverse(const LaunchCtx& c, int64_t L, const double* G, double* B0, double* B1, double* B2, double* dv0, double* dv1, double* partials,
-                             const char* what, const char* gname, int factor, bool pivot_fallback, double** Xout, DenseInv* st) {
-    *st = DenseInv{};
-    INV_HIP(hipStreamSynchronize(c.stream));                               // G is formed: the clock of the inversion stage starts here
-    const auto t0 = std::chrono::steady_clock::now();
-    auto stamp = [&]() { st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
-    if (factor == FOS_DIRECT_FACTOR_CHOLESKY) {
-        const int64_t l = c.l;
-        {   // the non-finite check of the power iteration: one product with its start vector
-            std::vector<double> v((size_t)l), w((size_t)l);
-            direct_test_vector(l, 0, v);
-            INV_HIP(hipMemcpyAsync(dv0, v.data(), sizeof(double) * l, hipMemcpyHostToDevice, c.stream));
-            launch_dense_symv(c, L, G, dv0, dv1);
-            INV_HIP(hipMemcpyAsync(w.data(), dv1, sizeof(double) * l, hipMemcpyDeviceToHost, c.stream));
-            INV_HIP(hipStreamSynchronize(c.stream));
-            double nw = 0.0;
-            for (int64_t i = 0; i < l; ++i) nw += w[i] * w[i];
-            if (!(nw == nw) || std::sqrt(nw) > 1e300) { set_error("direct=true: the operator has non-finite entries"); return FOS_EINVAL; }
-        }
-        int32_t* dinfo = nullptr;
-        INV_HIP(hipMalloc((void**)&dinfo, sizeof(int32_t)));
-        int32_t info = 0;
-        launch_dense_spd_inverse_chol(c, L, G, B2, B0, B1, dinfo);          // B0: the factor, B1: its inverse, B2: G^-1
-        hipError_t e = hipMemcpyAsync(&info, dinfo, sizeof(int32_t), hipMemcpyDeviceToHost, c.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-        (void)hipFree(dinfo);
-        if (e != hipSuccess) { set_error("%s set-up: Cholesky factorisation -> %s", what, hipGetErrorString(e)); return FOS_EHIP; }
-        FOS_TRY(check_launch("direct=true set-up (Cholesky factorisation)"));
-        bool ok = info == 0;
-        if (!ok) {
-            st->bad_col = (int64_t)info - 1;
-            if (!pivot_fallback) {
-                set_error("%s: Cholesky factorisation of %s: the pivot of column %lld is not a positive finite number (the matrix is not positive definite)", what, gname, (long long)st->bad_col);
-                return FOS_EINVAL;
-            }
-        } else {
-            double *X = B2, *Xn = B1;
-            FOS_TRY(dense_inverse_probe(c, L, G, X, dv0, dv1, what, &st->probe));
-            while (!(st->probe <= 1e-12) && st->steps < 2) {
-                launch_dense_gemm(c, (int)L, 1.0, G, X, 0.0, nullptr, B0);      // Y = G X
-                launch_dense_gemm(c, (int)L, -1.0, X, B0, 2.0, X, Xn);          // X <- 2 X - X Y
-                std::swap(X, Xn);
-                st->steps += 1;
-                FOS_TRY(dense_inverse_probe(c, L, G, X, dv0, dv1, what, &st->probe));
-            }
-            ok = st->probe <= 1e-12;
-            if (ok) { st->used = FOS_DIRECT_FACTOR_CHOLESKY; *Xout = X; stamp(); return FOS_OK; }
-        }
-        st->fell_back = true;
-    }
-    st->used = FOS_DIRECT_FACTOR_NEWTON;
-    FOS_TRY(dense_inverse_newton(c, L, G, B0, B1, B2, dv0, dv1, partials, what, gname, Xout, &st->steps));
-    stamp();
-    return FOS_OK;
-}
-#undef INV_HIP
-
-// direct = true: build (I + Q Q')^-1 once.  A is handed over again (the handle keeps only its device format).
-// G = I + Q Q' = I - Q Q is symmetric positive definite with lambda_min >= 1; its inverse is formed by the Newton-Schulz iteration
-//     X_0 = I / (1.25 lambda~),   X_{k+1} = 2 X_k - X_k (G X_k),        lambda~ = a power-iteration estimate of lambda_max(G),
-// whose residual I - G X_k squares every step: ceil(log2 lambda~) + 7 steps reach rounding level (verified at the end: the
-// entries of G X - I).  Only matrix products are needed: the hand-written fp64 MFMA GEMM of vecops.hip.
-static int enable_direct_auto(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval, int factor) {
-    if (h->row_sharded) { set_error("direct=true is not available on row-sharded handles"); return FOS_EUNSUPPORTED; }
-    if (h->Ginv || (h->blk_ginv && h->blk_ready)) { h->direct = true; h->direct_blk = h->blk_ginv != nullptr && h->blk_ready; return FOS_OK; }
-    const int64_t l = h->l, nnz = colptr[h->n] - 1;
-    // which exact form (FOS_DIRECT_MODE=block|dense|cg forces one; default: the first that applies)
-    const char* mode_env = getenv("FOS_DIRECT_MODE");
-    const std::string mode = mode_env ? mode_env : "auto";
-    if (nnz != h->nnz) { set_error("fos_enable_direct: A has %lld non-zeros, the handle was created with %lld", (long long)nnz, (long long)h->nnz); return FOS_EINVAL; }
-    // (1) block-separable operators: I + A'A block diagonal with small blocks -> three sweeps per projection, any size (blkdir_setup)
-    if (mode == "auto" || mode == "block") {
-        FOS_HIP(hipSetDevice(h->device));
-        bool ok = false;
-        FOS_TRY(blkdir_setup(h, colptr, rowval, nzval, &ok));
-        if (ok) { h->blk_ready = true; h->direct_blk = true; h->direct = true; return FOS_OK; }
-        if (mode == "block") { set_error("FOS_DIRECT_MODE=block: A'A has a diagonal block of more than %d columns", BLKDIR_MAX); return FOS_EUNSUPPORTED; }
-    }
-    // cone-sharded handles: only the block form (its three scalar exchanges per projection go through the handle's transport); collective -- every rank
-    // has taken part in blkdir_setup's vote above
-    if (h->sharded()) { set_error("direct=true on a sharded handle needs the block form on every rank (I + A'A block diagonal with blocks of at most %d columns)", BLKDIR_MAX); return FOS_EUNSUPPORTED; }
-    // beyond what a dense l x l inverse can hold, S1 = IndAffine([Q -I], 0) and S1 = AffinePlusLinear(Q, 0, 0, 1) are still the SAME set (HSDE.jl:12-15 / :22): the
-    // exact projection is what the warm-started CG converges to, so "direct" becomes CG run to its tolerance floor l eps from the first call on
-    // (no 0.2^sqrt(i) schedule: affinepluslinear.jl:108-112 is what direct = true switches off) -- the reference's sparse factorisation is not rebuilt.
-    const int64_t dense_max = getenv("FOS_DIRECT_DENSE_MAX") ? atoll(getenv("FOS_DIRECT_DENSE_MAX")) : 46000;
-    if (l > dense_max || mode == "cg") { h->direct_cg = true; h->direct = false; return FOS_OK; }
-    FOS_HIP(hipSetDevice(h->device));
-    LaunchCtx c = h->ctx();
-    const int64_t L = (l + 63) / 64 * 64;
-    const size_t L2 = (size_t)L * (size_t)L;
-    int64_t *dcp = nullptr, *drv = nullptr;
-    double *dnz = nullptr, *B0 = nullptr, *B1 = nullptr, *B2 = nullptr;       // B0: Q, later Y = G X;  B1, B2: X ping-pong
-    auto cleanup = [&]() { (void)hipFree(dcp); (void)hipFree(drv); (void)hipFree(dnz); (void)hipFree(B0); (void)hipFree(B1); (void)hipFree(B2); };
-    hipError_t e = hipMalloc((void**)&dcp, sizeof(int64_t) * (h->n + 1));
-    if (e == hipSuccess) e = hipMalloc((void**)&drv, sizeof(int64_t) * std::max<int64_t>(nnz, 1));
-    if (e == hipSuccess) e = hipMalloc((void**)&dnz, sizeof(double) * std::max<int64_t>(nnz, 1));
-    if (e == hipSuccess) e = hipMalloc((void**)&B0, sizeof(double) * L2);
-    if (e == hipSuccess) e = hipMalloc((void**)&B1, sizeof(double) * L2);
-    if (e == hipSuccess) e = hipMalloc((void**)&B2, sizeof(double) * L2);
-    if (e != hipSuccess) { cleanup(); set_error("direct=true: hipMalloc of the dense set-up buffers (4 x %zu bytes) failed: %s", L2 * 8, hipGetErrorString(e)); return FOS_ENOMEM; }
-    double* G = nullptr;
-    int rc = dev_alloc(h, &G, L2);
-    if (rc == FOS_OK && !h->dvec[0]) rc = dev_alloc(h, &h->dvec[0], (size_t)L);
-    if (rc == FOS_OK && !h->dvec[1]) rc = dev_alloc(h, &h->dvec[1], (size_t)L);
-    if (rc != FOS_OK) { cleanup(); return rc; }
-    auto fail = [&](int code) { cleanup(); return code; };
-#define DIRECT_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error("direct=true set-up: %s -> %s", #expr, hipGetErrorString(_e)); return fail(FOS_EHIP); } } while (0)
-    DIRECT_HIP(hipMemcpyAsync(dcp, colptr, sizeof(int64_t) * (h->n + 1), hipMemcpyHostToDevice, h->stream));
-    if (nnz) DIRECT_HIP(hipMemcpyAsync(drv, rowval, sizeof(int64_t) * nnz, hipMemcpyHostToDevice, h->stream));
-    if (nnz) DIRECT_HIP(hipMemcpyAsync(dnz, nzval, sizeof(double) * nnz, hipMemcpyHostToDevice, h->stream));
-    DIRECT_HIP(hipMemsetAsync(B0, 0, sizeof(double) * L2, h->stream));
-    DIRECT_HIP(hipMemsetAsync(B1, 0, sizeof(double) * L2, h->stream));
-    launch_dense_q_fill(c, dcp, drv, dnz, B0, L);                           // B0 = Q (zero padded to L x L)
-    launch_dense_scale_identity(c, L, B1, 1.0);                             // B1 = I
-    launch_dense_gemm(c, (int)L, -1.0, B0, B0, 1.0, B1, G);                 // G = I - Q Q  (padding rows/columns: identity)
-    double* X = nullptr;
-    DenseInv inv;
-    rc = dense_spd_inverse(c, L, G, B0, B1, B2, h->dvec[0], h->dvec[1], h->partials, "direct=true", "I + Q Q'", factor, true, &X, &inv);
-    if (rc != FOS_OK) return fail(rc);
-    DIRECT_HIP(hipMemcpyAsync(G, X, sizeof(double) * L2, hipMemcpyDeviceToDevice, h->stream));     // keep the inverse in the handle's buffer
-    DIRECT_HIP(hipStreamSynchronize(h->stream));
-#undef DIRECT_HIP
-    rc = check_launch("direct=true set-up");
-    cleanup();
-    if (rc != FOS_OK) return rc;
-    h->Ginv = G; h->Gld = L; h->direct_iters = inv.steps;
-    h->direct_factor_req = factor; h->direct_factor = inv.used; h->direct_invert_s = inv.seconds; h->direct_probe = inv.probe; h->direct_fell_back = inv.fell_back;
-    h->direct = true;
-    return FOS_OK;
-}
-
-// direct = true, reduced form: K = I + B'B of order k = min(m, n) (B = A, or A' when m < n) formed densely from the sparse A, inverted by the same Newton-Schulz
-// iteration as the dense form, repacked as the tiles of its lower triangle; then p = D^-1 h, q = D^-1 g and the 2 x 2 border system through the projection's own path.
-static void reduced_release(fos_solver* h) {
-    dev_release(h, &h->red.tiles); dev_release(h, &h->red.rowslot); dev_release(h, &h->red.colslot);
-    { RedUnit* u = const_cast<RedUnit*>(h->red.units); dev_release(h, &u); h->red.units = nullptr; }
-    { int32_t* u = const_cast<int32_t*>(h->red.strip_u0); dev_release(h, &u); h->red.strip_u0 = nullptr; }
-    dev_release(h, &h->red_pq); dev_release(h, &h->red_yk); dev_release(h, &h->red_s); dev_release(h, &h->red_d); dev_release(h, &h->red_r); dev_release(h, &h->red_z);
-    dev_release(h, &h->red_p); dev_release(h, &h->red_q); dev_release(h, &h->red_g); dev_release(h, &h->red_dots);
-    h->red_ready = false; h->direct_red = false;
-}
-static int reduced_setup(fos_solver* h, const int64_t* colptr, const int64_t* rowval, const double* nzval, int factor) {
-    const int64_t n = h->n, m = h->m, l = h->l, nnz = colptr[n] - 1;
-    if (h->row_sharded || h->sharded()) { set_error("direct=true, reduced form: not available on sharded handles"); return FOS_EUNSUPPORTED; }
-    if (nnz != h->nnz) { set_error("fos_enable_direct2: A has %lld non-zeros, the handle was created with %lld", (long long)nnz, (long long)h->nnz); return FOS_EINVAL; }
-    const int64_t k = std::min(m, n);
-    const int64_t kmax = getenv("FOS_DIRECT_REDUCED_MAX") ? atoll(getenv("FOS_DIRECT_REDUCED_MAX")) : 46000;
-    if (k < 1) { set_error("direct=true, reduced form: min(m, n) = 0, nothing to factorise"); return FOS_EUNSUPPORTED; }
-    if (k > kmax) { set_error("direct=true, reduced form: min(m, n) = %lld exceeds the largest order of the stored inverse (%lld; FOS_DIRECT_REDUCED_MAX)", (long long)k, (long long)kmax); return FOS_EUNSUPPORTED; }
-    if (nnz > INT32_MAX || m > INT32_MAX || n > INT32_MAX) { set_error("direct=true, reduced form: operator too large for 32-bit indices"); return FOS_EUNSUPPORTED; }
-    h->red_refine = getenv("FOS_DIRECT_REDUCED_REFINE") ? std::max(0, std::min(4, atoi(getenv("FOS_DIRECT_REDUCED_REFINE")))) : 1;
-    // ---- A by columns and by rows, 0-based (the rows in column order: the summation order of K's entries)
-    std::vector<int32_t> cp((size_t)n + 1), ci((size_t)nnz), rp((size_t)m + 1, 0), ri((size_t)nnz);
-    std::vector<double> rv((size_t)nnz);
-    for (int64_t j = 0; j <= n; ++j) {
-        if (colptr[j] < 1 || colptr[j] > nnz + 1 || (j > 0 && colptr[j] < colptr[j - 1])) { set_error("fos_enable_direct2: malformed colptr"); return FOS_EINVAL; }
-        cp[j] = (int32_t)(colptr[j] - 1);
-    }
-    for (int64_t e = 0; e < nnz; ++e) {
-        const int64_t r = rowval[e] - 1;
-        if (r < 0 || r >= m) { set_error("fos_enable_direct2: row index out of range"); return FOS_EINVAL; }
-        ci[e] = (int32_t)r;
-        rp[r + 1] += 1;
-    }
-    for (int64_t r = 0; r < m; ++r) rp[r + 1] += rp[r];
-    {
-        std::vector<int32_t> fill(rp.begin(), rp.end() - 1);
-        for (int64_t j = 0; j < n; ++j)
-            for (int32_t e = cp[j]; e < cp[j + 1]; ++e) { const int32_t q = fill[ci[e]]++; ri[q] = (int32_t)j; rv[q] = nzval[e]; }
-    }
-    FOS_HIP(hipSetDevice(h->device));
-    LaunchCtx c = h->ctx();
-    const int swap = m < n ? 1 : 0;
-    const int64_t L = (k + 63) / 64 * 64;
-    const size_t L2 = (size_t)L * (size_t)L;
-    reduced_release(h);
-    build_reduced_plan(k, &h->red_plan);
-    const RedPlan& P = h->red_plan;
-    int32_t *dcp = nullptr, *dci = nullptr, *drp = nullptr, *dri = nullptr;
-    double *dcv = nullptr, *drv = nullptr, *G = nullptr, *B0 = nullptr, *B1 = nullptr, *B2 = nullptr;
-    auto cleanup = [&]() { (void)hipFree(dcp); (void)hipFree(dci); (void)hipFree(drp); (void)hipFree(dri); (void)hipFree(dcv); (void)hipFree(drv);
-                           (void)hipFree(G); (void)hipFree(B0); (void)hipFree(B1); (void)hipFree(B2); };
-    auto fail = [&](int code) { cleanup(); reduced_release(h); return code; };
-    const size_t ne = (size_t)std::max<int64_t>(nnz, 1);
-    hipError_t e = hipMalloc((void**)&dcp, sizeof(int32_t) * (n + 1));
-    if (e == hipSuccess) e = hipMalloc((void**)&dci, sizeof(int32_t) * ne);
-    if (e == hipSuccess) e = hipMalloc((void**)&dcv, sizeof(double) * ne);
-    if (e == hipSuccess) e = hipMalloc((void**)&drp, sizeof(int32_t) * (m + 1));
-    if (e == hipSuccess) e = hipMalloc((void**)&dri, sizeof(int32_t) * ne);
-    if (e == hipSuccess) e = hipMalloc((void**)&drv, sizeof(double) * ne);
-    if (e == hipSuccess) e = hipMalloc((void**)&G, sizeof(double) * L2);
-    if (e == hipSuccess) e = hipMalloc((void**)&B0, sizeof(double) * L2);
-    if (e == hipSuccess) e = hipMalloc((void**)&B1, sizeof(double) * L2);
-    if (e == hipSuccess) e = hipMalloc((void**)&B2, sizeof(double) * L2);
-    if (e != hipSuccess) { set_error("direct=true, reduced form: hipMalloc of the set-up buffers (4 x %zu bytes) failed: %s", L2 * 8, hipGetErrorString(e)); return fail(FOS_ENOMEM); }
-    const size_t lpad = (size_t)((l + 63) / 64 * 64), kpad = (size_t)P.nt * RED_TR;
-    int rc = FOS_OK;
-    RedUnit* dunits = nullptr; int32_t* dstrip = nullptr;
-    if (rc == FOS_OK) rc = dev_alloc(h, &dunits, P.units.size());
-    if (rc == FOS_OK) rc = dev_alloc(h, &dstrip, P.strip_u0.size());
-    h->red.units = dunits; h->red.strip_u0 = dstrip;
-    if (rc == FOS_OK) rc = dev_alloc(h, &h->red.tiles, (size_t)P.ntiles * RED_TILE);
-    if (rc == FOS_OK) rc = dev_alloc(h, &h->red.rowslot, (size_t)P.ntiles * 64);
-    if (rc == FOS_OK) rc = dev_alloc(h, &h->red.colslot, P.units.size() * 64);
-    if (rc == FOS_OK) rc = dev_alloc(h, &h->red_pq, kpad);
-    if (rc == FOS_OK) rc = dev_alloc(h, &h->red_yk, kpad);
-    for (double** v : {&h->red_s, &h->red_d, &h->red_r, &h->red_z, &h->red_p, &h->red_q, &h->red_g})
-        if (rc == FOS_OK) rc = dev_alloc(h, v, lpad);
-    if (rc == FOS_OK) rc = dev_alloc(h, &h->red_dots, (size_t)2 * RED_DOT_BLOCKS);
-    if (rc == FOS_OK && !h->dvec[0]) rc = dev_alloc(h, &h->dvec[0], lpad);
-    if (rc == FOS_OK && !h->dvec[1]) rc = dev_alloc(h, &h->dvec[1], lpad);
-    if (rc != FOS_OK) return fail(rc);
-    h->red.k = k; h->red.kpad = (int64_t)kpad; h->red.nt = P.nt; h->red.nunits = (int)P.units.size();
-    h->red_swap = swap;
-#define DIRECT_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error("direct=true set-up (reduced form): %s -> %s", #expr, hipGetErrorString(_e)); return fail(FOS_EHIP); } } while (0)
-    DIRECT_HIP(hipMemcpyAsync(dunits, P.units.data(), sizeof(RedUnit) * P.units.size(), hipMemcpyHostToDevice, h->stream));
-    DIRECT_HIP(hipMemcpyAsync(dstrip, P.strip_u0.data(), sizeof(int32_t) * P.strip_u0.size(), hipMemcpyHostToDevice, h->stream));
-    DIRECT_HIP(hipMemcpyAsync(dcp, cp.data(), sizeof(int32_t) * (n + 1), hipMemcpyHostToDevice, h->stream));
-    DIRECT_HIP(hipMemcpyAsync(drp, rp.data(), sizeof(int32_t) * (m + 1), hipMemcpyHostToDevice, h->stream));
-    if (nnz) {
-        DIRECT_HIP(hipMemcpyAsync(dci, ci.data(), sizeof(int32_t) * nnz, hipMemcpyHostToDevice, h->stream));
-        DIRECT_HIP(hipMemcpyAsync(dcv, nzval, sizeof(double) * nnz, hipMemcpyHostToDevice, h->stream));
-        DIRECT_HIP(hipMemcpyAsync(dri, ri.data(), sizeof(int32_t) * nnz, hipMemcpyHostToDevice, h->stream));
-        DIRECT_HIP(hipMemcpyAsync(drv, rv.data(), sizeof(double) * nnz, hipMemcpyHostToDevice, h->stream));
-    }
-    DIRECT_HIP(hipMemsetAsync(G, 0, sizeof(double) * L2, h->stream));
-    for (double* v : {h->red_s, h->red_d, h->red_r, h->red_z, h->red_p, h->red_q, h->red_g}) DIRECT_HIP(hipMemsetAsync(v, 0, sizeof(double) * lpad, h->stream));
-    // K = I + B'B: B = A (its columns: A's columns, its rows: A's rows), or B = A' (the two exchanged)
-    if (!swap) launch_red_form_k(c, k, L, dcp, dci, dcv, drp, dri, drv, G);
-    else launch_red_form_k(c, k, L, drp, dri, drv, dcp, dci, dcv, G);
-    // ---- K^-1: Newton-Schulz as in the dense form, or the blocked Cholesky factorisation
-    LaunchCtx ck = c;
-    ck.l = k;
-    double* X = nullptr;
-    DenseInv inv;
-    rc = dense_spd_inverse(ck, L, G, B0, B1, B2, h->dvec[0], h->dvec[1], h->partials, "direct=true, reduced form", "K", factor, true, &X, &inv);
-    if (rc != FOS_OK) return fail(rc);
-    launch_red_pack_tiles(c, h->red, L, X);
-    DIRECT_HIP(hipStreamSynchronize(h->stream));
-    rc = check_launch("direct=true set-up (reduced form)");
-    cleanup();                                                              // the square buffers go: the handle keeps the packed triangle
-    dcp = dci = drp = dri = nullptr; dcv = drv = G = B0 = B1 = B2 = nullptr;
-    if (rc != FOS_OK) return fail(rc);
-    // ---- g = -Q0 h, p = D^-1 h, q = D^-1 g through the projection's path; the border system on the host
-    const int64_t nm = n + m;
-    double* hfull = h->dvec[0];
-    DIRECT_HIP(hipMemsetAsync(hfull, 0, sizeof(double) * lpad, h->stream));
-    DIRECT_HIP(hipMemcpyAsync(hfull, h->cb, sizeof(double) * nm, hipMemcpyDeviceToDevice, h->stream));
-    launch_set_comp(c, h->AP, hfull, 0);
-    launch_q1(c, Q_PLAIN, h->AP, 0, -1.0, h->red_g);                        // rows 0 .. n+m-1 of -Q (h, 0) = -Q0 h (the tau entry of red_g stays 0)
-    (void)reduced_dinv(h, c, hfull, h->red_p, nullptr);
-    (void)reduced_dinv(h, c, h->red_g, h->red_q, nullptr);
-    std::vector<double> hh((size_t)nm), gg((size_t)nm), pp((size_t)nm), qq((size_t)nm);
-    DIRECT_HIP(hipMemcpyAsync(hh.data(), h->cb, sizeof(double) * nm, hipMemcpyDeviceToHost, h->stream));
-    DIRECT_HIP(hipMemcpyAsync(gg.data(), h->red_g, sizeof(double) * nm, hipMemcpyDeviceToHost, h->stream));
-    DIRECT_HIP(hipMemcpyAsync(pp.data(), h->red_p, sizeof(double) * nm, hipMemcpyDeviceToHost, h->stream));
-    DIRECT_HIP(hipMemcpyAsync(qq.data(), h->red_q, sizeof(double) * nm, hipMemcpyDeviceToHost, h->stream));
-    DIRECT_HIP(hipStreamSynchronize(h->stream));
-#undef DIRECT_HIP
-    rc = check_launch("direct=true set-up (reduced form, border)");
-    if (rc != FOS_OK) return fail(rc);
-    long double hp = 0, hq = 0, gp = 0, gq = 0, h2 = 0;
-    for (int64_t i = 0; i < nm; ++i) { hp += (long double)hh[i] * pp[i]; hq += (long double)hh[i] * qq[i]; gp += (long double)gg[i] * pp[i]; gq += (long double)gg[i] * qq[i]; h2 += (long double)hh[i] * hh[i]; }
-    const long double a00 = 1.0L + hp, a01 = hq, a10 = gp, a11 = gq - (1.0L + h2);
-    const long double det = a00 * a11 - a01 * a10;
-    if (!(fabsl(det) > 0.0L) || !std::isfinite((double)det)) { set_error("direct=true, reduced form: the 2 x 2 border system is singular"); return fail(FOS_EINVAL); }
-    h->red_minv[0] = (double)(a11 / det); h->red_minv[1] = (double)(-a01 / det); h->red_minv[2] = (double)(-a10 / det); h->red_minv[3] = (double)(a00 / det);
-    h->direct_iters = inv.steps;
-    h->direct_factor_req = factor; h->direct_factor = inv.used; h->direct_invert_s = inv.seconds; h->direct_probe = inv.probe; h->direct_fell_back = inv.fell_back;
-    h->red_ready = true;
-    return FOS_OK;
-}
-
-int fos_enable_direct3(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval, int32_t form, int32_t factor) {
-    if (!h || !colptr || (!rowval && colptr[h->n] > 1)) { set_error("NULL argument"); return FOS_EINVAL; }
-    if (form != FOS_DIRECT_FORM_AUTO && form != FOS_DIRECT_FORM_REDUCED) { set_error("fos_enable_direct3: form must be FOS_DIRECT_FORM_AUTO or FOS_DIRECT_FORM_REDUCED"); return FOS_EINVAL; }
-    if (factor != FOS_DIRECT_FACTOR_NEWTON && factor != FOS_DIRECT_FACTOR_CHOLESKY) { set_error("fos_enable_direct3: factor must be FOS_DIRECT_FACTOR_NEWTON or FOS_DIRECT_FACTOR_CHOLESKY"); return FOS_EINVAL; }
-    const char* mode_env = getenv("FOS_DIRECT_MODE");
-    if (form == FOS_DIRECT_FORM_AUTO && mode_env && std::string(mode_env) == "reduced") form = FOS_DIRECT_FORM_REDUCED;
-    if (const char* fenv = getenv("FOS_DIRECT_FACTOR")) {                  // only for callers that did not choose: the old entries pass NEWTON
-        const std::string f = fenv;
-        if (f != "newton" && f != "cholesky") { set_error("FOS_DIRECT_FACTOR must be newton or cholesky, not '%s'", fenv); return FOS_EINVAL; }
-        if (factor == FOS_DIRECT_FACTOR_NEWTON && f == "cholesky") factor = FOS_DIRECT_FACTOR_CHOLESKY;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc;
-    if (form == FOS_DIRECT_FORM_REDUCED) {
-        if (!h->red_ready || h->direct_factor_req != factor) {             // another factor: the set-up runs again
-            FOS_TRY(reduced_setup(h, colptr, rowval, nzval, factor));
-            h->direct_setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        }
-        if (h->Ginv) { dev_release(h, &h->Ginv); h->Gld = 0; }            // one form's inverse at a time
-        h->direct = true; h->direct_red = true; h->direct_blk = false; h->direct_cg = false;
-        return FOS_OK;
-    }
-    if (h->Ginv && h->direct_factor_req != factor) { dev_release(h, &h->Ginv); h->Gld = 0; }
-    const bool had = h->Ginv || (h->blk_ginv && h->blk_ready);
-    rc = enable_direct_auto(h, colptr, rowval, nzval, factor);
-    if (rc == FOS_OK) {
-        if (h->red_ready) reduced_release(h);
-        h->direct_red = false;
-        if (!had) h->direct_setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return rc;
-}
-int fos_enable_direct2(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval, int32_t form) {
-    return fos_enable_direct3(h, colptr, rowval, nzval, form, FOS_DIRECT_FACTOR_NEWTON);
-}
-int fos_enable_direct(fos_handle h, const int64_t* colptr, const int64_t* rowval, const double* nzval) {
-    return fos_enable_direct3(h, colptr, rowval, nzval, FOS_DIRECT_FORM_AUTO, FOS_DIRECT_FACTOR_NEWTON);
-}
-
-// form (as fos_get_direct_mode), order of the stored inverse (dense: l, reduced: min(m, n), else 0), wall seconds of the last set-up, its Newton-Schulz steps
-int fos_get_direct_stats(fos_handle h, double* out4) {
-    if (!h || !out4) { set_error("NULL argument"); return FOS_EINVAL; }
-    int32_t mode = 0;
-    FOS_TRY(fos_get_direct_mode(h, &mode));
-    out4[0] = (double)mode;
-    out4[1] = mode == 4 ? (double)h->red.k : (mode == 1 ? (double)h->l : 0.0);
-    out4[2] = h->direct_setup_s;
-    out4[3] = (mode == 1 || mode == 4) ? (double)h->direct_iters : 0.0;
-    return FOS_OK;
-}
-
-// the four values of fos_get_direct_stats, then: the factor that built the stored inverse (FOS_DIRECT_FACTOR_*), the seconds of the inversion stage alone, the
-// last probe residual of the Cholesky path, 1.0 if that path fell back to Newton-Schulz
-int fos_get_direct_stats2(fos_handle h, double* out8) {
-    if (!h || !out8) { set_error("NULL argument"); return FOS_EINVAL; }
-    FOS_TRY(fos_get_direct_stats(h, out8));
-    const bool stored = out8[0] == 1.0 || out8[0] == 4.0;
-    out8[4] = stored ? (double)h->direct_factor : 0.0;
-    out8[5] = stored ? h->direct_invert_s : 0.0;
-    out8[6] = stored ? h->direct_probe : 0.0;
-    out8[7] = stored && h->direct_fell_back ? 1.0 : 0.0;
-    return FOS_OK;
-}
-
-// test-only: X = K^-1 for a symmetric positive definite k x k host matrix (column-major) through the set-up's own path (padding, factor, probe, polish, fallback
-// for a probe that stays above the bar; a bad pivot is an error here).  info4: bad-pivot column or -1, Newton-Schulz / polish steps, probe residual, fallback flag
-int fos_dense_spd_inverse(int32_t device, int64_t k, const double* K, double* X, int32_t factor, double* info4) {
-    if (k < 1 || k > 46000 || !K || !X || !info4) { set_error("fos_dense_spd_inverse: bad argument"); return FOS_EINVAL; }
-    if (factor != FOS_DIRECT_FACTOR_NEWTON && factor != FOS_DIRECT_FACTOR_CHOLESKY) { set_error("fos_dense_spd_inverse: factor must be FOS_DIRECT_FACTOR_NEWTON or FOS_DIRECT_FACTOR_CHOLESKY"); return FOS_EINVAL; }
-    info4[0] = -1.0; info4[1] = info4[2] = info4[3] = 0.0;
-    FOS_HIP(hipSetDevice(device));
-    const int64_t L = (k + 63) / 64 * 64;
-    const size_t L2 = (size_t)L * (size_t)L;
-    std::vector<double> pad(L2, 0.0);
-    for (int64_t i = 0; i < L; ++i) pad[(size_t)i + (size_t)i * L] = 1.0;
-    for (int64_t j = 0; j < k; ++j) std::copy(K + j * k, K + j * k + k, pad.begin() + (size_t)j * L);
-    double* buf[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};       // G, B0, B1, B2, two vectors, partials
-    hipStream_t stream = nullptr;
-    auto cleanup = [&]() { for (double* b : buf) (void)hipFree(b); if (stream) (void)hipStreamDestroy(stream); };
-    hipError_t e = hipStreamCreate(&stream);
-    for (int q = 0; q < 7 && e == hipSuccess; ++q) e = hipMalloc((void**)&buf[q], sizeof(double) * (q < 4 ? L2 : (q < 6 ? (size_t)L : 256)));
-    if (e == hipSuccess) e = hipMemcpyAsync(buf[0], pad.data(), sizeof(double) * L2, hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) { cleanup(); set_error("fos_dense_spd_inverse: %s", hipGetErrorString(e)); return FOS_EHIP; }
-    LaunchCtx c{};
-    c.stream = stream;
-    c.l = k;
-    double* Xd = nullptr;
-    DenseInv inv;
-    int rc = dense_spd_inverse(c, L, buf[0], buf[1], buf[2], buf[3], buf[4], buf[5], buf[6], "fos_dense_spd_inverse", "K", factor, false, &Xd, &inv);
-    info4[0] = (double)inv.bad_col; info4[1] = (double)inv.steps; info4[2] = inv.probe; info4[3] = inv.fell_back ? 1.0 : 0.0;
-    if (rc == FOS_OK) {
-        e = hipMemcpyAsync(pad.data(), Xd, sizeof(double) * L2, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) { set_error("fos_dense_spd_inverse: %s", hipGetErrorString(e)); rc = FOS_EHIP; }
-        else for (int64_t j = 0; j < k; ++j) std::copy(pad.begin() + (size_t)j * L, pad.begin() + (size_t)j * L + k, X + j * k);
-    } else {
-        (void)hipStreamSynchronize(stream);
-    }
-    cleanup();
-    return rc;
-}
-
-// test-only, host: the blocked Cholesky inverse of dense_chol.hip with the same blocking and block order on the CPU; *bad_pivot: the first bad column or -1
-int fos_host_chol_inverse(int64_t k, const double* K, double* X, int64_t* bad_pivot) {
-    if (k < 1 || !K || !X || !bad_pivot) { set_error("bad argument"); return FOS_EINVAL; }
-    *bad_pivot = host_chol_inverse(k, K, X);
-    if (*bad_pivot >= 0) { set_error("fos_host_chol_inverse: the pivot of column %lld is not a positive finite number (the matrix is not positive definite)", (long long)*bad_pivot); return FOS_EINVAL; }
-    return FOS_OK;
-}
-
-// test-only, host: the reduced form's tile packing and the tile product in the kernels' summation order, for a symmetric k x k matrix X (column-major) and k
-// operand pairs pq; y: k pairs; count (k x k, may be NULL): in how many tile slots each entry is stored
-int fos_host_reduced_symm(int64_t k, const double* X, const double* pq, double* y, int32_t* count) {
-    if (k < 1 || !X || !pq || !y) { set_error("bad argument"); return FOS_EINVAL; }
-    RedPlan P;
-    build_reduced_plan(k, &P);
-    std::vector<double> tiles;
-    if (count) std::fill(count, count + k * k, 0);
-    host_reduced_pack(P, X, &tiles, count);
-    const size_t kpad = (size_t)P.nt * RED_TR;
-    std::vector<double> pin(2 * kpad, 0.0), out(2 * kpad, 0.0);
-    std::copy(pq, pq + 2 * k, pin.begin());
-    host_reduced_symm(P, tiles, pin.data(), out.data());
-    std::copy(out.begin(), out.begin() + 2 * k, y);
-    return FOS_OK;
-}
-
-int fos_disable_direct(fos_handle h) {
-    if (!h) { set_error("NULL handle"); return FOS_EINVAL; }
-    h->direct = false; h->direct_cg = false; h->direct_blk = false; h->direct_red = false;
-    return FOS_OK;
-}
-
-// which form S1 = IndAffine([Q -I], 0) runs in: 0 = off (AffinePlusLinear's CG schedule), 1 = dense inverse, 2 = block form, 3 = CG at its tolerance floor, 4 = reduced form
-int fos_get_direct_mode(fos_handle h, int32_t* mode) {
-    if (!h || !mode) { set_error("NULL argument"); return FOS_EINVAL; }
-    *mode = h->direct ? (h->direct_red ? 4 : (h->direct_blk ? 2 : 1)) : (h->direct_cg ? 3 : 0);
     return FOS_OK;
 }
 

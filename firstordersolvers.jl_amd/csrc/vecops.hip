@@ -1174,7 +1174,7 @@ void launch_direct_finish(const LaunchCtx& c, const double2* x, const double2* W
 }
 
 // ---- direct = true on a BLOCK-SEPARABLE operator (HSDE.jl:12-15: S1 = IndAffine([Q -I], 0); fos_internal.hpp BlkDirect).  The exact projection
-// (u^, Q u^), u^ = (I - Q^2)^-1 (u - Q v), with I - Q^2 = blkdiag(I + A'A, I + AA', delta) + W C W' (three border columns: solver.cpp
+// (u^, Q u^), u^ = (I - Q^2)^-1 (u - Q v), with I - Q^2 = blkdiag(I + A'A, I + AA', delta) + W C W' (three border columns: direct.cpp
 // prox_affine_direct_block), in three KKT sweeps: the small blocks of I + A'A are inverted once on the host, (I + AA')^-1 = I - A (I + A'A)^-1 A'.
 // (1) from T = M (u, v) (T.x = g = u - Q v): W2 = (0, g restricted to the rows of A), W3 zeroed outside the x part, partial sums of ph.g and pg.g
 __global__ __launch_bounds__(VEC_THREADS) void blkdir_prep_kernel(int64_t l, int64_t n, const d2* __restrict__ T, const d2* __restrict__ phg,
