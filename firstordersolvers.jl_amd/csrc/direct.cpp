@@ -158,11 +158,13 @@ static int reduced_q_plain(fos_solver* h, const LaunchCtx& c, const double* v, d
     launch_q1_finalize(c, Q_PLAIN, h->AP, 0, 1.0, out, fr);
     return FOS_OK;
 }
-// the dense and the reduced form: t = Q u - v, w = (I + Q Q')^-1 t, result (u + Q w, v + w); the two differ in how w is found
+// the dense and the reduced form: t = Q u - v, w = (I + Q Q')^-1 t, u+ = u + Q w; the two differ in how w is found.  The second half of the result is
+// Q u+ from a sweep of its own, not v + w: the two agree only as far as the stored inverse solves its system (1e-13 .. 1e-12 relative), and the result is
+// to satisfy v = Q u to the rounding of one product, as the CG path's (u, Q u) and the block form's do.
 int fos::prox_affine_direct(fos_solver* h, const d2* x) {
     if (h->direct_form == DIRECT_BLOCK) return prox_affine_direct_block(h, x, h->SOL);
     const bool red = h->direct_form == DIRECT_REDUCED;
-    RoctxRange range(red ? "fos:prox_affine_direct_reduced (Q sweeps + one pass over the lower triangle of K^-1)" : "fos:prox_affine_direct (2 Q sweeps + dense symmetric matvec)");
+    RoctxRange range(red ? "fos:prox_affine_direct_reduced (Q sweeps + one pass over the lower triangle of K^-1)" : "fos:prox_affine_direct (3 Q sweeps + dense symmetric matvec)");
     LaunchCtx c = h->ctx();
     int fr = 0;
     double *t = h->dvec[0], *w = h->dvec[1];
@@ -183,7 +185,10 @@ int fos::prox_affine_direct(fos_solver* h, const d2* x) {
     launch_q1(c, Q_VFROMU, h->AP, 0, 1.0, h->R);                       // R = (w, Q w)
     FOS_TRY(finish_reduce(h, c, c.S.npart, 1, 0, &fr, c.S.part_off));
     launch_q1_finalize(c, Q_VFROMU, h->AP, 0, 1.0, h->R, fr);
-    launch_direct_finish(c, x, h->R, h->SOL);                          // (u + Q w, v + w)
+    launch_direct_finish(c, x, h->R, h->AP);                           // AP = (u + Q w, v + w): its first half is u+
+    launch_q1(c, Q_VFROMU, h->AP, 0, 1.0, h->SOL);                     // SOL = (u+, Q u+)
+    FOS_TRY(finish_reduce(h, c, c.S.npart, 1, 0, &fr, c.S.part_off));
+    launch_q1_finalize(c, Q_VFROMU, h->AP, 0, 1.0, h->SOL, fr);
     h->cgiter = 0;
     return check_launch(red ? "reduced direct affine projection" : "direct affine projection");
 }

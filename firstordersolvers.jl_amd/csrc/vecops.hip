@@ -1024,9 +1024,10 @@ void launch_dykstra_corr(const LaunchCtx& c, double2* p, const double2* x, const
 // ------------------------------------------------------------------------------------------------ direct = true (HSDE.jl:12-15)
 // S1 = IndAffine([Q -I], 0): the exact projection of [u; v] onto {Q u = v},
 //     w = (I + Q Q')^-1 (Q u - v),   u+ = u - Q'w = u + Q w,   v+ = v + w        (Q' = -Q, HSDEAffine.jl:61-65)
+// (v+ is returned as Q u+ from a sweep of its own, so that the result satisfies v = Q u to the rounding of one product: direct.cpp)
 // with G^-1 = (I + Q Q')^-1 = (I - Q Q)^-1 formed ONCE as a dense matrix by the Newton-Schulz iteration X <- 2X - X (G X) on a
 // hand-written fp64 MFMA GEMM (quadratically convergent for the symmetric positive definite G, lambda_min(G) >= 1; needs only
-// matrix products -- the vendor's dense solver library alone takes minutes to load on a fresh box); per projection two Q sweeps,
+// matrix products -- the vendor's dense solver library alone takes minutes to load on a fresh box); per projection three Q sweeps,
 // one dense symmetric matrix-vector product (HBM bound: 8 l^2 bytes) and two elementwise passes.
 
 // dense Q (column-major, l x l) from the CSC of A: column j < n holds -A(:,j) in rows n.., -c_j in the last row; column n+i holds

@@ -186,8 +186,8 @@ int fos_reset_affine(fos_handle h);
  * projection onto {Q u = v} through a factorisation formed once, instead of AffinePlusLinear's warm-started CG.  The
  * reference factorises the sparse [Q -I] on the CPU (ProximalOperators.IndAffine); here (I + Q Q')^-1 is formed once as a
  * dense matrix on the device (Newton-Schulz iteration on a hand-written fp64 MFMA GEMM: l <= 46000, 8 l^2 bytes of HBM kept,
- * four times that during set-up, ~(2 log2(lambda_max) + 14) l x l x l products) and a projection is two Q sweeps and one
- * dense symmetric matrix-vector product.  A (the arrays fos_create was given) is passed
+ * four times that during set-up, ~(2 log2(lambda_max) + 14) l x l x l products) and a projection is three Q sweeps and one
+ * dense symmetric matrix-vector product; the result is (u+, Q u+), so v = Q u holds to the rounding of one product.  A (the arrays fos_create was given) is passed
  * again: the handle keeps only its device format.  No CG runs: fos_check_result.cgiter stays 0 and the host prints the table
  * without the cg column (HSDEStatus.jl:44-50,79).  fos_disable_direct returns to CG.  Sharded handles: the block form below only (see there).
  * l > 46000 (C3, C4, C5): the dense inverse does not fit; IndAffine([Q -I], 0) and AffinePlusLinear(Q, 0, 0, 1) being the same set (HSDE.jl:12-15 / :22), the

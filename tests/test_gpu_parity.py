@@ -117,19 +117,26 @@ def test_kkt_apply(pkg, dev_ops):
         assert relerr(d.kkt_apply(x), y_ref) < 1e-13, name
 
 
-@pytest.mark.parametrize("geom", ["1", "2"])
-def test_operators_on_forced_window_panels(pkg, geom, monkeypatch):
-    """The same Q, Q', KKT and status products with the operator forced into window panels (FOS_WINDOWS = 1: 2016-row panels, 2: the tall
-    geometry): shapes with rows longer than a window's register slots, empty rows and columns, a dense row and column, panels with fewer
+def window_panel_shapes(rng):
+    """wide, tall, mid, tiny: rows longer than a window's register slots, empty rows and columns, a dense row and column, panels with fewer
     than 64 rows, a panel that touches MORE THAN 64 windows (the record chunks of the walk), a last window cut by the end of the vector."""
-    monkeypatch.setenv("FOS_WINDOWS", geom)
-    rng = np.random.default_rng(77)
     wide = sp.random(150, 420000, density=2.5e-5, format="csc", random_state=rng, data_rvs=rng.standard_normal)   # its rows' panel spans > 64 windows of 6144
     tall_ = sp.random(9000, 300, density=0.01, format="csc", random_state=rng, data_rvs=rng.standard_normal)
     mid = sp.random(5000, 4100, density=0.004, format="csc", random_state=rng, data_rvs=rng.standard_normal).tolil()
     mid[3, :] = rng.standard_normal(4100) * (rng.random(4100) < 0.5)                 # a row with ~2000 entries: far beyond the register slots
     mid[:, 1] = rng.standard_normal((5000, 1))
-    for name, A in (("wide", wide), ("tall", tall_), ("mid", sp.csc_matrix(mid)), ("tiny", sp.random(3, 5, density=0.5, format="csc", random_state=rng))):
+    return wide, tall_, sp.csc_matrix(mid), sp.random(3, 5, density=0.5, format="csc", random_state=rng)
+
+
+@pytest.mark.parametrize("geom", ["1", "2"])
+def test_operators_on_forced_window_panels(pkg, geom, monkeypatch):
+    """The same Q, Q', KKT and status products with the operator forced into window panels (FOS_WINDOWS = 1: 2016-row panels, 2: the tall
+    geometry) on the shapes of window_panel_shapes.  The status sums (fos_check) are held against the extended-precision reference of
+    tests/status_reference.py at twice its worst-case fp64 allowance."""
+    import status_reference as sref
+    monkeypatch.setenv("FOS_WINDOWS", geom)
+    rng = np.random.default_rng(77)
+    for name, A in zip(("wide", "tall", "mid", "tiny"), window_panel_shapes(rng)):
         m, n = A.shape
         b, c = rng.standard_normal(m), rng.standard_normal(n)
         d = pkg.HipHSDE(A, b, c, [("Free", m)], [("Free", n)])
@@ -148,6 +155,13 @@ def test_operators_on_forced_window_panels(pkg, geom, monkeypatch):
         z_ref = np.empty(d.N)
         orc.KKTMatrix(Q).mul(z_ref, z)
         assert relerr(d.kkt_apply(z), z_ref) < 1e-13, name
+        res = d.check(z, 1e-5)
+        vals, allow = sref.reference(A, b, c, z)
+        got = dict(p=res.p, d=res.d, g=res.g, ctx=res.ctx, bty=res.bty, nAxs=res.norm_axs, nATy=res.norm_aty, nb=res.norm_b, nc=res.norm_c,
+                   tau=res.tau, kappa=res.kappa)
+        rat = sref.ratios(got, vals, allow)
+        print("window panels FOS_WINDOWS=%s %-5s worst |check - reference| / allowance: %.3g (%s)" % (geom, name, max(rat.values()), max(rat, key=rat.get)))
+        assert max(rat.values()) <= 2.0, (name, rat)
         d.close()
 
 
