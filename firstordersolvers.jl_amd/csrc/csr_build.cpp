@@ -1095,13 +1095,18 @@ bool build_resident_plan(const HostBlkCsr& S, int64_t m, int64_t n, int gmax, Re
                 tiles_max = std::max(tiles_max, tb - ta);
             }
         }
-        // tiles per compute wavefront (resident.hip, rs_split: the communication wavefront walks the last min(nblk % 7, 3) tiles itself)
+        // tiles per compute wavefront: the kernel instance is chosen for the deal in which the communication wavefront walks min(nblk % 7, 3)
+        // tiles -- never fewer tiles per compute wavefront than the table (rs_deal, fos_internal.hpp) hands out: the table only moves tiles
+        // from the compute wavefronts to the communication wavefront
         int nt = 0;
         for (const ResWG& w : wgs) {
-            const int per = w.nblk / RS_NCOMP, r = w.nblk % RS_NCOMP, kc = std::min(r, 3);
+            const int per = w.nblk / RS_NCOMP, r = w.nblk % RS_NCOMP, kc = std::min(r, RS_NTC_BASE);
             nt = std::max(nt, per + (r - kc > 0 ? 1 : 0));
         }
         if (nt > nt_cap) return no(why_not_registers);
+        // the deal of every workgroup's tiles to its eight wavefronts (FOS_RS_NTC: timing experiments -- the communication wavefront's share; read once per process)
+        static const int ntc_exp = getenv("FOS_RS_NTC") ? std::max(0, atoi(getenv("FOS_RS_NTC"))) : RS_NTC;
+        for (ResWG& w : wgs) w.T = (int32_t)rs_deal(w.nblk, std::min(ntc_exp, rs_ntc(tmax)));
         // what the kernel can index: a tile is walked in whole groups of 8 steps, each pass of 32 steps from its unit's offset in the workgroup's
         // <= 64 columns (rs_sweep: s_gcol[64] and the wavefront's 64 column sums) -- a unit that starts late in the workgroup and ends on a ragged
         // group would read past the column elements and add into the next wavefront's column sums

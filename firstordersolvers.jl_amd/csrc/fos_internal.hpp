@@ -12,6 +12,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
@@ -431,6 +432,7 @@ void launch_cgm_start(const LaunchCtx& c, const CgmIter& it, const double2* rhs,
 // Across GPUs the four sums go on through the handle's mailboxes (peer_fold_sum), exactly as in cgm_update_kernel.
 struct ResWG { int32_t blk0, nblk, c0, tc, T, wg0, wpu, idx; };     // 32 bytes: tiles blk0 .. blk0 + nblk - 1 of S.blk, the unit's columns [c0, c0 + tc), T steps;
                                                                     // the unit's workgroups wg0 .. wg0 + wpu - 1, this one is number idx
+                                                                    // (a STREAMED workgroup: T is its tiles' deal to the wavefronts, rs_deal below)
 constexpr int RES_GMAX = 512;        // workgroups of a resident solve (records every workgroup adds)
 constexpr int RES_WPU_MAX = 16;      // workgroups per unit
 constexpr int RES_SLOTS = 21;        // tiles per workgroup
@@ -439,10 +441,36 @@ constexpr int RES_SLOTS = 21;        // tiles per workgroup
 constexpr int RS_GMAX = 256;
 constexpr int RS_WPU_MAX = 4;
 constexpr int RS_NCOMP = 7;
-constexpr int RS_NTC = 3;
+constexpr int RS_NTC = 6;
+// THE DEAL of a streamed workgroup's tiles to its wavefronts: a table of eight tile counts carried in the plan (ResWG::T of a streamed workgroup:
+// wavefront w's count in bits 4 w .. 4 w + 3), not a formula in the kernel.  Wavefront w walks the cnt[w] tiles behind those of the wavefronts in front
+// of it -- slot order = tile order, the communication wavefront (w = RS_NCOMP) last -- so the rows' p and s sit in LDS by tile number.
+// The table: the communication wavefront takes min(nblk % 7, RS_NTC_BASE) tiles, as it always did, and up to RS_NTC where that still leaves it
+// RS_COMM_LEAD tiles lighter than the heaviest compute wavefront (it publishes and polls behind its sweep; 8 tiles or fewer: never); the other tiles go to
+// the compute wavefronts evenly, the LATER wavefronts one tile fewer: they end their sweeps last (the stamps), and every CU's sweep ends on its last
+// wavefront.  C4's 66 tiles: 9 9 9 9 8 8 8 + 6, where 9 x 7 + 3 left three of eight wavefronts streaming for the last 2 us of every sweep.
+constexpr int RS_NTC_BASE = 3;
+constexpr int RS_COMM_LEAD = 2;
+// (tiles of more than 32 steps are walked in two passes each: their kernels keep the communication wavefront's three)
+inline int rs_ntc(int tmax) { return tmax > 32 ? RS_NTC_BASE : RS_NTC; }
+inline uint32_t rs_deal(int nblk, int ntc = RS_NTC) {
+    int kc = std::min(nblk % RS_NCOMP, RS_NTC_BASE);
+    for (int k = std::min(ntc, RS_NTC); k > kc; --k)
+        if (k <= (nblk - k + RS_NCOMP - 1) / RS_NCOMP - RS_COMM_LEAD) { kc = k; break; }
+    const int per = (nblk - kc) / RS_NCOMP, rem = (nblk - kc) % RS_NCOMP;
+    uint32_t deal = (uint32_t)kc << (4 * RS_NCOMP);
+    for (int w = 0; w < RS_NCOMP; ++w) deal |= (uint32_t)(per + (w < rem ? 1 : 0)) << (4 * w);      // (at most 10 tiles per wavefront: four bits)
+    return deal;
+}
+// which tiles of its workgroup wavefront w walks (w < RS_NCOMP: compute; w == RS_NCOMP: the communication wavefront, the LAST tiles)
+__host__ __device__ inline void rs_split(uint32_t deal, int w, int& t0, int& cnt) {
+    t0 = 0;
+    for (int k = 0; k < w; ++k) t0 += (int)((deal >> (4 * k)) & 15u);
+    cnt = (int)((deal >> (4 * w)) & 15u);
+}
 // LDS of a launch (one function for the planner and the launch): the dynamic bytes of cg_stream_kernel for a workgroup of `tiles` tiles -- the wavefronts'
 // column sums, the G records, the other workgroups' column sums, the rows' p and s -- and of cg_resident_kernel<TMAX = tmax, NSLOT = nslot>; the planner adds
-// RS_STATIC_LDS_MAX for the kernel's static arrays (2104 bytes) and refuses a plan beyond the 160 KiB of a gfx950 CU, resident_setup checks the launch
+// RS_STATIC_LDS_MAX for the kernel's static arrays (2176 bytes) and refuses a plan beyond the 160 KiB of a gfx950 CU, resident_setup checks the launch
 // against the device's limit and the kernel's own static size
 constexpr size_t RES_LDS_BUDGET = 160 * 1024;
 constexpr size_t RS_STATIC_LDS_MAX = 2560;

@@ -111,8 +111,8 @@ __device__ long long g_res_stamps[4 * 16 * 64 * 16];
 // (s_memtime -- the shader clock -- not the 100 MHz s_memrealtime of wall_clock64(): the latter takes long enough to return that two stamps in a row
 //  showed microseconds; slot [63][6..7] of every (workgroup, who) holds one (s_memtime, s_memrealtime) pair taken at kernel entry and slot [62][6..7] one
 //  at the end, from which the tool derives the clock rate)
-#define RES_STAMP(ph) do { if (stamp_slot >= 0 && stamp_it < 62) { __builtin_amdgcn_sched_barrier(0); g_res_stamps[((size_t)stamp_slot * 64 + stamp_it) * 16 + (ph)] = (long long)__builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); } } while (0)
-#define RES_STAMP_CAL(where) do { if (stamp_slot >= 0) { g_res_stamps[((size_t)stamp_slot * 64 + (where)) * 16 + 6] = (long long)__builtin_readcyclecounter(); g_res_stamps[((size_t)stamp_slot * 64 + (where)) * 16 + 7] = wall_clock64(); } } while (0)
+#define RES_STAMP(ph) do { if (stamp_slot >= 0 && stamp_it < 62 && (threadIdx.x & 63) == 0) { __builtin_amdgcn_sched_barrier(0); g_res_stamps[((size_t)stamp_slot * 64 + stamp_it) * 16 + (ph)] = (long long)__builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); } } while (0)
+#define RES_STAMP_CAL(where) do { if (stamp_slot >= 0 && (threadIdx.x & 63) == 0) { g_res_stamps[((size_t)stamp_slot * 64 + (where)) * 16 + 6] = (long long)__builtin_readcyclecounter(); g_res_stamps[((size_t)stamp_slot * 64 + (where)) * 16 + 7] = wall_clock64(); } } while (0)
 #define RES_STAMP_NEXT() do { stamp_it += 1; } while (0)
 #else
 #define RES_STAMP(ph) do { } while (0)
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(LB) void cg_resident_kernel(ResArgs a) {
     {
         const int b = (int)blockIdx.x;
         const int wslot = b == 0 ? 0 : (b == 1 ? 1 : (b == a.G / 2 ? 2 : (b == a.G - 1 ? 3 : -1)));
-        if (wslot >= 0 && lane == 0 && wv < 16) stamp_slot = wslot * 16 + wv;          // (the first lane of every wavefront)
+        if (wslot >= 0 && wv < 16) stamp_slot = wslot * 16 + wv;                       // (wavefront-uniform: scalar registers; the first lane of every wavefront writes)
     }
 #endif
     if (a.pb.nranks > 0 && st->xchg_failed) return;
@@ -647,14 +647,8 @@ __device__ __forceinline__ void res_tile_plain(const double (&val)[TMAX], int T,
     }
 }
 
-// (RS_NTC = 3: tiles the communication wavefront sweeps itself -- it waits at barrier (A) otherwise: 66 tiles = 7 x 9 + 3)
-
-// which tiles of a workgroup wavefront w walks (w < RS_NCOMP: compute; w == RS_NCOMP: the communication wavefront, the LAST tiles)
-__host__ __device__ inline void rs_split(int nblk, int w, int& t0, int& cnt) {
-    const int per = nblk / RS_NCOMP, r = nblk % RS_NCOMP, kc = r < RS_NTC ? r : RS_NTC, rem = r - kc;
-    if (w < RS_NCOMP) { cnt = per + (w < rem ? 1 : 0); t0 = w * per + (w < rem ? w : rem); }
-    else { cnt = kc; t0 = nblk - kc; }
-}
+// (RS_NTC = 6: tiles the communication wavefront may sweep itself -- it waits at barrier (A) otherwise; which tiles a wavefront walks is the plan's
+//  table: rs_deal / rs_split, fos_internal.hpp -- 66 tiles = 9 9 9 9 8 8 8 + 6)
 
 // the rows of a wavefront's tiles that never leave the registers: residual, w = M r of the last sweep, the iterate
 template <int NT> struct RsRows { d2 rr[NT], ww[NT], xx[NT]; };
@@ -821,6 +815,9 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
     __shared__ double s_ctl[RC_COUNT];
     __shared__ uint32_t s_halves[PEER_MAX_RANKS * 8];
     __shared__ int s_cnt, s_failed;
+    // the tau element's x, p, s and the last iteration's scalars: the communication wavefront needs them between the totals and barrier (B) alone, and
+    // PARKS them here -- live across its sweep, 20 registers of wavefront-uniform values were what its six tiles' rows did not fit beside
+    __shared__ double s_tau[9];
     extern __shared__ __attribute__((aligned(16))) double s_dyn[];
     d2* const s_colpart = reinterpret_cast<d2*>(s_dyn);                       // [RS_NCOMP + 1][64]: a wavefront's column sums of a sweep
     double* const s_all = reinterpret_cast<double*>(s_colpart + (RS_NCOMP + 1) * 64);      // [4][RS_GMAX], zero beyond G
@@ -838,14 +835,14 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
     {
         const int b = (int)blockIdx.x;
         const int wslot = b == 0 ? 0 : (b == 1 ? 1 : (b == a.G / 2 ? 2 : (b == a.G - 1 ? 3 : -1)));
-        if (wslot >= 0 && lane == 0 && wv < 16) stamp_slot = wslot * 16 + wv;
+        if (wslot >= 0 && wv < 16) stamp_slot = wslot * 16 + wv;
     }
 #endif
     if (a.pb.nranks > 0 && st->xchg_failed) return;
     if (tid == 0) { s_cnt = 0; s_failed = 0; }
     RES_STAMP_CAL(63);
     int t0, cnt;
-    rs_split(me.nblk, wv, t0, cnt);                        // (compute wavefronts: cnt <= NT, the communication wavefront: cnt <= RS_NTC -- the plan's promise)
+    rs_split((uint32_t)me.T, wv, t0, cnt);                      // (compute wavefronts: cnt <= NT, the communication wavefront: cnt <= RS_NTC -- the plan's promise)
 
     if (wv < ncomp) {
         // =========================================================== COMPUTE wavefronts: their tiles streamed once per iteration
@@ -897,25 +894,25 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
     // =============================================================== COMMUNICATION wavefronts (the register form's, a unit = this workgroup alone)
     const int cw = wv - ncomp, ct = tid - 64 * ncomp;
     const bool c0wave = cw == 0, leader = me.idx == 0;              // (a unit split over wpu workgroups: its columns are counted once, by the first)
-    d2 cx = make_double2(0.0, 0.0), cr = cx, cpv = cx, csv = cx, crhs = cx;
+    d2 cx = make_double2(0.0, 0.0), cpv = cx, csv = cx;
     double cc = 0.0;
-    d2 gt = a.v[nm], xt = a.x[nm], pt = make_double2(0.0, 0.0), stt = pt;
-    const d2 rhst = a.rhs[nm];
     for (int q = ct; q < 4 * RS_GMAX; q += 64 * ncomm) s_all[q] = 0.0;
     for (int q = ct + (ncomp + 1) * 4; q < 16 * 4; q += 64 * ncomm) (&s_red[0][0])[q] = 0.0;
-    // (this wavefront waits at barrier (A) while the others sweep: it walks the workgroup's last RS_NTC tiles itself -- 66 tiles are 7 x 9 + 3)
-    RsRows<RS_NTC> R;
-    rs_rows_load<RS_NTC>(a, me.blk0 + t0, c0wave ? cnt : 0, lane, R);
+    // (this wavefront waits at barrier (A) while the others sweep: it walks the workgroup's last tiles itself, at most RS_NTC -- the plan's deal)
+    constexpr int NTC = TMAX > 32 ? RS_NTC_BASE : RS_NTC;      // (64-step tiles: two passes per tile, the share it always had)
+    RsRows<NTC> R;
+    rs_rows_load<NTC>(a, me.blk0 + t0, c0wave ? cnt : 0, lane, R);
     d2* const mycol = s_colpart + ncomp * 64;
     if (c0wave) {
-        if (lane < tc) { cr = a.v[c0 + lane]; cx = a.x[c0 + lane]; crhs = a.rhs[c0 + lane]; cc = a.cb[c0 + lane]; }
+        d2 cr = make_double2(0.0, 0.0);
+        if (lane < tc) { cr = a.v[c0 + lane]; cx = a.x[c0 + lane]; cc = a.cb[c0 + lane]; }
         s_gcol[lane] = cr;
+        const d2 gt = a.v[nm], xt = a.x[nm];
         if (lane == 0) { s_ctl[RC_GTX] = gt.x; s_ctl[RC_GTY] = gt.y; s_ctl[RC_STOP] = 0.0; }      // (the compute wavefronts read the tau element here, from the start)
+        if (lane == 0) { s_tau[0] = xt.x; s_tau[1] = xt.y; s_tau[2] = s_tau[3] = s_tau[4] = s_tau[5] = s_tau[6] = s_tau[7] = s_tau[8] = 0.0; }
         if (blockIdx.x == 0 && lane == 0) { st->tol = a.tol; st->maxit = a.maxit; st->hit_max = 0; st->rn_old = 0.0; }
     }
     __syncthreads();                                           // (0)
-    double colG = 0.0;
-    double g_prev = 0.0, a_prev = 0.0, gam = 0.0;
     int iter = 0;
     uint32_t nx = 0;
     RES_STAMP(0);
@@ -927,7 +924,7 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
         nx += 1;
         if (c0wave) {
             double racc[4];
-            rs_sweep<TMAX, RS_NTC>(a, me.blk0 + t0, cnt, c0, lane, s_gcol, s_ctl, mycol, R, racc, early);
+            rs_sweep<TMAX, NTC>(a, me.blk0 + t0, cnt, c0, lane, s_gcol, s_ctl, mycol, R, racc, early);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const double v = wave_sum(racc[k]);
@@ -937,7 +934,22 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
         __syncthreads();                                       // (A)
         RES_STAMP(1);
         d2 cp = make_double2(0.0, 0.0);
+        // the tau element and the columns of the vector being swept (the first communication wavefront's) are read back from where the compute
+        // wavefronts read them, not held across the sweep; the columns' share of r.r is formed from them (it is unused at the start: no r.r there)
+        d2 gt = make_double2(0.0, 0.0), cr = gt, crhs = gt, rhst = gt;
+        double colG = 0.0;
         if (c0wave) {
+            gt = make_double2(s_ctl[RC_GTX], s_ctl[RC_GTY]);
+            cr = s_gcol[lane];                                   // (zeros beyond the workgroup's columns)
+            // (the start: the rhs of the columns and of the tau element, requested here -- they arrive under the exchange and are held from here to
+            //  barrier (B), not across a sweep)
+            if (i < 0) { crhs = lane < tc ? a.rhs[c0 + lane] : make_double2(0.0, 0.0); rhst = a.rhs[nm]; }
+            {   // (formed from copies the compiler cannot see through: sharing the squares with w.g below, it no longer fused them there as it did
+                //  when this sum was formed behind the update -- other roundings, not the same bits as before)
+                double rx = cr.x, ry = cr.y;
+                asm volatile("" : "+v"(rx), "+v"(ry));
+                colG = (leader && lane < tc) ? rx * rx + ry * ry : 0.0;
+            }
             double acc[4] = {0.0, 0.0, 0.0, 0.0};
             {
                 d2 o[ncomp + 1];
@@ -1005,6 +1017,8 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
             }
             RES_STAMP(4);
             bool failed = __hip_atomic_load(&s_failed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0;
+            d2 xt = make_double2(s_tau[0], s_tau[1]), pt = make_double2(s_tau[2], s_tau[3]), stt = make_double2(s_tau[4], s_tau[5]);
+            double g_prev = s_tau[6], a_prev = s_tau[7], gam = s_tau[8];
             double tot[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -1070,13 +1084,11 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
                     }
                 }
             }
-            if (stopf == 0.0 && !early) {
-                colG = (leader && lane < tc) ? cr.x * cr.x + cr.y * cr.y : 0.0;
-                s_gcol[lane] = lane < tc ? cr : make_double2(0.0, 0.0);
-            }
+            if (stopf == 0.0 && !early) s_gcol[lane] = lane < tc ? cr : make_double2(0.0, 0.0);
             if (lane == 0) {
                 if (!early) { s_ctl[RC_ALPHA] = alpha; s_ctl[RC_BETA] = beta; s_ctl[RC_GTX] = gt.x; s_ctl[RC_GTY] = gt.y; s_ctl[RC_NEAR] = near; }
                 s_ctl[RC_STOP] = stopf;
+                s_tau[0] = xt.x; s_tau[1] = xt.y; s_tau[2] = pt.x; s_tau[3] = pt.y; s_tau[4] = stt.x; s_tau[5] = stt.y; s_tau[6] = g_prev; s_tau[7] = a_prev; s_tau[8] = gam;
             }
         }
         RES_STAMP(6);                                           // scalars, columns, tau
@@ -1086,7 +1098,7 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
         RES_STAMP(0);
         if (s_ctl[RC_STOP] != 0.0) break;
         if (!early) {
-            if (c0wave) rs_update<RS_NTC>(a, me.blk0 + t0, t0, cnt, lane, i, s_ctl[RC_ALPHA], s_ctl[RC_BETA], s_ps, R);
+            if (c0wave) rs_update<NTC>(a, me.blk0 + t0, t0, cnt, lane, i, s_ctl[RC_ALPHA], s_ctl[RC_BETA], s_ps, R);
             early = s_ctl[RC_NEAR] != 0.0;
             ++i;
         } else early = false;                                  // (not converged yet: the sweep of the same iteration follows)
@@ -1094,11 +1106,12 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
     RES_STAMP_CAL(62);
     if (c0wave) {
         const bool ok = s_ctl[RC_STOP] == 1.0;
-        if (ok) rs_rows_store<RS_NTC>(a, me.blk0 + t0, cnt, lane, R);
+        if (ok) rs_rows_store<NTC>(a, me.blk0 + t0, cnt, lane, R);
         if (ok && leader && lane < tc) a.x[c0 + lane] = cx;
         if (blockIdx.x == 0 && lane == 0) {
             if (ok) {
-                a.x[nm] = xt;
+                a.x[nm] = make_double2(s_tau[0], s_tau[1]);
+                const double gam = s_tau[8];
                 st->rr = gam;
                 cg_signal_stop(st, iter, a.maxit, gam, a.seq_base >> 11);
             } else {

@@ -2589,6 +2589,17 @@ int fos_host_resident_plan(int64_t m, int64_t n, const int64_t* colptr, const in
     return FOS_OK;
 }
 
+// (not part of the ABI: the CPU test-suite's view of the streamed form's deal -- cnt8 = the tiles each of the eight wavefronts of a workgroup of `tiles`
+//  tiles of at most `steps` steps walks, seven compute wavefronts and then the communication wavefront, consecutive tiles in wavefront order, as the
+//  plan carries them to the kernel; lds_bytes (may be NULL) = the dynamic LDS of the launch)
+extern "C" int fos_debug_resident_deal(int32_t tiles, int32_t steps, int32_t* cnt8, int64_t* lds_bytes) {
+    if (tiles < 0 || steps < 1 || steps > 64 || !cnt8) { set_error("bad argument"); return FOS_EINVAL; }
+    const uint32_t deal = rs_deal(tiles, rs_ntc(steps));
+    for (int w = 0, t0, cnt; w <= RS_NCOMP; ++w) { rs_split(deal, w, t0, cnt); cnt8[w] = cnt; }
+    if (lds_bytes) *lds_bytes = (int64_t)res_stream_lds_bytes(tiles);
+    return FOS_OK;
+}
+
 int fos_host_stacked_spmv(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval,
                           const double* v, double* out, int32_t spmv_workgroups, int32_t resident_waves, int64_t* stats) {
     if (!colptr || !v || !out || m < 0 || n < 0) { set_error("bad argument"); return FOS_EINVAL; }
