@@ -14,6 +14,7 @@ LIB_PATH = Path(os.environ["FOSHIP_LIB"]) if os.environ.get("FOSHIP_LIB") else _
 FOS_OK = 0
 CONE_CODES = {"Free": 0, "Zero": 1, "NonNeg": 2, "NonPos": 3, "SOC": 4, "SOCRotated": 5, "SDP": 6,
               "ExpPrimal": 7, "ExpDual": 8}
+SET_CODES = {"IndFree": 0, "IndBallL2": 1, "IndBallL1": 2, "IndSimplex": 3, "IndHalfspace": 4, "IndHyperslab": 5, "IndPoint": 6, "IndBox": 7}      # FOS_SET_*
 ALG_GAP, ALG_GAPA, ALG_FISTA, ALG_DYKSTRA = 0, 1, 2, 3
 CG_REFERENCE, CG_FUSED_P, CG_MERGED_SWEEP, CG_MERGED_UPDATE, CG_RESIDENT = 0, 1, 2, 3, 4
 DEBUG_PUPDATE_DELAY = 1
@@ -129,6 +130,9 @@ PROTOTYPES = {
     "fos_feas_set_box_arrays": (C.c_int, [_h, C.c_int32, _dp, _dp]),
     "fos_feas_set_cones": (C.c_int, [_h, C.c_int32, C.c_int64, _i32p, _i64p]),
     "fos_feas_set_callback": (C.c_int, [_h, C.c_int32, C.c_void_p, C.c_void_p]),
+    "fos_feas_set_blocks": (C.c_int, [_h, C.c_int32, C.c_int64, _i32p, _i64p, _dp, _dp]),
+    "fos_feas_set_stats": (C.c_int, [_h, C.c_int32, _dp]),
+    "fos_host_set_project": (C.c_int, [C.c_int32, C.c_int64, _dp, _dp, _dp, _dp, _i32p]),
     "fos_feas_set_alg": (C.c_int, [_h, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double]),
     "fos_feas_set_gapp": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, C.c_int64]),
     "fos_feas_gapp_log": (C.c_int, [_h, _dp]),

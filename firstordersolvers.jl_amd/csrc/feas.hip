@@ -158,8 +158,9 @@ __global__ __launch_bounds__(FEAS_THREADS) void feas_pad_identity_kernel(int64_t
 }
 
 struct FeasSet {
-    int kind = 0;                   // 0 unset, 1 IndAffine (dense), 2 IndBox, 3 ConeProduct, 4 host callback, 5 IndAffine (sparse A)
+    int kind = 0;                   // 0 unset, 1 IndAffine (dense), 2 IndBox, 3 ConeProduct, 4 host callback, 5 IndAffine (sparse A), 6 separable sum of sets
     SparseAffine* sa = nullptr;     // kind 5 (affine_sparse.hip)
+    SetBlocks* sb = nullptr;        // kind 6 (sets.hip)
     fos_prox_fn cb = nullptr;       // kind 4: prox!(y, S, x) evaluated by the caller on pinned host vectors
     void* cb_ctx = nullptr;
     double *cb_x = nullptr, *cb_y = nullptr;
@@ -271,6 +272,8 @@ int feas_prox(fos_feas* h, int which, double* y, const double* x) {
         FEAS_K(feas_from_parts_kernel, h->n, y, (const double2*)h->zout);
     } else if (s.kind == 5) {                                             // IndAffine over a sparse A: CG on the normal equations, exact to the residual's rounding level
         FOS_TRY(sparse_affine_project(s.sa, h->stream, y, x));
+    } else if (s.kind == 6) {                                             // balls, simplex, halfspaces ... in contiguous blocks: a fixed number of launches, no copy
+        FOS_TRY(set_blocks_project(s.sb, h->stream, y, x));
     } else if (s.kind == 4) {                                             // any other ProximableFunction: the caller's prox! on host vectors
         FOS_HIP(hipMemcpyAsync(s.cb_x, x, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
         FOS_HIP(hipStreamSynchronize(h->stream));
@@ -472,7 +475,7 @@ int fos_feas_destroy(fos_feas_handle h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (void* q : h->owned) (void)hipFree(q);
-    for (FeasSet& s : h->S) { if (s.cb_x) (void)hipHostFree(s.cb_x); if (s.cb_y) (void)hipHostFree(s.cb_y); psd_sign_destroy(s.psd_big); sparse_affine_destroy(s.sa); }
+    for (FeasSet& s : h->S) { if (s.cb_x) (void)hipHostFree(s.cb_x); if (s.cb_y) (void)hipHostFree(s.cb_y); psd_sign_destroy(s.psd_big); sparse_affine_destroy(s.sa); set_blocks_destroy(s.sb); }
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return FOS_OK;
@@ -690,6 +693,24 @@ int fos_feas_set_callback(fos_feas_handle h, int32_t which, fos_prox_fn fn, void
     s.cb = fn; s.cb_ctx = ctx;
     s.kind = 4;
     return FOS_OK;
+}
+
+// A separable sum of convex vector sets (sets.hip; Feasibility.jl:2-6): validated and built first, so that a refused call leaves the set as it was
+int fos_feas_set_blocks(fos_feas_handle h, int32_t which, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec) {
+    if (!h || which < 1 || which > 2) { set_error("fos_feas_set_blocks: NULL handle or which not in {1, 2}"); return FOS_EINVAL; }
+    FOS_HIP(hipSetDevice(h->device));
+    SetBlocks* sb = nullptr;
+    FOS_TRY(set_blocks_setup(h->n, nblocks, kind, len, scal, vec, &sb));
+    FeasSet& s = h->S[which - 1];
+    FOS_HIP(hipStreamSynchronize(h->stream));                          // (a projection onto the set being replaced may still run)
+    set_blocks_destroy(s.sb);
+    s.sb = sb; s.kind = 6;
+    return FOS_OK;
+}
+int fos_feas_set_stats(fos_feas_handle h, int32_t which, double* out8) {
+    if (!h || !out8 || which < 1 || which > 2 || h->S[which - 1].kind != 6) { set_error("fos_feas_set_stats: set %d was not defined by fos_feas_set_blocks", (int)which); return FOS_EINVAL; }
+    FOS_HIP(hipSetDevice(h->device));
+    return set_blocks_stats(h->S[which - 1].sb, h->stream, out8);
 }
 
 int fos_feas_set_alg(fos_feas_handle h, int32_t alg, double alpha, double alpha1, double alpha2, double beta) {

@@ -653,6 +653,12 @@ int sparse_affine_project(SparseAffine* a, hipStream_t stream, double* y, const 
 void sparse_affine_reset(SparseAffine* a, hipStream_t stream);                                   // a new solve: lambda = 0
 void sparse_affine_stats(const SparseAffine* a, double* out8);
 void sparse_affine_destroy(SparseAffine* a);
+// Separable sums of convex vector sets (sets.hip): norm balls, simplex, halfspace / hyperslab, point, free, scalar box -- contiguous blocks covering 1..n
+struct SetBlocks;
+int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec, SetBlocks** out);
+int set_blocks_project(SetBlocks* p, hipStream_t stream, double* y, const double* x);           // y, x: device vectors of length n, y must not alias x
+int set_blocks_stats(SetBlocks* p, hipStream_t stream, double* out8);
+void set_blocks_destroy(SetBlocks* p);
 size_t psd_scratch_bytes(int kmax, int ncones);
 size_t psd_basis_doubles(int kmax, int ncones);
 

@@ -857,11 +857,156 @@ class ConeProduct:
                 raise ValueError("unknown cone %r (supportedcones: %s)" % (k, ", ".join(_lib.CONE_CODES)))
 
 
+# Convex vector sets projected by the kernels of csrc/sets.hip (fos_feas_set_blocks).  Parameter holders like IndBox: validation, no arithmetic.
+# ProximalOperators.jl's definitions: the projection of each is stated in its docstring.
+
+def _finite_scalar(name, v):
+    v = float(v)
+    if not np.isfinite(v):
+        raise ValueError("%s must be finite, got %r" % (name, v))
+    return v
+
+
+def _finite_vector(name, v):
+    v = np.ascontiguousarray(np.asarray(v, dtype=np.float64))
+    if v.ndim != 1 or v.size < 1 or not np.all(np.isfinite(v)):
+        raise ValueError("%s must be a non-empty vector of finite numbers" % name)
+    return v
+
+
+class _VectorSet:
+    """One block of a SeparableSum: `kind` (a key of _lib.SET_CODES), the two scalars and the vector fos_feas_set_blocks takes for it."""
+    kind, scal, vec = "IndFree", (0.0, 0.0), None
+
+    def _block(self, length):
+        if self.vec is not None and self.vec.shape[0] != length:
+            raise ValueError("%s: its vector has %d entries, the block has %d" % (self.kind, self.vec.shape[0], length))
+        return _lib.SET_CODES[self.kind], self.scal, self.vec
+
+
+class IndBallL2(_VectorSet):
+    """{x : |x - c|_2 <= r}.  d = x - c: y = x if |d| <= r, else c + d (r / |d|)."""
+    kind = "IndBallL2"
+
+    def __init__(self, r=1.0, center=None):
+        self.r = _finite_scalar("IndBallL2: r", r)
+        if self.r < 0.0:
+            raise ValueError("IndBallL2: r >= 0 is required")
+        self.center = self.vec = None if center is None else _finite_vector("IndBallL2: center", center)
+        self.scal = (self.r, 0.0)
+
+
+class IndBallL1(_VectorSet):
+    """{x : |x|_1 <= r}.  y = x if |x|_1 <= r, else sign(x) max(|x| - tau, 0) with sum max(|x_i| - tau, 0) = r."""
+    kind = "IndBallL1"
+
+    def __init__(self, r=1.0):
+        self.r = _finite_scalar("IndBallL1: r", r)
+        if self.r < 0.0:
+            raise ValueError("IndBallL1: r >= 0 is required")
+        self.scal = (self.r, 0.0)
+
+
+class IndSimplex(_VectorSet):
+    """{x : x >= 0, sum x = a}.  y = max(x - tau, 0) with sum max(x_i - tau, 0) = a (always thresholded; tau may be negative)."""
+    kind = "IndSimplex"
+
+    def __init__(self, a=1.0):
+        self.a = _finite_scalar("IndSimplex: a", a)
+        if not self.a > 0.0:
+            raise ValueError("IndSimplex: a > 0 is required")
+        self.scal = (self.a, 0.0)
+
+
+class IndHalfspace(_VectorSet):
+    """{x : <a, x> <= b}.  y = x - max(0, (<a, x> - b) / <a, a>) a."""
+    kind = "IndHalfspace"
+
+    def __init__(self, a, b):
+        self.a = self.vec = _finite_vector("IndHalfspace: a", a)
+        if not np.any(self.a != 0.0):
+            raise ValueError("IndHalfspace: the normal vector is zero")
+        self.b = _finite_scalar("IndHalfspace: b", b)
+        self.scal = (self.b, 0.0)
+
+
+class IndHyperslab(_VectorSet):
+    """{x : lo <= <a, x> <= hi}.  The halfspace's projection, towards whichever side is violated."""
+    kind = "IndHyperslab"
+
+    def __init__(self, lo, a, hi):
+        self.a = self.vec = _finite_vector("IndHyperslab: a", a)
+        if not np.any(self.a != 0.0):
+            raise ValueError("IndHyperslab: the normal vector is zero")
+        self.lo, self.hi = _finite_scalar("IndHyperslab: lo", lo), _finite_scalar("IndHyperslab: hi", hi)
+        if self.lo > self.hi:
+            raise ValueError("IndHyperslab: lo <= hi is required")
+        self.scal = (self.lo, self.hi)
+
+
+class IndPoint(_VectorSet):
+    """{p}.  y = p."""
+    kind = "IndPoint"
+
+    def __init__(self, p):
+        self.p = self.vec = _finite_vector("IndPoint: p", p)
+
+
+class IndFree(_VectorSet):
+    """R^k.  y = x."""
+    kind = "IndFree"
+
+
+class SeparableSum:
+    """The analogue of ProximalOperators.SlicedSeparableSum over index ranges, in the style of ConeProduct: blocks = [(set, length), ...], contiguous, in
+    order, together covering 1..n.  A set is one of IndBallL2, IndBallL1, IndSimplex, IndHalfspace, IndHyperslab, IndPoint, IndFree or an IndBox with
+    scalar bounds (cones stay in ConeProduct).  A bare set used as S1 or S2 is the one-block case of length n."""
+
+    def __init__(self, blocks):
+        self.blocks = []
+        for S, length in blocks:
+            length = int(length)
+            if length < 1:
+                raise ValueError("SeparableSum: block %d has length %d < 1" % (len(self.blocks) + 1, length))
+            if isinstance(S, IndBox):
+                if S.arrays:
+                    raise ValueError("SeparableSum: block %d: an IndBox inside a SeparableSum takes scalar bounds" % (len(self.blocks) + 1))
+                if not S.lo <= S.hi:
+                    raise ValueError("SeparableSum: block %d: IndBox needs lo <= hi" % (len(self.blocks) + 1))
+            elif not isinstance(S, _VectorSet):
+                raise ValueError("SeparableSum: block %d is %s: not one of the vector sets of the device path" % (len(self.blocks) + 1, type(S).__name__))
+            else:
+                S._block(length)                                       # (the length of its vector)
+            self.blocks.append((S, length))
+        if not self.blocks:
+            raise ValueError("SeparableSum: at least one block is required")
+        self.n = sum(l for _, l in self.blocks)
+
+    def pack(self, n):
+        """-> (kind[nblocks] int32, len[nblocks] int64, scal[2 nblocks], vec[n]): the arguments of fos_feas_set_blocks"""
+        if self.n != n:
+            raise ValueError("SeparableSum: the blocks cover %d entries, the problem has n = %d" % (self.n, n))
+        kinds, lens = np.zeros(len(self.blocks), dtype=np.int32), np.zeros(len(self.blocks), dtype=np.int64)
+        scal, vec = np.zeros(2 * len(self.blocks)), np.zeros(n)
+        pos = 0
+        for i, (S, length) in enumerate(self.blocks):
+            if isinstance(S, IndBox):
+                kinds[i], scal[2 * i], scal[2 * i + 1] = _lib.SET_CODES["IndBox"], S.lo, S.hi
+            else:
+                kinds[i], (scal[2 * i], scal[2 * i + 1]), v = S._block(length)
+                if v is not None:
+                    vec[pos:pos + length] = v
+            lens[i] = length
+            pos += length
+        return kinds, lens, scal, vec
+
+
 PROX_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double))     # fos_prox_fn
 
 
 class Feasibility:
-    """struct Feasibility{T1,T2}(S1, S2, n)   Feasibility.jl:2-6.  S1, S2: IndAffine, IndBox, ConeProduct (device resident) or any
+    """struct Feasibility{T1,T2}(S1, S2, n)   Feasibility.jl:2-6.  S1, S2: IndAffine, IndBox, ConeProduct, a vector set (IndBallL2, IndBallL1,
+    IndSimplex, IndHalfspace, IndHyperslab, IndPoint, IndFree) or a SeparableSum of them (all device resident), or any
     object with a `prox(y, x)` method filling y = prox_S(x) in place (the ProximableFunction protocol; evaluated on the host)."""
 
     def __init__(self, S1, S2, n):
@@ -879,15 +1024,23 @@ class HipFeasibility:
     """The device handle of a Feasibility problem (fos_feas_*): both sets, the algorithm's vectors and the status state."""
 
     def __init__(self, problem: Feasibility, device=0):
-        self._lib = _lib.load()
         self.n = problem.n
+        packed = {}                                                     # the vector sets are checked against n before any device call
+        for which, S in ((1, problem.S1), (2, problem.S2)):
+            if isinstance(S, _VectorSet):
+                S = SeparableSum([(S, self.n)])
+            if isinstance(S, SeparableSum):
+                packed[which] = S.pack(self.n)
+        self._lib = _lib.load()
         h = C.c_void_p()
         _lib.check(self._lib.fos_feas_create(self.n, device, C.byref(h)))
         self._h = h
         self._callbacks = []
         self.callback_error = None
         for which, S in ((1, problem.S1), (2, problem.S2)):
-            if isinstance(S, IndAffine):
+            if which in packed:                                         # before the `prox` test: these never become callbacks
+                self.set_blocks(which, *packed[which])
+            elif isinstance(S, IndAffine):
                 if S.A.shape[1] != self.n:
                     raise ValueError("IndAffine: A has %d columns, the problem has n = %d" % (S.A.shape[1], self.n))
                 if S.sparse:
@@ -910,12 +1063,31 @@ class HipFeasibility:
                 _lib.check(self._lib.fos_feas_set_cones(self._h, which, len(S.cones), types.ctypes.data_as(C.POINTER(C.c_int32)),
                                                         lens.ctypes.data_as(C.POINTER(C.c_int64))))
             elif callable(getattr(S, "prox", None)):                    # any other ProximableFunction: prox!(y, S, x) as a host callback
-                cb = PROX_FN(self._make_prox_callback(S))
-                self._callbacks.append(cb)                              # (the library keeps the pointer: it must outlive the handle)
-                _lib.check(self._lib.fos_feas_set_callback(self._h, which, C.cast(cb, C.c_void_p), None))
+                self.set_callback(which, S)
             else:
                 raise _lib.FosError(-4, "Feasibility: set %d must be IndAffine, IndBox, ConeProduct or an object with a prox(y, x) method "
                                         "(evaluated on the host through fos_feas_set_callback), got %s" % (which, type(S).__name__))
+
+    def set_blocks(self, which, kinds, lens, scal, vec):
+        """fos_feas_set_blocks with raw arrays (SeparableSum.pack): replaces set `which`"""
+        kinds, lens = np.ascontiguousarray(kinds, dtype=np.int32), np.ascontiguousarray(lens, dtype=np.int64)
+        scal = np.ascontiguousarray(scal, dtype=np.float64)
+        vec = None if vec is None else np.ascontiguousarray(vec, dtype=np.float64)
+        _lib.check(self._lib.fos_feas_set_blocks(self._h, which, len(kinds), kinds.ctypes.data_as(C.POINTER(C.c_int32)), lens.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 _lib.dptr(scal), None if vec is None else _lib.dptr(vec)))
+
+    def set_callback(self, which, S):
+        """fos_feas_set_callback: set `which` becomes the object S, its prox(y, x) evaluated on the host"""
+        cb = PROX_FN(self._make_prox_callback(S))
+        self._callbacks.append(cb)                                      # (the library keeps the pointer: it must outlive the handle)
+        _lib.check(self._lib.fos_feas_set_callback(self._h, which, C.cast(cb, C.c_void_p), None))
+
+    def set_stats(self, which):
+        """the counters of a set defined by fos_feas_set_blocks (fos_feas_set_stats)"""
+        o = np.zeros(8)
+        _lib.check(self._lib.fos_feas_set_stats(self._h, which, _lib.dptr(o)))
+        return {"blocks": int(o[0]), "wave_blocks": int(o[1]), "workgroup_blocks": int(o[2]), "grid_blocks": int(o[3]), "launches": int(o[4]),
+                "last_passes": int(o[5]), "pass_cap": int(o[6]), "candidates": int(o[7])}
 
     def _make_prox_callback(self, S):
         n = self.n

@@ -309,7 +309,8 @@ end
 
 # ---- Feasibility form [problemforms/Feasibility/Feasibility.jl, FeasibilityStatus.jl]: solve!(Feasibility(S1, S2, n), alg; gpu=true)
 #      with S1, S2 among ProximalOperators.IndAffine (dense A), IndBox -- the sets of test/testfeasibility.jl -- and
-#      FirstOrderSolvers.ConeProduct on the device; any other ProximableFunction through a host callback (fos_feas_set_callback).
+#      FirstOrderSolvers.ConeProduct on the device, as are IndBallL2, IndBallL1, IndSimplex, IndHalfspace, IndHyperslab, IndPoint and IndFree
+#      (fos_feas_set_blocks); any other ProximableFunction through a host callback (fos_feas_set_callback).
 #      init_algorithm! returns a HipFeasData; iterate dispatches on it; FeasibilityModel, populate_solution and the printed table
 #      stay the reference's own code.
 import ..FirstOrderSolvers: FeasibilityModel, FeasibilityStatus
@@ -325,6 +326,56 @@ function prox_trampoline(ctx::Ptr{Cvoid}, n::Int64, x::Ptr{Cdouble}, y::Ptr{Cdou
     end
 end
 const PROX_TRAMPOLINE = Ref{Ptr{Cvoid}}(C_NULL)             # @cfunction pointers are made at run time (__init__)
+
+# Vector sets with kernels of their own (csrc/sets.hip, fos_feas_set_blocks) [Feasibility.jl:2-6 takes any two ProximableFunctions]: kind codes of
+# include/foship.h, and the (kind, scalar 1, scalar 2, vector | nothing) of the ProximalOperators types that map onto one block of length n
+const FOS_SET_FREE = Int32(0)
+const FOS_SET_BALL_L2 = Int32(1)
+const FOS_SET_BALL_L1 = Int32(2)
+const FOS_SET_SIMPLEX = Int32(3)
+const FOS_SET_HALFSPACE = Int32(4)
+const FOS_SET_HYPERSLAB = Int32(5)
+const FOS_SET_POINT = Int32(6)
+const FOS_SET_BOX = Int32(7)
+vectorset_block(S) = nothing
+vectorset_block(S::ProximalOperators.IndFree) = (FOS_SET_FREE, 0.0, 0.0, nothing)
+vectorset_block(S::ProximalOperators.IndBallL2) = (FOS_SET_BALL_L2, Float64(S.r), 0.0, nothing)
+vectorset_block(S::ProximalOperators.IndBallL1) = (FOS_SET_BALL_L1, Float64(S.r), 0.0, nothing)
+vectorset_block(S::ProximalOperators.IndSimplex) = (FOS_SET_SIMPLEX, Float64(S.a), 0.0, nothing)
+vectorset_block(S::ProximalOperators.IndHalfspace) = (FOS_SET_HALFSPACE, Float64(S.b), 0.0, Vector{Float64}(vec(S.a)))
+vectorset_block(S::ProximalOperators.IndHyperslab) = (FOS_SET_HYPERSLAB, Float64(S.low), Float64(S.upp), Vector{Float64}(vec(S.a)))
+vectorset_block(S::ProximalOperators.IndPoint) = (FOS_SET_POINT, 0.0, 0.0, Vector{Float64}(vec(S.p)))
+# blocks = [(kind, s1, s2, vector | nothing, length), ...]: contiguous, in order, covering 1..n
+function feas_set_blocks!(handle::Ptr{Cvoid}, which::Integer, n::Integer, blocks)
+    kinds = Int32[b[1] for b in blocks]
+    lens = Int64[b[5] for b in blocks]
+    scal = Float64[]
+    v = zeros(Float64, n)
+    pos = 0
+    for b in blocks
+        push!(scal, b[2], b[3])
+        b[4] === nothing || (v[pos+1:pos+b[5]] .= b[4])
+        pos += b[5]
+    end
+    GC.@preserve kinds lens scal v check(ccall((:fos_feas_set_blocks, libfoship), Cint,
+                                               (Ptr{Cvoid}, Int32, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}),
+                                               handle, Int32(which), Int64(length(blocks)), kinds, lens, scal, v))
+end
+function feas_set_stats(handle::Ptr{Cvoid}, which::Integer)
+    out = zeros(Float64, 8)
+    check(ccall((:fos_feas_set_stats, libfoship), Cint, (Ptr{Cvoid}, Int32, Ptr{Cdouble}), handle, Int32(which), out))
+    return (blocks = Int(out[1]), wave_blocks = Int(out[2]), workgroup_blocks = Int(out[3]), grid_blocks = Int(out[4]), launches = Int(out[5]),
+            last_passes = Int(out[6]), pass_cap = Int(out[7]), candidates = Int(out[8]))
+end
+# test entry: the host emulation of one block's projection (no GPU needed)
+function host_set_project(kind::Integer, scal::NTuple{2,Float64}, v::Union{Nothing,Vector{Float64}}, x::Vector{Float64})
+    y = similar(x)
+    passes = Ref{Int32}(0)
+    sc = [scal[1], scal[2]]
+    check(ccall((:fos_host_set_project, libfoship), Cint, (Int32, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Int32}),
+                Int32(kind), Int64(length(x)), sc, v === nothing ? C_NULL : pointer(v), x, y, passes))
+    return y, Int(passes[])
+end
 
 mutable struct HipFeasData <: FOSSolverData
     handle::Ptr{Cvoid}
@@ -359,6 +410,8 @@ mutable struct HipFeasData <: FOSSolverData
                 GC.@preserve As b check(ccall((:fos_feas_set_affine_sparse, libfoship), Cint,
                                               (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}),
                                               d.handle, which, Int64(size(As, 1)), As.colptr, As.rowval, As.nzval, b))
+            elseif vectorset_block(S) !== nothing           # a ball, simplex, halfspace, hyperslab, point or the free set: one block of length n
+                feas_set_blocks!(d.handle, which, model.n, [(vectorset_block(S)..., Int64(model.n))])
             else                                            # any other ProximableFunction: prox!(y, S, x) on host vectors [Feasibility.jl:2-6]
                 push!(d.sets, Ref{Any}(S))                  # (rooted: the library keeps a pointer to it)
                 check(ccall((:fos_feas_set_callback, libfoship), Cint, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}),

@@ -464,7 +464,8 @@ int fos_debug_set(fos_handle h, int32_t what, int64_t value);
  *                        evaluation (16 eps | |A||y| + |b| |) -- y - x is in the range of A' by construction (affine_sparse.hip).  Fails
  *                        loudly (FOS_EINVAL) when that level cannot be reached (A without full row rank).  fos_feas_affine_stats: iteration counts.
  *   fos_feas_set_box     IndBox(lo, hi), scalar bounds (fos_feas_set_box_arrays: array bounds), +-INFINITY allowed;
- *   fos_feas_set_cones   the reference's own ConeProduct (src/cones.jl), any of its nine cone types.
+ *   fos_feas_set_cones   the reference's own ConeProduct (src/cones.jl), any of its nine cone types;
+ *   fos_feas_set_blocks  norm balls, simplex, halfspace / hyperslab, point, free and scalar box, alone or as a separable sum of blocks.
  * `which` = 1 | 2 (S1, S2).  Steps: gap.jl:42-87 (GAP / DR / AP), gapa.jl:61-112, fista.jl:28-56, dykstra.jl:25-44; LineSearchWrapper. */
 typedef struct fos_feas* fos_feas_handle;
 int fos_feas_create(int64_t n, int32_t device, fos_feas_handle* out);
@@ -483,6 +484,31 @@ int fos_feas_set_cones(fos_feas_handle h, int32_t which, int64_t ncones, const i
  * of the iteration -- the other set, the relaxations, the status test -- stays on the device.  fn and ctx must outlive the handle. */
 typedef int32_t (*fos_prox_fn)(void* ctx, int64_t n, const double* x, double* y);
 int fos_feas_set_callback(fos_feas_handle h, int32_t which, fos_prox_fn fn, void* ctx);
+/* Separable sums of convex vector sets on the device (Feasibility.jl:2-6 takes any two ProximableFunctions; these no longer need the callback):
+ * nblocks contiguous blocks, in order, covering 1..n (the shape of SlicedSeparableSum); block i is the set kind[i] (FOS_SET_*) on len[i] entries.
+ *   scal[2 i], scal[2 i + 1]   r, - (IndBallL2, IndBallL1: |x - c|_2 <= r, |x|_1 <= r, r >= 0) | a, - (IndSimplex: x >= 0, sum x = a, a > 0) |
+ *                              b, - (IndHalfspace: <a, x> <= b) | lo, hi (IndHyperslab: lo <= <a, x> <= hi; IndBox: lo <= x <= hi, +-INFINITY allowed)
+ *   vec (n entries or NULL)    the centre / normal / point of each block AT THAT BLOCK'S OWN INDICES; ignored where a kind has none; NULL: all centres
+ *                              are the origin (an error if a block needs a normal or a point)
+ * Everything is validated again (FOS_EINVAL, the message names the block; the set `which` held before stays usable), <a, a> is computed once, and the
+ * set replaces whatever `which` was.  One projection is a fixed number of kernel launches, whatever the data, with no host synchronise or copy; sums
+ * have a fixed order (two runs give the same bits).  Blocks of up to 1024 entries take one wavefront each, up to 16 384 one workgroup each (both:
+ * one launch for all of them, the block read once and written once); longer blocks take grid-wide passes, one block after another. */
+#define FOS_SET_FREE       0   /* IndFree()                */
+#define FOS_SET_BALL_L2    1   /* IndBallL2(r) + centre    */
+#define FOS_SET_BALL_L1    2   /* IndBallL1(r)             */
+#define FOS_SET_SIMPLEX    3   /* IndSimplex(a)            */
+#define FOS_SET_HALFSPACE  4   /* IndHalfspace(a, b)       */
+#define FOS_SET_HYPERSLAB  5   /* IndHyperslab(lo, a, hi)  */
+#define FOS_SET_POINT      6   /* IndPoint(p)              */
+#define FOS_SET_BOX        7   /* IndBox(lo, hi), scalars  */
+int fos_feas_set_blocks(fos_feas_handle h, int32_t which, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec);
+/* out8 = blocks, blocks of the wavefront / workgroup / grid class, kernel launches of one projection, threshold passes the last projection needed
+ * (IndSimplex, IndBallL1: max over the blocks), the pass cap, candidates per pass.  FOS_EINVAL unless `which` was set by fos_feas_set_blocks. */
+int fos_feas_set_stats(fos_feas_handle h, int32_t which, double* out8);
+/* Test-only host emulation of ONE block's projection (no GPU needed; as fos_host_chol_inverse): the threshold search and the formulas of the kernels,
+ * with the partial sums of the class `len` falls in.  vec: centre / normal / point or NULL; passes (may be NULL): threshold passes used. */
+int fos_host_set_project(int32_t kind, int64_t len, const double* scal2, const double* vec, const double* x, double* y, int32_t* passes);
 int fos_feas_set_alg(fos_feas_handle h, int32_t alg, double alpha, double alpha1, double alpha2, double beta);
 /* GAPP ("projected GAP", src/solvers/gapproj.jl:5-81; test/testfeasibility.jl:36): GAP whose every iproj-th iteration searches 21 step
  * lengths 2^k along P_S1(P_S2(P_S1 x)) - P_S1 x.  out23 = the 21 test norms, alpha_best, iteration of the last search. */
