@@ -30,7 +30,8 @@ static_assert(2 * CH_OP >= CH_B * CH_LDX, "a whole 64 x 64 tile must fit the two
 typedef double ch_v4d __attribute__((ext_vector_type(4)));
 
 // An operand is a 64 x K matrix E(x, k).  KM = false: E(x, k) = P[x + k ld] (x contiguous), staged [k][x];  KM = true: E(x, k) = P[k + x ld] (k contiguous), staged [x][k].
-template <bool KM> __device__ __forceinline__ void ch_fetch(double (&r)[8], const double* __restrict__ P, size_t ld, int tid) {
+// GUARD (KM only): rows x >= nx of the operand are not read and count as zero.
+template <bool KM, bool GUARD = false> __device__ __forceinline__ void ch_fetch(double (&r)[8], const double* __restrict__ P, size_t ld, int tid, int nx = CH_B) {
     if (!KM) {
         const int x = tid & 63, k = tid >> 6;
 #pragma unroll
@@ -38,7 +39,7 @@ template <bool KM> __device__ __forceinline__ void ch_fetch(double (&r)[8], cons
     } else {
         const int k = tid & 31, x = tid >> 5;
 #pragma unroll
-        for (int q = 0; q < 8; ++q) r[q] = P[(size_t)k + (size_t)(x + 8 * q) * ld];
+        for (int q = 0; q < 8; ++q) r[q] = (!GUARD || x + 8 * q < nx) ? P[(size_t)k + (size_t)(x + 8 * q) * ld] : 0.0;
     }
 }
 template <bool KM> __device__ __forceinline__ void ch_stash(const double (&r)[8], double* __restrict__ S, int tid) {
@@ -56,16 +57,17 @@ template <bool KM> __device__ __forceinline__ double ch_frag(const double* __res
 
 // acc += A B over K (a multiple of CH_KC): A(i, k) and B(j, k) given as operands above (the product is sum_k A(i, k) B(j, k)).  The next chunk's global loads are
 // issued before the current chunk's MFMAs: with about one workgroup per CU in the panel chain nothing else hides their latency.  Ends behind a barrier.
-template <bool KA, bool KB>
-__device__ __forceinline__ void ch_tile_mma(ch_v4d (&acc)[2][2], const double* __restrict__ A, size_t lda, const double* __restrict__ B, size_t ldb, int K, double* sh) {
+template <bool KA, bool KB, bool GUARD = false>
+__device__ __forceinline__ void ch_tile_mma(ch_v4d (&acc)[2][2], const double* __restrict__ A, size_t lda, const double* __restrict__ B, size_t ldb, int K, double* sh,
+                                            int na = CH_B, int nb = CH_B) {
     if (K <= 0) return;
     double* As = sh;
     double* Bs = sh + CH_OP;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int wr = (wv >> 1) * 32, wc = (wv & 1) * 32, lr = lane & 15, lk = lane >> 4;
     double ra[8], rb[8];
-    ch_fetch<KA>(ra, A, lda, tid);
-    ch_fetch<KB>(rb, B, ldb, tid);
+    ch_fetch<KA, GUARD>(ra, A, lda, tid, na);
+    ch_fetch<KB, GUARD>(rb, B, ldb, tid, nb);
     for (int k0 = 0; k0 < K; k0 += CH_KC) {
         ch_stash<KA>(ra, As, tid);
         ch_stash<KB>(rb, Bs, tid);
@@ -73,8 +75,8 @@ __device__ __forceinline__ void ch_tile_mma(ch_v4d (&acc)[2][2], const double* _
         if (k0 + CH_KC < K) {
             A += KA ? (size_t)CH_KC : (size_t)CH_KC * lda;
             B += KB ? (size_t)CH_KC : (size_t)CH_KC * ldb;
-            ch_fetch<KA>(ra, A, lda, tid);
-            ch_fetch<KB>(rb, B, ldb, tid);
+            ch_fetch<KA, GUARD>(ra, A, lda, tid, na);
+            ch_fetch<KB, GUARD>(rb, B, ldb, tid, nb);
         }
 #pragma unroll
         for (int ks = 0; ks < CH_KC; ks += 4) {
@@ -229,7 +231,34 @@ __global__ __launch_bounds__(CH_T) void chol_wtw_kernel(int64_t L, const double*
         }
     });
 }
+
+// G = A A' + E for a ROW-major m x ld matrix A (ld % 64 == 0), E the identity on the padding m .. L-1: tiles i >= j of the L x L result, stored at (i, j) and mirrored
+// at (j, i), so G is exactly symmetric.  Both operands are contiguous along K = ld (the [x][34] staging); K is walked in order by the tile's one workgroup: no split,
+// nothing atomic, the same bits from every set-up.  Rows >= m of A do not exist: they are not read.
+__global__ __launch_bounds__(CH_T) void gram_rows_kernel(int64_t m, int64_t ld, const double* __restrict__ A, int64_t L, double* __restrict__ G) {
+    __shared__ double sh[2 * CH_OP];
+    const int i = blockIdx.x, j = blockIdx.y;
+    if (j > i) return;
+    const size_t i0 = (size_t)i * CH_B, j0 = (size_t)j * CH_B;
+    const int na = (int)std::min<int64_t>(CH_B, std::max<int64_t>(0, m - (int64_t)i0)), nb = (int)std::min<int64_t>(CH_B, std::max<int64_t>(0, m - (int64_t)j0));
+    ch_v4d acc[2][2];
+    ch_zero(acc);
+    ch_tile_mma<true, true, true>(acc, A + i0 * (size_t)ld, (size_t)ld, A + j0 * (size_t)ld, (size_t)ld, (int)ld, sh, na, nb);
+    ch_for_result(acc, [&](int row, int col, double v) {
+        if (i != j || row >= col) {
+            const size_t gi = i0 + row, gj = j0 + col;
+            if (gi == gj && gi >= (size_t)m) v = 1.0;
+            G[gi + gj * (size_t)L] = v;
+            G[gj + gi * (size_t)L] = v;
+        }
+    });
+}
 }  // namespace
+
+void launch_dense_gram_rows(const LaunchCtx& c, int64_t m, int64_t ld, const double* A, int64_t L, double* G) {
+    const int nb = (int)(L / CH_B);
+    hipLaunchKernelGGL(gram_rows_kernel, dim3(nb, nb), dim3(CH_T), 0, c.stream, m, ld, A, L, G);
+}
 
 // X = G^-1 for the symmetric positive definite G (column-major, leading dimension L, L % 64 == 0, padding = identity), on c.stream.  Lw and Ww: L x L work
 // buffers (the factor and its inverse; only their lower tiles are touched), X: the full symmetric inverse.  G is not modified.  *info (device): 0, or the first

@@ -49,23 +49,7 @@ struct DirectEnv {
     const int reduced_refine = getenv("FOS_DIRECT_REDUCED_REFINE") ? std::max(0, std::min(4, atoi(getenv("FOS_DIRECT_REDUCED_REFINE")))) : 1;   // refinement steps per projection
 };
 
-// ---- set-up scratch: device buffers that live to the end of a scope.  The first hipMalloc that fails stays in `err` (later requests give nullptr): ask for
-// everything, then look at err once.
-struct Scratch {
-    std::vector<void*> held;
-    hipError_t err = hipSuccess;
-    Scratch() = default;
-    Scratch(const Scratch&) = delete;
-    Scratch& operator=(const Scratch&) = delete;
-    ~Scratch() { for (void* p : held) (void)hipFree(p); }
-    template <class T> T* alloc(size_t count) {
-        void* p = nullptr;
-        if (err == hipSuccess) err = hipMalloc(&p, sizeof(T) * count);
-        if (err != hipSuccess) return nullptr;
-        held.push_back(p);
-        return static_cast<T*>(p);
-    }
-};
+// (the set-up scratch, `Scratch`, is in fos_solver.hpp: the factored IndAffine of the Feasibility form shares it with the inversion below)
 // a HIP call of a set-up: its failure is reported under the set-up's name (`what`) and the call's
 static int hip_ok(const char* what, const char* call, hipError_t e) {
     if (e != hipSuccess) { set_error("%s set-up: %s -> %s", what, call, hipGetErrorString(e)); return FOS_EHIP; }
@@ -424,28 +408,10 @@ static int blkdir_setup(fos_solver* h, const int64_t* colptr, const int64_t* row
     return FOS_OK;
 }
 
-// ---- the inverse of the dense symmetric positive definite matrix of a direct form (I + Q Q' or K), shared by the dense form, the reduced form and the test entry.
-// Its work-set: G (the caller's), L x L column-major (L % 64 == 0, padding = identity) of order c.l; B0, B1, B2: L x L work buffers; v0, v1: two L-vectors; partials: 256 doubles.
-// The launches take the stream (and symv the order) from c.
-struct DenseWork {
-    LaunchCtx c{};
-    int64_t L = 0;
-    double *G = nullptr, *B0 = nullptr, *B1 = nullptr, *B2 = nullptr, *v0 = nullptr, *v1 = nullptr, *partials = nullptr;
-    // the buffers the caller did not bring, from the set-up's scratch (a failure stays in s.err)
-    void fill(Scratch& s) {
-        const size_t L2 = (size_t)L * (size_t)L;
-        for (double** b : {&B0, &B1, &B2}) *b = s.alloc<double>(L2);
-        for (double** v : {&v0, &v1}) if (!*v) *v = s.alloc<double>((size_t)L);
-        if (!partials) partials = s.alloc<double>(256);
-    }
-};
-struct DenseOpts {
-    const char *what, *gname;                  // the caller's name and the matrix's in messages
-    int factor;                                // FOS_DIRECT_FACTOR_*
-    bool pivot_fallback;                       // a pivot that fails on finite entries: Newton-Schulz instead of FOS_EINVAL
-};
+// ---- the inverse of the dense symmetric positive definite matrix of a direct form (I + Q Q' or K), shared by the dense form, the reduced form, the test entry and
+// the factored IndAffine of the Feasibility form (affine_dense.hip).  Its work-set and options, DenseWork and DenseOpts, are in fos_solver.hpp.
 // the start vector of the power iteration (which = 0) and three more of its kind for the probe
-static void direct_test_vector(int64_t k, int which, std::vector<double>& v) {
+void fos::direct_test_vector(int64_t k, int which, std::vector<double>& v) {
     for (int64_t i = 0; i < k; ++i) v[i] = 1.0 + 0.37 * std::sin((1.7 + 0.6 * which) * (double)i + (double)which);
 }
 // v <- G v through the device, *nw = |G v|_2; FOS_EINVAL when that is not a finite number: the check both factors make of the operator
@@ -461,7 +427,7 @@ static int dense_symv_norm(const DenseWork& k, const DenseOpts& o, std::vector<d
     if (!(*nw == *nw) || *nw > 1e300) { set_error("direct=true: the operator has non-finite entries"); return FOS_EINVAL; }
     return FOS_OK;
 }
-// Newton-Schulz:  X_0 = I / (1.25 lambda~),  X_{k+1} = 2 X_k - X_k (G X_k),  lambda~ a power-iteration estimate of lambda_max(G); accepted when max |G X - I| <= 1e-12
+// Newton-Schulz:  X_0 = I / (1.25 lambda~),  X_{k+1} = 2 X_k - X_k (G X_k),  lambda~ a power-iteration estimate of lambda_max(G); accepted when max |G X - I| <= o.bar (1e-12)
 static int dense_inverse_newton(const DenseWork& k, const DenseOpts& o, double** Xout, int* steps) {
     const LaunchCtx& c = k.c;
     const int64_t l = c.l, L = k.L;
@@ -485,7 +451,7 @@ static int dense_inverse_newton(const DenseWork& k, const DenseOpts& o, double**
     double resid = 1.0;
     int it = 0;
     std::vector<double> part(256);
-    for (; it < planned + 6; ++it) {
+    for (; it < planned + o.newton_extra; ++it) {
         launch_dense_gemm(c, (int)L, 1.0, k.G, X, 0.0, nullptr, k.B0);      // Y = G X
         if (it >= planned) {                                                // converged?  max |Y - I|
             launch_dense_resid(c, L, k.B0, k.partials, 256);
@@ -493,12 +459,12 @@ static int dense_inverse_newton(const DenseWork& k, const DenseOpts& o, double**
             FOS_TRY(hip_ok(o.what, "hipStreamSynchronize", hipStreamSynchronize(c.stream)));
             resid = 0.0;
             for (double r : part) resid = (r > resid || r != r) ? r : resid;
-            if (resid <= 1e-12) break;
+            if (resid <= o.bar) break;
         }
         launch_dense_gemm(c, (int)L, -1.0, X, k.B0, 2.0, X, Xn);            // X <- 2 X - X Y
         std::swap(X, Xn);
     }
-    if (!(resid <= 1e-12)) { set_error("%s: the inverse of %s did not converge (max |G X - I| = %.3e after %d steps, lambda_max ~ %.3e)", o.what, o.gname, resid, it, lam); return FOS_EINVAL; }
+    if (!(resid <= o.bar)) { set_error("%s: the inverse of %s did not converge (max |G X - I| = %.3e after %d steps, lambda_max ~ %.3e)", o.what, o.gname, resid, it, lam); return FOS_EINVAL; }
     *Xout = X; *steps = it;
     return FOS_OK;
 }
@@ -523,10 +489,10 @@ static int dense_inverse_probe(const DenseWork& k, const DenseOpts& o, const dou
     *r = worst;
     return FOS_OK;
 }
-// factor = FOS_DIRECT_FACTOR_CHOLESKY: blocked Cholesky (dense_chol.hip), probe, at most two Newton-Schulz polish steps, then -- if the probe stays above 1e-12, or
+// factor = FOS_DIRECT_FACTOR_CHOLESKY: blocked Cholesky (dense_chol.hip), probe, at most two Newton-Schulz polish steps, then -- if the probe stays above o.bar (1e-12), or
 // (pivot_fallback) a pivot failed on finite entries -- the Newton-Schulz set-up as if it had been asked for.  Without pivot_fallback a bad pivot is FOS_EINVAL.
 // *Xout: the buffer (B1 or B2) that holds the accepted inverse.
-static int dense_spd_inverse(const DenseWork& k, const DenseOpts& o, double** Xout, DenseInv* st) {
+int fos::dense_spd_inverse(const DenseWork& k, const DenseOpts& o, double** Xout, DenseInv* st) {
     const LaunchCtx& c = k.c;
     *st = DenseInv{};
     FOS_TRY(hip_ok(o.what, "hipStreamSynchronize", hipStreamSynchronize(c.stream)));                   // G is formed: the clock of the inversion stage starts here
@@ -555,14 +521,14 @@ static int dense_spd_inverse(const DenseWork& k, const DenseOpts& o, double** Xo
         } else {
             double *X = k.B2, *Xn = k.B1;
             FOS_TRY(dense_inverse_probe(k, o, X, &st->probe));
-            while (!(st->probe <= 1e-12) && st->steps < 2) {
+            while (!(st->probe <= o.bar) && st->steps < 2) {
                 launch_dense_gemm(c, (int)k.L, 1.0, k.G, X, 0.0, nullptr, k.B0);    // Y = G X
                 launch_dense_gemm(c, (int)k.L, -1.0, X, k.B0, 2.0, X, Xn);          // X <- 2 X - X Y
                 std::swap(X, Xn);
                 st->steps += 1;
                 FOS_TRY(dense_inverse_probe(k, o, X, &st->probe));
             }
-            if (st->probe <= 1e-12) { st->used = FOS_DIRECT_FACTOR_CHOLESKY; *Xout = X; stamp(); return FOS_OK; }
+            if (st->probe <= o.bar) { st->used = FOS_DIRECT_FACTOR_CHOLESKY; *Xout = X; stamp(); return FOS_OK; }
         }
         st->fell_back = true;
     }

@@ -158,8 +158,9 @@ __global__ __launch_bounds__(FEAS_THREADS) void feas_pad_identity_kernel(int64_t
 }
 
 struct FeasSet {
-    int kind = 0;                   // 0 unset, 1 IndAffine (dense), 2 IndBox, 3 ConeProduct, 4 host callback, 5 IndAffine (sparse A), 6 separable sum of sets
+    int kind = 0;                   // 0 unset, 1 IndAffine (dense), 2 IndBox, 3 ConeProduct, 4 host callback, 5 IndAffine (sparse A), 6 separable sum of sets, 7 IndAffine (dense, factored)
     SparseAffine* sa = nullptr;     // kind 5 (affine_sparse.hip)
+    DenseAffine* da = nullptr;      // kind 7 (affine_dense.hip)
     SetBlocks* sb = nullptr;        // kind 6 (sets.hip)
     fos_prox_fn cb = nullptr;       // kind 4: prox!(y, S, x) evaluated by the caller on pinned host vectors
     void* cb_ctx = nullptr;
@@ -272,6 +273,8 @@ int feas_prox(fos_feas* h, int which, double* y, const double* x) {
         FEAS_K(feas_from_parts_kernel, h->n, y, (const double2*)h->zout);
     } else if (s.kind == 5) {                                             // IndAffine over a sparse A: CG on the normal equations, exact to the residual's rounding level
         FOS_TRY(sparse_affine_project(s.sa, h->stream, y, x));
+    } else if (s.kind == 7) {                                             // IndAffine over a dense A, factored: two passes over A and the inverse of A A', a fixed number of launches
+        FOS_TRY(dense_affine_project(s.da, h->stream, y, x));
     } else if (s.kind == 6) {                                             // balls, simplex, halfspaces ... in contiguous blocks: a fixed number of launches, no copy
         FOS_TRY(set_blocks_project(s.sb, h->stream, y, x));
     } else if (s.kind == 4) {                                             // any other ProximableFunction: the caller's prox! on host vectors
@@ -475,7 +478,7 @@ int fos_feas_destroy(fos_feas_handle h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (void* q : h->owned) (void)hipFree(q);
-    for (FeasSet& s : h->S) { if (s.cb_x) (void)hipHostFree(s.cb_x); if (s.cb_y) (void)hipHostFree(s.cb_y); psd_sign_destroy(s.psd_big); sparse_affine_destroy(s.sa); set_blocks_destroy(s.sb); }
+    for (FeasSet& s : h->S) { if (s.cb_x) (void)hipHostFree(s.cb_x); if (s.cb_y) (void)hipHostFree(s.cb_y); psd_sign_destroy(s.psd_big); sparse_affine_destroy(s.sa); dense_affine_destroy(s.da); set_blocks_destroy(s.sb); }
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return FOS_OK;
@@ -576,6 +579,32 @@ int fos_feas_affine_stats(fos_feas_handle h, int32_t which, double* out8) {
     if (!h || !out8 || which < 1 || which > 2 || h->S[which - 1].kind != 5) { set_error("fos_feas_affine_stats: set %d is not a sparse IndAffine", (int)which); return FOS_EINVAL; }
     sparse_affine_stats(h->S[which - 1].sa, out8);
     return FOS_OK;
+}
+
+// IndAffine(A, b), A dense m x n ROW-major, factored form (affine_dense.hip): built first, so that a refused call leaves the set as it was
+int fos_feas_set_affine_factored(fos_feas_handle h, int32_t which, int64_t m, const double* A, const double* b, int32_t factor, int32_t refine) {
+    if (!h || which < 1 || which > 2 || m < 1 || m > h->n) { set_error("fos_feas_set_affine_factored: bad argument (1 <= m <= n, which = 1 | 2)"); return FOS_EINVAL; }
+    FOS_HIP(hipSetDevice(h->device));
+    DenseAffine* da = nullptr;
+    FOS_TRY(dense_affine_setup(m, h->n, A, b, factor, refine, h->cus, h->stream, &da));       // (synchronises the stream: no projection onto the set being replaced runs any more)
+    FeasSet& s = h->S[which - 1];
+    dense_affine_destroy(s.da);
+    s.da = da; s.kind = 7;
+    return FOS_OK;
+}
+int fos_feas_affine_factored_stats(fos_feas_handle h, int32_t which, double* out8) {
+    if (!h || !out8 || which < 1 || which > 2 || h->S[which - 1].kind != 7) { set_error("fos_feas_affine_factored_stats: set %d is not a factored IndAffine", (int)which); return FOS_EINVAL; }
+    dense_affine_stats(h->S[which - 1].da, out8);
+    return FOS_OK;
+}
+int fos_feas_affine_factored_plan(fos_feas_handle h, int32_t which, int64_t* out6) {
+    if (!h || !out6 || which < 1 || which > 2 || h->S[which - 1].kind != 7) { set_error("fos_feas_affine_factored_plan: set %d is not a factored IndAffine", (int)which); return FOS_EINVAL; }
+    dense_affine_plan(h->S[which - 1].da, out6);
+    return FOS_OK;
+}
+// test-only, host: the factored form's scaling, inverse and two passes in the kernels' order (affine_dense.hip)
+int fos_host_affine_factored(int64_t m, int64_t n, const double* A, const double* b, int32_t refine, const double* x, double* y) {
+    return host_affine_factored(m, n, A, b, refine, x, y);
 }
 
 int fos_feas_set_box(fos_feas_handle h, int32_t which, double lo, double hi) {

@@ -565,6 +565,8 @@ void launch_dense_symv(const LaunchCtx& c, int64_t ld, const double* G, const do
 // the inverse of a dense symmetric positive definite matrix through a blocked Cholesky factorisation (dense_chol.hip); the same blocking on the host (tests)
 void launch_dense_spd_inverse_chol(const LaunchCtx& c, int64_t L, const double* G, double* X, double* Lw, double* Ww, int32_t* info);
 int64_t host_chol_inverse(int64_t k, const double* K, double* X);
+// G = A A' + (identity on the padding m .. L-1) for a ROW-major m x ld matrix A (ld % 64 == 0): L x L column-major, exactly symmetric, fixed summation order (dense_chol.hip)
+void launch_dense_gram_rows(const LaunchCtx& c, int64_t m, int64_t ld, const double* A, int64_t L, double* G);
 void launch_direct_rhs(const LaunchCtx& c, const double2* W, const double2* x, double* t);
 void launch_direct_finish(const LaunchCtx& c, const double2* x, const double2* W, double2* out);
 
@@ -653,6 +655,14 @@ int sparse_affine_project(SparseAffine* a, hipStream_t stream, double* y, const 
 void sparse_affine_reset(SparseAffine* a, hipStream_t stream);                                   // a new solve: lambda = 0
 void sparse_affine_stats(const SparseAffine* a, double* out8);
 void sparse_affine_destroy(SparseAffine* a);
+// IndAffine(A, b) with a dense A, factored form (affine_dense.hip): A kept once, (A A')^-1 of order m, two passes over A per projection
+struct DenseAffine;
+int dense_affine_setup(int64_t m, int64_t n, const double* A, const double* b, int factor, int refine, int cus, hipStream_t stream, DenseAffine** out);
+int dense_affine_project(DenseAffine* a, hipStream_t stream, double* y, const double* x);        // y, x: device vectors of length n, y must not alias x
+void dense_affine_stats(const DenseAffine* a, double* out8);
+void dense_affine_plan(const DenseAffine* a, int64_t* out6);
+void dense_affine_destroy(DenseAffine* a);
+int host_affine_factored(int64_t m, int64_t n, const double* A, const double* b, int refine, const double* x, double* y);
 // Separable sums of convex vector sets (sets.hip): norm balls, simplex, halfspace / hyperslab, point, free, scalar box -- contiguous blocks covering 1..n
 struct SetBlocks;
 int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec, SetBlocks** out);

@@ -243,6 +243,49 @@ int kkt_apply_full(fos_solver* h, const LaunchCtx& c, const d2* w, d2* out, bool
 // direct.cpp: prox!(y, S1::IndAffine([Q -I], 0), x) in the handle's exact form, the result left in h->SOL
 int prox_affine_direct(fos_solver* h, const d2* x);
 
+// ---- set-up scratch: device buffers that live to the end of a scope.  The first hipMalloc that fails stays in `err` (later requests give nullptr): ask for
+// everything, then look at err once.
+struct Scratch {
+    std::vector<void*> held;
+    hipError_t err = hipSuccess;
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() { for (void* p : held) (void)hipFree(p); }
+    template <class T> T* alloc(size_t count) {
+        void* p = nullptr;
+        if (err == hipSuccess) err = hipMalloc(&p, sizeof(T) * count);
+        if (err != hipSuccess) return nullptr;
+        held.push_back(p);
+        return static_cast<T*>(p);
+    }
+};
+
+// ---- the inverse of the dense symmetric positive definite matrix of a direct form (I + Q Q' or K) or of the factored IndAffine (A A'), direct.cpp.
+// Its work-set: G (the caller's), L x L column-major (L % 64 == 0, padding = identity) of order c.l; B0, B1, B2: L x L work buffers; v0, v1: two L-vectors; partials: 256 doubles.
+// The launches take the stream (and symv the order) from c.
+struct DenseWork {
+    LaunchCtx c{};
+    int64_t L = 0;
+    double *G = nullptr, *B0 = nullptr, *B1 = nullptr, *B2 = nullptr, *v0 = nullptr, *v1 = nullptr, *partials = nullptr;
+    // the buffers the caller did not bring, from the set-up's scratch (a failure stays in s.err)
+    void fill(Scratch& s) {
+        const size_t L2 = (size_t)L * (size_t)L;
+        for (double** b : {&B0, &B1, &B2}) *b = s.alloc<double>(L2);
+        for (double** v : {&v0, &v1}) if (!*v) *v = s.alloc<double>((size_t)L);
+        if (!partials) partials = s.alloc<double>(256);
+    }
+};
+struct DenseOpts {
+    const char *what, *gname;                  // the caller's name and the matrix's in messages
+    int factor;                                // FOS_DIRECT_FACTOR_*
+    bool pivot_fallback;                       // a pivot that fails on finite entries: Newton-Schulz instead of FOS_EINVAL
+    double bar = 1e-12;                        // the inverse is accepted at this probe residual (Cholesky path) / max |G X - I| (Newton-Schulz)
+    int newton_extra = 6;                      // Newton-Schulz steps past the planned ceil(log2 lambda_max) + 7, each followed by a look at the residual
+};
+int dense_spd_inverse(const DenseWork& k, const DenseOpts& o, double** Xout, DenseInv* st);
+void direct_test_vector(int64_t k, int which, std::vector<double>& v);      // the four fixed vectors of the probe (which = 0: also the power iteration's start)
+
 template <class T>
 int dev_alloc(fos_solver* h, T** p, size_t count) {
     void* q = nullptr;

@@ -819,12 +819,27 @@ def solve(problem, alg, device=0, out=None):
 class IndAffine:
     """ProximalOperators.IndAffine(A, b): {x : A x = b}, A m x n of full row rank.  A dense A (n <= 46 000) becomes a dense projector on the
     device (fos_feas_set_affine); a scipy.sparse A stays sparse at any n (fos_feas_set_affine_sparse: warm-started CG on the row-scaled normal
-    equations, ended by the recomputed residual) -- `sparse=True / False` forces either form."""
+    equations, ended by the recomputed residual) -- `sparse=True / False` forces either form.
+    form="factored" (opt-in; form=None keeps the selection above to the letter): the dense A is kept once on the device with the inverse of A A'
+    (order m <= 46 000, any n) and a projection is two passes over A (fos_feas_set_affine_factored); factor = "cholesky" | "newton" builds the
+    inverse, refine = 0..2 refinement steps follow every projection.  A scipy.sparse A is densified."""
 
     DENSE_MAX = 46000
+    FACTORED_MAX = 46000
 
-    def __init__(self, A, b, sparse=None):
-        self.sparse = bool(sp.issparse(A) or np.shape(A)[1] > self.DENSE_MAX) if sparse is None else bool(sparse)
+    def __init__(self, A, b, sparse=None, form=None, factor="cholesky", refine=0):
+        if form not in (None, "factored"):
+            raise ValueError("IndAffine: form must be None or 'factored', not %r" % (form,))
+        self.form, self.factor, self.refine = form, factor, int(refine)
+        if form == "factored":
+            if sparse:
+                raise ValueError("IndAffine: form='factored' keeps a dense A (sparse=True asks for the sparse form)")
+            direct_factor_code(factor)
+            if not 0 <= self.refine <= 2:
+                raise ValueError("IndAffine: refine must be 0, 1 or 2, not %r" % (refine,))
+            self.sparse = False
+        else:
+            self.sparse = bool(sp.issparse(A) or np.shape(A)[1] > self.DENSE_MAX) if sparse is None else bool(sparse)
         if self.sparse:
             self.A = sp.csc_matrix(A, dtype=np.float64)
             self.A.sum_duplicates(); self.A.sort_indices()
@@ -833,6 +848,8 @@ class IndAffine:
         self.b = np.ascontiguousarray(np.asarray(b, dtype=np.float64))
         if self.A.ndim != 2 or self.b.shape != (self.A.shape[0],):
             raise ValueError("IndAffine(A, b): A must be m x n and b of length m")
+        if form == "factored" and self.A.shape[0] > self.FACTORED_MAX:
+            raise ValueError("IndAffine(form='factored'): m = %d, the inverse of A A' is supported up to m = %d" % (self.A.shape[0], self.FACTORED_MAX))
 
 
 class IndBox:
@@ -1040,33 +1057,40 @@ class HipFeasibility:
         for which, S in ((1, problem.S1), (2, problem.S2)):
             if which in packed:                                         # before the `prox` test: these never become callbacks
                 self.set_blocks(which, *packed[which])
-            elif isinstance(S, IndAffine):
-                if S.A.shape[1] != self.n:
-                    raise ValueError("IndAffine: A has %d columns, the problem has n = %d" % (S.A.shape[1], self.n))
-                if S.sparse:
-                    i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-                    colptr = np.ascontiguousarray(S.A.indptr, dtype=np.int64) + 1          # Julia 1-based
-                    rowval = np.ascontiguousarray(S.A.indices, dtype=np.int64) + 1
-                    nzval = np.ascontiguousarray(S.A.data, dtype=np.float64)
-                    _lib.check(self._lib.fos_feas_set_affine_sparse(self._h, which, S.A.shape[0], i64(colptr), i64(rowval), _lib.dptr(nzval), _lib.dptr(S.b)))
-                else:
-                    _lib.check(self._lib.fos_feas_set_affine(self._h, which, S.A.shape[0], _lib.dptr(S.A), _lib.dptr(S.b)))
-            elif isinstance(S, IndBox) and S.arrays:
-                lo = np.ascontiguousarray(np.broadcast_to(S.lo, (self.n,)), dtype=np.float64)
-                hi = np.ascontiguousarray(np.broadcast_to(S.hi, (self.n,)), dtype=np.float64)
-                _lib.check(self._lib.fos_feas_set_box_arrays(self._h, which, _lib.dptr(lo), _lib.dptr(hi)))
-            elif isinstance(S, IndBox):
-                _lib.check(self._lib.fos_feas_set_box(self._h, which, S.lo, S.hi))
-            elif isinstance(S, ConeProduct):
-                types = np.ascontiguousarray([_lib.CONE_CODES[k] for k, _ in S.cones], dtype=np.int32)
-                lens = np.ascontiguousarray([l for _, l in S.cones], dtype=np.int64)
-                _lib.check(self._lib.fos_feas_set_cones(self._h, which, len(S.cones), types.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                        lens.ctypes.data_as(C.POINTER(C.c_int64))))
-            elif callable(getattr(S, "prox", None)):                    # any other ProximableFunction: prox!(y, S, x) as a host callback
-                self.set_callback(which, S)
             else:
-                raise _lib.FosError(-4, "Feasibility: set %d must be IndAffine, IndBox, ConeProduct or an object with a prox(y, x) method "
-                                        "(evaluated on the host through fos_feas_set_callback), got %s" % (which, type(S).__name__))
+                self.set_set(which, S)
+
+    def set_set(self, which, S):
+        """set `which` (1 | 2) becomes S: an IndAffine, IndBox, ConeProduct or an object with a prox(y, x) method; replaces what was there"""
+        if isinstance(S, IndAffine):
+            if S.A.shape[1] != self.n:
+                raise ValueError("IndAffine: A has %d columns, the problem has n = %d" % (S.A.shape[1], self.n))
+            if S.form == "factored":
+                _lib.check(self._lib.fos_feas_set_affine_factored(self._h, which, S.A.shape[0], _lib.dptr(S.A), _lib.dptr(S.b), direct_factor_code(S.factor), S.refine))
+            elif S.sparse:
+                i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+                colptr = np.ascontiguousarray(S.A.indptr, dtype=np.int64) + 1          # Julia 1-based
+                rowval = np.ascontiguousarray(S.A.indices, dtype=np.int64) + 1
+                nzval = np.ascontiguousarray(S.A.data, dtype=np.float64)
+                _lib.check(self._lib.fos_feas_set_affine_sparse(self._h, which, S.A.shape[0], i64(colptr), i64(rowval), _lib.dptr(nzval), _lib.dptr(S.b)))
+            else:
+                _lib.check(self._lib.fos_feas_set_affine(self._h, which, S.A.shape[0], _lib.dptr(S.A), _lib.dptr(S.b)))
+        elif isinstance(S, IndBox) and S.arrays:
+            lo = np.ascontiguousarray(np.broadcast_to(S.lo, (self.n,)), dtype=np.float64)
+            hi = np.ascontiguousarray(np.broadcast_to(S.hi, (self.n,)), dtype=np.float64)
+            _lib.check(self._lib.fos_feas_set_box_arrays(self._h, which, _lib.dptr(lo), _lib.dptr(hi)))
+        elif isinstance(S, IndBox):
+            _lib.check(self._lib.fos_feas_set_box(self._h, which, S.lo, S.hi))
+        elif isinstance(S, ConeProduct):
+            types = np.ascontiguousarray([_lib.CONE_CODES[k] for k, _ in S.cones], dtype=np.int32)
+            lens = np.ascontiguousarray([l for _, l in S.cones], dtype=np.int64)
+            _lib.check(self._lib.fos_feas_set_cones(self._h, which, len(S.cones), types.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    lens.ctypes.data_as(C.POINTER(C.c_int64))))
+        elif callable(getattr(S, "prox", None)):                    # any other ProximableFunction: prox!(y, S, x) as a host callback
+            self.set_callback(which, S)
+        else:
+            raise _lib.FosError(-4, "Feasibility: set %d must be IndAffine, IndBox, ConeProduct or an object with a prox(y, x) method "
+                                    "(evaluated on the host through fos_feas_set_callback), got %s" % (which, type(S).__name__))
 
     def set_blocks(self, which, kinds, lens, scal, vec):
         """fos_feas_set_blocks with raw arrays (SeparableSum.pack): replaces set `which`"""
@@ -1196,6 +1220,15 @@ class HipFeasibility:
         _lib.check(self._lib.fos_feas_affine_stats(self._h, which, _lib.dptr(o)))
         return {"projections": int(o[0]), "cg_iterations": int(o[1]), "last_cg_iterations": int(o[2]), "last_restarts": int(o[3]), "last_residual": o[4],
                 "last_rounding_level": o[5], "nnz": int(o[6]), "lanes_per_row": (int(o[7]) // 1000, int(o[7]) % 1000)}
+
+    def affine_factored_stats(self, which):
+        """the factored IndAffine's set-up record and the split of its two passes (fos_feas_affine_factored_stats, fos_feas_affine_factored_plan)"""
+        o, p = np.zeros(8), np.zeros(6, dtype=np.int64)
+        _lib.check(self._lib.fos_feas_affine_factored_stats(self._h, which, _lib.dptr(o)))
+        _lib.check(self._lib.fos_feas_affine_factored_plan(self._h, which, p.ctypes.data_as(C.POINTER(C.c_int64))))
+        return {"m": int(o[0]), "n": int(o[1]), "refine": int(o[2]), "factor": DIRECT_FACTOR_NAMES[int(o[3])], "fell_back": int(o[4]), "probe_resid": float(o[5]),
+                "launches": int(o[6]), "bytes": int(o[7]), "ld": int(p[0]), "gram_order": int(p[1]), "span_cols": int(p[2]), "spans": int(p[3]),
+                "rows_per_block": int(p[4]), "row_blocks": int(p[5])}
 
 
 class FeasibilityModel:

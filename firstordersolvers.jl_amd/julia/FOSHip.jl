@@ -367,6 +367,13 @@ function feas_set_stats(handle::Ptr{Cvoid}, which::Integer)
     return (blocks = Int(out[1]), wave_blocks = Int(out[2]), workgroup_blocks = Int(out[3]), grid_blocks = Int(out[4]), launches = Int(out[5]),
             last_passes = Int(out[6]), pass_cap = Int(out[7]), candidates = Int(out[8]))
 end
+function feas_affine_factored_stats(handle::Ptr{Cvoid}, which::Integer)
+    out, plan = zeros(Float64, 8), zeros(Int64, 6)
+    check(ccall((:fos_feas_affine_factored_stats, libfoship), Cint, (Ptr{Cvoid}, Int32, Ptr{Cdouble}), handle, Int32(which), out))
+    check(ccall((:fos_feas_affine_factored_plan, libfoship), Cint, (Ptr{Cvoid}, Int32, Ptr{Int64}), handle, Int32(which), plan))
+    return (m = Int(out[1]), n = Int(out[2]), refine = Int(out[3]), factor = out[4] == 1 ? :cholesky : :newton, fell_back = out[5] != 0, probe_resid = out[6],
+            launches = Int(out[7]), bytes = Int(out[8]), ld = plan[1], gram_order = plan[2], span_cols = plan[3], spans = plan[4], rows_per_block = plan[5], row_blocks = plan[6])
+end
 # test entry: the host emulation of one block's projection (no GPU needed)
 function host_set_project(kind::Integer, scal::NTuple{2,Float64}, v::Union{Nothing,Vector{Float64}}, x::Vector{Float64})
     y = similar(x)
@@ -398,6 +405,14 @@ mutable struct HipFeasData <: FOSSolverData
                 types, _, lens = conearrays(S)
                 GC.@preserve types lens check(ccall((:fos_feas_set_cones, libfoship), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Int32}, Ptr{Int64}),
                                                     d.handle, which, Int64(length(types)), types, lens))
+            elseif S isa ProximalOperators.IndAffine && S.A isa AbstractMatrix && get(model.options, :affine_form, nothing) == :factored
+                # solve!(...; affine_form = :factored [, affine_factor = :cholesky | :newton, affine_refine = 0..2]): A (a sparse one densified) kept once with the
+                # inverse of A A' (m <= 46 000, any n), a projection is two passes over A
+                At = Matrix{Float64}(transpose(S.A))
+                b = Vector{Float64}(S.b)
+                factor = get(model.options, :affine_factor, :cholesky) == :newton ? Int32(0) : Int32(1)      # FOS_DIRECT_FACTOR_*
+                GC.@preserve At b check(ccall((:fos_feas_set_affine_factored, libfoship), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Int32),
+                                              d.handle, which, Int64(size(S.A, 1)), At, b, factor, Int32(get(model.options, :affine_refine, 0))))
             elseif S isa ProximalOperators.IndAffine && S.A isa AbstractMatrix && !(S.A isa SparseArrays.AbstractSparseMatrix)
                 At = Matrix{Float64}(transpose(S.A))        # IndAffine(A, b), dense: the C ABI takes A row-major = column-major A'
                 b = Vector{Float64}(S.b)

@@ -473,6 +473,21 @@ int fos_feas_destroy(fos_feas_handle h);
 int fos_feas_set_affine(fos_feas_handle h, int32_t which, int64_t m, const double* A, const double* b);
 int fos_feas_set_affine_sparse(fos_feas_handle h, int32_t which, int64_t m, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b);
 int fos_feas_affine_stats(fos_feas_handle h, int32_t which, double* out8);
+/* IndAffine(A, b), A dense m x n ROW-major, full row rank, 1 <= m <= min(n, 46000), any n: A kept once, (A A')^-1 of order m; the FACTORED form of the dense set
+ * (opt-in; fos_feas_set_affine keeps the n x n projector).  The rows of [A | b] are scaled to unit norm, the scaled A is kept row-major (leading dimension n
+ * rounded up to 64), G = A A' is inverted once (factor: FOS_DIRECT_FACTOR_*, the machinery of direct = true; accepted at a residual of 1e-7, which the projection
+ * squares).  A projection evaluates x - A'(A A')^-1 (A x - b) as written: r = A x - b (one pass over A), d = X r, d += X (r - G d), y = x - A'd (a second pass),
+ * then `refine` (0..2) times r = A y - b, d = X r, y -= A'd.  16 m n + O(m^2) bytes per projection instead of 8 n^2; a fixed number of launches, no host
+ * synchronise; the same bits from run to run (csrc/affine_dense.hip).  A zero row, m > n or an inverse that is not accepted (A without full row rank): FOS_EINVAL. */
+int fos_feas_set_affine_factored(fos_feas_handle h, int32_t which, int64_t m, const double* A, const double* b, int32_t factor, int32_t refine);
+/* out8 = m, n, refine, factor that produced the accepted inverse, fell_back, probe residual, kernel launches per projection, bytes kept */
+int fos_feas_affine_factored_stats(fos_feas_handle h, int32_t which, double* out8);
+/* how the two passes are split (chosen at set-up from m, n and the CU count): out6 = leading dimension of A, padded order of A A', pass 1: columns per span and
+ * spans, pass 2: rows per row block and row blocks */
+int fos_feas_affine_factored_plan(fos_feas_handle h, int32_t which, int64_t* out6);
+/* Test-only host emulation of the factored form (no GPU needed): the same scaling, the blocked Cholesky inverse of fos_host_chol_inverse accepted by the same probe,
+ * and the two passes with the kernels' split and summation order for this (m, n) on 256 CUs.  x, y: n-vectors. */
+int fos_host_affine_factored(int64_t m, int64_t n, const double* A, const double* b, int32_t refine, const double* x, double* y);
 int fos_feas_set_box(fos_feas_handle h, int32_t which, double lo, double hi);
 int fos_feas_set_box_arrays(fos_feas_handle h, int32_t which, const double* lo, const double* hi);     /* IndBox with array bounds (n each) */
 /* ConeProduct (src/cones.jl:31-94): ncones cones of type[i] (FOS_CONE_*) and len[i] entries, in order, contiguous, covering all n entries;
