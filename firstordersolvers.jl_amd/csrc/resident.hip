@@ -612,39 +612,55 @@ __global__ __launch_bounds__(LB) void cg_resident_kernel(ResArgs a) {
 // (RS_GMAX = 256 workgroups = records: one per CU; RS_WPU_MAX = 4 workgroups a unit may be split over -- fewer units than CUs: a shard of a four-GPU
 //  run; RS_NCOMP = 7 compute wavefronts per workgroup + 1 that communicates: two wavefronts per SIMD, 256 registers each -- fos_internal.hpp)
 
-// a tile in NATURAL column order (as stored): row sums against the workgroup's column elements at gcol (LDS, uniform addresses: broadcasts),
-// column sums ADDED to the wavefront's own array (lanes 0..7, program order inside the wavefront)
-template <int TMAX>
-__device__ __forceinline__ void res_tile_plain(const double (&val)[TMAX], int T, const d2 g, const d2* __restrict__ gcol, d2* __restrict__ colacc, int lane,
-                                               double& u1, double& u2) {
-    u1 = 0.0; u2 = 0.0;
+// A wavefront walks its tiles GROUP-MAJOR, in CHUNKS: chunk (grp, q) = the eight steps of column group grp of its tile q -- 4 KB, contiguous, natural column
+// order (as stored).  A lane adds the chunk's row sums (against the workgroup's column elements at gcol: LDS, uniform addresses -- broadcasts) to its row's
+// running sums u, and its products with its row's element g to the SEGMENT's accumulators a1, a2 (a segment = the wavefront's consecutive tiles of one unit):
+// the lanes are reduced once per (segment, group, right-hand side), behind the segment's last tile -- not once per tile, which was 650 of a tile's 786
+// vector instructions (v_cndmask, DPP moves, permlane swaps: eight transpose-reductions per tile)
+#ifndef RS_XC
+#define RS_XC 2
+#endif
+__device__ __forceinline__ void res_tile_plain(const double (&val)[TILE_GROUP], const d2 g, const d2* __restrict__ gcol, d2& u, double (&a1)[TILE_GROUP],
+                                               double (&a2)[TILE_GROUP]) {
 #pragma unroll
-    for (int grp = 0; grp < TMAX / TILE_GROUP; ++grp) {
-        if (grp * TILE_GROUP < T) {                                  // wave-uniform
-            double p[TILE_GROUP];
+    for (int h = 0; h < TILE_GROUP / RS_XC; ++h) {                   // (RS_XC column elements in flight at a time: four registers each)
+        d2 xc[RS_XC];
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {                            // (four column elements = 16 registers in flight at a time)
+        for (int k = 0; k < RS_XC; ++k) xc[k] = gcol[RS_XC * h + k];
 #pragma unroll
-                for (int u = 4 * h; u < 4 * h + 4; ++u) {
-                    const d2 xc = gcol[grp * TILE_GROUP + u];
-                    u1 += val[grp * TILE_GROUP + u] * xc.x; u2 += val[grp * TILE_GROUP + u] * xc.y;
-                    p[u] = val[grp * TILE_GROUP + u] * g.x;
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            const double s1 = tile_colsum8(p, lane);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < TILE_GROUP; ++u) p[u] = val[grp * TILE_GROUP + u] * g.y;
-            const double s2 = tile_colsum8(p, lane);
-            if (lane < TILE_GROUP) {
-                d2 o = colacc[grp * TILE_GROUP + lane];
-                o.x += s1; o.y += s2;
-                colacc[grp * TILE_GROUP + lane] = o;
-            }
-            __builtin_amdgcn_sched_barrier(0);                       // (keeps the next group's LDS reads from being hoisted up here)
+        for (int k = 0; k < RS_XC; ++k) {
+            const double v = val[RS_XC * h + k];
+            u.x += v * xc[k].x; u.y += v * xc[k].y;
+            a1[RS_XC * h + k] += v * g.x; a2[RS_XC * h + k] += v * g.y;
         }
+        __builtin_amdgcn_sched_barrier(0);
     }
+}
+
+// A tile's descriptor through the CONSTANT address space: a wave-uniform address there is read by a scalar load into scalar registers.  A plain load of
+// a.blk[i] inside the solve's loop is a VECTOR load and a v_readfirstlane per field (the compiler cannot prove that no store of the loop touches the
+// descriptors), so every tile's values waited for a vector-memory round trip of their own before they could be requested.  The descriptors are written
+// before the launch and by nobody during it, which is what the scalar cache asks for.
+__device__ __forceinline__ BlkDesc rs_desc(const BlkDesc* blk, int i) {
+    typedef const __attribute__((address_space(4))) int64_t cs64;
+    cs64* p = (cs64*)(blk + i);
+    const int64_t w3 = p[3], w4 = p[4], w5 = p[5];
+    BlkDesc d;
+    d.nnz0 = p[0]; d.colpos = p[1]; d.cnt = p[2];
+    d.row0 = (int32_t)w3; d.info = (int32_t)(w3 >> 32);
+    d.meta[0] = (int32_t)w4; d.meta[1] = (int32_t)(w4 >> 32); d.meta[2] = (int32_t)w5; d.meta[3] = (int32_t)(w5 >> 32);
+    return d;
+}
+
+// requests chunk `grp` of tile `blk`.  ALWAYS eight loads: for a tile without that group (a narrower unit; the group behind the walk's last) they all read
+// the tile's first value, one address for the wavefront, and are never consumed -- a request that is there on one path and not on another leaves the
+// compiler no count of the loads in flight behind a chunk, and every chunk then waits for ALL requests (s_waitcnt vmcnt(0)): the ring held one chunk
+__device__ __forceinline__ void rs_request(const ResArgs& a, int blk, int grp, int lane, double (&val)[TILE_GROUP]) {
+    const BlkDesc d = rs_desc(a.blk, blk);
+    const bool live = TILE_GROUP * grp < d.steps();                  // wave-uniform
+    const double* __restrict__ vp = a.val + d.nnz0 + (live ? 64 * TILE_GROUP * grp : 0) + (live ? lane : 0);
+#pragma unroll
+    for (int t = 0; t < TILE_GROUP; ++t) val[t] = __builtin_nontemporal_load(vp + 64 * t);      // (zero-padded storage beyond the tile's rows and columns)
 }
 
 // (RS_NTC = 6: tiles the communication wavefront may sweep itself -- it waits at barrier (A) otherwise; which tiles a wavefront walks is the plan's
@@ -659,7 +675,7 @@ __device__ __forceinline__ void rs_rows_load(const ResArgs& a, int blk_first, in
     for (int q = 0; q < NT; ++q) {
         R.rr[q] = R.ww[q] = R.xx[q] = make_double2(0.0, 0.0);
         if (q < cnt) {
-            const BlkDesc d = a.blk[blk_first + q];
+            const BlkDesc d = rs_desc(a.blk, blk_first + q);
             if (lane < d.nrows()) { R.rr[q] = a.v[d.row0 + lane]; R.xx[q] = a.x[d.row0 + lane]; }
         }
     }
@@ -669,50 +685,102 @@ __device__ __forceinline__ void rs_rows_store(const ResArgs& a, int blk_first, i
 #pragma unroll
     for (int q = 0; q < NT; ++q) {
         if (q < cnt) {
-            const BlkDesc d = a.blk[blk_first + q];
+            const BlkDesc d = rs_desc(a.blk, blk_first + q);
             if (lane < d.nrows()) a.x[d.row0 + lane] = R.xx[q];
         }
     }
 }
 
+// one column group of a wavefront's tiles Q, Q + 1, ...: the tiles NEST (tile Q + 1 inside tile Q's branch), so the paths of wavefronts with fewer tiles
+// leave the group and do not meet the others again inside it
+template <int Q, int NT, int D>
+__device__ __forceinline__ void rs_group(const ResArgs& a, int bf, int cnt, int grp, int c0, int lane, const d2* __restrict__ s_gcol, d2* __restrict__ mycol,
+                                         RsRows<NT>& R, double (&val)[D][TILE_GROUP], double (&a1)[TILE_GROUP], double (&a2)[TILE_GROUP]) {
+    if constexpr (Q < NT) {
+        if (Q < cnt) {                             // wave-uniform
+            const BlkDesc d = rs_desc(a.blk, bf + Q);
+            const int coff = d.meta[0] - c0 + TILE_GROUP * grp;
+            const bool in = TILE_GROUP * grp < d.steps();
+            if (in) res_tile_plain(val[Q % D], R.rr[Q], s_gcol + coff, R.ww[Q], a1, a2);
+            if (Q + D < NT && Q + D < cnt) rs_request(a, bf + Q + D, grp, lane, val[Q % D]);
+            else rs_request(a, bf + Q % D, grp + 1, lane, val[Q % D]);
+            // the segment's last tile: the column sums of this group
+            const bool last = Q + 1 == NT || Q + 1 >= cnt || rs_desc(a.blk, bf + Q + 1).meta[0] != d.meta[0];
+            if (in && last) {
+                const double s1 = tile_colsum8(a1, lane);
+                const double s2 = tile_colsum8(a2, lane);
+                // (the unit's REAL columns alone: the zero sums of a last group's padding would land on the next unit's columns)
+                if (lane < TILE_GROUP && TILE_GROUP * grp + lane < d.meta[3]) mycol[coff + lane] = make_double2(s1, s2);
+#pragma unroll
+                for (int u = 0; u < TILE_GROUP; ++u) a1[u] = a2[u] = 0.0;
+            }
+            rs_group<Q + 1, NT, D>(a, bf, cnt, grp, c0, lane, s_gcol, mycol, R, val, a1, a2);
+        }
+    }
+}
+
 // one sweep of a wavefront's tiles: w = M g on their rows (g = R.rr), their column sums into the wavefront's array, the four sums of the rows
-// (the tiles' descriptors are read again in every sweep, by scalar loads: kept in registers across the solve, they and everything derived from
+// (the tiles' descriptors are read again for every chunk, by scalar loads: kept in registers across the solve, they and everything derived from
 //  them -- addresses, masks, offsets of every tile -- were hoisted out of the loop and spilled by the hundred; a branch per tile for the same reason)
+// The walk: for every column group, the wavefront's tiles in tile order (res_tile_plain); R.ww[q] is tile q's row-sum accumulator (per row the columns in
+// ascending order: the order of a tile-major walk).  RS_RING chunks are in flight: chunk (grp, q) sits in ring slot q % RS_RING, and when it has been
+// consumed the slot is refilled with (grp, q + RS_RING), or -- from the last tile of the slot's class -- with (grp + 1, q % RS_RING): the requests run
+// across tile and group boundaries, nothing is requested ahead of the sweep's first chunk (barrier B, an early round: measured dead ends).  Every refill
+// is eight loads (rs_request) and the tiles of a group nest, so behind a group's first chunk the waits are exact counts (rs_group).
+// Column sums: per lane over the segment's tiles in tile order, then tile_colsum8's lane order, STORED (a unit is one segment per wavefront: no
+// read-modify-write); the wavefronts are added in wavefront order by the communication wavefront.
+#ifndef RS_RING
+#define RS_RING 2
+#endif
 template <int TMAX, int NT>
 __device__ __forceinline__ void rs_sweep(const ResArgs& a, int blk_first, int cnt, int c0, int lane, const d2* __restrict__ s_gcol, const double* s_ctl,
                                          d2* __restrict__ mycol, RsRows<NT>& R, double (&acc)[4], bool early = false) {
+    constexpr int D = NT < RS_RING ? NT : RS_RING;
     // (early: an exchange round that carries r.r alone -- no tile is walked, the other three sums are zero)
     if (early) cnt = 0;
     mycol[lane] = make_double2(0.0, 0.0);
     acc[0] = acc[1] = acc[2] = acc[3] = 0.0;
+    if (cnt > 0) {                                 // wave-uniform
+        int tw = 0;                                // the wavefront's longest tile: its groups bound the walk
 #pragma unroll
-    for (int q = 0; q < NT; ++q) {
-        if (q < cnt) {                             // wave-uniform
-            const BlkDesc d = a.blk[blk_first + q];
-            const int T = d.steps(), coff = d.meta[0] - c0;
-            const bool valid = lane < d.nrows();
-            const double* __restrict__ vp = a.val + d.nnz0 + lane;
-            // (requesting a wavefront's first tile BEFORE the exchange in front of it was measured: 70.5 against 66.3 us per iteration --
-            //  the bulk loads delay the exchange's words)
-            const d2 gq = R.rr[q];
-            double u1 = 0.0, u2 = 0.0;
+        for (int q = 0; q < NT; ++q) { const int t = rs_desc(a.blk, blk_first + (q < cnt ? q : cnt - 1)).steps(); tw = t > tw ? t : tw; }
+        const int ngrp = ((tw < TMAX ? tw : TMAX) + TILE_GROUP - 1) / TILE_GROUP;
+        double val[D][TILE_GROUP], a1[TILE_GROUP], a2[TILE_GROUP];
 #pragma unroll
-            for (int hf = 0; hf < TMAX / 32; ++hf) {       // (32 steps = 64 registers of matrix values at a time; 64-step tiles: two such passes)
-                double val[32];
+        for (int s = 0; s < D; ++s) if (s < cnt) rs_request(a, blk_first + s, 0, lane, val[s]);
 #pragma unroll
-                for (int t = 0; t < 32; ++t) val[t] = (((32 * hf + t) & ~7) < T) ? __builtin_nontemporal_load(vp + 64 * (32 * hf + t)) : 0.0;   // (zero-padded storage beyond the tile's rows)
-                double h1, h2;
-                res_tile_plain<32>(val, T - 32 * hf, gq, s_gcol + coff + 32 * hf, mycol + coff + 32 * hf, lane, h1, h2);
-                u1 += h1; u2 += h2;
+        for (int q = 0; q < NT; ++q) R.ww[q] = make_double2(0.0, 0.0);
+#pragma unroll
+        for (int u = 0; u < TILE_GROUP; ++u) a1[u] = a2[u] = 0.0;
+        for (int grp = 0; grp < ngrp; ++grp) {
+            int bf = blk_first;
+            asm volatile("" : "+s"(bf));           // (opaque per group: the descriptor loads stay in the loop, see above)
+            rs_group<0, NT, D>(a, bf, cnt, grp, c0, lane, s_gcol, mycol, R, val, a1, a2);
+        }
+        // the rows' epilogue: [c; b] of all tiles requested together
+        double cb[NT];
+#pragma unroll
+        for (int q = 0; q < NT; ++q) {
+            cb[q] = 0.0;
+            if (q < cnt) {
+                const BlkDesc d = rs_desc(a.blk, blk_first + q);
+                if (lane < d.nrows()) cb[q] = a.cb[d.row0 + lane];
             }
-            const double c = valid ? a.cb[d.row0 + lane] : 0.0;
-            const d2 gt = make_double2(s_ctl[RC_GTX], s_ctl[RC_GTY]);            // (read here, not held across the tile: registers)
-            const double q1 = -(u1 - gt.x * c), q2 = -(u2 - gt.y * c);           // rows of A: EpiKkt::row, i >= n   (HSDEAffine.jl:52,55)
-            d2 w = make_double2(gq.x - q2, q1 - gq.y);                           // affinepluslinear.jl:45-48
-            if (!valid) w = make_double2(0.0, 0.0);
-            R.ww[q] = w;
-            acc[2] += c * gq.x;
-            acc[3] += c * gq.y;
+        }
+        const d2 gt = make_double2(s_ctl[RC_GTX], s_ctl[RC_GTY]);                // (read here, not held across the walk: registers)
+#pragma unroll
+        for (int q = 0; q < NT; ++q) {
+            if (q < cnt) {
+                const bool valid = lane < rs_desc(a.blk, blk_first + q).nrows();
+                const d2 gq = R.rr[q];
+                const double c = cb[q], u1 = R.ww[q].x, u2 = R.ww[q].y;
+                const double q1 = -(u1 - gt.x * c), q2 = -(u2 - gt.y * c);       // rows of A: EpiKkt::row, i >= n   (HSDEAffine.jl:52,55)
+                d2 w = make_double2(gq.x - q2, q1 - gq.y);                       // affinepluslinear.jl:45-48
+                if (!valid) w = make_double2(0.0, 0.0);
+                R.ww[q] = w;
+                acc[2] += c * gq.x;
+                acc[3] += c * gq.y;
+            }
         }
     }
 #pragma unroll
@@ -899,7 +967,7 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
     for (int q = ct; q < 4 * RS_GMAX; q += 64 * ncomm) s_all[q] = 0.0;
     for (int q = ct + (ncomp + 1) * 4; q < 16 * 4; q += 64 * ncomm) (&s_red[0][0])[q] = 0.0;
     // (this wavefront waits at barrier (A) while the others sweep: it walks the workgroup's last tiles itself, at most RS_NTC -- the plan's deal)
-    constexpr int NTC = TMAX > 32 ? RS_NTC_BASE : RS_NTC;      // (64-step tiles: two passes per tile, the share it always had)
+    constexpr int NTC = TMAX > 32 ? RS_NTC_BASE : RS_NTC;      // (64-step tiles: eight groups per tile, the share it always had)
     RsRows<NTC> R;
     rs_rows_load<NTC>(a, me.blk0 + t0, c0wave ? cnt : 0, lane, R);
     d2* const mycol = s_colpart + ncomp * 64;
