@@ -98,7 +98,7 @@ static int prox_affine_direct_block(fos_solver* h, const d2* x, d2* out, bool fr
     prof_end(h, pe);
     po = prof_begin_other(h, 0);
     launch_blkdir_combine(c, T, W3, V, h->blk_phg, h->blk_qphg, h->blk_prm, zero_kappa ? 1 : 0, out, p1, p2, fr);
-    if (sh && h->peer_on && c.peer) {
+    if (sh && h->tr.peer_on && c.peer) {
         // mailbox transports: the tau kernel sums the rank's record, exchanges it and forms the tau row itself (one launch instead of three)
         launch_blkdir_tau(c, T, h->blk_qphg, h->blk_prm, zero_kappa ? 1 : 0, out, p1, p2, h->blk_ctx, h->blk_n, 2);
     } else {

@@ -1,4 +1,4 @@
-// struct fos_solver (the handle behind fos_handle) and the helpers that solver.cpp and direct.cpp share.  Private: not part of the ABI.
+// struct fos_solver (the handle behind fos_handle) and the helpers that solver.cpp, direct.cpp and transport.cpp share.  Private: not part of the ABI.
 #pragma once
 
 #include <rccl/rccl.h>
@@ -19,6 +19,40 @@ struct DenseInv {
     double seconds = 0.0, probe = 0.0;         // the inversion stage alone (matrix formed -> inverse accepted); last probe residual of the Cholesky path (0 on the Newton path)
     bool fell_back = false;                    // the Cholesky path gave up and Newton-Schulz ran
     int64_t bad_col = -1;                      // first column whose Cholesky pivot was not a positive finite number
+};
+
+// ------------------------------------------------------------------------------------------------ the transports' state (transport.cpp)
+// which of them carries a sharded handle's sums: VIA_PEER before VIA_HOST before VIA_RCCL, whatever else is set up beside it
+enum ReduceVia { VIA_NONE, VIA_RCCL, VIA_HOST, VIA_PEER };
+// the POSIX shared-memory segment behind the host-pinned mailboxes
+struct HostSeg {
+    void* p = nullptr;                         // the mapping (nullptr: no segment)
+    int fd = -1;                               // kept open: host_seg_stale asks it whether the mapped segment is still linked under its name
+    size_t bytes = 0;
+    std::string name;
+    bool creator = false;                      // this process created the name (rank 0) and unlinks it
+    // the last page: every rank's device identity, written by the rank when it opens the segment (zero: that rank has not opened it yet)
+    volatile unsigned long long* ids() const { return reinterpret_cast<volatile unsigned long long*>(static_cast<char*>(p) + bytes - 4096); }
+};
+struct Transport {
+    ncclComm_t comm = nullptr;                 // in-stream RCCL all-reduce (fos_comm_init)
+    // the caller's own collective on host buffers (fos_comm_init_host: MPI.jl, gloo, ...)
+    fos_allreduce_fn host_fn = nullptr; void* host_user = nullptr;
+    double* host_buf = nullptr;                // pinned, max(2n, 16) doubles
+    // peer mailboxes: in device memory, mapped through HIP IPC (fos_peer_open), or in one host-pinned shm segment (fos_peer_open_host)
+    unsigned long long* peer_mbox = nullptr;   // own mailbox (uncached device memory, exported through HIP IPC)
+    unsigned long long* peer_relay = nullptr;  // host-pinned mailboxes: the local relay
+    std::vector<void*> peer_opened;            // IPC mappings of the peers' mailboxes
+    fos::PeerBox peer{};                       // the installed mailboxes (box != nullptr: open)
+    bool peer_on{false};                       // ... and whether the sums go through them (fos_peer_enable)
+    bool peer_same_device = false;             // a peer rank's mailbox lives on THIS device (several ranks on one GPU: tests)
+    HostSeg host_seg;                          // the mapped + registered shm segment
+    // row-sharded + peer mailboxes: the n-vector A'y crosses the ranks through peer-mapped memory too (fos_internal.hpp, fos::VecBox)
+    double* vec_buf = nullptr;                 // own exchange buffer: [2][nranks][2n] doubles, then [2][nranks] flags (uncached, IPC-exported)
+    std::vector<void*> vec_opened;
+    fos::VecBox vec{};
+    uint32_t vec_seq = 0;                      // exchanges enqueued so far (the same on every rank: all make the same calls)
+    ReduceVia via() const { return peer_on ? VIA_PEER : (host_fn ? VIA_HOST : (comm ? VIA_RCCL : VIA_NONE)); }
 };
 
 // ------------------------------------------------------------------------------------------------ the handle
@@ -65,7 +99,6 @@ struct fos_solver {
     int psd_refine = -1;                       // FOS_PSD_REFINE
     bool psd_extrapolate = true;               // FOS_PSD_EXTRAPOLATE
     double psd_theta = 0.0;                    // FOS_PSD_THETA
-    bool peer_same_device = false;             // a peer rank's mailbox lives on THIS device (several ranks on one GPU: tests)
 
     // scalars
     fos::DevState* st = nullptr;
@@ -153,31 +186,11 @@ struct fos_solver {
     int cg_same_run = 0;                       // consecutive solves that took exactly last_cg_pred iterations
     const d2* last_checked = nullptr;          // vector the last checkstatus was evaluated on
 
-    // sharding: scalar sums cross GPUs either by an in-stream RCCL all-reduce (comm) or through peer mailboxes (peer_on)
-    ncclComm_t comm = nullptr;
+    // sharding: how the sums cross the ranks is the transport's business (transport.cpp); what is sharded, and the solves' sequence windows, is the handle's
+    Transport tr;
     int nranks = 1, rank = 0;
-    unsigned long long* peer_mbox = nullptr;   // own mailbox (uncached device memory, exported through HIP IPC)
-    std::vector<void*> peer_opened;            // IPC mappings of the peers' mailboxes
-    fos::PeerBox peer{};
-    bool peer_on = false;
-    // host-pinned mailboxes (fos_peer_open_host): the mapped + registered shm segment, its name (rank 0 unlinks it), the local relay
-    void* host_seg = nullptr;
-    int host_seg_fd = -1;                      // kept open: fos_peer_selftest asks it whether the mapped segment is still linked under its name
-    size_t host_seg_bytes = 0;
-    std::string host_seg_name;
-    unsigned long long* peer_relay = nullptr;
     uint32_t cg_epoch = 0;                     // windows of 2048 sequence numbers used so far (cg_solve): the folded exchanges, the resident solve
-    // ... or through the caller's own collective on host buffers (fos_comm_init_host: MPI.jl, gloo, ...)
-    fos_allreduce_fn host_fn = nullptr;
-    void* host_user = nullptr;
-    double* host_buf = nullptr;                // pinned, max(2n, 16) doubles
-    // row-sharded + peer mailboxes: the n-vector A'y crosses the ranks through peer-mapped memory too (fos_internal.hpp, fos::VecBox)
-    double* vec_buf = nullptr;                 // own exchange buffer: [2][nranks][2n] doubles, then [2][nranks] flags (uncached, IPC-exported)
-    std::vector<void*> vec_opened;
-    fos::VecBox vec{};
-    uint32_t vec_seq = 0;                      // exchanges enqueued so far (the same on every rank: all make the same calls)
-    int vec_nranks = 0;
-    bool sharded() const { return comm != nullptr || peer_on || host_fn != nullptr; }
+    bool sharded() const { return tr.via() != VIA_NONE; }
     // row sharding of a non-block-diagonal A: the first n entries (and tau, kappa) of every vector are replicated,
     // the slots of the rows of A' are summed over the ranks (RCCL all-reduce of 2n doubles) between a sweep and its slot-list sums
     bool row_sharded = false;
@@ -198,7 +211,7 @@ struct fos_solver {
     bool prof_step_on = false;                 // the outer iteration in flight brackets its FOS_PROF_OTHER groups
     static constexpr size_t PROF_CAP = 16384;
 
-    static int sum_slots_over_ranks(void* self);      // solver.cpp (needs the RCCL table)
+    static int sum_slots_over_ranks(void* self);      // transport.cpp
     // row-sharded WITH dual tiles: the sweep fills local slot lists (S.slots = slots_rd + 2n doubles); between sweep and consumers the
     // lists of the n rows of A' are added up (cmp_rec / cmp_idx -> cmp_local) and THAT n-vector crosses the ranks into slots_rd[0..n);
     // the consumers' records (S.def_rec) name slot j for row j < n and the local lists, shifted by n, for the rows of A
@@ -207,17 +220,18 @@ struct fos_solver {
     double* cmp_local = nullptr;
     int cmp_lpr = 1;
 
-    fos::LaunchCtx ctx() const {
+    // mailboxes = true: with the open mailboxes attached although the sums do not go through them (yet): fos_peer_selftest
+    fos::LaunchCtx ctx(bool mailboxes = false) const {
         fos::LaunchCtx c;
         c.stream = stream; c.S = S; c.cb = cb; c.n = n; c.m = m; c.l = l; c.st = st;
         c.partials = partials; c.reduced = reduced; c.vec_blocks = vec_blocks; c.cg_blocks = cg_blocks;
-        c.peer = peer_on ? &peer : nullptr;
+        c.peer = (tr.peer_on || mailboxes) ? &tr.peer : nullptr;
         c.def_mask = def_mask;
         c.pre = pre_on ? pre_sums : nullptr;
         c.between = nullptr; c.between_arg = nullptr;
         c.cus = cus; c.psd_wave = psd_wave; c.psd_narrow = psd_narrow; c.psd_wide = psd_wide; c.psd_wide_threads = psd_wide_threads;
         c.psd_attr_set = &psd_attr_set; c.psd_attr_set_r = &psd_attr_set_r; c.psd_refine = psd_refine; c.psd_extrapolate = psd_extrapolate; c.psd_theta = psd_theta;
-        c.psd_refine_max_mats = (peer_same_device && nranks > 1) ? std::max(1, cus / nranks) : 0;
+        c.psd_refine_max_mats = (tr.peer_same_device && nranks > 1) ? std::max(1, cus / nranks) : 0;
         c.count_repl = (!row_sharded || rank == 0) ? 1 : 0;
         c.n_repl = row_sharded ? n : 0;
         if (row_sharded) { c.between = &fos_solver::sum_slots_over_ranks; c.between_arg = const_cast<fos_solver*>(this); }
@@ -225,15 +239,23 @@ struct fos_solver {
     }
 };
 
-// ------------------------------------------------------------------------------------------------ shared helpers (defined in solver.cpp)
+// ------------------------------------------------------------------------------------------------ shared helpers (defined in solver.cpp where no other file is named)
 namespace fos {
+// transport.cpp: the sums of a sharded handle (allreduce: `count` doubles in h->reduced, in place, in stream), the end of its transports, the two switches
+// of the mailboxes (FOS_PEER_FOLD: read once per process; FOS_PEER_LOOPBACK: at every call)
+int allreduce(fos_solver* h, int count);
+int finish_reduce(fos_solver* h, const LaunchCtx& c, int count, int nacc, int gate, int* from_reduced, int off = 0);
+void transport_teardown(fos_solver* h, bool destroy = false);
+bool peer_fold_env(), peer_loopback_env();
+// solver.cpp, for transport.cpp: the sharded set-up, the resident plan and the process-wide pool of uncached memory
+int global_setup(fos_solver* h);
+int resident_setup(fos_solver* h, int gmax);
+int uncached_acquire(int device, size_t bytes, bool allow_plain, void** out, const char* what);
 struct RoctxRange {                            // a named range for `rocprofv3 --marker-trace` (FOS_ROCTX=1)
     bool on;
     explicit RoctxRange(const char* name);
     ~RoctxRange();
 };
-int allreduce(fos_solver* h, int count);
-int finish_reduce(fos_solver* h, const LaunchCtx& c, int count, int nacc, int gate, int* from_reduced, int off = 0);
 int check_launch(const char* where);
 int prof_begin(fos_solver* h, int cls, int j, int64_t ordinal);
 int prof_begin_other(fos_solver* h, int post);

@@ -1062,7 +1062,7 @@ __global__ __launch_bounds__(DEF_THREADS) void kkt2_deferred_kernel(DevBlkCsr S,
 }
 
 // Row-sharded operators with dual tiles: the LOCAL slot list of every row of A' (its own partial + the column sums of the tiles
-// above it, list order) -> one partial sum per row, the n-vector that crosses the ranks (solver.cpp, sum_slots_over_ranks).
+// above it, list order) -> one partial sum per row, the n-vector that crosses the ranks (transport.cpp, sum_slots_over_ranks).
 __global__ __launch_bounds__(DEF_THREADS) void slots_compact_kernel(int nrows, const DefRow* __restrict__ rec, const int32_t* __restrict__ idx,
                                                                     const d2* __restrict__ slots, d2* __restrict__ out, int lpr) {
     const int sh = 31 - __clz(lpr);

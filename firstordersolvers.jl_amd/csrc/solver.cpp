@@ -3,10 +3,6 @@
 // in HBM between fos_create and fos_destroy (the only transfers are N doubles at set/get-iterate and ~100 bytes of
 // scalars per CG poll / convergence check).
 #include <dlfcn.h>
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 #include <functional>
 
 #include <chrono>
@@ -17,19 +13,6 @@
 
 namespace fos {
 const char* last_error_cstr();
-
-// ------------------------------------------------------------------------------------------------ RCCL via dlopen
-// (no link-time dependency: single-GPU users never load it; inside a torch process dlopen returns the copy torch
-// already mapped, so both share one RCCL instance)
-struct Rccl {
-    void* lib = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    const char* (*GetErrorString)(ncclResult_t) = nullptr;
-};
-static Rccl g_rccl;
 
 // ------------------------------------------------------------------------------------------------ roctx ranges
 // Named ranges around the phases of an outer iteration (affine projection / cone projection / status check) for
@@ -59,76 +42,13 @@ static bool roctx_on() {
     return g_roctx.state == 1;
 }
 
-static int rccl_load() {
-    if (g_rccl.lib) return FOS_OK;
-    // ONE copy of RCCL per process: a host that already carries one (PyTorch ships its own librccl.so) must be joined, not
-    // doubled -- two copies interpose each other's globals and the process dies in their destructors at exit.  So: the copy that
-    // is already loaded, if any; otherwise a private one (local scope, own symbols first) that a later-loaded copy cannot touch.
-    const char* names[] = {"librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so.1"};
-    void* lib = nullptr;
-    for (const char* nm : names) {
-        lib = dlopen(nm, RTLD_NOW | RTLD_NOLOAD);
-        if (lib) break;
-    }
-    for (int k = 0; !lib && k < 3; ++k) lib = dlopen(names[k], RTLD_NOW | RTLD_LOCAL | RTLD_DEEPBIND);
-    if (!lib) { set_error("cannot dlopen librccl.so: %s", dlerror()); return FOS_ECOMM; }
-    g_rccl.GetUniqueId = (decltype(g_rccl.GetUniqueId))dlsym(lib, "ncclGetUniqueId");
-    g_rccl.CommInitRank = (decltype(g_rccl.CommInitRank))dlsym(lib, "ncclCommInitRank");
-    g_rccl.AllReduce = (decltype(g_rccl.AllReduce))dlsym(lib, "ncclAllReduce");
-    g_rccl.CommDestroy = (decltype(g_rccl.CommDestroy))dlsym(lib, "ncclCommDestroy");
-    g_rccl.GetErrorString = (decltype(g_rccl.GetErrorString))dlsym(lib, "ncclGetErrorString");
-    if (!g_rccl.GetUniqueId || !g_rccl.CommInitRank || !g_rccl.AllReduce || !g_rccl.CommDestroy) {
-        set_error("librccl.so lacks a required symbol");
-        return FOS_ECOMM;
-    }
-    g_rccl.lib = lib;
-    return FOS_OK;
-}
-
-#define FOS_NCCL(expr)                                                                                     \
-    do {                                                                                                   \
-        ncclResult_t _r = (expr);                                                                          \
-        if (_r != ncclSuccess) {                                                                           \
-            set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr,                                        \
-                      g_rccl.GetErrorString ? g_rccl.GetErrorString(_r) : "rccl error");                   \
-            return FOS_ECOMM;                                                                              \
-        }                                                                                                  \
-    } while (0)
-
 RoctxRange::RoctxRange(const char* name) : on(roctx_on()) { if (on) g_roctx.push(name); }
 RoctxRange::~RoctxRange() { if (on) g_roctx.pop(); }
-
-// the caller's collective: stage `count` doubles through the pinned host buffer (synchronises the stream; a slow path by design)
-static int host_allreduce(fos_solver* h, const double* src, double* dst, size_t count) {
-    if (hipMemcpyAsync(h->host_buf, src, sizeof(double) * count, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return FOS_EHIP;
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return FOS_EHIP;
-    if (h->host_fn(h->host_user, h->host_buf, (int64_t)count) != 0) { set_error("the caller's all-reduce callback failed"); return FOS_ECOMM; }
-    if (hipMemcpyAsync(dst, h->host_buf, sizeof(double) * count, hipMemcpyHostToDevice, h->stream) != hipSuccess) return FOS_EHIP;
-    return hipStreamSynchronize(h->stream) == hipSuccess ? FOS_OK : FOS_EHIP;          // the buffer is reused by the next call
-}
 
 static int psd_order(int64_t len) {
     int64_t k = (int64_t)std::llround(std::sqrt(0.25 + 2.0 * (double)len) - 0.5);
     if (k * (k + 1) / 2 != len) return -1;
     return (int)k;
-}
-
-// all-reduce of `count` doubles in h->reduced (in place, in stream) when sharded
-int allreduce(fos_solver* h, int count) {
-    if (h->peer_on) return FOS_OK;                             // peer mailboxes: launch_reduce1 already exchanged
-    if (h->host_fn) return host_allreduce(h, h->reduced, h->reduced, (size_t)count);
-    if (!h->comm) return FOS_OK;
-    FOS_NCCL(g_rccl.AllReduce(h->reduced, h->reduced, (size_t)count, ncclDouble, ncclSum, h->comm, h->stream));
-    return FOS_OK;
-}
-
-// partials[count][nacc] --(sharded: local reduce + all-reduce)--> returns from_reduced flag for the finalize kernel
-int finish_reduce(fos_solver* h, const LaunchCtx& c, int count, int nacc, int gate, int* from_reduced, int off) {
-    if (!h->sharded()) { *from_reduced = 0; return FOS_OK; }
-    launch_reduce1(c, count, nacc, gate, off);
-    FOS_TRY(allreduce(h, nacc));
-    *from_reduced = 1;
-    return FOS_OK;
 }
 
 // a kernel launch that the runtime rejected (bad configuration, missing attribute) is only reported by hipGetLastError
@@ -191,62 +111,6 @@ int kkt_apply_full(fos_solver* h, const LaunchCtx& c, const d2* w, d2* out, bool
     return FOS_OK;
 }
 
-}  // namespace fos
-
-using namespace fos;
-
-// row-sharded operators: slots (this rank's partial sums of A'y, 2n doubles) -> slots_rd (their sum over the ranks), in stream
-int fos_solver::sum_slots_over_ranks(void* self) {
-    fos_solver* h = static_cast<fos_solver*>(self);
-    const double* src = h->S.slots;            // one slot per row of A' ...
-    if (h->cmp_local) {                        // ... or, with dual tiles, the rows' local slot lists added up first
-        launch_slots_compact(h->ctx(), (int)h->n, h->cmp_rec, h->cmp_idx, h->cmp_lpr, h->S.slots, h->cmp_local);
-        src = h->cmp_local;
-    }
-    if (h->host_fn) return host_allreduce(h, src, h->slots_rd, (size_t)2 * (size_t)h->n);
-    if (h->peer_on && h->vec.buf) {            // peer-mapped memory: push + sum, in stream, no library call
-        launch_vec_exchange(h->ctx(), h->vec, ++h->vec_seq, src, h->slots_rd);
-        return FOS_OK;
-    }
-    if (!h->comm) {            // no communicator yet (set-up calls before fos_comm_init, or a single process): the sum is the copy
-        return hipMemcpyAsync(h->slots_rd, src, sizeof(double) * 2 * (size_t)h->n, hipMemcpyDeviceToDevice, h->stream) == hipSuccess ? FOS_OK : FOS_EHIP;
-    }
-    return g_rccl.AllReduce(src, h->slots_rd, (size_t)2 * (size_t)h->n, ncclDouble, ncclSum, h->comm, h->stream) == ncclSuccess ? FOS_OK : FOS_ECOMM;
-}
-
-namespace {
-
-// Has CG solve number `epoch` ended within its first batch of iterations?  No stream synchronisation and nothing in the stream:
-// the kernel that ends a solve writes HostMark.seq in pinned host memory, the marked p update of a batch that runs out before
-// convergence writes HostMark.batch; the host spins on the two (and looks at the stream now and then, in case neither comes).
-int wait_cg_mark(fos_solver* h, uint32_t epoch, int32_t batch_id, bool* ended) {
-    FOS_TRY(check_launch("poll"));
-    volatile HostMark* m = h->mark;
-    // a wall-clock bound (FOS_CG_WAIT_S, default 120 s): a kernel of the solve that never ends must not hang the host either
-    static const double wait_s = getenv("FOS_CG_WAIT_S") ? atof(getenv("FOS_CG_WAIT_S")) : 120.0;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t spin = 1;; ++spin) {
-        if (__atomic_load_n(&m->seq, __ATOMIC_ACQUIRE) == epoch) { *ended = true; break; }
-        if (__atomic_load_n(&m->batch, __ATOMIC_ACQUIRE) == batch_id) { *ended = false; break; }
-        __builtin_ia32_pause();
-        if ((spin & 0xFFFFu) == 0 && hipStreamQuery(h->stream) == hipSuccess) {          // everything enqueued has run
-            if (__atomic_load_n(&m->seq, __ATOMIC_ACQUIRE) == epoch) { *ended = true; break; }
-            if (__atomic_load_n(&m->batch, __ATOMIC_ACQUIRE) == batch_id) { *ended = false; break; }
-            // no mark: a kernel of the solve gave up (a peer exchange timed out, ...) -- the ordinary state read reports why
-            FOS_TRY(poll_state(h));
-            *ended = h->st_host->done != 0;
-            return FOS_OK;
-        }
-        if ((spin & 0xFFFFFu) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > wait_s) {
-            set_error("CG solve %u: neither its end mark nor its batch mark arrived within %.0f s (a kernel of the solve does not finish)", epoch, wait_s);
-            return FOS_EHIP;
-        }
-    }
-    if (*ended) { h->st_host->done = 1; h->st_host->iter = m->iter; h->st_host->hit_max = m->hit_max; h->st_host->rr = m->rr; }
-    else h->st_host->done = 0;
-    return FOS_OK;
-}
-
 // UNCACHED device memory (the mailboxes, the relay and vector-exchange buffers, the resident solve's record arrays) is kept for the life of the
 // process and handed from handle to handle, never returned to the runtime: on this image (ROCm 7.2), device memory that had been allocated
 // uncached, freed, and handed out again by a later hipMalloc gave a WRONG dense IndAffine set-up several handles later (deterministic;
@@ -259,7 +123,7 @@ std::vector<UncachedBlock> g_unc_free, g_unc_used;
 }
 // falls back to fine-grained memory (what the mailboxes accept), or with `allow_plain` (the records: cache-bypassing accesses work on any
 // memory) to ordinary memory
-static int uncached_acquire(int device, size_t bytes, bool allow_plain, void** out, const char* what) {
+int uncached_acquire(int device, size_t bytes, bool allow_plain, void** out, const char* what) {
     UncachedBlock r{device, nullptr, 0, false};
     {
         std::lock_guard<std::mutex> lk(g_unc_mu);
@@ -337,9 +201,9 @@ int resident_setup(fos_solver* h, int gmax) {
 int global_setup(fos_solver* h) {
     // the resident CG solve runs on a sharded handle only where EVERY rank's shard qualifies (all ranks must run the same exchanges) and
     // the sums cross the ranks through mailboxes (no collective call can sit inside a kernel): a vote through the handle's transport
-    FOS_TRY(resident_setup(h, (h->peer_same_device && h->nranks > 1) ? std::max(1, h->cus / h->nranks) : h->cus));
+    FOS_TRY(resident_setup(h, (h->tr.peer_same_device && h->nranks > 1) ? std::max(1, h->cus / h->nranks) : h->cus));
     h->res_all = false;
-    if (h->peer_on) {
+    if (h->tr.peer_on) {
         LaunchCtx cv = h->ctx();
         double q = h->res_ok ? 1.0 : 0.0;
         FOS_HIP(hipMemcpyAsync(h->partials, &q, sizeof(q), hipMemcpyHostToDevice, h->stream));
@@ -363,6 +227,43 @@ int global_setup(fos_solver* h) {
     return FOS_OK;
 }
 
+}  // namespace fos
+
+using namespace fos;
+
+namespace {
+
+// Has CG solve number `epoch` ended within its first batch of iterations?  No stream synchronisation and nothing in the stream:
+// the kernel that ends a solve writes HostMark.seq in pinned host memory, the marked p update of a batch that runs out before
+// convergence writes HostMark.batch; the host spins on the two (and looks at the stream now and then, in case neither comes).
+int wait_cg_mark(fos_solver* h, uint32_t epoch, int32_t batch_id, bool* ended) {
+    FOS_TRY(check_launch("poll"));
+    volatile HostMark* m = h->mark;
+    // a wall-clock bound (FOS_CG_WAIT_S, default 120 s): a kernel of the solve that never ends must not hang the host either
+    static const double wait_s = getenv("FOS_CG_WAIT_S") ? atof(getenv("FOS_CG_WAIT_S")) : 120.0;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint32_t spin = 1;; ++spin) {
+        if (__atomic_load_n(&m->seq, __ATOMIC_ACQUIRE) == epoch) { *ended = true; break; }
+        if (__atomic_load_n(&m->batch, __ATOMIC_ACQUIRE) == batch_id) { *ended = false; break; }
+        __builtin_ia32_pause();
+        if ((spin & 0xFFFFu) == 0 && hipStreamQuery(h->stream) == hipSuccess) {          // everything enqueued has run
+            if (__atomic_load_n(&m->seq, __ATOMIC_ACQUIRE) == epoch) { *ended = true; break; }
+            if (__atomic_load_n(&m->batch, __ATOMIC_ACQUIRE) == batch_id) { *ended = false; break; }
+            // no mark: a kernel of the solve gave up (a peer exchange timed out, ...) -- the ordinary state read reports why
+            FOS_TRY(poll_state(h));
+            *ended = h->st_host->done != 0;
+            return FOS_OK;
+        }
+        if ((spin & 0xFFFFFu) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > wait_s) {
+            set_error("CG solve %u: neither its end mark nor its batch mark arrived within %.0f s (a kernel of the solve does not finish)", epoch, wait_s);
+            return FOS_EHIP;
+        }
+    }
+    if (*ended) { h->st_host->done = 1; h->st_host->iter = m->iter; h->st_host->hit_max = m->hit_max; h->st_host->rr = m->rr; }
+    else h->st_host->done = 0;
+    return FOS_OK;
+}
+
 // conjugategradient!(x, KKTMatrix(Q), rhs, r, p, Ap; tol, max_iters)      conjugategradients.jl:31-55
 // Device resident: the host enqueues iterations AHEAD (every CG kernel is gated on DevState.done) and polls once per batch.
 // `apply_on` (default: x): the vector the start residual's operator product is taken of -- prox_affine passes x - (0, in.y)
@@ -377,8 +278,7 @@ int cg_solve(fos_solver* h, d2* x, const d2* rhs, double tol, int maxit, int64_t
              const PostFn* post = nullptr, bool* post_ran = nullptr) {
     LaunchCtx c = h->ctx();
     int next_j = 1;                          // iteration number of the next enqueued launch group (if CG still runs)
-    static const bool fold_env = !(getenv("FOS_PEER_FOLD") && atoi(getenv("FOS_PEER_FOLD")) == 0);
-    const bool fold = h->peer_on && fold_env;
+    const bool fold = h->tr.peer_on && peer_fold_env();
     const bool rccl = h->sharded() && !fold;  // sums cross the ranks between the kernels (reduce kernel + all-reduce, or unfolded mailboxes)
     // which recurrence: the reference's (three launches, two reduction points per iteration) or the merged-reduction form (two
     // launches, one reduction point); sharded handles take the latter by default and always close in the update kernel
@@ -404,14 +304,14 @@ int cg_solve(fos_solver* h, d2* x, const d2* rhs, double tol, int maxit, int64_t
     auto iter_desc = [&](int j) {
         CgIter it;
         it.j = j; it.r = h->R; it.p_prev = h->PB[(j - 1) & 1]; it.p_cur = h->PB[j & 1];
-        it.fuse_p = fuse_p; it.rr_from_reduced = rccl ? 1 : 0; it.fold = fold ? &h->peer : nullptr; it.seq_base = seq_base;
+        it.fuse_p = fuse_p; it.rr_from_reduced = rccl ? 1 : 0; it.fold = fold ? &h->tr.peer : nullptr; it.seq_base = seq_base;
         it.start_fused = start_fused;
         return it;
     };
     auto merged_desc = [&](int j) {
         CgmIter it;
         it.j = j; it.x = x; it.r = h->R; it.p = h->PB[0]; it.s = h->PB[1]; it.w = h->AP;
-        it.close_in_update = close_in_update; it.from_reduced = rccl ? 1 : 0; it.fold = fold ? &h->peer : nullptr; it.seq_base = seq_base;
+        it.close_in_update = close_in_update; it.from_reduced = rccl ? 1 : 0; it.fold = fold ? &h->tr.peer : nullptr; it.seq_base = seq_base;
         return it;
     };
     const size_t prof_start = h->prof_used;
@@ -438,7 +338,7 @@ int cg_solve(fos_solver* h, d2* x, const d2* rhs, double tol, int maxit, int64_t
         // the whole solve is ONE launch (resident.hip): nothing to enqueue ahead, nothing to predict; what follows the solve is enqueued behind it
         // (gated on DevState.done, which the launch sets when it ends) and the host reads the iteration count from the mark the launch leaves
         const int pe = prof_begin(h, FOS_PROF_RESIDENT, 1, h->prof_seen[FOS_PROF_RESIDENT]++);
-        const hipError_t le = launch_cg_resident(c, h->res, x, rhs, apply_on ? apply_on : x, tol, maxit, fold ? &h->peer : nullptr, seq_base);
+        const hipError_t le = launch_cg_resident(c, h->res, x, rhs, apply_on ? apply_on : x, tol, maxit, fold ? &h->tr.peer : nullptr, seq_base);
         prof_end(h, pe);
         if (le != hipSuccess) { set_error("resident CG launch: %s", hipGetErrorString(le)); return FOS_EHIP; }
         if (spec) {
@@ -1589,16 +1489,7 @@ int fos_destroy(fos_handle h) {
     if (!h) return FOS_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
-    if (h->host_buf) (void)hipHostFree(h->host_buf);
-    for (void* q : h->peer_opened) (void)hipIpcCloseMemHandle(q);
-    for (void* q : h->vec_opened) (void)hipIpcCloseMemHandle(q);
-    if (h->host_seg) {
-        (void)hipHostUnregister(h->host_seg);
-        (void)munmap(h->host_seg, h->host_seg_bytes);
-        if (h->host_seg_fd >= 0) close(h->host_seg_fd);
-        if (h->rank == 0 && !h->host_seg_name.empty()) (void)shm_unlink(h->host_seg_name.c_str());
-    }
+    transport_teardown(h, true);
     for (auto& r : h->prof_recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     psd_sign_destroy(h->psd_big);
     for (void* p : h->pooled) uncached_release(p);
@@ -1617,391 +1508,6 @@ int fos_sizes(fos_handle h, int64_t* m, int64_t* n, int64_t* N, int64_t* nnz) {
     if (N) *N = 2 * h->l;
     if (nnz) *nnz = h->nnz;
     return FOS_OK;
-}
-
-int fos_comm_get_unique_id(void* id128) {
-    FOS_TRY(rccl_load());
-    static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
-    ncclUniqueId id;
-    FOS_NCCL(g_rccl.GetUniqueId(&id));
-    memcpy(id128, &id, sizeof(id));
-    return FOS_OK;
-}
-
-int fos_comm_init(fos_handle h, int nranks, int rank, const void* id128) {
-    if (!h || nranks < 1 || rank < 0 || rank >= nranks) { set_error("bad comm arguments"); return FOS_EINVAL; }
-    if (h->ls_interval > 0 || h->gapp_iproj > 0) { set_error("switch the LineSearchWrapper / GAPP off before sharding the handle (fos_set_linesearch(h, 0), fos_set_gapp(h, 0))"); return FOS_EUNSUPPORTED; }
-    FOS_TRY(rccl_load());
-    FOS_HIP(hipSetDevice(h->device));
-    ncclUniqueId id;
-    memcpy(&id, id128, sizeof(id));
-    FOS_NCCL(g_rccl.CommInitRank(&h->comm, nranks, id, rank));
-    h->nranks = nranks; h->rank = rank;
-    return global_setup(h);            // all-reduce [n+m, ||b||^2, ||c||^2]
-}
-
-// Sharding with the CALLER's collective (MPI.jl's Allreduce!, torch.distributed on any backend, ...): every cross-rank sum is
-// staged through a pinned host buffer and handed to `fn` (in place, blocking).  Correct for both shardings, slow (one stream
-// synchronisation per sum): the path for a host that owns no RCCL communicator, and the one a single-GPU box can run with two
-// processes (tests/test_gpu_peer_mailbox.py::test_row_sharded_two_processes_host_exchange).
-int fos_comm_init_host(fos_handle h, int nranks, int rank, fos_allreduce_fn fn, void* user) {
-    if (!h || !fn || nranks < 1 || rank < 0 || rank >= nranks) { set_error("bad comm arguments"); return FOS_EINVAL; }
-    if (h->ls_interval > 0 || h->gapp_iproj > 0) { set_error("switch the LineSearchWrapper / GAPP off before sharding the handle (fos_set_linesearch(h, 0), fos_set_gapp(h, 0))"); return FOS_EUNSUPPORTED; }
-    if (h->comm || h->peer_on) { set_error("this handle already has a communicator"); return FOS_EINVAL; }
-    FOS_HIP(hipSetDevice(h->device));
-    if (!h->host_buf) {
-        void* q = nullptr;
-        FOS_HIP(hipHostMalloc(&q, sizeof(double) * std::max<size_t>((size_t)2 * (size_t)h->n, 16), hipHostMallocDefault));
-        h->host_buf = static_cast<double*>(q);
-    }
-    h->host_fn = fn; h->host_user = user;
-    h->nranks = nranks; h->rank = rank;
-    return global_setup(h);
-}
-
-// ---- peer mailboxes: the sharded scalar sums without a collective library (fos_internal.hpp, PeerBox)
-int fos_peer_export(fos_handle h, void* handle64) {
-    if (!h || !handle64) { set_error("NULL argument"); return FOS_EINVAL; }
-    static_assert(sizeof(hipIpcMemHandle_t) == 64, "hipIpcMemHandle_t is 64 bytes");
-    FOS_HIP(hipSetDevice(h->device));
-    if (!h->peer_mbox) {
-        void* q = nullptr;
-        const size_t bytes = PEER_BOX_TOTAL_WORDS * sizeof(unsigned long long);    // region 0 + region 1 (four slots)
-        FOS_TRY(uncached_acquire(h->device, bytes, false, &q, "mailbox"));
-        h->pooled.push_back(q);
-        FOS_HIP(hipMemset(q, 0, bytes));                         // sequence number 0 is never sent
-        h->peer_mbox = reinterpret_cast<unsigned long long*>(q);
-    }
-    hipIpcMemHandle_t ipc;
-    FOS_HIP(hipIpcGetMemHandle(&ipc, h->peer_mbox));
-    memcpy(handle64, &ipc, sizeof(ipc));
-    return FOS_OK;
-}
-
-int fos_peer_open(fos_handle h, int nranks, int rank, const void* handles, double timeout_s) {
-    if (!h || !handles || nranks < 1 || nranks > PEER_MAX_RANKS || rank < 0 || rank >= nranks) {
-        set_error("bad peer arguments (1 <= nranks <= %d)", PEER_MAX_RANKS); return FOS_EINVAL;
-    }
-    if (!h->peer_mbox) { set_error("fos_peer_open before fos_peer_export"); return FOS_EINVAL; }
-    if (!h->peer_opened.empty() || h->peer.box) { set_error("peer mailboxes are already open"); return FOS_EINVAL; }
-    if (h->comm && (h->nranks != nranks || h->rank != rank)) { set_error("peer ranks differ from the RCCL communicator's"); return FOS_EINVAL; }
-    FOS_HIP(hipSetDevice(h->device));
-    std::vector<unsigned long long*> tab((size_t)nranks, nullptr);
-    for (int r = 0; r < nranks; ++r) {
-        if (r == rank) { tab[r] = h->peer_mbox; continue; }
-        hipIpcMemHandle_t ipc;
-        memcpy(&ipc, (const char*)handles + (size_t)r * sizeof(ipc), sizeof(ipc));
-        void* q = nullptr;
-        hipError_t e = hipIpcOpenMemHandle(&q, ipc, hipIpcMemLazyEnablePeerAccess);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            for (void* o : h->peer_opened) (void)hipIpcCloseMemHandle(o);
-            h->peer_opened.clear();
-            set_error("hipIpcOpenMemHandle(mailbox of rank %d): %s", r, hipGetErrorString(e));
-            return FOS_ECOMM;
-        }
-        h->peer_opened.push_back(q);
-        tab[r] = reinterpret_cast<unsigned long long*>(q);
-        // first contact between DIFFERENT devices: the mapping can succeed where loads and stores over the link cannot -- ask the
-        // runtime, and say which pair it is (the caller falls back to its collective: bench.py `peer_fallback_reason`)
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, q) == hipSuccess && attr.device == h->device) h->peer_same_device = true;
-        if (hipPointerGetAttributes(&attr, q) == hipSuccess && attr.device >= 0 && attr.device != h->device) {
-            int can = 0;
-            if (hipDeviceCanAccessPeer(&can, h->device, attr.device) == hipSuccess && !can) {
-                for (void* o : h->peer_opened) (void)hipIpcCloseMemHandle(o);
-                h->peer_opened.clear();
-                set_error("device %d cannot access the memory of device %d, rank %d's (hipDeviceCanAccessPeer = 0)", h->device, attr.device, r);
-                return FOS_ECOMM;
-            }
-        } else (void)hipGetLastError();
-    }
-    unsigned long long** dtab = nullptr;
-    FOS_TRY(dev_upload(h, &dtab, tab));
-    uint32_t* seq = nullptr;
-    FOS_TRY(dev_alloc(h, &seq, 1));
-    FOS_HIP(hipMemset(seq, 0, sizeof(uint32_t)));
-    h->peer = PeerBox{};
-    h->peer.box = dtab; h->peer.seq = seq; h->peer.nranks = nranks; h->peer.rank = rank;
-    h->peer.timeout_ticks = (int64_t)((timeout_s > 0 ? timeout_s : 20.0) * 1e8);
-    h->peer.loopback = (getenv("FOS_PEER_LOOPBACK") && atoi(getenv("FOS_PEER_LOOPBACK")) != 0) ? 1 : 0;
-    h->nranks = nranks; h->rank = rank;
-    return FOS_OK;
-}
-
-// Host-pinned mailboxes: ONE shm segment of mailbox size that every rank maps and registers; every box[r] is that segment (PeerBox::shared),
-// workgroup 0 of a folded exchange republishes the peers' words in a local relay (PeerBox::relay).
-int fos_peer_open_host(fos_handle h, int nranks, int rank, const char* shm_name, double timeout_s) {
-    if (!h || !shm_name || shm_name[0] != '/' || nranks < 1 || nranks > PEER_MAX_RANKS || rank < 0 || rank >= nranks) {
-        set_error("bad arguments (shm_name \"/...\", 1 <= nranks <= %d)", PEER_MAX_RANKS); return FOS_EINVAL;
-    }
-    if (!h->peer_opened.empty() || h->peer.box || h->host_seg) { set_error("peer mailboxes are already open (fos_peer_close first)"); return FOS_EINVAL; }
-    if (h->row_sharded) { set_error("host-pinned mailboxes carry the scalar sums of cone-sharded handles only"); return FOS_EUNSUPPORTED; }
-    if (h->comm && (h->nranks != nranks || h->rank != rank)) { set_error("peer ranks differ from the RCCL communicator's"); return FOS_EINVAL; }
-    FOS_HIP(hipSetDevice(h->device));
-    // (one more page behind the mailbox words: every rank's device identity, so that ranks which share a device can find out -- fos_peer_selftest)
-    const size_t bytes = ((PEER_BOX_TOTAL_WORDS * sizeof(unsigned long long) + 4095) / 4096) * 4096 + 4096;
-    // Rank 0 CREATES the segment -- exclusively, after unlinking whatever a crashed run left under the name: a fresh segment is zero filled (sequence number 0
-    // is never sent), a reused one would carry sequence-tagged words that validate themselves.  The other ranks open it WITHOUT creating, waiting for it to
-    // appear at its full size.  A rank that was quick enough to open a stale segment before rank 0 unlinked it holds an unlinked file: fos_peer_selftest
-    // (behind the caller's barrier) sees st_nlink == 0 on the descriptor kept here and fails the self test.
-    int fd = -1;
-    if (rank == 0) {
-        (void)shm_unlink(shm_name);
-        fd = shm_open(shm_name, O_CREAT | O_EXCL | O_RDWR, 0600);
-        if (fd < 0 && errno == EEXIST) { (void)shm_unlink(shm_name); fd = shm_open(shm_name, O_CREAT | O_EXCL | O_RDWR, 0600); }
-        if (fd < 0) { set_error("shm_open(%s, O_CREAT | O_EXCL): %s", shm_name, strerror(errno)); return FOS_ECOMM; }
-        if (ftruncate(fd, (off_t)bytes) != 0) { const int e = errno; close(fd); (void)shm_unlink(shm_name); set_error("ftruncate(%s, %zu): %s", shm_name, bytes, strerror(e)); return FOS_ECOMM; }
-    } else {
-        const auto t0 = std::chrono::steady_clock::now();
-        const double wait_s = timeout_s > 0 ? std::max(timeout_s, 5.0) : 20.0;
-        for (;;) {
-            fd = shm_open(shm_name, O_RDWR, 0600);
-            if (fd >= 0) {
-                struct stat sb;
-                if (fstat(fd, &sb) == 0 && (size_t)sb.st_size >= bytes) break;
-                close(fd); fd = -1;
-            } else if (errno != ENOENT) { set_error("shm_open(%s): %s", shm_name, strerror(errno)); return FOS_ECOMM; }
-            if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > wait_s) { set_error("shm_open(%s): rank 0 did not create the segment within %.0f s", shm_name, wait_s); return FOS_ECOMM; }
-            usleep(1000);
-        }
-    }
-    void* seg = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    if (seg == MAP_FAILED) { const int e = errno; close(fd); if (rank == 0) (void)shm_unlink(shm_name); set_error("mmap(%s): %s", shm_name, strerror(e)); return FOS_ECOMM; }
-    hipError_t e = hipHostRegister(seg, bytes, hipHostRegisterMapped | hipHostRegisterPortable);
-    void* dptr = nullptr;
-    if (e == hipSuccess) e = hipHostGetDevicePointer(&dptr, seg, 0);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipHostUnregister(seg);
-        (void)hipGetLastError();
-        munmap(seg, bytes);
-        close(fd);
-        if (rank == 0) (void)shm_unlink(shm_name);
-        set_error("hipHostRegister / hipHostGetDevicePointer(%s): %s", shm_name, hipGetErrorString(e));
-        return FOS_ECOMM;
-    }
-    h->host_seg_fd = fd;
-    h->host_seg = seg; h->host_seg_bytes = bytes; h->host_seg_name = shm_name;
-    {
-        char bus[64] = {0};
-        unsigned long long id = 0x9E3779B97F4A7C15ull;
-        if (hipDeviceGetPCIBusId(bus, (int)sizeof(bus), h->device) == hipSuccess) { for (const char* q = bus; *q; ++q) id = (id ^ (unsigned char)*q) * 0x100000001B3ull; }
-        else { (void)hipGetLastError(); id ^= (unsigned long long)(h->device + 1); }
-        volatile unsigned long long* ids = reinterpret_cast<volatile unsigned long long*>(static_cast<char*>(seg) + bytes - 4096);
-        ids[rank] = id | 1ull;                                  // (never zero: a zero entry = that rank has not opened the segment yet)
-    }
-    if (!h->peer_relay) {
-        void* q = nullptr;
-        const size_t rb = PEER_BOX_TOTAL_WORDS * sizeof(unsigned long long);
-        FOS_TRY(uncached_acquire(h->device, rb, false, &q, "relay"));
-        h->pooled.push_back(q);
-        h->peer_relay = reinterpret_cast<unsigned long long*>(q);
-    }
-    FOS_HIP(hipMemset(h->peer_relay, 0, PEER_BOX_TOTAL_WORDS * sizeof(unsigned long long)));
-    std::vector<unsigned long long*> tab((size_t)nranks, reinterpret_cast<unsigned long long*>(dptr));
-    unsigned long long** dtab = nullptr;
-    FOS_TRY(dev_upload(h, &dtab, tab));
-    uint32_t* seq = nullptr;
-    FOS_TRY(dev_alloc(h, &seq, 1));
-    FOS_HIP(hipMemset(seq, 0, sizeof(uint32_t)));
-    h->peer = PeerBox{};
-    h->peer.box = dtab; h->peer.seq = seq; h->peer.nranks = nranks; h->peer.rank = rank;
-    h->peer.timeout_ticks = (int64_t)((timeout_s > 0 ? timeout_s : 20.0) * 1e8);
-    h->peer.relay = h->peer_relay; h->peer.shared = 1;
-    h->peer.loopback = (getenv("FOS_PEER_LOOPBACK") && atoi(getenv("FOS_PEER_LOOPBACK")) != 0) ? 1 : 0;
-    h->nranks = nranks; h->rank = rank;
-    return FOS_OK;
-}
-
-// drop the open mailboxes (device or host): another transport may be opened on the handle afterwards
-int fos_peer_close(fos_handle h) {
-    if (!h) { set_error("NULL handle"); return FOS_EINVAL; }
-    FOS_HIP(hipSetDevice(h->device));
-    FOS_HIP(hipStreamSynchronize(h->stream));
-    if (h->peer_on) FOS_TRY(fos_peer_enable(h, 0));
-    for (void* q : h->peer_opened) (void)hipIpcCloseMemHandle(q);
-    h->peer_opened.clear();
-    for (void* q : h->vec_opened) (void)hipIpcCloseMemHandle(q);
-    h->vec_opened.clear();
-    h->vec = VecBox{};
-    if (h->host_seg) {
-        (void)hipHostUnregister(h->host_seg);
-        (void)munmap(h->host_seg, h->host_seg_bytes);
-        if (h->host_seg_fd >= 0) { close(h->host_seg_fd); h->host_seg_fd = -1; }
-        if (h->rank == 0 && !h->host_seg_name.empty()) (void)shm_unlink(h->host_seg_name.c_str());
-        h->host_seg = nullptr; h->host_seg_bytes = 0; h->host_seg_name.clear();
-    }
-    if (h->peer_mbox) FOS_HIP(hipMemset(h->peer_mbox, 0, PEER_BOX_TOTAL_WORDS * sizeof(unsigned long long)));   // (a re-opened mailbox starts its sequence numbers again)
-    h->peer = PeerBox{};                       // (the small device tables stay owned by the handle until fos_destroy)
-    h->peer_same_device = false;
-    // a failed exchange leaves its mark in the device state: clear it, the next transport starts clean
-    DevState z;
-    FOS_HIP(hipMemcpy(&z, h->st, sizeof(DevState), hipMemcpyDeviceToHost));
-    z.xchg_failed = 0; z.done = 0;
-    FOS_HIP(hipMemcpy(h->st, &z, sizeof(DevState), hipMemcpyHostToDevice));
-    h->st_host->xchg_failed = 0;
-    return FOS_OK;
-}
-
-// `rounds` exchanges of known values, checked exactly; *ok = 0 on a mismatch or a time-out (the handle then keeps
-// whatever reduction it had: RCCL if fos_comm_init was called).  Collective: every rank calls it with the same rounds.
-int fos_peer_selftest(fos_handle h, int rounds, int32_t* ok) {
-    if (!h || !ok) { set_error("NULL argument"); return FOS_EINVAL; }
-    if (!h->peer.box) { set_error("fos_peer_selftest before fos_peer_open"); return FOS_EINVAL; }
-    FOS_HIP(hipSetDevice(h->device));
-    if (h->host_seg && h->host_seg_fd >= 0) {
-        // (the caller's barrier stands between the opens and this call: rank 0 has unlinked and re-created the segment by now -- a descriptor whose
-        //  file is no longer linked is a segment some crashed run left behind, opened before rank 0 got to it)
-        struct stat sb;
-        if (fstat(h->host_seg_fd, &sb) != 0 || sb.st_nlink == 0) {
-            set_error("rank %d mapped a stale shared-memory segment under %s (a crashed run's): the self test fails, use another transport or name", h->peer.rank, h->host_seg_name.c_str());
-            *ok = 0;
-            return FOS_OK;
-        }
-    }
-    if (h->host_seg) {
-        // host-pinned mailboxes: do ranks share THIS device (tests: several ranks on one GPU)?  Every rank left its device's identity behind the
-        // mailbox words when it opened the segment, and the caller's barrier stands between the opens and this call.  A shared device keeps the
-        // PSD refinement kernel to small batches (it needs whole CUs, which a peer's spinning CG kernel may hold: DESIGN 3)
-        const volatile unsigned long long* ids = reinterpret_cast<const volatile unsigned long long*>(static_cast<const char*>(h->host_seg) + h->host_seg_bytes - 4096);
-        for (int r = 0; r < h->peer.nranks; ++r)
-            if (r != h->peer.rank && ids[r] != 0ull && ids[r] == ids[h->peer.rank]) h->peer_same_device = true;
-    }
-    const bool was_on = h->peer_on;
-    h->peer_on = true;
-    LaunchCtx c = h->ctx();
-    h->peer_on = was_on;
-    *ok = 1;
-    auto val = [](int r, int k, int a) { return (a == 0) ? (double)(r + 1) * (k + 1) : (a == 1 ? 0.1 * (r + 1) + 1e-3 * k : -1.0 / (r + 1 + k)); };
-    for (int k = 0; k < rounds && *ok; ++k) {
-        const int nacc = (k % 3 == 0) ? 3 : (k % 3 == 1 ? 1 : 6);
-        double loc[6], got[6];
-        for (int a = 0; a < nacc; ++a) loc[a] = val(h->peer.rank, k, a % 3) + a;
-        FOS_HIP(hipMemcpyAsync(h->partials, loc, sizeof(double) * nacc, hipMemcpyHostToDevice, h->stream));
-        launch_reduce1(c, 1, nacc, 0);
-        FOS_HIP(hipMemcpyAsync(got, h->reduced, sizeof(double) * nacc, hipMemcpyDeviceToHost, h->stream));
-        FOS_HIP(hipMemcpyAsync(h->st_host, h->st, sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
-        FOS_HIP(hipStreamSynchronize(h->stream));
-        if (h->st_host->xchg_failed) { *ok = 0; break; }
-        for (int a = 0; a < nacc; ++a) {
-            double s = 0.0;
-            for (int r = 0; r < h->peer.nranks; ++r) s += val(r, k, a % 3) + a;
-            if (s != got[a]) *ok = 0;
-        }
-    }
-    if (h->st_host->xchg_failed) {              // leave the handle usable with its previous reduction
-        DevState z;
-        FOS_HIP(hipMemcpy(&z, h->st, sizeof(DevState), hipMemcpyDeviceToHost));
-        z.xchg_failed = 0; z.done = 0;
-        FOS_HIP(hipMemcpy(h->st, &z, sizeof(DevState), hipMemcpyHostToDevice));
-        h->st_host->xchg_failed = 0;
-    }
-    return FOS_OK;
-}
-
-// What ONE exchange of four doubles costs on the transport this sharded handle uses -- `rounds` of them back to back, in stream, between two events:
-// mailboxes: inside one launch (no launch or host round trip between them); RCCL: `rounds` ncclAllReduce calls.  Collective (every rank, same rounds).
-int fos_exchange_bench(fos_handle h, int rounds, double* us_per_exchange) {
-    if (!h || !us_per_exchange || rounds < 1) { set_error("bad argument"); return FOS_EINVAL; }
-    *us_per_exchange = 0.0;
-    if (!h->sharded() || h->host_fn) { set_error("fos_exchange_bench: the handle has no in-stream transport (mailboxes or RCCL)"); return FOS_EUNSUPPORTED; }
-    FOS_HIP(hipSetDevice(h->device));
-    LaunchCtx c = h->ctx();
-    hipEvent_t e0, e1;
-    FOS_HIP(hipEventCreate(&e0));
-    FOS_HIP(hipEventCreate(&e1));
-    auto run = [&](int n) -> int {
-        if (h->peer_on) { launch_peer_chain(c, n); return FOS_OK; }
-        for (int r = 0; r < n; ++r) FOS_TRY(allreduce(h, 4));
-        return FOS_OK;
-    };
-    int rc = run(4);                                     // warm
-    if (rc == FOS_OK) rc = hipEventRecord(e0, h->stream) == hipSuccess ? FOS_OK : FOS_EHIP;
-    if (rc == FOS_OK) rc = run(rounds);
-    if (rc == FOS_OK) rc = hipEventRecord(e1, h->stream) == hipSuccess ? FOS_OK : FOS_EHIP;
-    if (rc == FOS_OK) rc = poll_state(h);
-    float ms = 0.f;
-    if (rc == FOS_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = FOS_EHIP;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (rc != FOS_OK) return rc;
-    *us_per_exchange = 1e3 * (double)ms / (double)rounds;
-    return FOS_OK;
-}
-
-// Row-sharded handles: the exchange buffer of the n-vector A'y (fos_internal.hpp, VecBox).  Protocol as for the mailboxes, after
-// fos_peer_open (which fixes nranks): fos_peer_vec_export -> the host all-gathers the 64-byte handles -> fos_peer_vec_open.
-int fos_peer_vec_export(fos_handle h, void* handle64) {
-    if (!h || !handle64) { set_error("NULL argument"); return FOS_EINVAL; }
-    if (!h->row_sharded) { set_error("fos_peer_vec_export: not a row-sharded handle"); return FOS_EINVAL; }
-    if (!h->peer.box) { set_error("fos_peer_vec_export before fos_peer_open"); return FOS_EINVAL; }
-    FOS_HIP(hipSetDevice(h->device));
-    if (!h->vec_buf) {
-        const int g = h->peer.nranks;
-        const size_t doubles = (size_t)2 * g * 2 * (size_t)h->n;
-        const size_t bytes = doubles * sizeof(double) + (size_t)4 * g * sizeof(uint32_t) + 64;       // flags: [stage 1 | stage 2][parity][rank]
-        void* q = nullptr;
-        FOS_TRY(uncached_acquire(h->device, bytes, false, &q, "vector exchange buffer"));
-        h->pooled.push_back(q);
-        FOS_HIP(hipMemset(q, 0, bytes));                         // exchange number 0 is never sent
-        h->vec_buf = reinterpret_cast<double*>(q);
-        h->vec_nranks = g;
-    }
-    hipIpcMemHandle_t ipc;
-    FOS_HIP(hipIpcGetMemHandle(&ipc, h->vec_buf));
-    memcpy(handle64, &ipc, sizeof(ipc));
-    return FOS_OK;
-}
-int fos_peer_vec_open(fos_handle h, const void* handles) {
-    if (!h || !handles) { set_error("NULL argument"); return FOS_EINVAL; }
-    if (!h->vec_buf || !h->peer.box) { set_error("fos_peer_vec_open before fos_peer_vec_export"); return FOS_EINVAL; }
-    if (!h->vec_opened.empty() || h->vec.buf) { set_error("the vector exchange buffers are already open"); return FOS_EINVAL; }
-    FOS_HIP(hipSetDevice(h->device));
-    const int g = h->peer.nranks, me = h->peer.rank;
-    const size_t doubles = (size_t)2 * g * 2 * (size_t)h->n;
-    std::vector<double*> bt((size_t)g, nullptr);
-    std::vector<uint32_t*> ft((size_t)g, nullptr);
-    for (int r = 0; r < g; ++r) {
-        void* q = h->vec_buf;
-        if (r != me) {
-            hipIpcMemHandle_t ipc;
-            memcpy(&ipc, (const char*)handles + (size_t)r * sizeof(ipc), sizeof(ipc));
-            hipError_t e = hipIpcOpenMemHandle(&q, ipc, hipIpcMemLazyEnablePeerAccess);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                for (void* o : h->vec_opened) (void)hipIpcCloseMemHandle(o);
-                h->vec_opened.clear();
-                set_error("hipIpcOpenMemHandle(vector exchange buffer of rank %d): %s", r, hipGetErrorString(e));
-                return FOS_ECOMM;
-            }
-            h->vec_opened.push_back(q);
-        }
-        bt[r] = reinterpret_cast<double*>(q);
-        ft[r] = reinterpret_cast<uint32_t*>(reinterpret_cast<double*>(q) + doubles);
-    }
-    double** dbt = nullptr; uint32_t** dft = nullptr; uint32_t* cnt = nullptr;
-    FOS_TRY(dev_upload(h, &dbt, bt));
-    FOS_TRY(dev_upload(h, &dft, ft));
-    FOS_TRY(dev_alloc(h, &cnt, 1));
-    FOS_HIP(hipMemset(cnt, 0, sizeof(uint32_t)));
-    h->vec.buf = dbt; h->vec.flags = dft; h->vec.counter = cnt; h->vec.nranks = g; h->vec.rank = me;
-    h->vec.n2 = 2 * h->n; h->vec.timeout_ticks = h->peer.timeout_ticks;
-    return FOS_OK;
-}
-
-// switch the sharded sums to the peer mailboxes (collective: all ranks make the same choice after the self test)
-int fos_peer_enable(fos_handle h, int32_t on) {
-    if (!h) { set_error("NULL handle"); return FOS_EINVAL; }
-    if (on && !h->peer.box) { set_error("fos_peer_enable before fos_peer_open"); return FOS_EINVAL; }
-    if (on && h->row_sharded && !h->vec.buf) { set_error("row-sharded handle: fos_peer_vec_export / fos_peer_vec_open before fos_peer_enable"); return FOS_EINVAL; }
-    if (on && (h->ls_interval > 0 || h->gapp_iproj > 0)) { set_error("switch the LineSearchWrapper / GAPP off before sharding the handle (fos_set_linesearch(h, 0), fos_set_gapp(h, 0))"); return FOS_EUNSUPPORTED; }
-    FOS_HIP(hipSetDevice(h->device));
-    FOS_HIP(hipStreamSynchronize(h->stream));
-    h->peer_on = on != 0;
-    if (h->sharded()) return global_setup(h);
-    h->l_global = h->l; h->nb = h->nb_local; h->nc = h->nc_local;
-    return resident_setup(h, h->cus);          // (the whole device is this handle's again)
 }
 
 int fos_set_alg(fos_handle h, int alg, double alpha, double alpha1, double alpha2, double beta) {
@@ -2687,7 +2193,7 @@ int fos_set_cg_variant(fos_handle h, int32_t variant) {
 // the variant the next affine projection will run (the default resolved: sharded handles take the merged recurrence)
 int fos_get_cg_variant(fos_handle h, int32_t* variant) {
     if (!h || !variant) { set_error("NULL argument"); return FOS_EINVAL; }
-    static const bool fold_env = !(getenv("FOS_PEER_FOLD") && atoi(getenv("FOS_PEER_FOLD")) == 0);
+    const bool fold_env = peer_fold_env();
     // default: the reference's recurrence -- except where a CG iteration is bound by its launches, not its bytes: sharded handles (one
     // exchange per iteration instead of two) and cache-resident gather-type operators of 32 768 rows or more (C3: two launches per iteration
     // instead of three, 370 -> 385 iterations/s; the streamed operators C2 / C4 / C5 are faster on the reference recurrence; small problems
@@ -2699,14 +2205,14 @@ int fos_get_cg_variant(fos_handle h, int32_t* variant) {
     // whose shards ALL qualify (FOS_RESIDENT_DEFAULT=0: never by default).  Sharded without mailboxes (RCCL, the caller's collective): a
     // collective call cannot sit inside a kernel -- the launch-per-iteration form of the same recurrence runs instead.
     const bool res_default = !(getenv("FOS_RESIDENT_DEFAULT") && atoi(getenv("FOS_RESIDENT_DEFAULT")) == 0);      // (read at every call: bench.py turns it off after a failed warm-up)
-    const bool res_usable = h->res_ok && !h->row_sharded && (!h->sharded() || (h->peer_on && fold_env && h->res_all));
+    const bool res_usable = h->res_ok && !h->row_sharded && (!h->sharded() || (h->tr.peer_on && fold_env && h->res_all));
     if (h->cg_variant < 0 && !h->fuse_p && h->sharded() && res_usable && res_default) v = FOS_CG_RESIDENT;
     // one GPU: the STREAMED form where it fills at least half of the chip (C4: 66.3 us per CG iteration against 89 for three launches); operators
     // small enough for the register form keep the reference's arithmetic by default
     if (h->cg_variant < 0 && !h->fuse_p && !h->sharded() && res_usable && res_default && h->res_plan.stream && 2 * h->res_plan.G >= h->cus) v = FOS_CG_RESIDENT;
     if (v == FOS_CG_RESIDENT && !res_usable) v = FOS_CG_MERGED_UPDATE;
     if (v == FOS_CG_MERGED_SWEEP && h->sharded()) v = FOS_CG_MERGED_UPDATE;
-    if (v == FOS_CG_MERGED_UPDATE && h->peer_on && !fold_env) v = FOS_CG_REFERENCE;
+    if (v == FOS_CG_MERGED_UPDATE && h->tr.peer_on && !fold_env) v = FOS_CG_REFERENCE;
     *variant = v;
     return FOS_OK;
 }
