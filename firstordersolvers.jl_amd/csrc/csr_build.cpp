@@ -1095,18 +1095,35 @@ bool build_resident_plan(const HostBlkCsr& S, int64_t m, int64_t n, int gmax, Re
                 tiles_max = std::max(tiles_max, tb - ta);
             }
         }
-        // tiles per compute wavefront: the kernel instance is chosen for the deal in which the communication wavefront walks min(nblk % 7, 3)
-        // tiles -- never fewer tiles per compute wavefront than the table (rs_deal, fos_internal.hpp) hands out: the table only moves tiles
-        // from the compute wavefronts to the communication wavefront
+        // the deal of every workgroup's tiles to its eight wavefronts (rs_deal, fos_internal.hpp).  Timing experiments, read once per process:
+        // FOS_RS_NTC -- the communication wavefront's share; FOS_RS_DEAL -- the whole table, eight hex digits, compute wavefronts 0 .. 6 and then the
+        // communication wavefront: refused unless it deals every workgroup's tiles exactly once within what the kernels hold (rs_deal_ok)
+        static const int ntc_exp = getenv("FOS_RS_NTC") ? std::max(0, atoi(getenv("FOS_RS_NTC"))) : RS_NTC;
+        static const std::string deal_exp = getenv("FOS_RS_DEAL") ? getenv("FOS_RS_DEAL") : "";
+        if (!deal_exp.empty()) {
+            int cnt[RS_NCOMP + 1];
+            bool ok = deal_exp.size() == RS_NCOMP + 1;
+            for (int w = 0; ok && w <= RS_NCOMP; ++w) {
+                const char ch = deal_exp[(size_t)w];
+                cnt[w] = ch >= '0' && ch <= '9' ? ch - '0' : (ch >= 'a' && ch <= 'f' ? ch - 'a' + 10 : (ch >= 'A' && ch <= 'F' ? ch - 'A' + 10 : -1));
+                ok = cnt[w] >= 0;
+            }
+            if (!ok) return no("FOS_RS_DEAL is not eight hex digits (streamed form)");
+            for (ResWG& w : wgs) {
+                w.T = (int32_t)rs_pack(cnt);
+                if (!rs_deal_ok((uint32_t)w.T, w.nblk, nt_cap, rs_ntc(tmax))) return no("FOS_RS_DEAL does not deal a workgroup's tiles within the kernels' limits (streamed form)");
+            }
+        } else
+            for (ResWG& w : wgs) w.T = (int32_t)rs_deal(w.nblk, std::min(ntc_exp, rs_ntc(tmax)));
+        // tiles per compute wavefront: the kernel instance is chosen for the heaviest compute wavefront of any workgroup's table -- and never a smaller
+        // one than the deal in which the communication wavefront walks min(nblk % 7, 3) tiles asks for (the instance every plan has had so far: a table
+        // that only moves tiles to the communication wavefront stays below it, one that hands a compute wavefront more does not)
         int nt = 0;
         for (const ResWG& w : wgs) {
             const int per = w.nblk / RS_NCOMP, r = w.nblk % RS_NCOMP, kc = std::min(r, RS_NTC_BASE);
-            nt = std::max(nt, per + (r - kc > 0 ? 1 : 0));
+            nt = std::max({nt, per + (r - kc > 0 ? 1 : 0), rs_deal_nt((uint32_t)w.T)});
         }
         if (nt > nt_cap) return no(why_not_registers);
-        // the deal of every workgroup's tiles to its eight wavefronts (FOS_RS_NTC: timing experiments -- the communication wavefront's share; read once per process)
-        static const int ntc_exp = getenv("FOS_RS_NTC") ? std::max(0, atoi(getenv("FOS_RS_NTC"))) : RS_NTC;
-        for (ResWG& w : wgs) w.T = (int32_t)rs_deal(w.nblk, std::min(ntc_exp, rs_ntc(tmax)));
         // what the kernel can index: a tile is walked in whole groups of 8 steps, each pass of 32 steps from its unit's offset in the workgroup's
         // <= 64 columns (rs_sweep: s_gcol[64] and the wavefront's 64 column sums) -- a unit that starts late in the workgroup and ends on a ragged
         // group would read past the column elements and add into the next wavefront's column sums

@@ -453,20 +453,46 @@ constexpr int RS_NTC_BASE = 3;
 constexpr int RS_COMM_LEAD = 2;
 // (tiles of more than 32 steps are walked in two passes each: their kernels keep the communication wavefront's three)
 inline int rs_ntc(int tmax) { return tmax > 32 ? RS_NTC_BASE : RS_NTC; }
-inline uint32_t rs_deal(int nblk, int ntc = RS_NTC) {
-    int kc = std::min(nblk % RS_NCOMP, RS_NTC_BASE);
-    for (int k = std::min(ntc, RS_NTC); k > kc; --k)
-        if (k <= (nblk - k + RS_NCOMP - 1) / RS_NCOMP - RS_COMM_LEAD) { kc = k; break; }
-    const int per = (nblk - kc) / RS_NCOMP, rem = (nblk - kc) % RS_NCOMP;
-    uint32_t deal = (uint32_t)kc << (4 * RS_NCOMP);
-    for (int w = 0; w < RS_NCOMP; ++w) deal |= (uint32_t)(per + (w < rem ? 1 : 0)) << (4 * w);      // (at most 10 tiles per wavefront: four bits)
-    return deal;
-}
 // which tiles of its workgroup wavefront w walks (w < RS_NCOMP: compute; w == RS_NCOMP: the communication wavefront, the LAST tiles)
 __host__ __device__ inline void rs_split(uint32_t deal, int w, int& t0, int& cnt) {
     t0 = 0;
     for (int k = 0; k < w; ++k) t0 += (int)((deal >> (4 * k)) & 15u);
     cnt = (int)((deal >> (4 * w)) & 15u);
+}
+inline uint32_t rs_pack(const int (&cnt)[RS_NCOMP + 1]) {
+    uint32_t deal = 0;
+    for (int w = 0; w <= RS_NCOMP; ++w) deal |= (uint32_t)cnt[w] << (4 * w);       // (at most 10 tiles per wavefront: four bits)
+    return deal;
+}
+inline uint32_t rs_deal(int nblk, int ntc = RS_NTC) {
+    int kc = std::min(nblk % RS_NCOMP, RS_NTC_BASE);
+    for (int k = std::min(ntc, RS_NTC); k > kc; --k)
+        if (k <= (nblk - k + RS_NCOMP - 1) / RS_NCOMP - RS_COMM_LEAD) { kc = k; break; }
+    const int per = (nblk - kc) / RS_NCOMP, rem = (nblk - kc) % RS_NCOMP;
+    int cnt[RS_NCOMP + 1];
+    for (int w = 0; w < RS_NCOMP; ++w) cnt[w] = per + (w < rem ? 1 : 0);
+    cnt[RS_NCOMP] = kc;
+    return rs_pack(cnt);
+}
+// what the kernels ask of ANY table for a workgroup of nblk tiles (the planner checks a forced one, FOS_RS_DEAL, against it): every tile dealt once, at
+// most nt_cap per compute wavefront and ntc for the communication wavefront, and no compute wavefront with tiles behind one without (slots = tiles)
+inline bool rs_deal_ok(uint32_t deal, int nblk, int nt_cap, int ntc) {
+    int sum = 0;
+    bool gap = false;
+    for (int w = 0, t0, cnt; w <= RS_NCOMP; ++w) {
+        rs_split(deal, w, t0, cnt);
+        if (cnt > (w < RS_NCOMP ? nt_cap : ntc)) return false;
+        if (w < RS_NCOMP && cnt > 0 && gap) return false;
+        if (cnt == 0) gap = true;
+        sum += cnt;
+    }
+    return sum == nblk;
+}
+// the heaviest compute wavefront of a table: what the kernel instance's NT must hold
+inline int rs_deal_nt(uint32_t deal) {
+    int nt = 0;
+    for (int w = 0, t0, cnt; w < RS_NCOMP; ++w) { rs_split(deal, w, t0, cnt); nt = std::max(nt, cnt); }
+    return nt;
 }
 // LDS of a launch (one function for the planner and the launch): the dynamic bytes of cg_stream_kernel for a workgroup of `tiles` tiles -- the wavefronts'
 // column sums, the G records, the other workgroups' column sums, the rows' p and s -- and of cg_resident_kernel<TMAX = tmax, NSLOT = nslot>; the planner adds

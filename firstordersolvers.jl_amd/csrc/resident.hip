@@ -106,6 +106,7 @@ __device__ __forceinline__ void res_tile(const double (&val)[TMAX], int T, const
 
 // In-kernel time stamps of the resident solve (timing experiments; -DFOS_RES_STAMPS, tools/res_stamps.py): workgroups 0, 1, G / 2, G - 1; the first lane of
 // every wavefront wv; iteration it (0: the start), phase ph < 16 -> g_res_stamps[((slot * 16 + wv) * 64 + it) * 16 + ph], ticks of the shader clock.
+// (records 62 and 63 of a wavefront: the calibration pairs of exit and entry in phases 6, 7; the streamed kernel also leaves its hardware id in [63][5])
 #ifdef FOS_RES_STAMPS
 __device__ long long g_res_stamps[4 * 16 * 64 * 16];
 // (s_memtime -- the shader clock -- not the 100 MHz s_memrealtime of wall_clock64(): the latter takes long enough to return that two stamps in a row
@@ -734,7 +735,8 @@ __device__ __forceinline__ void rs_group(const ResArgs& a, int bf, int cnt, int 
 #endif
 template <int TMAX, int NT>
 __device__ __forceinline__ void rs_sweep(const ResArgs& a, int blk_first, int cnt, int c0, int lane, const d2* __restrict__ s_gcol, const double* s_ctl,
-                                         d2* __restrict__ mycol, RsRows<NT>& R, double (&acc)[4], bool early = false) {
+                                         d2* __restrict__ mycol, RsRows<NT>& R, double (&acc)[4], bool early = false,
+                                         const double* __restrict__ cbh = nullptr) {
     constexpr int D = NT < RS_RING ? NT : RS_RING;
     // (early: an exchange round that carries r.r alone -- no tile is walked, the other three sums are zero)
     if (early) cnt = 0;
@@ -757,12 +759,13 @@ __device__ __forceinline__ void rs_sweep(const ResArgs& a, int blk_first, int cn
             asm volatile("" : "+s"(bf));           // (opaque per group: the descriptor loads stay in the loop, see above)
             rs_group<0, NT, D>(a, bf, cnt, grp, c0, lane, s_gcol, mycol, R, val, a1, a2);
         }
-        // the rows' epilogue: [c; b] of all tiles requested together
+        // the rows' epilogue: [c; b] from the caller's registers (cbh), or of all tiles requested together
         double cb[NT];
 #pragma unroll
         for (int q = 0; q < NT; ++q) {
             cb[q] = 0.0;
-            if (q < cnt) {
+            if (cbh) cb[q] = cbh[q];
+            else if (q < cnt) {
                 const BlkDesc d = rs_desc(a.blk, blk_first + q);
                 if (lane < d.nrows()) cb[q] = a.cb[d.row0 + lane];
             }
@@ -909,6 +912,10 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
     if (a.pb.nranks > 0 && st->xchg_failed) return;
     if (tid == 0) { s_cnt = 0; s_failed = 0; }
     RES_STAMP_CAL(63);
+#ifdef FOS_RES_STAMPS
+    // (which SIMD the wavefront runs on: the hardware id register, bits 5:4 -- read once, beside the calibration pair)
+    if (stamp_slot >= 0 && lane == 0) g_res_stamps[((size_t)stamp_slot * 64 + 63) * 16 + 5] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);
+#endif
     int t0, cnt;
     rs_split((uint32_t)me.T, wv, t0, cnt);                      // (compute wavefronts: cnt <= NT, the communication wavefront: cnt <= RS_NTC -- the plan's promise)
 
@@ -916,6 +923,19 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
         // =========================================================== COMPUTE wavefronts: their tiles streamed once per iteration
         RsRows<NT> R;
         rs_rows_load<NT>(a, me.blk0 + t0, cnt, lane, R);
+        // [c; b] of the wavefront's rows does not change during a solve: read once and HELD, not requested behind every sweep -- there the rows' epilogue
+        // waited for a memory round trip with nothing else in flight, on every wavefront of the chip, 18 times per solve.  One register pair per tile:
+        // <32, 9> has them (235 -> 252 VGPRs); <32, 10> sits at 250 of 256 and keeps reading them in the sweep, as the communication wavefront does
+        constexpr bool HOLD_CB = NT <= 9;
+        double cbh[NT];
+#pragma unroll
+        for (int q = 0; q < NT; ++q) {
+            cbh[q] = 0.0;
+            if (HOLD_CB && q < cnt) {
+                const BlkDesc d = rs_desc(a.blk, me.blk0 + t0 + q);
+                if (lane < d.nrows()) cbh[q] = a.cb[d.row0 + lane];
+            }
+        }
         d2* const mycol = s_colpart + wv * 64;
         __syncthreads();                                   // (0) the communication wavefront has staged the v columns and the tau element
         RES_STAMP(0);
@@ -925,7 +945,7 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
         bool early = false;
         for (int i = -1, xr = 0;; ++xr) {
             double acc[4];
-            rs_sweep<TMAX, NT>(a, me.blk0 + t0, cnt, c0, lane, s_gcol, s_ctl, mycol, R, acc, early);
+            rs_sweep<TMAX, NT>(a, me.blk0 + t0, cnt, c0, lane, s_gcol, s_ctl, mycol, R, acc, early, HOLD_CB ? cbh : nullptr);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const double v = wave_sum(acc[k]);
@@ -999,6 +1019,7 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
                 if (lane == 0) s_red[ncomp][k] = v;
             }
         }
+        RES_STAMP(14);                                          // swept (the compute wavefronts' stamp 1)
         __syncthreads();                                       // (A)
         RES_STAMP(1);
         d2 cp = make_double2(0.0, 0.0);

@@ -44,6 +44,8 @@ tops = [st[0, 0, k, 0] for k in range(62) if st[0, 0, k, 0] > 0]
 if e0 > 0 and e1 > e0 and tops:
     print("workgroup 0, compute wavefront 0: kernel entry -> first sweep %.2f us (tiles and vectors -> registers / LDS), %d exchanges in %.2f us, last loop top -> exit %.2f us; entry -> exit %.2f us"
           % ((tops[0] - e0) / rate, len(tops), (tops[-1] - tops[0]) / rate, (e1 - tops[-1]) / rate, (e1 - e0) / rate))
+# which SIMD a wavefront runs on: the hardware id it read at entry (bits 5:4; 3:0 its slot there, 11:8 the CU), beside the calibration pair
+hwid = cal[:, :, 1, 5].astype(np.int64)
 st[:, :, 62:, :] = 0
 st = st / rate * 100.0                      # -> the unit the code below divides by 100
 t00 = st[st > 0].min()
@@ -55,6 +57,12 @@ for w, wn in enumerate(("wg 0", "wg 1", "wg G/2", "wg G-1")):
         t0w = min(tops)
         print("%s, iteration %d, per compute wavefront (loop top -> swept, us after the earliest top): " % (wn, it5) +
               "  ".join("w%d %.2f->%.2f" % (v, (st[w, v, it5, 0] - t0w) / 100.0, (st[w, v, it5, 1] - t0w) / 100.0) for v in range(ncomp) if st[w, v, it5, 0] > 0))
+        # the communication wavefront sweeps its own tiles in front of barrier A: stamp 14 is its "swept"
+        if st[w, ncomp, it5, 0] > 0 and st[w, ncomp, it5, 14] > 0:
+            print("%s, iteration %d, communication wavefront (loop top -> swept, same origin): w%d %.2f->%.2f; barrier A released at %.2f"
+                  % (wn, it5, ncomp, (st[w, ncomp, it5, 0] - t0w) / 100.0, (st[w, ncomp, it5, 14] - t0w) / 100.0, (st[w, ncomp, it5, 1] - t0w) / 100.0))
+        print("%s, SIMD of each wavefront (hardware id; wavefronts that share one compete for its issue slots): " % wn +
+              "  ".join("w%d simd %d" % (v, (hwid[w, v] >> 4) & 3) for v in range(ncomp + 1)) + "  (CU %d)" % ((hwid[w, 0] >> 8) & 15))
     for who, whn, names, last in ((0, "compute wave 0", cnames, 4), (ncomp, "comm wave 0", mnames, 7)):
         s = st[w, who]
         its = [k for k in range(64) if s[k, 0] > 0 and s[k, last] > 0]
