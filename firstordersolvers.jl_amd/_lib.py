@@ -107,6 +107,7 @@ PROTOTYPES = {
     "fos_bench_kkt": (C.c_int, [_h, C.c_int32, _dp]),
     "fos_psd_debug": (C.c_int, [_h, C.c_int32, C.c_int32]),
     "fos_psd_stats": (C.c_int, [_h, _i32p, C.c_int64, _i64p]),
+    "fos_psd_fused_steps": (C.c_int, [_h, _i64p]),
     "fos_sync": (C.c_int, [_h]),
     "fos_host_stacked_spmv": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _dp, _dp, _dp, C.c_int32, C.c_int32, _i64p]),
     "fos_host_resident_cg": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _dp, _dp, _dp, C.c_int32, _dp, _dp, C.c_double, C.c_int64, _i64p, _i64p]),

@@ -99,6 +99,9 @@ struct fos_solver {
     int psd_refine = -1;                       // FOS_PSD_REFINE
     bool psd_extrapolate = true;               // FOS_PSD_EXTRAPOLATE
     double psd_theta = 0.0;                    // FOS_PSD_THETA
+    bool psd_fuse = true;                      // FOS_PSD_FUSE=0: relaxation, projection and the step's last pass stay separate launches
+    bool relax_ew = true;                      // FOS_RELAX_EW=0: the relaxation does not project the elementwise cones in the same pass
+    int64_t psd_fused_steps = 0;               // steps taken through the fused launch (host count; fos_psd_fused_steps)
 
     // scalars
     fos::DevState* st = nullptr;

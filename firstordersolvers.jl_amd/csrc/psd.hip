@@ -822,8 +822,10 @@ __global__ __launch_bounds__(64) void psd64_wave_kernel(d2* __restrict__ out, co
 // slow path through LDS; couplings below the rounding level of the products (RF_NOISE ||M||_F) are left alone whatever the gap
 // (a cluster is an invariant subspace: any basis of it gives the same projection).  A matrix that needs more than RF_MAX_ROT
 // rotations or RF_MAX_IT iterations (a cold basis, a jump of the iterate, a cluster split by the change) is FLAGGED (record 1) and
-// left to the Jacobi kernel, which the launcher runs behind this one for the flagged matrices only, from a cold start.  Record 2:
-// accepted, but columns were rotated -- the next call must not extrapolate across that.
+// projected by the Jacobi code (psd_block) in the SAME workgroup and the same LDS, from a cold start; inside a fused step that workgroup
+// first writes its t1 over the input vector and afterwards takes t2 on to the step's last pass.  The next call starts such a matrix from
+// the Jacobi basis without extrapolation; columns that were rotated in an accepted call (the column mask kept beside the record) are not
+// extrapolated in the next one either.
 // One workgroup of four wavefronts per matrix; wavefront w owns the 16-column block w of every product (operand and result
 // layouts of v_mfma_f64_16x16x4_f64 chain without data movement: a result tile IS the B operand of the next product); M and V
 // live in LDS (leading dimension 66; the rotation path borrows M's array and unpacks M again afterwards).

@@ -812,13 +812,14 @@ int long_finish(fos_solver* h, int64_t i) {
 // suffice the gated launches were no-ops: the host-side state they advanced is rolled back and `post` runs again, ungated.
 int affine_then(fos_solver* h, const LaunchCtx& c, const d2* in, const PostFn& post) {
     const int psd_cur = h->psd_cur, psd_have_prev = h->psd_have_prev;
+    const int64_t psd_fused_steps = h->psd_fused_steps;
     const size_t prof_used = h->prof_used;
     const int64_t psd_seen = h->prof_seen[FOS_PROF_PSD];
     const double fista_t = h->fista_t;
     bool ran = false;
     FOS_TRY(prox_affine(h, in, &post, &ran));
     if (!ran) {
-        h->psd_cur = psd_cur; h->psd_have_prev = psd_have_prev; h->prof_seen[FOS_PROF_PSD] = psd_seen; h->fista_t = fista_t;
+        h->psd_cur = psd_cur; h->psd_have_prev = psd_have_prev; h->psd_fused_steps = psd_fused_steps; h->prof_seen[FOS_PROF_PSD] = psd_seen; h->fista_t = fista_t;
         // (event pairs recorded around no-op launches: forget them; the CG records of this solve stay)
         for (size_t k = prof_used; k < h->prof_used; ++k)
             if (h->prof_recs[k].cls == FOS_PROF_PSD || (h->prof_recs[k].cls == FOS_PROF_OTHER && h->prof_recs[k].j == 1)) h->prof_recs[k].cls = -1;
@@ -848,8 +849,7 @@ int step_once(fos_solver* h, int64_t i, const d2** check_on, bool will_check, bo
             // gated, so that the GPU does not wait for the host to learn the iteration count
             const bool gapa = h->alg == FOS_ALG_GAPA;
             const PostFn post = [h, gapa, will_check](const LaunchCtx& cg) -> int {
-                static const bool fuse_ew = !(getenv("FOS_RELAX_EW") && atoi(getenv("FOS_RELAX_EW")) == 0);
-                static const bool fuse_psd = !(getenv("FOS_PSD_FUSE") && atoi(getenv("FOS_PSD_FUSE")) == 0);
+                const bool fuse_ew = h->relax_ew, fuse_psd = h->psd_fuse;          // (per handle: read at fos_create)
                 // GAP / DR, no status check in this step, every non-elementwise cone a PSD(64) cone with a basis from the last projection:
                 // relaxation, projection and the step's last pass are ONE launch (PsdFuse, fos_internal.hpp)
                 if (fuse_psd && !gapa && !will_check && h->nsoc == 0 && h->nexp == 0 && !h->psd_big && !h->ls_interval && !h->gapp_iproj && !h->lp.interval &&
@@ -866,6 +866,7 @@ int step_once(fos_solver* h, int64_t i, const d2** check_on, bool will_check, bo
                                              h->psd_V[1 - h->psd_cur], h->psd_have_prev, h->psd_stats, 0, h->psd_redo, &fz));
                     prof_end(h, pe);
                     h->psd_cur = 1 - h->psd_cur; h->psd_have_prev = std::min(h->psd_have_prev + 1, 2);
+                    h->psd_fused_steps += 1;
                     h->shift_ready = sh;
                     return check_launch("fused relaxation + PSD projection + final pass");
                 }
@@ -1222,6 +1223,8 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     if (const char* e = getenv("FOS_PSD_REFINE")) h->psd_refine = atoi(e);
     if (const char* e = getenv("FOS_PSD_EXTRAPOLATE")) h->psd_extrapolate = atoi(e) != 0;
     if (const char* e = getenv("FOS_PSD_THETA")) h->psd_theta = atof(e);
+    h->psd_fuse = !(getenv("FOS_PSD_FUSE") && atoi(getenv("FOS_PSD_FUSE")) == 0);
+    h->relax_ew = !(getenv("FOS_RELAX_EW") && atoi(getenv("FOS_RELAX_EW")) == 0);
     h->psd_narrow = getenv("FOS_PSD_NARROW") != nullptr;
     h->psd_wide = getenv("FOS_PSD_WIDE") != nullptr;
     if (const char* e = getenv("FOS_PSD_THREADS")) h->psd_wide_threads = atoi(e);
@@ -1956,6 +1959,12 @@ int fos_psd_stats(fos_handle h, int32_t* sweeps, int64_t cap, int64_t* count) {
         FOS_HIP(hipStreamSynchronize(h->stream));
         FOS_HIP(hipMemcpy(sweeps, h->psd_stats, sizeof(int32_t) * (size_t)std::min<int64_t>(cap, *count), hipMemcpyDeviceToHost));
     }
+    return FOS_OK;
+}
+
+int fos_psd_fused_steps(fos_handle h, int64_t* count) {
+    if (!h || !count) { set_error("NULL argument"); return FOS_EINVAL; }
+    *count = h->psd_fused_steps;
     return FOS_OK;
 }
 

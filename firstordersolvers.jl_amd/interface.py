@@ -515,6 +515,12 @@ class HipHSDE:
         _lib.check(self._lib.fos_psd_stats(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), n.value, C.byref(n)))
         return out[:n.value]
 
+    def psd_fused_steps(self):
+        """Steps taken so far with relaxation, PSD(64) projection and the step's last pass in one launch (fos_psd_fused_steps)."""
+        v = C.c_int64(0)
+        _lib.check(self._lib.fos_psd_fused_steps(self._h, C.byref(v)))
+        return v.value
+
     def bench_cg_chain(self, iters, reps=5, use_graph=False):
         """ms per CG iteration of a chain that never converges (fos_bench_cg_chain)."""
         ms = C.c_double(0)

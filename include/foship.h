@@ -378,6 +378,9 @@ int fos_bench_kkt(fos_handle h, int32_t reps, double* total_ms);
  * the kernel after load+shift / warm-start product / sweeps / weights+basis -- results are then WRONG, timing use only. */
 int fos_psd_debug(fos_handle h, int32_t collect_stats, int32_t phase_limit);
 int fos_psd_stats(fos_handle h, int32_t* sweeps, int64_t cap, int64_t* count);
+/* *count: the steps this handle has taken with relaxation, PSD(64) projection and the step's last pass in ONE launch (GAP / DR / AP,
+ * no status check in the step; FOS_PSD_FUSE=0 at fos_create switches the launch off).  A host-side count: no synchronisation. */
+int fos_psd_fused_steps(fos_handle h, int64_t* count);
 int fos_sync(fos_handle h);
 
 /* Host-only self check of the device operator format (no GPU needed): builds the block format of
