@@ -131,6 +131,10 @@ PROTOTYPES = {
     "fos_feas_affine_factored_stats": (C.c_int, [_h, C.c_int32, _dp]),
     "fos_feas_affine_factored_plan": (C.c_int, [_h, C.c_int32, _i64p]),
     "fos_host_affine_factored": (C.c_int, [C.c_int64, C.c_int64, _dp, _dp, C.c_int32, _dp, _dp]),
+    "fos_feas_set_affine_sparse_factored": (C.c_int, [_h, C.c_int32, C.c_int64, _i64p, _i64p, _dp, _dp, C.c_int32, C.c_int32]),
+    "fos_feas_affine_sparse_factored_stats": (C.c_int, [_h, C.c_int32, _dp]),
+    "fos_feas_affine_sparse_factored_plan": (C.c_int, [_h, C.c_int32, _i64p]),
+    "fos_host_affine_sparse_factored": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _dp, _dp, C.c_int32, _dp, _dp]),
     "fos_feas_set_box": (C.c_int, [_h, C.c_int32, C.c_double, C.c_double]),
     "fos_feas_set_box_arrays": (C.c_int, [_h, C.c_int32, _dp, _dp]),
     "fos_feas_set_cones": (C.c_int, [_h, C.c_int32, C.c_int64, _i32p, _i64p]),

@@ -275,6 +275,11 @@ int dense_affine_setup(int64_t m, int64_t n, const double* A, const double* b, i
     return FOS_OK;
 }
 
+// the m-space product for the factored forms (this file and affine_sparse_factored.hip)
+void launch_da_symv(hipStream_t s, int64_t l, int64_t ld, const double* M, const double* v, const double* add, double sign, double* out) {
+    hipLaunchKernelGGL(da_symv_kernel, dim3((unsigned)((l + DA_T / 64 - 1) / (DA_T / 64))), dim3(DA_T), 0, s, l, ld, M, v, add, sign, out);
+}
+
 namespace {
 // r = A v - b
 void da_residual(const DenseAffine* a, hipStream_t s, const double* v) {
@@ -286,7 +291,7 @@ void da_residual(const DenseAffine* a, hipStream_t s, const double* v) {
                        (const double*)a->b, a->r);
 }
 void da_symv(const DenseAffine* a, hipStream_t s, const double* M, const double* v, const double* add, double sign, double* out) {
-    hipLaunchKernelGGL(da_symv_kernel, dim3((unsigned)((a->m + DA_T / 64 - 1) / (DA_T / 64))), dim3(DA_T), 0, s, a->m, a->p.Lm, M, v, add, sign, out);
+    launch_da_symv(s, a->m, a->p.Lm, M, v, add, sign, out);
 }
 // y = x - A'd
 void da_correct(const DenseAffine* a, hipStream_t s, double* y, const double* x) {
@@ -347,6 +352,33 @@ void da_host_symv(int64_t l, int64_t ld, const double* M, const double* v, const
 }
 }  // namespace
 
+void host_da_symv(int64_t l, int64_t ld, const double* M, const double* v, const double* add, double sign, double* out) { da_host_symv(l, ld, M, v, add, sign, out); }
+double host_da_wave(const double* lane64) {
+    double lane[64];
+    for (int i = 0; i < 64; ++i) lane[i] = lane64[i];
+    return da_host_wave(lane);
+}
+// X = G^-1 by host_chol_inverse (G, X: order m, column-major), accepted by the probe of dense_spd_inverse at DA_BAR, evaluated on the host
+int host_da_inverse(const char* what, int64_t m, const double* G, double* X) {
+    const int64_t bad = host_chol_inverse(m, G, X);
+    double probe = bad >= 0 ? INFINITY : 0.0;
+    std::vector<double> v((size_t)m), w((size_t)m), u((size_t)m);
+    for (int j = 0; j < 4 && bad < 0; ++j) {
+        direct_test_vector(m, j, v);
+        da_host_symv(m, m, X, v.data(), nullptr, 1.0, w.data());
+        da_host_symv(m, m, G, w.data(), nullptr, 1.0, u.data());
+        double dmax = 0.0, nv = 0.0;
+        for (int64_t i = 0; i < m; ++i) { const double e = std::fabs(u[(size_t)i] - v[(size_t)i]); dmax = (e > dmax || e != e) ? e : dmax; nv = std::max(nv, std::fabs(v[(size_t)i])); }
+        dmax /= nv;
+        probe = (dmax > probe || dmax != dmax) ? dmax : probe;
+    }
+    if (!(probe <= DA_BAR)) {
+        set_error("%s: the inverse of A A' (rows scaled to unit norm) was not accepted (probe residual %.3e): A needs full row rank", what, probe);
+        return FOS_EINVAL;
+    }
+    return FOS_OK;
+}
+
 // the same scaling, host_chol_inverse for X (accepted by the probe of dense_spd_inverse at DA_BAR, evaluated on the host), and the two passes with the split and
 // the summation order the kernels have for this (m, n) on a device of 256 CUs
 int host_affine_factored(int64_t m, int64_t n, const double* A, const double* b, int refine, const double* x, double* y) {
@@ -364,22 +396,7 @@ int host_affine_factored(int64_t m, int64_t n, const double* A, const double* b,
             for (int64_t k = 0; k < p.ld; ++k) s += As[(size_t)(i * p.ld + k)] * As[(size_t)(j * p.ld + k)];
             G[(size_t)(i + j * m)] = s; G[(size_t)(j + i * m)] = s;
         }
-    const int64_t bad = host_chol_inverse(m, G.data(), X.data());
-    double probe = bad >= 0 ? INFINITY : 0.0;
-    std::vector<double> v((size_t)m), w((size_t)m), u((size_t)m);
-    for (int j = 0; j < 4 && bad < 0; ++j) {
-        direct_test_vector(m, j, v);
-        da_host_symv(m, m, X.data(), v.data(), nullptr, 1.0, w.data());
-        da_host_symv(m, m, G.data(), w.data(), nullptr, 1.0, u.data());
-        double dmax = 0.0, nv = 0.0;
-        for (int64_t i = 0; i < m; ++i) { const double e = std::fabs(u[(size_t)i] - v[(size_t)i]); dmax = (e > dmax || e != e) ? e : dmax; nv = std::max(nv, std::fabs(v[(size_t)i])); }
-        dmax /= nv;
-        probe = (dmax > probe || dmax != dmax) ? dmax : probe;
-    }
-    if (!(probe <= DA_BAR)) {
-        set_error("IndAffine (factored): the inverse of A A' (rows scaled to unit norm) was not accepted (probe residual %.3e): A needs full row rank", probe);
-        return FOS_EINVAL;
-    }
+    FOS_TRY(host_da_inverse("IndAffine (factored)", m, G.data(), X.data()));
     std::vector<double> r((size_t)m), d((size_t)m), e((size_t)m), part((size_t)std::max(p.nspan, p.nrb));
     auto residual = [&](const double* vin) {                         // da_rows_kernel + da_rows_fold_kernel
         for (int64_t i = 0; i < m; ++i) {

@@ -197,35 +197,40 @@ void sparse_affine_destroy(SparseAffine* a) {
     delete a;
 }
 
-// A: m x n CSC, 1-based (Julia SparseMatrixCSC{Float64,Int64}); b[m].  Rows of [A | b] scaled to unit norm; A and A' to CSR; upload.
-int sparse_affine_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int cus, SparseAffine** out) {
-    if (m < 1 || n < 1 || !colptr || !rowval || !nzval || !b) { set_error("IndAffine (sparse): bad argument"); return FOS_EINVAL; }
-    if (colptr[0] != 1) { set_error("IndAffine (sparse): colptr must be 1-based (colptr[0] = %lld)", (long long)colptr[0]); return FOS_EINVAL; }
+// The host half of every sparse IndAffine set-up (this file and affine_sparse_factored.hip).  A: m x n CSC, 1-based (Julia SparseMatrixCSC{Float64,Int64}); b[m]:
+// validated, the rows of [A | b] scaled to unit norm, A and A' as two CSR matrices.  `what` names the caller in the messages.
+int sparse_affine_rows(const char* what, int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, SparseRows* out) {
+    if (m < 1 || n < 1 || !colptr || !rowval || !nzval || !b) { set_error("%s: bad argument", what); return FOS_EINVAL; }
+    if (colptr[0] != 1) { set_error("%s: colptr must be 1-based (colptr[0] = %lld)", what, (long long)colptr[0]); return FOS_EINVAL; }
     const int64_t nnz = colptr[n] - 1;
-    if (nnz < 1 || nnz > 2000000000LL) { set_error("IndAffine (sparse): %lld stored entries (1 .. 2e9 supported)", (long long)nnz); return FOS_EINVAL; }
+    if (nnz < 1 || nnz > 2000000000LL) { set_error("%s: %lld stored entries (1 .. 2e9 supported)", what, (long long)nnz); return FOS_EINVAL; }
     std::vector<double> rn2((size_t)m, 0.0);
     std::vector<int32_t> rcount((size_t)m + 1, 0);
     for (int64_t j = 0; j < n; ++j) {
-        if (colptr[j + 1] < colptr[j]) { set_error("IndAffine (sparse): colptr decreases at column %lld", (long long)j + 1); return FOS_EINVAL; }
+        if (colptr[j + 1] < colptr[j]) { set_error("%s: colptr decreases at column %lld", what, (long long)j + 1); return FOS_EINVAL; }
         for (int64_t e = colptr[j] - 1; e < colptr[j + 1] - 1; ++e) {
             const int64_t i = rowval[e] - 1;
             const double v = nzval[e];
-            if (i < 0 || i >= m) { set_error("IndAffine (sparse): row index %lld outside 1..%lld", (long long)rowval[e], (long long)m); return FOS_EINVAL; }
-            if (!(v == v) || std::fabs(v) > 1e300) { set_error("IndAffine (sparse): A has non-finite entries"); return FOS_EINVAL; }
+            if (i < 0 || i >= m) { set_error("%s: row index %lld outside 1..%lld", what, (long long)rowval[e], (long long)m); return FOS_EINVAL; }
+            if (!(v == v) || std::fabs(v) > 1e300) { set_error("%s: A has non-finite entries", what); return FOS_EINVAL; }
             rn2[(size_t)i] += v * v;
             rcount[(size_t)i + 1]++;
         }
     }
-    std::vector<double> scale((size_t)m), bs((size_t)m);
+    std::vector<double> scale((size_t)m);
+    std::vector<double>& bs = out->bs;
+    bs.resize((size_t)m);
     for (int64_t i = 0; i < m; ++i) {
-        if (!(rn2[(size_t)i] > 0.0)) { set_error("IndAffine (sparse): row %lld of A is zero (A must have full row rank)", (long long)i + 1); return FOS_EINVAL; }
-        if (!(b[i] == b[i]) || std::fabs(b[i]) > 1e300) { set_error("IndAffine (sparse): b has non-finite entries"); return FOS_EINVAL; }
+        if (!(rn2[(size_t)i] > 0.0)) { set_error("%s: row %lld of A is zero (A must have full row rank)", what, (long long)i + 1); return FOS_EINVAL; }
+        if (!(b[i] == b[i]) || std::fabs(b[i]) > 1e300) { set_error("%s: b has non-finite entries", what); return FOS_EINVAL; }
         scale[(size_t)i] = 1.0 / std::sqrt(rn2[(size_t)i]);
         bs[(size_t)i] = b[i] * scale[(size_t)i];
     }
     // A' in CSR = the CSC arrays as they are (0-based, scaled); A in CSR by a counting pass (columns ascending inside a row)
-    std::vector<int32_t> trp((size_t)n + 1), tci((size_t)nnz), rp((size_t)m + 1, 0), ci((size_t)nnz);
-    std::vector<double> tva((size_t)nnz), va((size_t)nnz);
+    std::vector<int32_t>&trp = out->trp, &tci = out->tci, &rp = out->rp, &ci = out->ci;
+    std::vector<double>&tva = out->tva, &va = out->va;
+    trp.resize((size_t)n + 1); tci.resize((size_t)nnz); rp.assign((size_t)m + 1, 0); ci.resize((size_t)nnz);
+    tva.resize((size_t)nnz); va.resize((size_t)nnz);
     for (int64_t i = 0; i < m; ++i) rp[(size_t)i + 1] = rp[(size_t)i] + rcount[(size_t)i + 1];
     std::vector<int32_t> fill(rp.begin(), rp.end() - 1);
     for (int64_t j = 0; j <= n; ++j) trp[(size_t)j] = (int32_t)(colptr[j] - 1);
@@ -237,6 +242,17 @@ int sparse_affine_setup(int64_t m, int64_t n, const int64_t* colptr, const int64
             const int32_t pos = fill[(size_t)i]++;
             ci[(size_t)pos] = (int32_t)j; va[(size_t)pos] = v;
         }
+    out->m = m; out->n = n; out->nnz = nnz;
+    return FOS_OK;
+}
+
+// A: m x n CSC, 1-based; b[m].  Rows of [A | b] scaled to unit norm; A and A' to CSR (sparse_affine_rows); upload.
+int sparse_affine_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int cus, SparseAffine** out) {
+    SparseRows R;
+    FOS_TRY(sparse_affine_rows("IndAffine (sparse)", m, n, colptr, rowval, nzval, b, &R));
+    const int64_t nnz = R.nnz;
+    const std::vector<int32_t>&rp = R.rp, &ci = R.ci, &trp = R.trp, &tci = R.tci;
+    const std::vector<double>&va = R.va, &tva = R.tva, &bs = R.bs;
     SparseAffine* a = new SparseAffine();
     a->m = m; a->n = n; a->nnz = nnz;
     int rc = FOS_OK;

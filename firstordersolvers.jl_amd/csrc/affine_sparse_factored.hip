@@ -1,0 +1,394 @@
+// IndAffine(A, b) with a SPARSE A on the device, factored form: the exact projection  y = x - A'(A A')^-1 (A x - b)  evaluated as written, A kept sparse and
+// (A A')^-1 of order m <= 46 000 kept dense -- the direct counterpart of affine_sparse.hip's conjugate gradients: a fixed number of launches whatever cond(A A'),
+// no host synchronise, no copy.  (ProximalOperators.IndAffine factorises A once and applies the factor; this is the same idea with the m-space kept as an inverse.)
+//
+//   * set-up: sparse_affine_rows (affine_sparse.hip) validates, scales the rows of [A | b] to unit norm and leaves A and A' as two CSR matrices (fp64 values, int32
+//     columns); G = A A' (order L = m rounded up to 64, identity on the padding) by sf_gram_kernel; X = G^-1 by dense_spd_inverse with the options of the dense
+//     factored form (affine_dense.hip: probe bar 1e-7, which the projection's correction step squares).  G and X stay, 16 L^2 bytes.
+//   * a projection:  r = A x - b (pass 1, the CSR of A);  d = X r;  d += X (r - G d) (da_symv_kernel, three launches);  y = x - A'd (pass 2, the CSR of A');
+//     then `refine` times  r = A y - b, d = X r, y -= A'd.
+//   * the two passes are one kernel over a table of WORK ITEMS, one wavefront each, built on the host: a row longer than SEG stored entries is cut into segments of
+//     at most SEG, one item each (the 64 lanes walk the segment's (column, value) stream side by side: coalesced, one wave_sum, the sum to part[segment]); the
+//     other rows are packed, neighbours together, into packets of 64 / g rows with g = 1 .. 64 lanes per row, g chosen PER PACKET so that no lane has more than
+//     SF_LANE_ENTRIES entries of the packet's longest row (or, at g = 64, SEG / 64).  No wavefront's work depends on the longest row of the matrix.  A packed row
+//     writes its result itself (r_j = s - b_j / y_i = x_i - s; an empty row of A': y_i = x_i); sf_fold_kernel adds a cut row's partials in segment order and
+//     applies the same epilogue.
+//   Nothing is atomic and every sum has a fixed order: the same input gives the same bits, from run to run and from handle to handle.
+#include "fos_solver.hpp"
+#include "dev_common.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+namespace fos {
+
+namespace {
+
+constexpr int SF_T = 256;                     // threads per workgroup: four work items
+constexpr int SF_SEG_DEFAULT = 2048;          // stored entries per segment (FOS_SF_SEG: a multiple of 64 from 64 up to this)
+constexpr int SF_LANE_ENTRIES = 4;            // packed rows: entries per lane of the packet's longest row, while g < 64
+constexpr double SF_BAR = 1e-7;               // the inverse of A A' is accepted at this probe residual (as affine_dense.hip)
+
+// a work item (16 bytes, read wave-uniformly):
+//   segment: a = row, b = first entry, c = entries (> 0), d = slot of part[] (-1: the row's only segment, never built: such rows are packed)
+//   packet:  a = first row, b = rows (<= 64 / g), c = -g (lanes per row, a power of two), d unused
+struct SfItem { int32_t a, b, c, d; };
+
+// PASS 1 (the CSR of A):  s = A[row, segment] in  ->  out[row] = s - aux[row]          (in = x or y, aux = b, out = r)
+// PASS 2 (the CSR of A'): s = A'[row, segment] in ->  out[row] = aux[row] - s          (in = d, aux = x or y, out = y; out may be aux: same lane reads and writes)
+template <int PASS>
+__global__ __launch_bounds__(SF_T) void sf_pass_kernel(int nitems, const SfItem* __restrict__ items, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
+                                                       const double* __restrict__ va, const double* __restrict__ in, const double* aux, double* out,
+                                                       double* __restrict__ part) {
+    const int lane = threadIdx.x & 63;
+    const int it = blockIdx.x * (SF_T / 64) + (threadIdx.x >> 6);
+    if (it >= nitems) return;                                                        // (wave-uniform)
+    const SfItem w = items[it];
+    const bool segment = w.c > 0;
+    const int g = segment ? 64 : -w.c;
+    const int sub = lane & (g - 1), k = lane >> __builtin_ctz(g);
+    const bool live = segment ? true : k < w.b;
+    const int row = segment ? w.a : w.a + k;
+    int e0 = 0, e1 = 0;
+    if (segment) { e0 = w.b; e1 = w.b + w.c; }
+    else if (live) { e0 = rp[row]; e1 = rp[row + 1]; }
+    double s = 0.0;
+    int e = e0 + sub;
+    for (; e + 3 * g < e1; e += 4 * g) {                                             // four loads of each stream in flight; the sum stays in entry order
+        const int c0 = ci[e], c1 = ci[e + g], c2 = ci[e + 2 * g], c3 = ci[e + 3 * g];
+        const double a0 = va[e], a1 = va[e + g], a2 = va[e + 2 * g], a3 = va[e + 3 * g];
+        const double v0 = in[c0], v1 = in[c1], v2 = in[c2], v3 = in[c3];
+        s += a0 * v0; s += a1 * v1; s += a2 * v2; s += a3 * v3;
+    }
+    for (; e < e1; e += g) s += va[e] * in[ci[e]];
+    s = group_sum(s, g);
+    if (!live || sub != 0) return;
+    if (segment) part[w.d] = s;
+    else out[row] = PASS == 1 ? s - aux[row] : aux[row] - s;
+}
+// the rows that were cut: out[frow[k]] = epilogue(sum of part[fptr[k] .. fptr[k + 1]) in segment order)
+template <int PASS>
+__global__ __launch_bounds__(SF_T) void sf_fold_kernel(int nfold, const int32_t* __restrict__ frow, const int32_t* __restrict__ fptr, const double* __restrict__ part,
+                                                       const double* aux, double* out) {
+    for (int k = blockIdx.x * SF_T + threadIdx.x; k < nfold; k += gridDim.x * SF_T) {
+        double s = 0.0;
+        for (int p = fptr[k]; p < fptr[k + 1]; ++p) s += part[p];
+        const int row = frow[k];
+        out[row] = PASS == 1 ? s - aux[row] : aux[row] - s;
+    }
+}
+// set-up: G = A A' + (identity on the padding), L x L column-major, zeroed by the caller.  One workgroup per column i of G: the entries (i, c) of row i one after
+// the other in column order, the entries of column c (= row c of A') side by side -- they hit distinct rows of G (the set-up refuses duplicated entries), so
+// nothing is atomic, every element is summed over c ascending, and G[i, j] and G[j, i] add the same products in the same order: exactly symmetric.
+__global__ __launch_bounds__(SF_T) void sf_gram_kernel(int64_t m, int64_t L, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci, const double* __restrict__ va,
+                                                       const int32_t* __restrict__ trp, const int32_t* __restrict__ tci, const double* __restrict__ tva, double* G) {
+    for (int64_t i = blockIdx.x; i < L; i += gridDim.x) {
+        double* col = G + i * L;
+        if (i < m) {
+            for (int e = rp[i]; e < rp[i + 1]; ++e) {
+                const int c = ci[e];
+                const double a = va[e];
+                for (int t = trp[c] + (int)threadIdx.x; t < trp[c + 1]; t += SF_T) col[tci[t]] += a * tva[t];
+                __syncthreads();
+            }
+        } else if (threadIdx.x == 0) col[i] = 1.0;
+    }
+}
+
+int sf_lanes(int len) {                                  // the fewest lanes (a power of two, at most 64) that leave a lane at most SF_LANE_ENTRIES entries of a row
+    int g = 1;
+    while (g < 64 && g * SF_LANE_ENTRIES < len) g <<= 1;
+    return g;
+}
+
+// the work items of one pass, from the row pointers and SEG alone
+struct SfPass {
+    std::vector<SfItem> items;
+    std::vector<int32_t> frow, fptr;                     // cut rows and their slots of part[]: fptr[k] .. fptr[k + 1] - 1, in segment order
+    int64_t nparts = 0;
+};
+void sf_plan_pass(int64_t nrows, const int32_t* rp, int seg, SfPass* P) {
+    P->items.clear(); P->frow.clear(); P->fptr.assign(1, 0); P->nparts = 0;
+    auto len = [&](int64_t r) { return rp[r + 1] - rp[r]; };
+    int64_t r = 0;
+    while (r < nrows) {
+        const int l0 = len(r);
+        if (l0 > seg) {
+            for (int e = rp[r]; e < rp[r + 1]; e += seg) P->items.push_back(SfItem{(int32_t)r, e, std::min(seg, rp[r + 1] - e), (int32_t)P->nparts++});
+            P->frow.push_back((int32_t)r); P->fptr.push_back((int32_t)P->nparts);
+            ++r;
+            continue;
+        }
+        int g = sf_lanes(l0), cnt = 1;
+        while (r + cnt < nrows && len(r + cnt) <= seg) {
+            const int g2 = std::max(g, sf_lanes(len(r + cnt)));
+            if ((cnt + 1) * g2 > 64) break;
+            g = g2; ++cnt;
+        }
+        P->items.push_back(SfItem{(int32_t)r, cnt, -g, -1});
+        r += cnt;
+    }
+}
+
+// FOS_SF_SEG (read at every set-up: per handle): a multiple of 64 from 64 up to the default
+int sf_segment_length(int* seg) {
+    *seg = SF_SEG_DEFAULT;
+    const char* s = std::getenv("FOS_SF_SEG");
+    if (!s || !*s) return FOS_OK;
+    char* end = nullptr;
+    const long v = std::strtol(s, &end, 10);
+    if (*end || v < 64 || v > SF_SEG_DEFAULT || v % 64) {
+        set_error("IndAffine (sparse, factored): FOS_SF_SEG = \"%s\" (a multiple of 64 from 64 to %d)", s, SF_SEG_DEFAULT);
+        return FOS_EINVAL;
+    }
+    *seg = (int)v;
+    return FOS_OK;
+}
+
+// what both the device set-up and the host emulation refuse, and the scaled rows
+int sf_rows(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int refine, SparseRows* R) {
+    const char* what = "IndAffine (sparse, factored)";
+    if (m < 1 || n < 1 || m > n) { set_error("%s: bad argument (1 <= m <= n)", what); return FOS_EINVAL; }
+    if (m > 46000) { set_error("%s: the inverse of A A' has order m = %lld: supported up to m = 46000", what, (long long)m); return FOS_EUNSUPPORTED; }
+    if (refine < 0 || refine > 2) { set_error("%s: refine = %d (0, 1 or 2 refinement steps per projection)", what, refine); return FOS_EINVAL; }
+    FOS_TRY(sparse_affine_rows(what, m, n, colptr, rowval, nzval, b, R));
+    for (int64_t j = 0; j < n; ++j)                                                   // (sf_gram_kernel adds a column's entries side by side)
+        for (int32_t e = R->trp[(size_t)j] + 1; e < R->trp[(size_t)j + 1]; ++e)
+            if (R->tci[(size_t)e] <= R->tci[(size_t)e - 1]) {
+                set_error("%s: the row indices of column %lld are not strictly ascending (duplicated or unsorted entries)", what, (long long)j + 1);
+                return FOS_EINVAL;
+            }
+    return FOS_OK;
+}
+
+}  // namespace
+
+struct SparseFactored {
+    int64_t m = 0, n = 0, nnz = 0, L = 0;
+    int refine = 0, seg = 0;
+    int32_t *rp = nullptr, *ci = nullptr, *trp = nullptr, *tci = nullptr;
+    double *va = nullptr, *tva = nullptr;
+    double *G = nullptr, *X = nullptr, *b = nullptr;                    // G, X: L x L column-major; b: scaled
+    double *r = nullptr, *d = nullptr, *e = nullptr;                    // m-space vectors (L)
+    SfItem *items1 = nullptr, *items2 = nullptr;
+    int32_t *frow1 = nullptr, *fptr1 = nullptr, *frow2 = nullptr, *fptr2 = nullptr;
+    double *part1 = nullptr, *part2 = nullptr;
+    int nitems1 = 0, nitems2 = 0, nfold1 = 0, nfold2 = 0;
+    int64_t nparts1 = 0, nparts2 = 0;
+    std::vector<void*> owned;
+    DenseInv inv;
+    size_t bytes = 0;
+};
+
+void sparse_factored_destroy(SparseFactored* a) {
+    if (!a) return;
+    for (void* q : a->owned) (void)hipFree(q);
+    delete a;
+}
+
+namespace {
+template <class T>
+int sf_alloc(SparseFactored* a, T** out, size_t count) {
+    void* q = nullptr;
+    const size_t bytes = sizeof(T) * std::max<size_t>(count, 1);
+    const hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); set_error("IndAffine (sparse, factored): hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e)); return FOS_ENOMEM; }
+    a->owned.push_back(q); a->bytes += bytes;
+    *out = static_cast<T*>(q);
+    return FOS_OK;
+}
+template <class T>
+int sf_upload(SparseFactored* a, T** out, const std::vector<T>& v, hipStream_t s) {
+    FOS_TRY(sf_alloc(a, out, v.size()));
+    if (!v.empty()) {
+        const hipError_t e = hipMemcpyAsync(*out, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) { set_error("IndAffine (sparse, factored) set-up: hipMemcpyAsync -> %s", hipGetErrorString(e)); return FOS_EHIP; }
+    }
+    return FOS_OK;
+}
+int sf_hip(const char* call, hipError_t e) {
+    if (e != hipSuccess) { set_error("IndAffine (sparse, factored) set-up: %s -> %s", call, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? FOS_ENOMEM : FOS_EHIP; }
+    return FOS_OK;
+}
+}  // namespace
+
+// A: m x n CSC, 1-based; b[m]; factor: FOS_DIRECT_FACTOR_*; refine: 0..2 refinement steps per projection.  Synchronises `stream`.
+int sparse_factored_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int factor, int refine,
+                          hipStream_t stream, SparseFactored** out) {
+    if (factor != FOS_DIRECT_FACTOR_NEWTON && factor != FOS_DIRECT_FACTOR_CHOLESKY) {
+        set_error("IndAffine (sparse, factored): factor must be FOS_DIRECT_FACTOR_NEWTON or FOS_DIRECT_FACTOR_CHOLESKY");
+        return FOS_EINVAL;
+    }
+    SparseRows R;
+    FOS_TRY(sf_rows(m, n, colptr, rowval, nzval, b, refine, &R));
+    int seg = 0;
+    FOS_TRY(sf_segment_length(&seg));
+    SfPass P1, P2;
+    sf_plan_pass(m, R.rp.data(), seg, &P1);
+    sf_plan_pass(n, R.trp.data(), seg, &P2);
+    SparseFactored* a = new SparseFactored();
+    a->m = m; a->n = n; a->nnz = R.nnz; a->L = (m + 63) / 64 * 64; a->refine = refine; a->seg = seg;
+    a->nitems1 = (int)P1.items.size(); a->nitems2 = (int)P2.items.size(); a->nfold1 = (int)P1.frow.size(); a->nfold2 = (int)P2.frow.size();
+    a->nparts1 = P1.nparts; a->nparts2 = P2.nparts;
+    const size_t L = (size_t)a->L, L2 = L * L;
+    auto fail = [&](int code) { (void)hipStreamSynchronize(stream); sparse_factored_destroy(a); return code; };
+    int rc = FOS_OK;
+    if ((rc = sf_upload(a, &a->rp, R.rp, stream)) != FOS_OK || (rc = sf_upload(a, &a->ci, R.ci, stream)) != FOS_OK || (rc = sf_upload(a, &a->va, R.va, stream)) != FOS_OK ||
+        (rc = sf_upload(a, &a->trp, R.trp, stream)) != FOS_OK || (rc = sf_upload(a, &a->tci, R.tci, stream)) != FOS_OK || (rc = sf_upload(a, &a->tva, R.tva, stream)) != FOS_OK ||
+        (rc = sf_upload(a, &a->items1, P1.items, stream)) != FOS_OK || (rc = sf_upload(a, &a->items2, P2.items, stream)) != FOS_OK ||
+        (rc = sf_upload(a, &a->frow1, P1.frow, stream)) != FOS_OK || (rc = sf_upload(a, &a->fptr1, P1.fptr, stream)) != FOS_OK ||
+        (rc = sf_upload(a, &a->frow2, P2.frow, stream)) != FOS_OK || (rc = sf_upload(a, &a->fptr2, P2.fptr, stream)) != FOS_OK ||
+        (rc = sf_alloc(a, &a->part1, (size_t)P1.nparts)) != FOS_OK || (rc = sf_alloc(a, &a->part2, (size_t)P2.nparts)) != FOS_OK ||
+        (rc = sf_alloc(a, &a->G, L2)) != FOS_OK || (rc = sf_alloc(a, &a->X, L2)) != FOS_OK)
+        return fail(rc);
+    for (double** v : {&a->b, &a->r, &a->d, &a->e}) if ((rc = sf_alloc(a, v, L)) != FOS_OK) return fail(rc);
+#define SF_HIP(expr) do { const int _r = sf_hip(#expr, (expr)); if (_r != FOS_OK) return fail(_r); } while (0)
+    for (double* v : {a->b, a->r, a->d, a->e}) SF_HIP(hipMemsetAsync(v, 0, sizeof(double) * L, stream));
+    SF_HIP(hipMemcpyAsync(a->b, R.bs.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
+    SF_HIP(hipMemsetAsync(a->G, 0, sizeof(double) * L2, stream));
+    hipLaunchKernelGGL(sf_gram_kernel, dim3((unsigned)std::min<int64_t>(a->L, 65536)), dim3(SF_T), 0, stream, m, a->L, (const int32_t*)a->rp, (const int32_t*)a->ci,
+                       (const double*)a->va, (const int32_t*)a->trp, (const int32_t*)a->tci, (const double*)a->tva, a->G);
+    {   // X = G^-1; the square work buffers go at the end of this block
+        DenseWork w;
+        w.c.stream = stream; w.c.l = m; w.L = a->L; w.G = a->G;
+        Scratch s;
+        w.fill(s);
+        if (s.err != hipSuccess) { (void)hipGetLastError(); set_error("IndAffine (sparse, factored): hipMalloc of the set-up buffers (3 x %zu bytes) failed: %s", L2 * 8, hipGetErrorString(s.err)); return fail(FOS_ENOMEM); }
+        double* X = nullptr;
+        DenseOpts o{"IndAffine (sparse, factored)", "A A'", factor, false};
+        o.bar = SF_BAR; o.newton_extra = 40;
+        rc = dense_spd_inverse(w, o, &X, &a->inv);
+        if (rc == FOS_EINVAL) {
+            const std::string why = fos_last_error();
+            set_error("IndAffine (sparse, factored): the inverse of A A' (rows scaled to unit norm) was not accepted: A needs full row rank  [%s]", why.c_str());
+        }
+        if (rc != FOS_OK) return fail(rc);
+        SF_HIP(hipMemcpyAsync(a->X, X, sizeof(double) * L2, hipMemcpyDeviceToDevice, stream));
+        SF_HIP(hipStreamSynchronize(stream));
+    }
+#undef SF_HIP
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("IndAffine (sparse, factored) set-up: a kernel launch failed: %s", hipGetErrorString(e)); return fail(FOS_EHIP); }
+    *out = a;
+    return FOS_OK;
+}
+
+namespace {
+unsigned sf_grid(int nitems) { return (unsigned)((nitems + SF_T / 64 - 1) / (SF_T / 64)); }
+// r = A v - b
+void sf_residual(const SparseFactored* a, hipStream_t s, const double* v) {
+    hipLaunchKernelGGL(sf_pass_kernel<1>, dim3(sf_grid(a->nitems1)), dim3(SF_T), 0, s, a->nitems1, (const SfItem*)a->items1, (const int32_t*)a->rp, (const int32_t*)a->ci,
+                       (const double*)a->va, v, (const double*)a->b, a->r, a->part1);
+    if (a->nfold1 > 0)
+        hipLaunchKernelGGL(sf_fold_kernel<1>, dim3((unsigned)std::min(1024, (a->nfold1 + SF_T - 1) / SF_T)), dim3(SF_T), 0, s, a->nfold1, (const int32_t*)a->frow1,
+                           (const int32_t*)a->fptr1, (const double*)a->part1, (const double*)a->b, a->r);
+}
+// y = x - A'd
+void sf_correct(const SparseFactored* a, hipStream_t s, double* y, const double* x) {
+    hipLaunchKernelGGL(sf_pass_kernel<2>, dim3(sf_grid(a->nitems2)), dim3(SF_T), 0, s, a->nitems2, (const SfItem*)a->items2, (const int32_t*)a->trp, (const int32_t*)a->tci,
+                       (const double*)a->tva, (const double*)a->d, x, y, a->part2);
+    if (a->nfold2 > 0)
+        hipLaunchKernelGGL(sf_fold_kernel<2>, dim3((unsigned)std::min(1024, (a->nfold2 + SF_T - 1) / SF_T)), dim3(SF_T), 0, s, a->nfold2, (const int32_t*)a->frow2,
+                           (const int32_t*)a->fptr2, (const double*)a->part2, x, y);
+}
+int sf_launches(const SparseFactored* a) {
+    const int p1 = 1 + (a->nfold1 > 0 ? 1 : 0), p2 = 1 + (a->nfold2 > 0 ? 1 : 0);
+    return (p1 + 3 + p2) + a->refine * (p1 + 1 + p2);
+}
+}  // namespace
+
+// y = the projection of x onto {A x = b} (device vectors of length n, y must not alias x), on `stream`: sf_launches(a) launches, nothing else
+int sparse_factored_project(SparseFactored* a, hipStream_t stream, double* y, const double* x) {
+    sf_residual(a, stream, x);                                                   // r = A x - b
+    launch_da_symv(stream, a->m, a->L, a->X, a->r, nullptr, 1.0, a->d);          // d = X r
+    launch_da_symv(stream, a->m, a->L, a->G, a->d, a->r, -1.0, a->e);            // e = r - G d
+    launch_da_symv(stream, a->m, a->L, a->X, a->e, a->d, 1.0, a->d);             // d += X e
+    sf_correct(a, stream, y, x);                                                 // y = x - A'd
+    for (int k = 0; k < a->refine; ++k) {
+        sf_residual(a, stream, y);                                               // r = A y - b
+        launch_da_symv(stream, a->m, a->L, a->X, a->r, nullptr, 1.0, a->d);      // d = X r
+        sf_correct(a, stream, y, y);                                             // y -= A'd
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("IndAffine (sparse, factored): a kernel launch failed: %s", hipGetErrorString(e)); return FOS_EHIP; }
+    return FOS_OK;
+}
+
+// out8 = m, n, refine, factor that produced the accepted inverse, fell_back, probe residual, kernel launches per projection, bytes kept
+void sparse_factored_stats(const SparseFactored* a, double* out8) {
+    out8[0] = (double)a->m; out8[1] = (double)a->n; out8[2] = (double)a->refine; out8[3] = (double)a->inv.used; out8[4] = a->inv.fell_back ? 1.0 : 0.0;
+    out8[5] = a->inv.probe; out8[6] = (double)sf_launches(a); out8[7] = (double)a->bytes;
+}
+// out8 = stored entries, padded order of A A', SEG in force, pass 1: work items, rows cut (folded); pass 2: work items, rows cut; segments of the cut rows of both passes
+void sparse_factored_plan(const SparseFactored* a, int64_t* out8) {
+    out8[0] = a->nnz; out8[1] = a->L; out8[2] = a->seg; out8[3] = a->nitems1; out8[4] = a->nfold1; out8[5] = a->nitems2; out8[6] = a->nfold2;
+    out8[7] = a->nparts1 + a->nparts2;
+}
+
+// ---------------------------------------------------------------------------------- host emulation (tests; no GPU)
+namespace {
+// one pass in sf_pass_kernel's and sf_fold_kernel's order: out[row] = s - aux[row] (pass 1) / aux[row] - s (pass 2)
+void sf_host_pass(int pass, const SfPass& P, const std::vector<int32_t>& rp, const std::vector<int32_t>& ci, const std::vector<double>& va, const double* in,
+                  const double* aux, double* out) {
+    std::vector<double> part((size_t)std::max<int64_t>(P.nparts, 1));
+    auto group = [&](int e0, int e1, int g) {                         // the lanes' sums in entry order, then group_sum's tree over g lanes
+        double lane[64] = {0.0};
+        for (int e = e0; e < e1; ++e) lane[(e - e0) % g] += va[(size_t)e] * in[ci[(size_t)e]];
+        for (int w = 1; w < g; w <<= 1)
+            for (int i = 0; i < g; i += 2 * w) lane[i] = lane[i] + lane[i + w];
+        return lane[0];
+    };
+    for (const SfItem& w : P.items) {
+        if (w.c > 0) { part[(size_t)w.d] = group(w.b, w.b + w.c, 64); continue; }
+        for (int k = 0; k < w.b; ++k) {
+            const int row = w.a + k;
+            const double s = group(rp[(size_t)row], rp[(size_t)row + 1], -w.c);
+            out[row] = pass == 1 ? s - aux[row] : aux[row] - s;
+        }
+    }
+    for (size_t k = 0; k < P.frow.size(); ++k) {
+        double s = 0.0;
+        for (int p = P.fptr[k]; p < P.fptr[k + 1]; ++p) s += part[(size_t)p];
+        const int row = P.frow[k];
+        out[row] = pass == 1 ? s - aux[row] : aux[row] - s;
+    }
+}
+}  // namespace
+
+// the same validation and scaling, G in sf_gram_kernel's order, host_da_inverse for X, the segment tables of this matrix (FOS_SF_SEG honoured; the tables do not depend on
+// the device) and both passes, the folds and the m-space products in the kernels' summation order
+int host_affine_sparse_factored(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int refine, const double* x,
+                                double* y) {
+    if (!x || !y) { set_error("IndAffine (sparse, factored): bad argument"); return FOS_EINVAL; }
+    SparseRows R;
+    FOS_TRY(sf_rows(m, n, colptr, rowval, nzval, b, refine, &R));
+    int seg = 0;
+    FOS_TRY(sf_segment_length(&seg));
+    SfPass P1, P2;
+    sf_plan_pass(m, R.rp.data(), seg, &P1);
+    sf_plan_pass(n, R.trp.data(), seg, &P2);
+    std::vector<double> G((size_t)m * (size_t)m, 0.0), X((size_t)m * (size_t)m);
+    for (int64_t i = 0; i < m; ++i)
+        for (int32_t e = R.rp[(size_t)i]; e < R.rp[(size_t)i + 1]; ++e) {
+            const int32_t c = R.ci[(size_t)e];
+            for (int32_t t = R.trp[(size_t)c]; t < R.trp[(size_t)c + 1]; ++t) G[(size_t)(R.tci[(size_t)t] + i * m)] += R.va[(size_t)e] * R.tva[(size_t)t];
+        }
+    FOS_TRY(host_da_inverse("IndAffine (sparse, factored)", m, G.data(), X.data()));
+    std::vector<double> r((size_t)m), d((size_t)m), e((size_t)m);
+    sf_host_pass(1, P1, R.rp, R.ci, R.va, x, R.bs.data(), r.data());
+    host_da_symv(m, m, X.data(), r.data(), nullptr, 1.0, d.data());
+    host_da_symv(m, m, G.data(), d.data(), r.data(), -1.0, e.data());
+    host_da_symv(m, m, X.data(), e.data(), d.data(), 1.0, d.data());
+    sf_host_pass(2, P2, R.trp, R.tci, R.tva, d.data(), x, y);
+    for (int k = 0; k < refine; ++k) {
+        sf_host_pass(1, P1, R.rp, R.ci, R.va, y, R.bs.data(), r.data());
+        host_da_symv(m, m, X.data(), r.data(), nullptr, 1.0, d.data());
+        sf_host_pass(2, P2, R.trp, R.tci, R.tva, d.data(), y, y);
+    }
+    return FOS_OK;
+}
+
+}  // namespace fos

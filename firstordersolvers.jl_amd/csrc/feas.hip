@@ -158,9 +158,10 @@ __global__ __launch_bounds__(FEAS_THREADS) void feas_pad_identity_kernel(int64_t
 }
 
 struct FeasSet {
-    int kind = 0;                   // 0 unset, 1 IndAffine (dense), 2 IndBox, 3 ConeProduct, 4 host callback, 5 IndAffine (sparse A), 6 separable sum of sets, 7 IndAffine (dense, factored)
+    int kind = 0;                   // 0 unset, 1 IndAffine (dense), 2 IndBox, 3 ConeProduct, 4 host callback, 5 IndAffine (sparse A), 6 separable sum of sets, 7 IndAffine (dense, factored), 8 IndAffine (sparse A, factored)
     SparseAffine* sa = nullptr;     // kind 5 (affine_sparse.hip)
     DenseAffine* da = nullptr;      // kind 7 (affine_dense.hip)
+    SparseFactored* sf = nullptr;   // kind 8 (affine_sparse_factored.hip)
     SetBlocks* sb = nullptr;        // kind 6 (sets.hip)
     fos_prox_fn cb = nullptr;       // kind 4: prox!(y, S, x) evaluated by the caller on pinned host vectors
     void* cb_ctx = nullptr;
@@ -275,6 +276,8 @@ int feas_prox(fos_feas* h, int which, double* y, const double* x) {
         FOS_TRY(sparse_affine_project(s.sa, h->stream, y, x));
     } else if (s.kind == 7) {                                             // IndAffine over a dense A, factored: two passes over A and the inverse of A A', a fixed number of launches
         FOS_TRY(dense_affine_project(s.da, h->stream, y, x));
+    } else if (s.kind == 8) {                                             // IndAffine over a sparse A, factored: two segmented sparse passes and the dense inverse of A A', a fixed number of launches
+        FOS_TRY(sparse_factored_project(s.sf, h->stream, y, x));
     } else if (s.kind == 6) {                                             // balls, simplex, halfspaces ... in contiguous blocks: a fixed number of launches, no copy
         FOS_TRY(set_blocks_project(s.sb, h->stream, y, x));
     } else if (s.kind == 4) {                                             // any other ProximableFunction: the caller's prox! on host vectors
@@ -478,7 +481,7 @@ int fos_feas_destroy(fos_feas_handle h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (void* q : h->owned) (void)hipFree(q);
-    for (FeasSet& s : h->S) { if (s.cb_x) (void)hipHostFree(s.cb_x); if (s.cb_y) (void)hipHostFree(s.cb_y); psd_sign_destroy(s.psd_big); sparse_affine_destroy(s.sa); dense_affine_destroy(s.da); set_blocks_destroy(s.sb); }
+    for (FeasSet& s : h->S) { if (s.cb_x) (void)hipHostFree(s.cb_x); if (s.cb_y) (void)hipHostFree(s.cb_y); psd_sign_destroy(s.psd_big); sparse_affine_destroy(s.sa); dense_affine_destroy(s.da); sparse_factored_destroy(s.sf); set_blocks_destroy(s.sb); }
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return FOS_OK;
@@ -605,6 +608,34 @@ int fos_feas_affine_factored_plan(fos_feas_handle h, int32_t which, int64_t* out
 // test-only, host: the factored form's scaling, inverse and two passes in the kernels' order (affine_dense.hip)
 int fos_host_affine_factored(int64_t m, int64_t n, const double* A, const double* b, int32_t refine, const double* x, double* y) {
     return host_affine_factored(m, n, A, b, refine, x, y);
+}
+
+// IndAffine(A, b), A sparse m x n (CSC, 1-based), factored form (affine_sparse_factored.hip): built first, so that a refused call leaves the set as it was
+int fos_feas_set_affine_sparse_factored(fos_feas_handle h, int32_t which, int64_t m, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b,
+                                        int32_t factor, int32_t refine) {
+    if (!h || which < 1 || which > 2 || m < 1) { set_error("fos_feas_set_affine_sparse_factored: bad argument (m >= 1, which = 1 | 2)"); return FOS_EINVAL; }
+    FOS_HIP(hipSetDevice(h->device));
+    SparseFactored* sf = nullptr;
+    FOS_TRY(sparse_factored_setup(m, h->n, colptr, rowval, nzval, b, factor, refine, h->stream, &sf));   // (synchronises the stream: no projection onto the set being replaced runs any more)
+    FeasSet& s = h->S[which - 1];
+    sparse_factored_destroy(s.sf);
+    s.sf = sf; s.kind = 8;
+    return FOS_OK;
+}
+int fos_feas_affine_sparse_factored_stats(fos_feas_handle h, int32_t which, double* out8) {
+    if (!h || !out8 || which < 1 || which > 2 || h->S[which - 1].kind != 8) { set_error("fos_feas_affine_sparse_factored_stats: set %d is not a sparse factored IndAffine", (int)which); return FOS_EINVAL; }
+    sparse_factored_stats(h->S[which - 1].sf, out8);
+    return FOS_OK;
+}
+int fos_feas_affine_sparse_factored_plan(fos_feas_handle h, int32_t which, int64_t* out8) {
+    if (!h || !out8 || which < 1 || which > 2 || h->S[which - 1].kind != 8) { set_error("fos_feas_affine_sparse_factored_plan: set %d is not a sparse factored IndAffine", (int)which); return FOS_EINVAL; }
+    sparse_factored_plan(h->S[which - 1].sf, out8);
+    return FOS_OK;
+}
+// test-only, host: the sparse factored form's scaling, inverse, segment tables and two passes in the kernels' order (affine_sparse_factored.hip)
+int fos_host_affine_sparse_factored(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int32_t refine,
+                                    const double* x, double* y) {
+    return host_affine_sparse_factored(m, n, colptr, rowval, nzval, b, refine, x, y);
 }
 
 int fos_feas_set_box(fos_feas_handle h, int32_t which, double lo, double hi) {

@@ -676,6 +676,12 @@ int psd_sign_count(const PsdSign* p);
 int launch_cones_psd_sign(const LaunchCtx& c, PsdSign* p, double2* out, const double2* in);
 // IndAffine(A, b) with a sparse A (affine_sparse.hip): exact projection by warm-started CG on the row-scaled normal equations, the true residual re-checked
 struct SparseAffine;
+struct SparseRows {                              // host: what sparse_affine_rows leaves -- the scaled A (rp / ci / va) and A' (trp / tci / tva) in CSR, the scaled b
+    int64_t m = 0, n = 0, nnz = 0;
+    std::vector<int32_t> rp, ci, trp, tci;
+    std::vector<double> va, tva, bs;
+};
+int sparse_affine_rows(const char* what, int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, SparseRows* out);
 int sparse_affine_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int cus, SparseAffine** out);
 int sparse_affine_project(SparseAffine* a, hipStream_t stream, double* y, const double* x);      // y, x: device vectors of length n, y must not alias x
 void sparse_affine_reset(SparseAffine* a, hipStream_t stream);                                   // a new solve: lambda = 0
@@ -689,6 +695,22 @@ void dense_affine_stats(const DenseAffine* a, double* out8);
 void dense_affine_plan(const DenseAffine* a, int64_t* out6);
 void dense_affine_destroy(DenseAffine* a);
 int host_affine_factored(int64_t m, int64_t n, const double* A, const double* b, int refine, const double* x, double* y);
+// the m-space product of the factored forms (da_symv_kernel): out = add + sign M v, M symmetric column-major of order l, leading dimension ld (add == nullptr: 0;
+// out may be add); the same on the host in the kernel's order, the host's wave_sum tree, and the host's accepted inverse of G (order m, unpadded; `what` in the message)
+void launch_da_symv(hipStream_t s, int64_t l, int64_t ld, const double* M, const double* v, const double* add, double sign, double* out);
+void host_da_symv(int64_t l, int64_t ld, const double* M, const double* v, const double* add, double sign, double* out);
+double host_da_wave(const double* lane64);
+int host_da_inverse(const char* what, int64_t m, const double* G, double* X);
+// IndAffine(A, b) with a sparse A, factored form (affine_sparse_factored.hip): A and A' kept as CSR, (A A')^-1 of order m dense, two segmented sparse passes per projection
+struct SparseFactored;
+int sparse_factored_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int factor, int refine,
+                          hipStream_t stream, SparseFactored** out);
+int sparse_factored_project(SparseFactored* a, hipStream_t stream, double* y, const double* x);  // y, x: device vectors of length n, y must not alias x
+void sparse_factored_stats(const SparseFactored* a, double* out8);
+void sparse_factored_plan(const SparseFactored* a, int64_t* out8);
+void sparse_factored_destroy(SparseFactored* a);
+int host_affine_sparse_factored(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int refine, const double* x,
+                                double* y);
 // Separable sums of convex vector sets (sets.hip): norm balls, simplex, halfspace / hyperslab, point, free, scalar box -- contiguous blocks covering 1..n
 struct SetBlocks;
 int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec, SetBlocks** out);

@@ -828,22 +828,27 @@ class IndAffine:
     equations, ended by the recomputed residual) -- `sparse=True / False` forces either form.
     form="factored" (opt-in; form=None keeps the selection above to the letter): the dense A is kept once on the device with the inverse of A A'
     (order m <= 46 000, any n) and a projection is two passes over A (fos_feas_set_affine_factored); factor = "cholesky" | "newton" builds the
-    inverse, refine = 0..2 refinement steps follow every projection.  A scipy.sparse A is densified."""
+    inverse, refine = 0..2 refinement steps follow every projection.  A scipy.sparse A is densified.
+    form="sparse_factored" (opt-in): A stays sparse (CSC on the host, two CSR matrices on the device) with the dense inverse of A A' (order m <= 46 000, any n);
+    a projection is two segmented sparse passes and three products of order m, a fixed number of launches whatever cond(A A')
+    (fos_feas_set_affine_sparse_factored); factor and refine as for form="factored"."""
 
     DENSE_MAX = 46000
     FACTORED_MAX = 46000
 
     def __init__(self, A, b, sparse=None, form=None, factor="cholesky", refine=0):
-        if form not in (None, "factored"):
-            raise ValueError("IndAffine: form must be None or 'factored', not %r" % (form,))
+        if form not in (None, "factored", "sparse_factored"):
+            raise ValueError("IndAffine: form must be None, 'factored' or 'sparse_factored', not %r" % (form,))
         self.form, self.factor, self.refine = form, factor, int(refine)
-        if form == "factored":
-            if sparse:
+        if form is not None:
+            if form == "factored" and sparse:
                 raise ValueError("IndAffine: form='factored' keeps a dense A (sparse=True asks for the sparse form)")
+            if form == "sparse_factored" and sparse is not None and not sparse:
+                raise ValueError("IndAffine: form='sparse_factored' keeps a sparse A (sparse=False asks for a dense form)")
             direct_factor_code(factor)
             if not 0 <= self.refine <= 2:
                 raise ValueError("IndAffine: refine must be 0, 1 or 2, not %r" % (refine,))
-            self.sparse = False
+            self.sparse = form == "sparse_factored"
         else:
             self.sparse = bool(sp.issparse(A) or np.shape(A)[1] > self.DENSE_MAX) if sparse is None else bool(sparse)
         if self.sparse:
@@ -854,8 +859,8 @@ class IndAffine:
         self.b = np.ascontiguousarray(np.asarray(b, dtype=np.float64))
         if self.A.ndim != 2 or self.b.shape != (self.A.shape[0],):
             raise ValueError("IndAffine(A, b): A must be m x n and b of length m")
-        if form == "factored" and self.A.shape[0] > self.FACTORED_MAX:
-            raise ValueError("IndAffine(form='factored'): m = %d, the inverse of A A' is supported up to m = %d" % (self.A.shape[0], self.FACTORED_MAX))
+        if form is not None and self.A.shape[0] > self.FACTORED_MAX:
+            raise ValueError("IndAffine(form=%r): m = %d, the inverse of A A' is supported up to m = %d" % (form, self.A.shape[0], self.FACTORED_MAX))
 
 
 class IndBox:
@@ -1078,7 +1083,11 @@ class HipFeasibility:
                 colptr = np.ascontiguousarray(S.A.indptr, dtype=np.int64) + 1          # Julia 1-based
                 rowval = np.ascontiguousarray(S.A.indices, dtype=np.int64) + 1
                 nzval = np.ascontiguousarray(S.A.data, dtype=np.float64)
-                _lib.check(self._lib.fos_feas_set_affine_sparse(self._h, which, S.A.shape[0], i64(colptr), i64(rowval), _lib.dptr(nzval), _lib.dptr(S.b)))
+                if S.form == "sparse_factored":
+                    _lib.check(self._lib.fos_feas_set_affine_sparse_factored(self._h, which, S.A.shape[0], i64(colptr), i64(rowval), _lib.dptr(nzval), _lib.dptr(S.b),
+                                                                             direct_factor_code(S.factor), S.refine))
+                else:
+                    _lib.check(self._lib.fos_feas_set_affine_sparse(self._h, which, S.A.shape[0], i64(colptr), i64(rowval), _lib.dptr(nzval), _lib.dptr(S.b)))
             else:
                 _lib.check(self._lib.fos_feas_set_affine(self._h, which, S.A.shape[0], _lib.dptr(S.A), _lib.dptr(S.b)))
         elif isinstance(S, IndBox) and S.arrays:
@@ -1235,6 +1244,15 @@ class HipFeasibility:
         return {"m": int(o[0]), "n": int(o[1]), "refine": int(o[2]), "factor": DIRECT_FACTOR_NAMES[int(o[3])], "fell_back": int(o[4]), "probe_resid": float(o[5]),
                 "launches": int(o[6]), "bytes": int(o[7]), "ld": int(p[0]), "gram_order": int(p[1]), "span_cols": int(p[2]), "spans": int(p[3]),
                 "rows_per_block": int(p[4]), "row_blocks": int(p[5])}
+
+    def affine_sparse_factored_stats(self, which):
+        """the sparse factored IndAffine's set-up record and the segment tables of its two passes (fos_feas_affine_sparse_factored_stats, ..._plan)"""
+        o, p = np.zeros(8), np.zeros(8, dtype=np.int64)
+        _lib.check(self._lib.fos_feas_affine_sparse_factored_stats(self._h, which, _lib.dptr(o)))
+        _lib.check(self._lib.fos_feas_affine_sparse_factored_plan(self._h, which, p.ctypes.data_as(C.POINTER(C.c_int64))))
+        return {"m": int(o[0]), "n": int(o[1]), "refine": int(o[2]), "factor": DIRECT_FACTOR_NAMES[int(o[3])], "fell_back": int(o[4]), "probe_resid": float(o[5]),
+                "launches": int(o[6]), "bytes": int(o[7]), "nnz": int(p[0]), "gram_order": int(p[1]), "seg": int(p[2]), "items_rows": int(p[3]),
+                "folded_rows": int(p[4]), "items_cols": int(p[5]), "folded_cols": int(p[6]), "segments": int(p[7])}
 
 
 class FeasibilityModel:

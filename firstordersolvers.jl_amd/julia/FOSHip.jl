@@ -374,6 +374,21 @@ function feas_affine_factored_stats(handle::Ptr{Cvoid}, which::Integer)
     return (m = Int(out[1]), n = Int(out[2]), refine = Int(out[3]), factor = out[4] == 1 ? :cholesky : :newton, fell_back = out[5] != 0, probe_resid = out[6],
             launches = Int(out[7]), bytes = Int(out[8]), ld = plan[1], gram_order = plan[2], span_cols = plan[3], spans = plan[4], rows_per_block = plan[5], row_blocks = plan[6])
 end
+function feas_affine_sparse_factored_stats(handle::Ptr{Cvoid}, which::Integer)
+    out, plan = zeros(Float64, 8), zeros(Int64, 8)
+    check(ccall((:fos_feas_affine_sparse_factored_stats, libfoship), Cint, (Ptr{Cvoid}, Int32, Ptr{Cdouble}), handle, Int32(which), out))
+    check(ccall((:fos_feas_affine_sparse_factored_plan, libfoship), Cint, (Ptr{Cvoid}, Int32, Ptr{Int64}), handle, Int32(which), plan))
+    return (m = Int(out[1]), n = Int(out[2]), refine = Int(out[3]), factor = out[4] == 1 ? :cholesky : :newton, fell_back = out[5] != 0, probe_resid = out[6],
+            launches = Int(out[7]), bytes = Int(out[8]), nnz = plan[1], gram_order = plan[2], seg = plan[3], items_rows = plan[4], folded_rows = plan[5],
+            items_cols = plan[6], folded_cols = plan[7], segments = plan[8])
+end
+# test entry: the host emulation of the sparse factored IndAffine (no GPU needed)
+function host_affine_sparse_factored(A::SparseArrays.SparseMatrixCSC{Float64,Int64}, b::Vector{Float64}, refine::Integer, x::Vector{Float64})
+    y = similar(x)
+    check(ccall((:fos_host_affine_sparse_factored, libfoship), Cint, (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}),
+                Int64(size(A, 1)), Int64(size(A, 2)), A.colptr, A.rowval, A.nzval, b, Int32(refine), x, y))
+    return y
+end
 # test entry: the host emulation of one block's projection (no GPU needed)
 function host_set_project(kind::Integer, scal::NTuple{2,Float64}, v::Union{Nothing,Vector{Float64}}, x::Vector{Float64})
     y = similar(x)
@@ -405,6 +420,15 @@ mutable struct HipFeasData <: FOSSolverData
                 types, _, lens = conearrays(S)
                 GC.@preserve types lens check(ccall((:fos_feas_set_cones, libfoship), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Int32}, Ptr{Int64}),
                                                     d.handle, which, Int64(length(types)), types, lens))
+            elseif S isa ProximalOperators.IndAffine && S.A isa AbstractMatrix && get(model.options, :affine_form, nothing) == :sparse_factored
+                # solve!(...; affine_form = :sparse_factored [, affine_factor, affine_refine]): A stays sparse (the arrays of the SparseMatrixCSC as they are; a dense A is
+                # converted) with the dense inverse of A A' (m <= 46 000, any n), a projection is two segmented sparse passes, a fixed number of launches
+                As = SparseArrays.SparseMatrixCSC{Float64,Int64}(S.A)
+                b = Vector{Float64}(S.b)
+                factor = get(model.options, :affine_factor, :cholesky) == :newton ? Int32(0) : Int32(1)      # FOS_DIRECT_FACTOR_*
+                GC.@preserve As b check(ccall((:fos_feas_set_affine_sparse_factored, libfoship), Cint,
+                                              (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Int32),
+                                              d.handle, which, Int64(size(As, 1)), As.colptr, As.rowval, As.nzval, b, factor, Int32(get(model.options, :affine_refine, 0))))
             elseif S isa ProximalOperators.IndAffine && S.A isa AbstractMatrix && get(model.options, :affine_form, nothing) == :factored
                 # solve!(...; affine_form = :factored [, affine_factor = :cholesky | :newton, affine_refine = 0..2]): A (a sparse one densified) kept once with the
                 # inverse of A A' (m <= 46 000, any n), a projection is two passes over A

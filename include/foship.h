@@ -491,6 +491,27 @@ int fos_feas_affine_factored_plan(fos_feas_handle h, int32_t which, int64_t* out
 /* Test-only host emulation of the factored form (no GPU needed): the same scaling, the blocked Cholesky inverse of fos_host_chol_inverse accepted by the same probe,
  * and the two passes with the kernels' split and summation order for this (m, n) on 256 CUs.  x, y: n-vectors. */
 int fos_host_affine_factored(int64_t m, int64_t n, const double* A, const double* b, int32_t refine, const double* x, double* y);
+/* IndAffine(A, b), A SPARSE m x n (CSC, 1-based, as fos_feas_set_affine_sparse; row indices strictly ascending inside a column), full row rank,
+ * 1 <= m <= min(n, 46000), any n: the FACTORED form of the sparse set (opt-in; fos_feas_set_affine_sparse keeps the conjugate gradients).  The rows of [A | b] are
+ * scaled to unit norm, A and A' are kept as two CSR matrices, G = A A' (dense, order m rounded up to 64) is formed on the device and inverted once (factor:
+ * FOS_DIRECT_FACTOR_*; accepted at a residual of 1e-7, which the projection squares).  A projection: r = A x - b (a pass over the CSR of A), d = X r,
+ * d += X (r - G d), y = x - A'd (a pass over the CSR of A'), then `refine` (0..2) times r = A y - b, d = X r, y -= A'd.  Both passes are segmented: a row longer than
+ * SEG stored entries (2048; FOS_SF_SEG, read at every set-up: a multiple of 64 from 64 up to that) is cut into segments of one wavefront each, whose sums a fold
+ * launch adds in segment order; shorter rows are packed several to a wavefront.  A fixed number of launches whatever cond(A A'), no host synchronise, nothing
+ * atomic; the same bits from run to run (csrc/affine_sparse_factored.hip).  A zero row, m > n, unsorted or duplicated entries, or an inverse that is not accepted
+ * (A without full row rank): FOS_EINVAL; m > 46000: FOS_EUNSUPPORTED. */
+int fos_feas_set_affine_sparse_factored(fos_feas_handle h, int32_t which, int64_t m, const int64_t* colptr, const int64_t* rowval,
+                                        const double* nzval, const double* b, int32_t factor, int32_t refine);
+/* out8 = m, n, refine, factor that produced the accepted inverse, fell_back, probe residual, kernel launches per projection, bytes kept */
+int fos_feas_affine_sparse_factored_stats(fos_feas_handle h, int32_t which, double* out8);
+/* how the two passes are split (chosen at set-up from the row lengths and SEG): out8 = stored entries, padded order L of A A', SEG in force, pass 1 (rows of A): work
+ * items (wavefronts) and rows cut into segments (= folded), pass 2 (rows of A'): work items and rows cut, the segments of the cut rows of both passes together */
+int fos_feas_affine_sparse_factored_plan(fos_feas_handle h, int32_t which, int64_t* out8);
+/* Test-only host emulation of the sparse factored form (no GPU needed): the same validation and scaling, G summed in the set-up kernel's order, the blocked Cholesky
+ * inverse of fos_host_chol_inverse accepted by the same probe, the segment tables (FOS_SF_SEG honoured) and both passes, folds and m-space products in the kernels'
+ * summation order.  x, y: n-vectors. */
+int fos_host_affine_sparse_factored(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b,
+                                    int32_t refine, const double* x, double* y);
 int fos_feas_set_box(fos_feas_handle h, int32_t which, double lo, double hi);
 int fos_feas_set_box_arrays(fos_feas_handle h, int32_t which, const double* lo, const double* hi);     /* IndBox with array bounds (n each) */
 /* ConeProduct (src/cones.jl:31-94): ncones cones of type[i] (FOS_CONE_*) and len[i] entries, in order, contiguous, covering all n entries;
