@@ -49,6 +49,11 @@ PROTOTYPES = {
                              C.c_int64, _i32p, _i64p, _i64p, C.c_int64, _i32p, _i64p, _i64p, C.c_int, C.POINTER(_h)]),
     "fos_create2": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _dp, _dp, _dp,
                               C.c_int64, _i32p, _i64p, _i64p, C.c_int64, _i32p, _i64p, _i64p, C.c_int, C.c_int32, C.POINTER(_h)]),
+    "fos_create3": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _dp, _dp, _dp,
+                              C.c_int64, _i32p, _i64p, _i64p, C.c_int64, _i32p, _i64p, _i64p, C.c_int, C.c_int32, C.c_int32, C.POINTER(_h)]),
+    "fos_get_equilibration": (C.c_int, [_h, _i32p, _dp, _dp, _dp]),
+    "fos_host_equilibrate": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _dp, _dp, _dp,
+                                       C.c_int64, _i32p, _i64p, _i64p, C.c_int64, _i32p, _i64p, _i64p, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]),
     "fos_destroy": (C.c_int, [_h]),
     "fos_sizes": (C.c_int, [_h, _i64p, _i64p, _i64p, _i64p]),
     "fos_get_cg_total": (C.c_int, [_h, _i64p]),

@@ -726,6 +726,17 @@ int fos_enable_direct3(fos_handle h, const int64_t* colptr, const int64_t* rowva
     if (!h || !colptr || (!rowval && colptr[h->n] > 1)) { set_error("NULL argument"); return FOS_EINVAL; }
     if (form != FOS_DIRECT_FORM_AUTO && form != FOS_DIRECT_FORM_REDUCED) { set_error("fos_enable_direct3: form must be FOS_DIRECT_FORM_AUTO or FOS_DIRECT_FORM_REDUCED"); return FOS_EINVAL; }
     if (factor != FOS_DIRECT_FACTOR_NEWTON && factor != FOS_DIRECT_FACTOR_CHOLESKY) { set_error("fos_enable_direct3: factor must be FOS_DIRECT_FACTOR_NEWTON or FOS_DIRECT_FACTOR_CHOLESKY"); return FOS_EINVAL; }
+    // an equilibrated handle (fos_create3) holds D A E: the caller's values are scaled the way its create path scaled them (equilibrate.cpp)
+    std::vector<double> scaled;
+    if (h->equilibrated() && nzval) {
+        scaled.resize((size_t)(colptr[h->n] - 1));
+        for (int64_t j = 0; j < h->n; ++j)
+            for (int64_t k = colptr[j] - 1; k < colptr[j + 1] - 1; ++k) {
+                if (rowval[k] < 1 || rowval[k] > h->m) { set_error("rowval[%lld] = %lld outside 1..%lld", (long long)k, (long long)rowval[k], (long long)h->m); return FOS_EINVAL; }
+                scaled[k] = (h->eq_D[rowval[k] - 1] * nzval[k]) * h->eq_E[j];
+            }
+        nzval = scaled.data();
+    }
     const DirectEnv env;
     if (form == FOS_DIRECT_FORM_AUTO && env.mode == "reduced") form = FOS_DIRECT_FORM_REDUCED;
     if (env.factor) {                                                      // only for callers that did not choose: the old entries pass NEWTON

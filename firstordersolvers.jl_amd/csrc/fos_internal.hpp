@@ -647,6 +647,26 @@ void launch_deinterleave(const LaunchCtx& c, double* plain, const double2* in);
 void launch_set_comp(const LaunchCtx& c, double2* out, const double* plain_l, int comp);   // out[i].comp = plain[i], other comp = 0
 void launch_get_plain(const LaunchCtx& c, double* plain_l, const double2* in, int comp);
 
+// opt-in equilibration (fos_create3): the scaling computed on the host (equilibrate.cpp) and the kernels of an equilibrated handle (equilibrate.hip)
+constexpr double EQ_TARGET_NORM = 10.0;          // |b^| = |c^| = this (workloads.TARGET_NORM)
+constexpr int EQ_MAX_PASSES = 50;
+constexpr int EQ_THREADS = 256, EQ_MAX_BLOCKS = 512;     // the kernels' grid: a workgroup per 256 elements up to 512, grid-stride beyond (l > 131 072)
+inline int eq_blocks(int64_t count) { return (int)std::max<int64_t>(1, std::min<int64_t>((count + EQ_THREADS - 1) / EQ_THREADS, EQ_MAX_BLOCKS)); }
+struct EqScaling {                               // host
+    int passes = 0;
+    std::vector<double> D, E;                    // m row factors (gamma folded in), n column factors
+    double sigma = 1.0, rho = 1.0, gamma = 1.0;
+    std::vector<double> nz, b, c;                // A^ = D A E in the caller's CSC pattern, b^ = sigma D b, c^ = rho E c
+};
+// validates the problem as fos_create does (FOS_EINVAL / FOS_EUNSUPPORTED with a message) and fills `out`; passes in 1 .. EQ_MAX_PASSES
+int host_equilibrate(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, const double* c,
+                     int64_t nK1, const int32_t* K1type, const int64_t* K1start, const int64_t* K1len,
+                     int64_t nK2, const int32_t* K2type, const int64_t* K2start, const int64_t* K2len, int passes, EqScaling* out);
+int validate_cone_table(const char* which, int64_t total, int64_t nK, const int32_t* type, const int64_t* start, const int64_t* len);   // solver.cpp
+void launch_eq_status(const LaunchCtx& c, const double2* z, const double* w, const double* cb, const double* inv, double* partials);
+void launch_eq_interleave(const LaunchCtx& c, double2* out, const double* plain, const double2* up);
+void launch_eq_deinterleave(const LaunchCtx& c, double* plain, const double2* in, const double2* up);
+
 // cones (cones.jl:122-142)
 void launch_cones_elementwise(const LaunchCtx& c, double2* out, const double2* in, const uint8_t* ew_op);
 // t1 = a sol + (1 - a) x (a, or alpha12 of the device state) and t2 = P(t1) on the elementwise cones' indices, one pass (vecops.hip)

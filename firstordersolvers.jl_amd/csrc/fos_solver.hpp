@@ -199,6 +199,15 @@ struct fos_solver {
     bool row_sharded = false;
     double* slots_rd = nullptr;
 
+    // opt-in equilibration (fos_create3): the handle holds the SCALED problem; eq_passes == 0: a plain handle, nothing below is allocated
+    int eq_passes = 0;
+    std::vector<double> eq_D, eq_E;            // host: row factors (gamma folded in), column factors
+    double eq_sigma = 1.0, eq_rho = 1.0, eq_gamma = 1.0;
+    double eq_nb = 0.0, eq_nc = 0.0;           // ||b||, ||c|| of the CALLER's data (nb, nc above are the scaled problem's)
+    d2* eq_up = nullptr;                       // [l] caller's (part 1, part 2) -> scaled, per element (equilibrate.hip)
+    double *eq_inv = nullptr, *eq_cb = nullptr, *eq_w = nullptr;   // [1 ./ E; 1 ./ D] and [c^; b^] (n + m each), w = Q^ u^ of a status check (l)
+    bool equilibrated() const { return eq_passes > 0; }
+
     // tuning / measurement
     int cg_chunk = 8;
     int nwg_target = 2048;

@@ -535,8 +535,51 @@ int prox_cones(fos_solver* h, d2* out, const d2* in, const int32_t* gate = nullp
     return check_launch("cone projection");
 }
 
+// the decision of checkstatus from its values                             HSDEStatus.jl:53-63
+static int32_t status_decide(const fos_check_result* res, double eps) {
+    const double nb = res->norm_b, nc = res->norm_c, ctx = res->ctx, bty = res->bty, tau = res->tau;
+    if (res->p <= eps * (1 + nb) && res->d <= eps * (1 + nc) &&
+        res->g <= eps * (1 + std::fabs(ctx / tau) + std::fabs(bty / tau)))
+        return FOS_STATUS_OPTIMAL;
+    if (res->norm_axs <= eps * (-ctx / nc)) return FOS_STATUS_UNBOUNDED;
+    if (res->norm_aty <= eps * (-bty / nb)) return FOS_STATUS_INFEASIBLE;
+    return FOS_STATUS_CONTINUE;
+}
+
+// The same on an equilibrated handle, in the CALLER's units: z is the scaled problem's iterate; w = Q^ u^ (rows 0 .. n+m-1; its tau row is not read, so no
+// finalize) feeds one kernel that forms the six sums on the caller's A, b, c (equilibrate.hip), and sigma, rho, tau come in here.
+static int eq_status_check(fos_solver* h, const d2* z, double eps, fos_check_result* res) {
+    RoctxRange range("fos:checkstatus_eq");
+    LaunchCtx c = h->ctx();
+    launch_q1(c, Q_PLAIN, z, 0, 1.0, h->eq_w);
+    launch_eq_status(c, z, h->eq_w, h->eq_cb, h->eq_inv, h->partials);
+    FOS_TRY(poll_state(h));
+    const double* s = h->st_host->stat;
+    const double sg = h->eq_sigma, rho = h->eq_rho;
+    const double tau = s[ST_TAU], kappa = s[ST_KAPPA] / (sg * rho);
+    const double nb = h->eq_nb, nc = h->eq_nc;
+    const double ctx = s[ST_CTX] / (sg * rho), bty = s[ST_BTY] / (sg * rho);
+    res->p = std::sqrt(s[ST_RP2]) / (sg * std::fabs(tau)) / std::fabs(1 + nb);             // :34
+    res->d = std::sqrt(s[ST_RD2]) / (rho * std::fabs(tau)) / std::fabs(1 + nc);            // :35
+    res->ctx = ctx;                                                                      // :36
+    res->bty = bty;                                                                      // :37
+    res->g = std::fabs(ctx / tau + bty / tau) / (1 + std::fabs(ctx / tau) + std::fabs(bty / tau));   // :38
+    res->kappa = kappa;
+    res->tau = tau;
+    res->norm_axs = std::sqrt(s[ST_AXS2]) / sg;
+    res->norm_aty = std::sqrt(s[ST_ATY2]) / rho;
+    res->norm_b = nb;
+    res->norm_c = nc;
+    res->cgiter = h->cgiter;
+    res->cg_maxiter_hit = h->hit_max_accum;
+    h->hit_max_accum = 0;
+    res->status = status_decide(res, eps);
+    return FOS_OK;
+}
+
 // checkstatus(status, z, override=true) values + decision               HSDEStatus.jl:27-63
 int status_check(fos_solver* h, const d2* z, double eps, fos_check_result* res) {
+    if (h->equilibrated()) return eq_status_check(h, z, eps, res);
     RoctxRange range("fos:checkstatus");
     LaunchCtx c = h->ctx();
     int fr = 0;
@@ -562,16 +605,7 @@ int status_check(fos_solver* h, const d2* z, double eps, fos_check_result* res) 
     res->cgiter = h->cgiter;
     res->cg_maxiter_hit = h->hit_max_accum;
     h->hit_max_accum = 0;
-    int status = FOS_STATUS_CONTINUE;                                                    // :53-63
-    if (res->p <= eps * (1 + nb) && res->d <= eps * (1 + nc) &&
-        res->g <= eps * (1 + std::fabs(ctx / tau) + std::fabs(bty / tau))) {
-        status = FOS_STATUS_OPTIMAL;
-    } else if (res->norm_axs <= eps * (-ctx / nc)) {
-        status = FOS_STATUS_UNBOUNDED;
-    } else if (res->norm_aty <= eps * (-bty / nb)) {
-        status = FOS_STATUS_INFEASIBLE;
-    }
-    res->status = status;
+    res->status = status_decide(res, eps);
     return FOS_OK;
 }
 
@@ -983,6 +1017,24 @@ int download_plain(fos_solver* h, double* z, const d2* src) {
     return FOS_OK;
 }
 
+// the iterate's way in and out of an equilibrated handle: the same staging with the scaling kernels (plain handles: upload_plain / download_plain)
+int upload_caller(fos_solver* h, d2* dst, const double* z) {
+    if (!h->equilibrated()) return upload_plain(h, dst, z);
+    LaunchCtx c = h->ctx();
+    FOS_HIP(hipMemcpyAsync(h->plain, z, sizeof(double) * 2 * h->l, hipMemcpyHostToDevice, h->stream));
+    launch_eq_interleave(c, dst, h->plain, h->eq_up);
+    FOS_HIP(hipStreamSynchronize(h->stream));
+    return FOS_OK;
+}
+int download_caller(fos_solver* h, double* z, const d2* src) {
+    if (!h->equilibrated()) return download_plain(h, z, src);
+    LaunchCtx c = h->ctx();
+    launch_eq_deinterleave(c, h->plain, src, h->eq_up);
+    FOS_HIP(hipMemcpyAsync(z, h->plain, sizeof(double) * 2 * h->l, hipMemcpyDeviceToHost, h->stream));
+    FOS_HIP(hipStreamSynchronize(h->stream));
+    return FOS_OK;
+}
+
 int validate_cones(const char* which, int64_t total, int64_t nK, const int32_t* type, const int64_t* start, const int64_t* len) {
     int64_t prev_end = 0;                                   // cones.jl:66-72
     for (int64_t i = 0; i < nK; ++i) {
@@ -1043,6 +1095,9 @@ void add_cones(int64_t offset, bool is_K1, int64_t nK, const int32_t* type, cons
 }  // namespace
 
 namespace fos {
+int validate_cone_table(const char* which, int64_t total, int64_t nK, const int32_t* type, const int64_t* start, const int64_t* len) {
+    return validate_cones(which, total, nK, type, start, len);
+}
 int long_project_planes(const LaunchCtx& c, LongPlanes& lp, d2* X, int64_t i) {
     const int K = (int)(2 * (lp.nsave + 1)), neq = (int)(lp.nsave + 1), nin = K - neq;
     const int nb = c.vec_blocks;
@@ -1488,6 +1543,72 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     return FOS_OK;
 }
 
+// fos_create2 with opt-in equilibration: the scaling is computed on the host from the caller's CSC arrays (equilibrate.cpp), the handle is built from
+// the SCALED data by the path above, and the vectors the caller's-units kernels read (equilibrate.hip) are added to it.
+int fos_create3(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval,
+                const double* b, const double* c,
+                int64_t nK1, const int32_t* K1type, const int64_t* K1start, const int64_t* K1len,
+                int64_t nK2, const int32_t* K2type, const int64_t* K2start, const int64_t* K2len,
+                int device, int32_t flags, int32_t equil_passes, fos_handle* out) {
+    if (equil_passes == 0) return fos_create2(m, n, colptr, rowval, nzval, b, c, nK1, K1type, K1start, K1len, nK2, K2type, K2start, K2len, device, flags, out);
+    if (!out) { set_error("out handle is NULL"); return FOS_EINVAL; }
+    *out = nullptr;
+    if (equil_passes < 0 || equil_passes > EQ_MAX_PASSES) { set_error("equil_passes = %d: 0 .. %d", (int)equil_passes, EQ_MAX_PASSES); return FOS_EINVAL; }
+    if (flags & FOS_CREATE_ROW_SHARDED) {
+        set_error("equilibration needs the whole problem on one handle: a rank knows neither the other ranks' column norms nor the global sigma, rho");
+        return FOS_EUNSUPPORTED;
+    }
+    EqScaling eq;
+    FOS_TRY(host_equilibrate(m, n, colptr, rowval, nzval, b, c, nK1, K1type, K1start, K1len, nK2, K2type, K2start, K2len, equil_passes, &eq));
+    fos_handle h = nullptr;
+    FOS_TRY(fos_create2(m, n, colptr, rowval, eq.nz.data(), eq.b.data(), eq.c.data(), nK1, K1type, K1start, K1len, nK2, K2type, K2start, K2len, device, flags, &h));
+    struct Guard {
+        fos_solver* h;
+        ~Guard() { if (h) fos_destroy(h); }
+    } guard{h};
+    double nb2 = 0, nc2 = 0;                               // the caller's norms, summed as fos_create2 sums the handle's
+    for (int64_t j = 0; j < n; ++j) nc2 += c[j] * c[j];
+    for (int64_t i = 0; i < m; ++i) nb2 += b[i] * b[i];
+    h->eq_nb = std::sqrt(nb2); h->eq_nc = std::sqrt(nc2);
+    h->eq_sigma = eq.sigma; h->eq_rho = eq.rho; h->eq_gamma = eq.gamma;
+    const size_t l = (size_t)h->l;
+    std::vector<d2> up(l);
+    std::vector<double> inv((size_t)(n + m)), cbv((size_t)(n + m));
+    for (int64_t j = 0; j < n; ++j) {
+        up[j] = make_double2(eq.sigma / eq.E[j], eq.rho * eq.E[j]);
+        inv[j] = 1.0 / eq.E[j];
+        cbv[j] = eq.c[j];
+    }
+    for (int64_t i = 0; i < m; ++i) {
+        up[n + i] = make_double2(eq.rho / eq.D[i], eq.sigma * eq.D[i]);
+        inv[n + i] = 1.0 / eq.D[i];
+        cbv[n + i] = eq.b[i];
+    }
+    up[l - 1] = make_double2(1.0, eq.sigma * eq.rho);
+    for (const d2& u : up)
+        if (!(u.x > 0.0) || !(u.y > 0.0) || !std::isfinite(u.x) || !std::isfinite(u.y)) { set_error("equilibration: a scale factor left the range of fp64"); return FOS_EINVAL; }
+    FOS_TRY(dev_upload(h, &h->eq_up, up));
+    FOS_TRY(dev_upload(h, &h->eq_inv, inv));
+    FOS_TRY(dev_upload(h, &h->eq_cb, cbv));
+    FOS_TRY(dev_alloc(h, &h->eq_w, l));
+    FOS_HIP(hipMemset(h->eq_w, 0, sizeof(double) * l));
+    h->eq_D.swap(eq.D);
+    h->eq_E.swap(eq.E);
+    h->eq_passes = equil_passes;
+    *out = h;
+    guard.h = nullptr;
+    return FOS_OK;
+}
+
+int fos_get_equilibration(fos_handle h, int32_t* passes, double* D, double* E, double* scal3) {
+    if (!h) { set_error("NULL handle"); return FOS_EINVAL; }
+    if (passes) *passes = h->eq_passes;
+    if (D) { if (h->equilibrated()) std::copy(h->eq_D.begin(), h->eq_D.end(), D); else std::fill(D, D + h->m, 1.0); }
+    if (E) { if (h->equilibrated()) std::copy(h->eq_E.begin(), h->eq_E.end(), E); else std::fill(E, E + h->n, 1.0); }
+    if (scal3) { scal3[0] = h->eq_sigma; scal3[1] = h->eq_rho; scal3[2] = h->eq_gamma; }
+    return FOS_OK;
+}
+
 int fos_destroy(fos_handle h) {
     if (!h) return FOS_OK;
     (void)hipSetDevice(h->device);
@@ -1545,7 +1666,7 @@ int fos_reset_affine(fos_handle h) {
 int fos_set_iterate(fos_handle h, const double* z) {
     if (!h) { set_error("NULL handle"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
-    if (z) return upload_plain(h, h->X, z);
+    if (z) return upload_caller(h, h->X, z);
     // HSDE_getinitialvalue: zeros, tau = kappa = 1     HSDE.jl:40-47
     FOS_HIP(hipMemsetAsync(h->X, 0, sizeof(d2) * h->l, h->stream));
     const d2 one = make_double2(1.0, 1.0);
@@ -1557,14 +1678,14 @@ int fos_set_iterate(fos_handle h, const double* z) {
 int fos_get_iterate(fos_handle h, double* z) {
     if (!h || !z) { set_error("NULL argument"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
-    return download_plain(h, z, h->X);
+    return download_caller(h, z, h->X);
 }
 
 int fos_get_checked(fos_handle h, double* z) {
     if (!h || !z) { set_error("NULL argument"); return FOS_EINVAL; }
     if (!h->last_checked) { set_error("no convergence check has run yet"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
-    return download_plain(h, z, h->last_checked);
+    return download_caller(h, z, h->last_checked);
 }
 
 int fos_step(fos_handle h, int64_t i_first, int64_t count, int64_t checki, double eps,
@@ -1683,7 +1804,7 @@ int fos_getsol(fos_handle h, double* z_out, int32_t force_check, double eps, fos
         FOS_TRY(status_check(h, h->T2, eps, res));
         h->last_checked = h->T2;
     }
-    if (z_out) FOS_TRY(download_plain(h, z_out, h->T2));
+    if (z_out) FOS_TRY(download_caller(h, z_out, h->T2));
     FOS_HIP(hipStreamSynchronize(h->stream));
     return FOS_OK;
 }
@@ -1840,7 +1961,7 @@ int fos_prox_cones(fos_handle h, double* y, const double* x) {
 int fos_check(fos_handle h, const double* z, double eps, fos_check_result* res) {
     if (!h || !z || !res) { set_error("NULL argument"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
-    FOS_TRY(upload_plain(h, h->W, z));
+    FOS_TRY(upload_caller(h, h->W, z));
     return status_check(h, h->W, eps, res);
 }
 

@@ -307,8 +307,14 @@ int fos_comm_get_unique_id(void* id128) {
     return FOS_OK;
 }
 
+// an equilibrated handle (fos_create3) cannot be a shard: its scaling came from this handle's data alone
+static int eq_refuse_sharding() {
+    set_error("an equilibrated handle cannot be sharded: a rank knows neither the other ranks' column norms nor the global sigma, rho (create it with equil_passes = 0)");
+    return FOS_EUNSUPPORTED;
+}
 int fos_comm_init(fos_handle h, int nranks, int rank, const void* id128) {
     if (!h || nranks < 1 || rank < 0 || rank >= nranks) { set_error("bad comm arguments"); return FOS_EINVAL; }
+    if (h->equilibrated()) return eq_refuse_sharding();
     if (h->ls_interval > 0 || h->gapp_iproj > 0) { set_error("switch the LineSearchWrapper / GAPP off before sharding the handle (fos_set_linesearch(h, 0), fos_set_gapp(h, 0))"); return FOS_EUNSUPPORTED; }
     FOS_TRY(rccl_load());
     FOS_HIP(hipSetDevice(h->device));
@@ -325,6 +331,7 @@ int fos_comm_init(fos_handle h, int nranks, int rank, const void* id128) {
 // processes (tests/test_gpu_peer_mailbox.py::test_row_sharded_two_processes_host_exchange).
 int fos_comm_init_host(fos_handle h, int nranks, int rank, fos_allreduce_fn fn, void* user) {
     if (!h || !fn || nranks < 1 || rank < 0 || rank >= nranks) { set_error("bad comm arguments"); return FOS_EINVAL; }
+    if (h->equilibrated()) return eq_refuse_sharding();
     if (h->ls_interval > 0 || h->gapp_iproj > 0) { set_error("switch the LineSearchWrapper / GAPP off before sharding the handle (fos_set_linesearch(h, 0), fos_set_gapp(h, 0))"); return FOS_EUNSUPPORTED; }
     Transport& t = h->tr;
     if (t.comm || t.peer_on) { set_error("this handle already has a communicator"); return FOS_EINVAL; }
@@ -355,6 +362,7 @@ int fos_peer_open(fos_handle h, int nranks, int rank, const void* handles, doubl
     if (!h || !handles || nranks < 1 || nranks > PEER_MAX_RANKS || rank < 0 || rank >= nranks) {
         set_error("bad peer arguments (1 <= nranks <= %d)", PEER_MAX_RANKS); return FOS_EINVAL;
     }
+    if (h->equilibrated()) return eq_refuse_sharding();
     Transport& t = h->tr;
     if (!t.peer_mbox) { set_error("fos_peer_open before fos_peer_export"); return FOS_EINVAL; }
     if (!t.peer_opened.empty() || t.peer.box) { set_error("peer mailboxes are already open"); return FOS_EINVAL; }
@@ -388,6 +396,7 @@ int fos_peer_open_host(fos_handle h, int nranks, int rank, const char* shm_name,
     if (!h || !shm_name || shm_name[0] != '/' || nranks < 1 || nranks > PEER_MAX_RANKS || rank < 0 || rank >= nranks) {
         set_error("bad arguments (shm_name \"/...\", 1 <= nranks <= %d)", PEER_MAX_RANKS); return FOS_EINVAL;
     }
+    if (h->equilibrated()) return eq_refuse_sharding();
     Transport& t = h->tr;
     if (!t.peer_opened.empty() || t.peer.box || t.host_seg.p) { set_error("peer mailboxes are already open (fos_peer_close first)"); return FOS_EINVAL; }
     if (h->row_sharded) { set_error("host-pinned mailboxes carry the scalar sums of cone-sharded handles only"); return FOS_EUNSUPPORTED; }

@@ -198,32 +198,70 @@ def direct_factor_code(factor):
     return DIRECT_FACTOR_NAMES.index(factor)
 
 
+EQUILIBRATE_DEFAULT_PASSES = 10
+
+
+def equilibrate_passes(equilibrate):
+    """the `equilibrate` option -> passes of fos_create3: False / None / 0 = off, True = 10 passes, an int = that many"""
+    if equilibrate is None or equilibrate is False:
+        return 0
+    if equilibrate is True:
+        return EQUILIBRATE_DEFAULT_PASSES
+    if not isinstance(equilibrate, (int, np.integer)):
+        raise TypeError("equilibrate must be a bool or a number of passes, not %r" % (equilibrate,))
+    return int(equilibrate)
+
+
+class _KeepAlive(tuple):
+    """a tuple of ctypes arguments that also holds the numpy arrays behind its pointers"""
+
+
+def _problem_args(A, b, c, K1, K2):
+    """(m, n, the leading arguments of fos_create* / fos_host_equilibrate, nnz); the tuple keeps the arrays the pointers refer to alive"""
+    A = sp.csc_matrix(A)                       # loadproblem! sparsifies dense input, FOSSolverInterface.jl:27-29
+    A.sort_indices()
+    m, n = A.shape
+    b = _lib.as_f64(b, m)
+    c = _lib.as_f64(c, n)
+    colptr = np.ascontiguousarray(A.indptr, dtype=np.int64) + 1          # Julia 1-based
+    rowval = np.ascontiguousarray(A.indices, dtype=np.int64) + 1
+    nzval = np.ascontiguousarray(A.data, dtype=np.float64)
+    k1t, k1s, k1l = _normalize_cones(K1, m, "K1")
+    k2t, k2s, k2l = _normalize_cones(K2, n, "K2")
+    i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    args = _KeepAlive((m, n, i64(colptr), i64(rowval), _lib.dptr(nzval), _lib.dptr(b), _lib.dptr(c),
+                       len(k1t), i32(k1t), i64(k1s), i64(k1l), len(k2t), i32(k2t), i64(k2s), i64(k2l)))
+    args.keep = (colptr, rowval, nzval, b, c, k1t, k1s, k1l, k2t, k2s, k2l)
+    return m, n, args, int(A.nnz)
+
+
+def host_equilibrate(A, b, c, K1, K2, passes=EQUILIBRATE_DEFAULT_PASSES):
+    """fos_host_equilibrate: the scaling fos_create3 computes, on the host (no GPU).  Returns dict(passes, D, E, sigma, rho, gamma, A, b, c) with
+    A = D A E (CSC, the pattern of the input), b = sigma D b, c = rho E c."""
+    lib = _lib.load()
+    m, n, args, nnz = _problem_args(A, b, c, K1, K2)
+    D, E, scal, nz, bo, co = np.empty(m), np.empty(n), np.empty(3), np.empty(nnz), np.empty(m), np.empty(n)
+    _lib.check(lib.fos_host_equilibrate(*args, int(passes), _lib.dptr(D), _lib.dptr(E), _lib.dptr(scal), _lib.dptr(nz), _lib.dptr(bo), _lib.dptr(co)))
+    colptr, rowval = args.keep[0], args.keep[1]
+    As = sp.csc_matrix((nz, (rowval - 1).astype(np.int64), (colptr - 1).astype(np.int64)), shape=(m, n))
+    return dict(passes=int(passes), D=D, E=E, sigma=float(scal[0]), rho=float(scal[1]), gamma=float(scal[2]), A=As, b=bo, c=co)
+
+
 class HipHSDE:
     """Owns one fos_handle: the device-resident S1 (AffinePlusLinear over HSDEMatrixQ), S2 (DualConeProduct),
     iterate and algorithm data.  == what init_algorithm!/get_sets_and_status build (FOSSolverInterface.jl:76-79)."""
 
-    def __init__(self, A, b, c, K1, K2, device=0, row_sharded=False):
+    def __init__(self, A, b, c, K1, K2, device=0, row_sharded=False, equilibrate=0):
         """row_sharded (SURVEY 8(f2)): this rank holds the rows of A of its K1 cones and all columns (sharding.shard_rows);
-        follow with comm_init on every rank."""
+        follow with comm_init on every rank.
+        equilibrate: passes (0..50; True = 10) of the opt-in scaling of fos_create3 -- the handle then solves D A E, sigma D b, rho E c; iterates and check
+        results stay in the caller's units, the fine-grained operators speak the scaled problem (include/foship.h)."""
         self._lib = _lib.load()
-        A = sp.csc_matrix(A)                       # loadproblem! sparsifies dense input, FOSSolverInterface.jl:27-29
-        A.sort_indices()
-        m, n = A.shape
+        m, n, args, self.nnz = _problem_args(A, b, c, K1, K2)
         self.m, self.n, self.l, self.N = m, n, m + n + 1, 2 * (m + n + 1)
-        self.nnz = int(A.nnz)
-        b = _lib.as_f64(b, m)
-        c = _lib.as_f64(c, n)
-        colptr = np.ascontiguousarray(A.indptr, dtype=np.int64) + 1          # Julia 1-based
-        rowval = np.ascontiguousarray(A.indices, dtype=np.int64) + 1
-        nzval = np.ascontiguousarray(A.data, dtype=np.float64)
-        k1t, k1s, k1l = _normalize_cones(K1, m, "K1")
-        k2t, k2s, k2l = _normalize_cones(K2, n, "K2")
         h = C.c_void_p()
-        i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        _lib.check(self._lib.fos_create2(m, n, i64(colptr), i64(rowval), _lib.dptr(nzval), _lib.dptr(b), _lib.dptr(c),
-                                         len(k1t), i32(k1t), i64(k1s), i64(k1l),
-                                         len(k2t), i32(k2t), i64(k2s), i64(k2l), device, 1 if row_sharded else 0, C.byref(h)))
+        _lib.check(self._lib.fos_create3(*args, device, 1 if row_sharded else 0, equilibrate_passes(equilibrate), C.byref(h)))
         self._h = h
 
     def close(self):
@@ -236,6 +274,13 @@ class HipHSDE:
             self.close()
         except Exception:
             pass
+
+    def equilibration(self):
+        """fos_get_equilibration: dict(passes, D, E, sigma, rho, gamma); a plain handle reports 0 passes and ones"""
+        p = C.c_int32(0)
+        D, E, scal = np.empty(self.m), np.empty(self.n), np.empty(3)
+        _lib.check(self._lib.fos_get_equilibration(self._h, C.byref(p), _lib.dptr(D), _lib.dptr(E), _lib.dptr(scal)))
+        return dict(passes=int(p.value), D=D, E=E, sigma=float(scal[0]), rho=float(scal[1]), gamma=float(scal[2]))
 
     # -- algorithm / state
     def set_alg(self, alg: FOSAlgorithm):
@@ -705,7 +750,8 @@ class FOSMathProgModel:
         self.K1, self.K2 = list(constr_cones), list(var_cones)
         if self.data is not None:
             self.data.close()
-        self.data = HipHSDE(A, self.b, self.c, self.K1, self.K2, device=self.device)     # init_algorithm!  :58
+        self.data = HipHSDE(A, self.b, self.c, self.K1, self.K2, device=self.device,     # init_algorithm!  :58
+                            equilibrate=self.options.get("equilibrate", 0))              # device-side key, like cg_variant: True = 10 passes, an int = that many
         self.data.set_alg(self.alg)
         if "cg_variant" in self.options:                           # device-side key (the reference ignores unknown option keys):
             self.data.set_cg_variant(self.options["cg_variant"])   # which CG recurrence the affine projection runs (foship.h FOS_CG_*)

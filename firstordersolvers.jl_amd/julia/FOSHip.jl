@@ -68,7 +68,9 @@ mutable struct HipData <: FOSSolverData
     cgiter::Int64
     lsinterval::Int64                     # > 0: LineSearchWrapper around the algorithm [wrappers/linesearch.jl]
     gappinterval::Int64                   # > 0: GAPP, its search interval [solvers/gapproj.jl]
-    function HipData(model::FOSMathProgModel, device::Integer)
+    # equilibrate: the option of the same name (device-side key, like cg_variant) -- false / 0: the problem as given [HSDE.jl:7-29]; true: 10 passes of the opt-in
+    # scaling of fos_create3, an integer 1..50: that many.  Iterates and check results stay in the caller's units (include/foship.h).
+    function HipData(model::FOSMathProgModel, device::Integer; equilibrate=get(model.options, :equilibrate, false))
         A = model.A                       # SparseMatrixCSC{Float64,Int}: colptr/rowval are Int64 and 1-based, as the ABI wants
         m, n = size(A)
         b = convert(Vector{Float64}, vec(model.b))
@@ -76,13 +78,23 @@ mutable struct HipData <: FOSSolverData
         t1, s1, l1 = conearrays(model.K1)
         t2, s2, l2 = conearrays(model.K2)
         h = Ref{Ptr{Cvoid}}(C_NULL)
+        passes = equilibrate === true ? Int32(10) : (equilibrate === false ? Int32(0) : Int32(equilibrate))
         GC.@preserve A b c t1 s1 l1 t2 s2 l2 begin
-            check(ccall((:fos_create, libfoship), Cint,
-                        (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
-                         Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Int64},
-                         Cint, Ref{Ptr{Cvoid}}),
-                        m, n, A.colptr, A.rowval, A.nzval, b, c,
-                        length(t1), t1, s1, l1, length(t2), t2, s2, l2, Cint(device), h))
+            if passes == 0
+                check(ccall((:fos_create, libfoship), Cint,
+                            (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                             Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Int64},
+                             Cint, Ref{Ptr{Cvoid}}),
+                            m, n, A.colptr, A.rowval, A.nzval, b, c,
+                            length(t1), t1, s1, l1, length(t2), t2, s2, l2, Cint(device), h))
+            else
+                check(ccall((:fos_create3, libfoship), Cint,
+                            (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                             Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Int64},
+                             Cint, Int32, Int32, Ref{Ptr{Cvoid}}),
+                            m, n, A.colptr, A.rowval, A.nzval, b, c,
+                            length(t1), t1, s1, l1, length(t2), t2, s2, l2, Cint(device), Int32(0), passes, h))
+            end
         end
         d = new(h[], m, n, 0, 0, 0)
         finalizer(x -> (x.handle != C_NULL && ccall((:fos_destroy, libfoship), Cint, (Ptr{Cvoid},), x.handle); x.handle = C_NULL), d)

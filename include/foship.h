@@ -116,6 +116,34 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
                 int64_t nK1, const int32_t* K1type, const int64_t* K1start, const int64_t* K1len,
                 int64_t nK2, const int32_t* K2type, const int64_t* K2start, const int64_t* K2len,
                 int device, int32_t flags, fos_handle* out);
+/* fos_create2 with OPT-IN EQUILIBRATION (no counterpart in the reference, which takes A, b, c as given: HSDE.jl:7-29).  equil_passes = 0 is fos_create2 to
+ * the letter; 1..50 passes of Ruiz scaling in the infinity norm run on the host and the handle is built from the scaled problem
+ *   A^ = D A E,  b^ = sigma D b,  c^ = rho E c        (D, E > 0 diagonal, CONSTANT over every SOC / SOCRotated / SDP / Exp cone, so K1 and K2 stay in place)
+ * with |A^|_F^2 = min(m, n) (gamma, folded into D) and |b^| = |c^| = 10.  Each pass: A^ = (D A) E from the caller's values, row and column maxima of |A^|
+ * (an empty row / column counts 1), their arithmetic mean over every non-separable cone, D /= sqrt(row maxima), E /= sqrt(column maxima).  The iterates map as
+ *   x = E x^ / sigma,  y = D y^ / rho,  tau = tau^,  r = r^ / (rho E),  s = s^ / (sigma D),  kappa = kappa^ / (sigma rho).
+ * Off by default: on data that is already well scaled it can cost iterations.  Outside 0..50: FOS_EINVAL; with FOS_CREATE_ROW_SHARDED, and fos_comm_init /
+ * fos_comm_init_host / fos_peer_open / fos_peer_open_host on such a handle: FOS_EUNSUPPORTED (a rank knows neither the other ranks' column norms nor the global
+ * sigma, rho).  What an equilibrated handle speaks at each entry point:
+ *   THE CALLER'S UNITS   fos_set_iterate(z != NULL), fos_get_iterate, fos_get_checked, the z_out of fos_getsol, the z of fos_check; every field of
+ *                        fos_check_result from fos_step, fos_getsol and fos_check -- p, d, g, ctx, bty, kappa, tau, norm_axs, norm_aty, norm_b, norm_c and the
+ *                        status are the quantities of HSDEStatus.jl:34-38,53-63 on the caller's A, b, c (one extra kernel per check, csrc/equilibrate.hip)
+ *   THE SCALED PROBLEM   fos_set_iterate(NULL) (its own standard start: zeros, tau^ = kappa^ = 1); fos_q_apply, fos_kkt_apply, fos_cg_kkt, fos_prox_*,
+ *                        fos_hsdematrix_prox; fos_get/set_affine_state, fos_get/set_alg_state; the logs of the wrappers (fos_linesearch_log, ...)
+ *   fos_enable_direct*   receives the CALLER's nzval again and scales it by the stored D, E itself.
+ * fos_get_equilibration: *passes (0 for a plain handle), D (m), E (n) -- either may be NULL; ones for a plain handle --, scal3 = sigma, rho, gamma.
+ * fos_host_equilibrate: the same code path without a GPU or a handle (same validation; passes 1..50): D, E, scal3, and the scaled data nz_out (in the pattern
+ * of colptr / rowval), b_out, c_out; any output may be NULL.  A plain handle created from these outputs takes the same steps as the equilibrated one. */
+int fos_create3(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval,
+                const double* b, const double* c,
+                int64_t nK1, const int32_t* K1type, const int64_t* K1start, const int64_t* K1len,
+                int64_t nK2, const int32_t* K2type, const int64_t* K2start, const int64_t* K2len,
+                int device, int32_t flags, int32_t equil_passes, fos_handle* out);
+int fos_get_equilibration(fos_handle h, int32_t* passes, double* D, double* E, double* scal3);
+int fos_host_equilibrate(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, const double* c,
+                         int64_t nK1, const int32_t* K1type, const int64_t* K1start, const int64_t* K1len,
+                         int64_t nK2, const int32_t* K2type, const int64_t* K2start, const int64_t* K2len,
+                         int32_t passes, double* D, double* E, double* scal3, double* nz_out, double* b_out, double* c_out);
 int fos_destroy(fos_handle h);                             /* Julia finalizer */
 int fos_sizes(fos_handle h, int64_t* m, int64_t* n, int64_t* N, int64_t* nnz);
 
