@@ -15,6 +15,11 @@
 //   * pass 2 (da_cols_kernel): a lane owns two adjacent columns and walks the rows of its row block with d in LDS; with one row block it writes x - sum itself,
 //     otherwise partial[rowblock][column], folded in index order by da_cols_fold_kernel.
 //   A is read exactly once per pass; nothing is atomic; every sum has a fixed order: the same input gives the same bits.
+//
+// LeastSquares(A, b, lambda), f(x) = lambda/2 |A x - b|^2, is the same object with a shifted G: prox_f(x) = x - A'(A A' + I/lambda)^-1 (A x - b) (from
+// lambda A'(A y - b) + y - x = 0 with y = x - A'u), with the rows scaled by D:  x - Ah'(Ah Ah' + D^2/lambda)^-1 (Ah x - D b).  The set-up adds scale[i]^2 / lambda
+// to the diagonal of G (da_shift_diag_kernel) and everything after it is unchanged; refine is 0 (its steps assume A y = b), a zero row keeps scale 1 and a
+// rank-deficient A is accepted (the shifted G is positive definite).  lambda = 0 is IndAffine, to the bit.
 #include "fos_solver.hpp"
 #include "dev_common.hpp"
 
@@ -145,6 +150,11 @@ __global__ __launch_bounds__(DA_T) void da_scale_rows_kernel(int64_t m, int64_t 
     for (int64_t e = blockIdx.x * (int64_t)DA_T + threadIdx.x; e < m * ld; e += (int64_t)gridDim.x * DA_T) A[e] *= scale[e / ld];
 }
 
+// set-up of LeastSquares: G[i, i] += scale[i]^2 / lambda
+__global__ __launch_bounds__(DA_T) void da_shift_diag_kernel(int64_t m, int64_t Lm, double* __restrict__ G, const double* __restrict__ scale, double inv_lambda) {
+    for (int64_t i = blockIdx.x * (int64_t)DA_T + threadIdx.x; i < m; i += (int64_t)gridDim.x * DA_T) G[i + i * Lm] += scale[i] * scale[i] * inv_lambda;
+}
+
 // how the two passes are split, from m, n and the CU count alone
 struct DaPlan {
     int64_t ld = 0, Lm = 0;
@@ -172,20 +182,41 @@ int da_hip(const char* call, hipError_t e) {
     if (e != hipSuccess) { set_error("IndAffine (factored) set-up: %s -> %s", call, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? FOS_ENOMEM : FOS_EHIP; }
     return FOS_OK;
 }
+const char* da_name(double lambda) { return lambda > 0.0 ? "LeastSquares" : "IndAffine (factored)"; }
+// the argument checks both objects share; lambda = 0: IndAffine
+int da_check_shape(int64_t m, int64_t n, bool ptrs, double lambda) {
+    if (!(lambda >= 0.0) || std::fabs(lambda) > 1e300) { set_error("LeastSquares: lambda must be finite and > 0"); return FOS_EINVAL; }
+    if (lambda > 0.0) {
+        if (m < 1 || n < 1 || m > n || !ptrs) {
+            set_error("LeastSquares: bad argument (1 <= m <= n; m > n is not supported on the device: pass an object with a prox(y, x) method, evaluated on the host through fos_feas_set_callback)");
+            return FOS_EINVAL;
+        }
+        if (m > 46000) {
+            set_error("LeastSquares: the inverse of A A' + I/lambda has order m = %lld: supported up to m = 46000 (beyond that: a host prox through fos_feas_set_callback)", (long long)m);
+            return FOS_EUNSUPPORTED;
+        }
+        return FOS_OK;
+    }
+    if (m < 1 || n < 1 || m > n || !ptrs) { set_error("IndAffine (factored): bad argument (1 <= m <= n)"); return FOS_EINVAL; }
+    if (m > 46000) { set_error("IndAffine (factored): the inverse of A A' has order m = %lld: supported up to m = 46000", (long long)m); return FOS_EUNSUPPORTED; }
+    return FOS_OK;
+}
 
-// validation and row scaling shared by the device set-up and the host emulation: scale[i] = 1 / |A[i, :]|, bs = scale .* b
-int da_scaling(int64_t m, int64_t n, const double* A, const double* b, std::vector<double>& scale, std::vector<double>& bs) {
+// validation and row scaling shared by the device set-up and the host emulation: scale[i] = 1 / |A[i, :]|, bs = scale .* b.  lambda > 0 (LeastSquares): a zero
+// row is legal and keeps scale 1
+int da_scaling(int64_t m, int64_t n, const double* A, const double* b, double lambda, std::vector<double>& scale, std::vector<double>& bs) {
+    const char* what = da_name(lambda);
     scale.assign((size_t)m, 0.0); bs.assign((size_t)m, 0.0);
     for (int64_t i = 0; i < m; ++i) {
         double s2 = 0.0;
         for (int64_t j = 0; j < n; ++j) {
             const double v = A[i * n + j];
-            if (!(v == v) || std::fabs(v) > 1e300) { set_error("IndAffine (factored): A has non-finite entries"); return FOS_EINVAL; }
+            if (!(v == v) || std::fabs(v) > 1e300) { set_error("%s: A has non-finite entries", what); return FOS_EINVAL; }
             s2 += v * v;
         }
-        if (!(s2 > 0.0)) { set_error("IndAffine (factored): row %lld of A is zero (A must have full row rank)", (long long)i + 1); return FOS_EINVAL; }
-        if (!(b[i] == b[i]) || std::fabs(b[i]) > 1e300) { set_error("IndAffine (factored): b has non-finite entries"); return FOS_EINVAL; }
-        scale[(size_t)i] = 1.0 / std::sqrt(s2);
+        if (!(s2 > 0.0) && !(lambda > 0.0)) { set_error("IndAffine (factored): row %lld of A is zero (A must have full row rank)", (long long)i + 1); return FOS_EINVAL; }
+        if (!(b[i] == b[i]) || std::fabs(b[i]) > 1e300) { set_error("%s: b has non-finite entries", what); return FOS_EINVAL; }
+        scale[(size_t)i] = s2 > 0.0 ? 1.0 / std::sqrt(s2) : 1.0;
         bs[(size_t)i] = b[i] * scale[(size_t)i];
     }
     return FOS_OK;
@@ -223,14 +254,15 @@ int da_alloc(DenseAffine* a, double** out, size_t count) {
 }
 }  // namespace
 
-// A: m x n ROW-major, b[m]; factor: FOS_DIRECT_FACTOR_*; refine: 0..2 refinement steps per projection.  Synchronises `stream`.
-int dense_affine_setup(int64_t m, int64_t n, const double* A, const double* b, int factor, int refine, int cus, hipStream_t stream, DenseAffine** out) {
-    if (m < 1 || n < 1 || m > n || !A || !b) { set_error("IndAffine (factored): bad argument (1 <= m <= n)"); return FOS_EINVAL; }
-    if (m > 46000) { set_error("IndAffine (factored): the inverse of A A' has order m = %lld: supported up to m = 46000", (long long)m); return FOS_EUNSUPPORTED; }
+// A: m x n ROW-major, b[m]; lambda: 0: IndAffine(A, b), > 0: LeastSquares(A, b, lambda) (refine is then 0); factor: FOS_DIRECT_FACTOR_*; refine: 0..2 refinement
+// steps per projection.  Synchronises `stream`.
+int dense_affine_setup(int64_t m, int64_t n, const double* A, const double* b, double lambda, int factor, int refine, int cus, hipStream_t stream, DenseAffine** out) {
+    FOS_TRY(da_check_shape(m, n, A && b, lambda));
+    if (lambda > 0.0) refine = 0;
     if (refine < 0 || refine > 2) { set_error("IndAffine (factored): refine = %d (0, 1 or 2 refinement steps per projection)", refine); return FOS_EINVAL; }
-    if (factor != FOS_DIRECT_FACTOR_NEWTON && factor != FOS_DIRECT_FACTOR_CHOLESKY) { set_error("IndAffine (factored): factor must be FOS_DIRECT_FACTOR_NEWTON or FOS_DIRECT_FACTOR_CHOLESKY"); return FOS_EINVAL; }
+    if (factor != FOS_DIRECT_FACTOR_NEWTON && factor != FOS_DIRECT_FACTOR_CHOLESKY) { set_error("%s: factor must be FOS_DIRECT_FACTOR_NEWTON or FOS_DIRECT_FACTOR_CHOLESKY", da_name(lambda)); return FOS_EINVAL; }
     std::vector<double> scale, bs;
-    FOS_TRY(da_scaling(m, n, A, b, scale, bs));
+    FOS_TRY(da_scaling(m, n, A, b, lambda, scale, bs));
     DenseAffine* a = new DenseAffine();
     a->m = m; a->n = n; a->refine = refine; a->p = da_plan(m, n, cus);
     const DaPlan& p = a->p;
@@ -252,14 +284,16 @@ int dense_affine_setup(int64_t m, int64_t n, const double* A, const double* b, i
         DenseWork w;
         w.c.stream = stream; w.c.l = m; w.L = p.Lm; w.G = a->G;
         launch_dense_gram_rows(w.c, m, p.ld, a->A, p.Lm, a->G);
+        if (lambda > 0.0)                                      // (the row scales are still in a->t)
+            hipLaunchKernelGGL(da_shift_diag_kernel, dim3((unsigned)std::min<int64_t>(256, (m + DA_T - 1) / DA_T)), dim3(DA_T), 0, stream, m, p.Lm, a->G, (const double*)a->t, 1.0 / lambda);
         Scratch s;
         w.fill(s);
         if (s.err != hipSuccess) { (void)hipGetLastError(); set_error("IndAffine (factored): hipMalloc of the set-up buffers (3 x %zu bytes) failed: %s", L2 * 8, hipGetErrorString(s.err)); return fail(FOS_ENOMEM); }
         double* X = nullptr;
-        DenseOpts o{"IndAffine (factored)", "A A'", factor, false};
+        DenseOpts o{da_name(lambda), lambda > 0.0 ? "A A' + I/lambda" : "A A'", factor, false};
         o.bar = DA_BAR; o.newton_extra = 40;               // cond(A A') up to ~1e8: ceil(log2 cond) + 7 steps at most, each of the extra ones checked
         rc = dense_spd_inverse(w, o, &X, &a->inv);
-        if (rc == FOS_EINVAL) {
+        if (rc == FOS_EINVAL && !(lambda > 0.0)) {
             const std::string why = fos_last_error();
             set_error("IndAffine (factored): the inverse of A A' (rows scaled to unit norm) was not accepted: A needs full row rank  [%s]", why.c_str());
         }
@@ -381,11 +415,13 @@ int host_da_inverse(const char* what, int64_t m, const double* G, double* X) {
 
 // the same scaling, host_chol_inverse for X (accepted by the probe of dense_spd_inverse at DA_BAR, evaluated on the host), and the two passes with the split and
 // the summation order the kernels have for this (m, n) on a device of 256 CUs
-int host_affine_factored(int64_t m, int64_t n, const double* A, const double* b, int refine, const double* x, double* y) {
-    if (m < 1 || n < 1 || m > n || !A || !b || !x || !y) { set_error("IndAffine (factored): bad argument (1 <= m <= n)"); return FOS_EINVAL; }
+// lambda > 0: LeastSquares(A, b, lambda) -- the diagonal of G shifted as in the set-up, refine = 0
+int host_affine_factored(int64_t m, int64_t n, const double* A, const double* b, double lambda, int refine, const double* x, double* y) {
+    FOS_TRY(da_check_shape(m, n, A && b && x && y, lambda));
+    if (lambda > 0.0) refine = 0;
     if (refine < 0 || refine > 2) { set_error("IndAffine (factored): refine = %d (0, 1 or 2 refinement steps per projection)", refine); return FOS_EINVAL; }
     std::vector<double> scale, bs;
-    FOS_TRY(da_scaling(m, n, A, b, scale, bs));
+    FOS_TRY(da_scaling(m, n, A, b, lambda, scale, bs));
     const DaPlan p = da_plan(m, n, 256);
     std::vector<double> As((size_t)m * (size_t)p.ld, 0.0), G((size_t)m * (size_t)m), X((size_t)m * (size_t)m);
     for (int64_t i = 0; i < m; ++i)
@@ -396,7 +432,9 @@ int host_affine_factored(int64_t m, int64_t n, const double* A, const double* b,
             for (int64_t k = 0; k < p.ld; ++k) s += As[(size_t)(i * p.ld + k)] * As[(size_t)(j * p.ld + k)];
             G[(size_t)(i + j * m)] = s; G[(size_t)(j + i * m)] = s;
         }
-    FOS_TRY(host_da_inverse("IndAffine (factored)", m, G.data(), X.data()));
+    if (lambda > 0.0)
+        for (int64_t i = 0; i < m; ++i) G[(size_t)(i + i * m)] += scale[(size_t)i] * scale[(size_t)i] * (1.0 / lambda);
+    FOS_TRY(host_da_inverse(da_name(lambda), m, G.data(), X.data()));
     std::vector<double> r((size_t)m), d((size_t)m), e((size_t)m), part((size_t)std::max(p.nspan, p.nrb));
     auto residual = [&](const double* vin) {                         // da_rows_kernel + da_rows_fold_kernel
         for (int64_t i = 0; i < m; ++i) {

@@ -589,7 +589,7 @@ int fos_feas_set_affine_factored(fos_feas_handle h, int32_t which, int64_t m, co
     if (!h || which < 1 || which > 2 || m < 1 || m > h->n) { set_error("fos_feas_set_affine_factored: bad argument (1 <= m <= n, which = 1 | 2)"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
     DenseAffine* da = nullptr;
-    FOS_TRY(dense_affine_setup(m, h->n, A, b, factor, refine, h->cus, h->stream, &da));       // (synchronises the stream: no projection onto the set being replaced runs any more)
+    FOS_TRY(dense_affine_setup(m, h->n, A, b, 0.0, factor, refine, h->cus, h->stream, &da));       // (synchronises the stream: no projection onto the set being replaced runs any more)
     FeasSet& s = h->S[which - 1];
     dense_affine_destroy(s.da);
     s.da = da; s.kind = 7;
@@ -607,7 +607,24 @@ int fos_feas_affine_factored_plan(fos_feas_handle h, int32_t which, int64_t* out
 }
 // test-only, host: the factored form's scaling, inverse and two passes in the kernels' order (affine_dense.hip)
 int fos_host_affine_factored(int64_t m, int64_t n, const double* A, const double* b, int32_t refine, const double* x, double* y) {
-    return host_affine_factored(m, n, A, b, refine, x, y);
+    return host_affine_factored(m, n, A, b, 0.0, refine, x, y);
+}
+// LeastSquares(A, b, lambda), A dense m x n ROW-major: the factored form with the diagonal of A A' shifted by 1 / lambda (affine_dense.hip); the same object
+// kind, so the stats and the plan of the factored form describe it.  Built first, so that a refused call leaves the set as it was
+int fos_feas_set_least_squares(fos_feas_handle h, int32_t which, int64_t m, const double* A, const double* b, double lambda, int32_t factor) {
+    if (!h || which < 1 || which > 2) { set_error("fos_feas_set_least_squares: NULL handle or which not in {1, 2}"); return FOS_EINVAL; }
+    if (!(lambda > 0.0) || lambda > 1e300) { set_error("LeastSquares: lambda must be finite and > 0"); return FOS_EINVAL; }
+    FOS_HIP(hipSetDevice(h->device));
+    DenseAffine* da = nullptr;
+    FOS_TRY(dense_affine_setup(m, h->n, A, b, lambda, factor, 0, h->cus, h->stream, &da));    // (synchronises the stream, as above)
+    FeasSet& s = h->S[which - 1];
+    dense_affine_destroy(s.da);
+    s.da = da; s.kind = 7;
+    return FOS_OK;
+}
+int fos_host_least_squares(int64_t m, int64_t n, const double* A, const double* b, double lambda, const double* x, double* y) {
+    if (!(lambda > 0.0) || lambda > 1e300) { set_error("LeastSquares: lambda must be finite and > 0"); return FOS_EINVAL; }
+    return host_affine_factored(m, n, A, b, lambda, 0, x, y);
 }
 
 // IndAffine(A, b), A sparse m x n (CSC, 1-based), factored form (affine_sparse_factored.hip): built first, so that a refused call leaves the set as it was

@@ -709,12 +709,12 @@ void sparse_affine_stats(const SparseAffine* a, double* out8);
 void sparse_affine_destroy(SparseAffine* a);
 // IndAffine(A, b) with a dense A, factored form (affine_dense.hip): A kept once, (A A')^-1 of order m, two passes over A per projection
 struct DenseAffine;
-int dense_affine_setup(int64_t m, int64_t n, const double* A, const double* b, int factor, int refine, int cus, hipStream_t stream, DenseAffine** out);
+int dense_affine_setup(int64_t m, int64_t n, const double* A, const double* b, double lambda, int factor, int refine, int cus, hipStream_t stream, DenseAffine** out);
 int dense_affine_project(DenseAffine* a, hipStream_t stream, double* y, const double* x);        // y, x: device vectors of length n, y must not alias x
 void dense_affine_stats(const DenseAffine* a, double* out8);
 void dense_affine_plan(const DenseAffine* a, int64_t* out6);
 void dense_affine_destroy(DenseAffine* a);
-int host_affine_factored(int64_t m, int64_t n, const double* A, const double* b, int refine, const double* x, double* y);
+int host_affine_factored(int64_t m, int64_t n, const double* A, const double* b, double lambda, int refine, const double* x, double* y);
 // the m-space product of the factored forms (da_symv_kernel): out = add + sign M v, M symmetric column-major of order l, leading dimension ld (add == nullptr: 0;
 // out may be add); the same on the host in the kernel's order, the host's wave_sum tree, and the host's accepted inverse of G (order m, unpadded; `what` in the message)
 void launch_da_symv(hipStream_t s, int64_t l, int64_t ld, const double* M, const double* v, const double* add, double sign, double* out);

@@ -21,6 +21,12 @@
 //   A pass divides the width by THR_C + 1 = 33 = 2^5.04, the first width is <= a, so after 10 narrowing passes it is <= 2^-50.4 a and the 11th pass
 //   finishes: THR_CAP = ceil(52 / log2(THR_C + 1)) = 11.  thr_decide ends the search at the cap in any case (NaN data cannot spin).
 // fos_host_set_project runs the same steps on the CPU (the same inline functions; lane-strided partial sums combined in the kernels' order).
+//
+// Proximable functions that are not indicators (FOS_FN_*, numbered from 32; the step is 1 as in prox!(y, S, x)) are further kinds of the same three classes:
+//   elementwise   NormL1 (soft threshold), SqrNormL2 (x / (1 + lambda)), ElasticNet (both), Linear (x - c)
+//   one reduction NormL2 and HuberLoss on |x|_2, the shape of IndBallL2
+//   threshold     NormLinf: prox = x - P_{|.|_1 <= lambda}(x) = sign(x) min(|x|, tau) with IndBallL1's tau for the radius lambda
+// A decision is 0 (apply the formula), 1 (y = x, the same bits) or 2 (y = 0).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,36 +52,72 @@ constexpr int THR_CAP = 11;                   // ceil(52 / log2(THR_C + 1))
 struct SetBlock {
     int64_t start, len;
     int32_t kind, pad;
-    double s0, s1;          // r, - | a, - | lo, hi (IndHalfspace: -inf, b) | IndBox lo, hi
-    double aa;              // <a, a> of a halfspace / hyperslab
+    double s0, s1;          // r, - | a, - | lo, hi (IndHalfspace: -inf, b) | IndBox lo, hi | lambda, - | ElasticNet mu, lambda | HuberLoss rho, mu
+    double aa;              // <a, a> of a halfspace / hyperslab | 1 / (1 + lambda) of SqrNormL2 and ElasticNet, 1 / (1 + mu) of HuberLoss
 };
 
 // ------------------------------------------------------------------------------------------ the formulas, shared by the kernels and the host emulation
-__host__ __device__ inline bool set_is_threshold(int kind) { return kind == FOS_SET_BALL_L1 || kind == FOS_SET_SIMPLEX; }
-__host__ __device__ inline bool set_is_scalar(int kind) { return kind == FOS_SET_BALL_L2 || kind == FOS_SET_HALFSPACE || kind == FOS_SET_HYPERSLAB; }
-// the summand of the one reduction a set needs: |x - c|^2, <a, x>, |x|_1
+// Kind tests are one shift of a constant bit set, not a chain of comparisons: the chain `kind == FOS_SET_BALL_L1 || kind == FOS_FN_NORM_LINF` becomes a two-case
+// switch whose gfx950 code lost the fabs of set_thr_value for FOS_SET_BALL_L1 (the optimised IR is right, the emitted code is not); a shift has no control
+// flow to lower.  Kinds are validated (set_block_make) to lie in 0..63.
+#define SET_BIT(k) (1ull << (k))
+__host__ __device__ inline bool set_kind_in(int kind, unsigned long long mask) { return (mask >> (kind & 63)) & 1ull; }
+__host__ __device__ inline bool set_is_threshold(int kind) { return set_kind_in(kind, SET_BIT(FOS_SET_BALL_L1) | SET_BIT(FOS_SET_SIMPLEX) | SET_BIT(FOS_FN_NORM_LINF)); }
+__host__ __device__ inline bool set_is_scalar(int kind) {
+    return set_kind_in(kind, SET_BIT(FOS_SET_BALL_L2) | SET_BIT(FOS_SET_HALFSPACE) | SET_BIT(FOS_SET_HYPERSLAB) | SET_BIT(FOS_FN_NORM_L2) | SET_BIT(FOS_FN_HUBER));
+}
+__host__ __device__ inline bool set_thr_abs(int kind) { return set_kind_in(kind, SET_BIT(FOS_SET_BALL_L1) | SET_BIT(FOS_FN_NORM_LINF)); }      // the search runs on |x|, after a test of |x|_1
+__host__ __device__ inline bool set_reads_vec(int kind) {
+    return set_kind_in(kind, SET_BIT(FOS_SET_BALL_L2) | SET_BIT(FOS_SET_HALFSPACE) | SET_BIT(FOS_SET_HYPERSLAB) | SET_BIT(FOS_SET_POINT) | SET_BIT(FOS_FN_LINEAR));
+}
+// the summand of the one reduction a set needs: |x - c|^2, <a, x>, |x|_1, |x|^2
 __host__ __device__ inline double set_term(int kind, double xi, double vi) {
     if (kind == FOS_SET_BALL_L2) { const double d = xi - vi; return d * d; }
     if (kind == FOS_SET_HALFSPACE || kind == FOS_SET_HYPERSLAB) return vi * xi;
-    if (kind == FOS_SET_BALL_L1) return fabs(xi);
+    if (set_thr_abs(kind)) return fabs(xi);
+    if (kind == FOS_FN_NORM_L2 || kind == FOS_FN_HUBER) return xi * xi;
     return 0.0;
 }
-__host__ __device__ inline double set_thr_value(int kind, double xi) { return kind == FOS_SET_BALL_L1 ? fabs(xi) : xi; }
+__host__ __device__ inline double set_thr_value(int kind, double xi) { return set_thr_abs(kind) ? fabs(xi) : xi; }
 
-struct SetDecision { int copy; double p0; };      // copy: y = x, the same bits; p0: the scale r / |d|, the step along the normal, the threshold
+// copy: 1: y = x, the same bits; 2: y = 0; 0: the formula with p0: the scale r / |d|, the step along the normal, the threshold, the shrink factor
+struct SetDecision { int copy; double p0; };
+// from the block's one sum s (set_term); a threshold kind that comes back with copy == 0 goes on to its search
 __host__ __device__ inline SetDecision set_decide_scalar(const SetBlock& b, double s) {
     SetDecision d{1, 0.0};
-    if (b.kind == FOS_SET_BALL_L2) {
+    switch (b.kind) {
+    case FOS_SET_BALL_L2: {
         const double nd = sqrt(s);
         if (!(nd <= b.s0)) { d.copy = 0; d.p0 = b.s0 / nd; }
-    } else {                                                       // towards whichever side is violated
+        break;
+    }
+    case FOS_SET_HALFSPACE:
+    case FOS_SET_HYPERSLAB:                                        // towards whichever side is violated
         if (s > b.s1) { d.copy = 0; d.p0 = (s - b.s1) / b.aa; }
         else if (s < b.s0) { d.copy = 0; d.p0 = (s - b.s0) / b.aa; }
+        break;
+    case FOS_SET_BALL_L1: d.copy = s <= b.s0; break;
+    case FOS_FN_NORM_LINF: d.copy = b.s0 == 0.0 ? 1 : s <= b.s0 ? 2 : 0; break;       // lambda = 0: f = 0; |x|_1 <= lambda: x is its own projection onto the ball
+    case FOS_FN_NORM_L2: {
+        const double nd = sqrt(s);
+        if (b.s0 == 0.0) break;
+        if (nd <= b.s0) d.copy = 2;
+        else { d.copy = 0; d.p0 = 1.0 - b.s0 / nd; }
+        break;
+    }
+    case FOS_FN_HUBER: {
+        const double nd = sqrt(s);
+        d.copy = 0;
+        d.p0 = nd <= b.s0 * (1.0 + b.s1) ? b.aa : 1.0 - b.s0 * b.s1 / nd;
+        break;
+    }
+    default: d.copy = b.kind == FOS_SET_FREE; break;               // no reduction: IndSimplex goes to its search, the elementwise kinds to set_apply
     }
     return d;
 }
+__host__ __device__ inline double set_soft(double xi, double t) { const double m = fabs(xi) - t; return copysign(m > 0.0 ? m : 0.0, xi); }
 __host__ __device__ inline double set_apply(const SetBlock& b, int copy, double p0, double xi, double vi) {
-    if (copy) return xi;
+    if (copy) return copy == 1 ? xi : 0.0;
     switch (b.kind) {
     case FOS_SET_BALL_L2: return vi + (xi - vi) * p0;
     case FOS_SET_BALL_L1: { const double m = fabs(xi) - p0; return copysign(m > 0.0 ? m : 0.0, xi); }
@@ -84,6 +126,13 @@ __host__ __device__ inline double set_apply(const SetBlock& b, int copy, double 
     case FOS_SET_HYPERSLAB: return xi - p0 * vi;
     case FOS_SET_POINT: return vi;
     case FOS_SET_BOX: return fmin(fmax(xi, b.s0), b.s1);
+    case FOS_FN_NORM_L1: return set_soft(xi, b.s0);                 // (lambda = 0: copysign(|x|, x), the same bits)
+    case FOS_FN_SQR_NORM_L2: return xi * b.aa;
+    case FOS_FN_ELASTIC_NET: return set_soft(xi, b.s0) * b.aa;
+    case FOS_FN_LINEAR: return xi - vi;
+    case FOS_FN_NORM_L2:
+    case FOS_FN_HUBER: return xi * p0;
+    case FOS_FN_NORM_LINF: return copysign(fmin(fabs(xi), p0), xi);
     default: return xi;                                            // FOS_SET_FREE
     }
 }
@@ -189,26 +238,26 @@ struct TeamValues<NT, 0> {
 template <int NT, int NV>
 __device__ __forceinline__ void set_block_onchip(const SetBlock& b, const double* __restrict__ x, const double* __restrict__ vec, double* __restrict__ y,
                                                  int32_t* __restrict__ passes, int t, double* sm, double* lds) {
-    const int len = (int)b.len, kind = b.kind;
+    const int len = (int)b.len, kind = __builtin_amdgcn_readfirstlane(b.kind);      // one block per team: the kind tests become scalar branches
     const double* vb = vec ? vec + b.start : nullptr;
     double* yb = y + b.start;
     TeamValues<NT, NV> xv;
     xv.load(x + b.start, len, t, lds);
-    int copy = kind == FOS_SET_FREE, npass = 0;
-    double p0 = 0.0;
-    if (set_is_scalar(kind) || kind == FOS_SET_BALL_L1) {
-        double s[1] = {0.0};
+    int npass = 0;
+    double s[1] = {0.0};
+    if (set_is_scalar(kind) || set_thr_abs(kind)) {
         xv.each(len, t, [&](int i, double xi) { s[0] += set_term(kind, xi, vb ? vb[i] : 0.0); });
         team_sum<NT, 1>(s, sm);
-        if (kind == FOS_SET_BALL_L1) copy = s[0] <= b.s0;
-        else { const SetDecision d = set_decide_scalar(b, s[0]); copy = d.copy; p0 = d.p0; }
     }
+    const SetDecision d = set_decide_scalar(b, s[0]);
+    const int copy = d.copy;
+    double p0 = d.p0;
     if (set_is_threshold(kind) && !copy) {
         double m = -INFINITY;
         xv.each(len, t, [&](int, double xi) { m = fmax(m, set_thr_value(kind, xi)); });
         m = team_max<NT>(m, sm);
         ThrState st;
-        thr_init(st, m, b.s0, (double)len, kind == FOS_SET_BALL_L1);
+        thr_init(st, m, b.s0, (double)len, set_thr_abs(kind));
         while (!st.done) {                                         // at most THR_CAP passes (thr_decide)
             double acc[THR_NACC];
 #pragma unroll
@@ -220,7 +269,7 @@ __device__ __forceinline__ void set_block_onchip(const SetBlock& b, const double
         }
         p0 = st.tau; npass = st.passes;
     }
-    const bool needs_vec = !copy && vb && (kind == FOS_SET_BALL_L2 || kind == FOS_SET_HALFSPACE || kind == FOS_SET_HYPERSLAB || kind == FOS_SET_POINT);
+    const bool needs_vec = !copy && vb && set_reads_vec(kind);
     xv.each(len, t, [&](int i, double xi) { yb[i] = set_apply(b, copy, p0, xi, needs_vec ? vb[i] : 0.0); });
     if (t == 0) *passes = npass;
 }
@@ -291,17 +340,12 @@ __global__ __launch_bounds__(64) void sets_grid_decide_kernel(SetBlock b, const 
     for (int r = lane; r < nparts; r += 64) { s += partials[2 * r]; m = fmax(m, partials[2 * r + 1]); }
     s = wave_sum(s); m = wave_max(m);
     if (lane != 0) return;
-    double done = 1.0, copy = 0.0, p0 = 0.0, lo = 0.0, hi = 0.0, scale = 0.0;
-    if (set_is_threshold(b.kind)) {
-        if (b.kind == FOS_SET_BALL_L1 && s <= b.s0) copy = 1.0;
-        else {
-            ThrState st;
-            thr_init(st, m, b.s0, (double)b.len, b.kind == FOS_SET_BALL_L1);
-            done = 0.0; lo = st.lo; hi = st.hi; scale = st.scale; p0 = st.tau;
-        }
-    } else {
-        const SetDecision d = set_decide_scalar(b, s);
-        copy = d.copy; p0 = d.p0;
+    const SetDecision d = set_decide_scalar(b, s);
+    double done = 1.0, copy = d.copy, p0 = d.p0, lo = 0.0, hi = 0.0, scale = 0.0;
+    if (set_is_threshold(b.kind) && !d.copy) {
+        ThrState st;
+        thr_init(st, m, b.s0, (double)b.len, set_thr_abs(b.kind));
+        done = 0.0; lo = st.lo; hi = st.hi; scale = st.scale; p0 = st.tau;
     }
     gs[GS_DONE] = done; gs[GS_COPY] = copy; gs[GS_P0] = p0; gs[GS_LO] = lo; gs[GS_HI] = hi; gs[GS_PASSES] = 0.0; gs[GS_SCALE] = scale;
 }
@@ -350,10 +394,10 @@ __global__ __launch_bounds__(SET_THREADS) void sets_grid_pass_decide_kernel(SetB
     thr_decide(st, red, b.s0);
     gs[GS_LO] = st.lo; gs[GS_HI] = st.hi; gs[GS_P0] = st.tau; gs[GS_PASSES] = (double)st.passes; gs[GS_DONE] = st.done ? 1.0 : 0.0;
 }
-// gs == nullptr: a set without a reduction (IndFree, IndPoint, IndBox)
+// gs == nullptr: a kind without a reduction (IndFree, IndPoint, IndBox, the elementwise functions)
 __global__ __launch_bounds__(SET_THREADS) void sets_grid_apply_kernel(SetBlock b, const double* __restrict__ x, const double* __restrict__ vec,
                                                                       double* __restrict__ y, const double* __restrict__ gs) {
-    const int copy = gs ? (gs[GS_COPY] != 0.0) : (b.kind == FOS_SET_FREE);
+    const int copy = gs ? (int)gs[GS_COPY] : (b.kind == FOS_SET_FREE);
     const double p0 = gs ? gs[GS_P0] : 0.0;
     set_grid_for(b.start, b.len, [&](int64_t i, bool two) {
         const double2 xx = set_ld2(x, i, two), vv = set_ld2(vec, i, two);
@@ -376,8 +420,11 @@ struct SetBlocks {
 
 namespace {
 
+bool set_kind_is_fn(int kind) { return kind >= FOS_FN_NORM_L1 && kind <= FOS_FN_NORM_LINF; }
 const char* set_kind_name(int kind) {
     static const char* names[] = {"IndFree", "IndBallL2", "IndBallL1", "IndSimplex", "IndHalfspace", "IndHyperslab", "IndPoint", "IndBox"};
+    static const char* fn_names[] = {"NormL1", "SqrNormL2", "ElasticNet", "Linear", "NormL2", "HuberLoss", "NormLinf"};
+    if (set_kind_is_fn(kind)) return fn_names[kind - FOS_FN_NORM_L1];
     return kind >= 0 && kind <= FOS_SET_BOX ? names[kind] : "?";
 }
 bool is_fin(double v) { return v == v && std::fabs(v) <= 1.79e308; }
@@ -392,13 +439,13 @@ int set_grid_size(int64_t len) { return (int)std::min<int64_t>(SET_PARTS, (len +
 
 // one block's parameters -> its descriptor; `blk` (1-based) names it in the message
 int set_block_make(int64_t blk, int32_t kind, int64_t start, int64_t len, const double* scal2, const double* vec, SetBlock* out) {
-    if (kind < FOS_SET_FREE || kind > FOS_SET_BOX) { set_error("set block %lld: unknown kind %d (FOS_SET_*)", (long long)blk, (int)kind); return FOS_EINVAL; }
+    if ((kind < FOS_SET_FREE || kind > FOS_SET_BOX) && !set_kind_is_fn(kind)) { set_error("set block %lld: unknown kind %d (FOS_SET_*, FOS_FN_*)", (long long)blk, (int)kind); return FOS_EINVAL; }
     if (len < 1) { set_error("set block %lld (%s): length %lld < 1", (long long)blk, set_kind_name(kind), (long long)len); return FOS_EINVAL; }
     SetBlock b{};
     b.start = start; b.len = len; b.kind = kind; b.s0 = scal2[0]; b.s1 = scal2[1]; b.aa = 0.0;
-    const bool needs_vec = kind == FOS_SET_HALFSPACE || kind == FOS_SET_HYPERSLAB || kind == FOS_SET_POINT;
+    const bool needs_vec = set_reads_vec(kind) && kind != FOS_SET_BALL_L2;                // (a ball without a centre is around the origin)
     if (needs_vec && !vec) { set_error("set block %lld (%s): the vector argument is required", (long long)blk, set_kind_name(kind)); return FOS_EINVAL; }
-    if (vec && (needs_vec || kind == FOS_SET_BALL_L2)) {
+    if (vec && set_reads_vec(kind)) {
         for (int64_t i = 0; i < len; ++i) if (!is_fin(vec[start + i])) { set_error("set block %lld (%s): entry %lld of its vector is not finite", (long long)blk, set_kind_name(kind), (long long)i + 1); return FOS_EINVAL; }
     }
     switch (kind) {
@@ -417,6 +464,15 @@ int set_block_make(int64_t blk, int32_t kind, int64_t start, int64_t len, const 
     case FOS_SET_BOX:
         if (!(b.s0 <= b.s1)) { set_error("set block %lld (IndBox): lo <= hi is required", (long long)blk); return FOS_EINVAL; }
         break;
+    case FOS_FN_NORM_L1: case FOS_FN_SQR_NORM_L2: case FOS_FN_NORM_L2: case FOS_FN_NORM_LINF:
+        if (!is_fin(b.s0) || b.s0 < 0.0) { set_error("set block %lld (%s): lambda must be finite and >= 0", (long long)blk, set_kind_name(kind)); return FOS_EINVAL; }
+        b.s1 = 0.0; b.aa = 1.0 / (1.0 + b.s0); break;
+    case FOS_FN_ELASTIC_NET:
+        if (!is_fin(b.s0) || b.s0 < 0.0 || !is_fin(b.s1) || b.s1 < 0.0) { set_error("set block %lld (ElasticNet): mu and lambda must be finite and >= 0", (long long)blk); return FOS_EINVAL; }
+        b.aa = 1.0 / (1.0 + b.s1); break;
+    case FOS_FN_HUBER:
+        if (!is_fin(b.s0) || !(b.s0 > 0.0) || !is_fin(b.s1) || b.s1 < 0.0) { set_error("set block %lld (HuberLoss): rho must be finite and > 0, mu finite and >= 0", (long long)blk); return FOS_EINVAL; }
+        b.aa = 1.0 / (1.0 + b.s1); break;
     default: b.s0 = b.s1 = 0.0; break;
     }
     if (kind == FOS_SET_HALFSPACE || kind == FOS_SET_HYPERSLAB) {
@@ -463,7 +519,7 @@ int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int6
         SetBlock b;
         const int rc = set_block_make(i + 1, kind[i], pos, len[i], scal + 2 * i, vec, &b);
         if (rc != FOS_OK) return fail(rc);
-        any_vec = any_vec || b.kind == FOS_SET_BALL_L2 || b.kind == FOS_SET_HALFSPACE || b.kind == FOS_SET_HYPERSLAB || b.kind == FOS_SET_POINT;
+        any_vec = any_vec || set_reads_vec(b.kind);
         if (b.len <= SET_WAVE_MAX) wave_ids.push_back((int32_t)i);
         else if (b.len <= SET_WG_MAX) { wg_ids.push_back((int32_t)i); p->wg_lds = std::max(p->wg_lds, sizeof(double) * (size_t)b.len); }
         else {
@@ -571,21 +627,22 @@ int fos_host_set_project(int32_t kind, int64_t len, const double* scal2, const d
     FOS_TRY(set_block_make(1, kind, 0, len, scal2, vec, &b));
     const int64_t T = len <= SET_WAVE_MAX ? 64 : len <= SET_WG_MAX ? SET_THREADS : (int64_t)set_grid_size(len) * SET_THREADS;
     auto V = [&](int64_t i) { return vec ? vec[i] : 0.0; };
-    int copy = kind == FOS_SET_FREE, npass = 0;
-    double p0 = 0.0;
+    int npass = 0;
+    double s = 0.0;
     std::vector<double> lane;
-    if (set_is_scalar(kind) || kind == FOS_SET_BALL_L1) {
+    if (set_is_scalar(kind) || set_thr_abs(kind)) {
         lane.assign((size_t)T, 0.0);
         for (int64_t i = 0; i < len; ++i) lane[(size_t)(i % T)] += set_term(kind, x[i], V(i));
-        const double s = host_combine(lane, T, 1, 0);
-        if (kind == FOS_SET_BALL_L1) copy = s <= b.s0;
-        else { const SetDecision d = set_decide_scalar(b, s); copy = d.copy; p0 = d.p0; }
+        s = host_combine(lane, T, 1, 0);
     }
+    const SetDecision d = set_decide_scalar(b, s);
+    const int copy = d.copy;
+    double p0 = d.p0;
     if (set_is_threshold(kind) && !copy) {
         double mx = -INFINITY;
         for (int64_t i = 0; i < len; ++i) mx = std::fmax(mx, set_thr_value(kind, x[i]));
         ThrState st;
-        thr_init(st, mx, b.s0, (double)len, kind == FOS_SET_BALL_L1);
+        thr_init(st, mx, b.s0, (double)len, set_thr_abs(kind));
         while (!st.done) {
             lane.assign((size_t)T * THR_NACC, 0.0);
             for (int64_t i = 0; i < len; ++i) thr_accumulate(set_thr_value(kind, x[i]), st.lo, st.hi, *reinterpret_cast<double(*)[THR_NACC]>(&lane[(size_t)(i % T) * THR_NACC]));

@@ -1031,10 +1031,117 @@ class IndFree(_VectorSet):
     kind = "IndFree"
 
 
+# Proximable functions that are not indicators, on the same kernels (kind codes _lib.FN_CODES, from 32): the block's "projection" is prox_f(x), step 1.
+
+def _nonneg_scalar(name, v):
+    v = _finite_scalar(name, v)
+    if v < 0.0:
+        raise ValueError("%s >= 0 is required" % name)
+    return v
+
+
+class _ProxFunction(_VectorSet):
+    """One block of a SeparableSum that is a function: `kind` is a key of _lib.FN_CODES."""
+
+    def _block(self, length):
+        if self.vec is not None and self.vec.shape[0] != length:
+            raise ValueError("%s: its vector has %d entries, the block has %d" % (self.kind, self.vec.shape[0], length))
+        return _lib.FN_CODES[self.kind], self.scal, self.vec
+
+
+class NormL1(_ProxFunction):
+    """f(x) = lam |x|_1.  y = sign(x) max(|x| - lam, 0)."""
+    kind = "NormL1"
+
+    def __init__(self, lam=1.0):
+        self.lam = _nonneg_scalar("NormL1: lam", lam)
+        self.scal = (self.lam, 0.0)
+
+
+class SqrNormL2(_ProxFunction):
+    """f(x) = lam/2 |x|_2^2.  y = x / (1 + lam)."""
+    kind = "SqrNormL2"
+
+    def __init__(self, lam=1.0):
+        self.lam = _nonneg_scalar("SqrNormL2: lam", lam)
+        self.scal = (self.lam, 0.0)
+
+
+class ElasticNet(_ProxFunction):
+    """f(x) = mu |x|_1 + lam/2 |x|_2^2.  y = sign(x) max(|x| - mu, 0) / (1 + lam)."""
+    kind = "ElasticNet"
+
+    def __init__(self, mu=1.0, lam=1.0):
+        self.mu, self.lam = _nonneg_scalar("ElasticNet: mu", mu), _nonneg_scalar("ElasticNet: lam", lam)
+        self.scal = (self.mu, self.lam)
+
+
+class Linear(_ProxFunction):
+    """f(x) = <c, x>.  y = x - c."""
+    kind = "Linear"
+
+    def __init__(self, c):
+        self.c = self.vec = _finite_vector("Linear: c", c)
+
+
+class NormL2(_ProxFunction):
+    """f(x) = lam |x|_2.  y = max(0, 1 - lam / |x|) x; zeros when |x| <= lam."""
+    kind = "NormL2"
+
+    def __init__(self, lam=1.0):
+        self.lam = _nonneg_scalar("NormL2: lam", lam)
+        self.scal = (self.lam, 0.0)
+
+
+class HuberLoss(_ProxFunction):
+    """f(x) = mu/2 |x|^2 if |x|_2 <= rho, else rho mu (|x| - rho/2).  y = x / (1 + mu) if |x| <= rho (1 + mu), else (1 - rho mu / |x|) x."""
+    kind = "HuberLoss"
+
+    def __init__(self, rho=1.0, mu=1.0):
+        self.rho, self.mu = _finite_scalar("HuberLoss: rho", rho), _nonneg_scalar("HuberLoss: mu", mu)
+        if not self.rho > 0.0:
+            raise ValueError("HuberLoss: rho > 0 is required")
+        self.scal = (self.rho, self.mu)
+
+
+class NormLinf(_ProxFunction):
+    """f(x) = lam |x|_inf.  y = x - P(x), P the projection onto {|.|_1 <= lam}: zeros when |x|_1 <= lam, else sign(x) min(|x|, tau) with IndBallL1(lam)'s tau."""
+    kind = "NormLinf"
+
+    def __init__(self, lam=1.0):
+        self.lam = _nonneg_scalar("NormLinf: lam", lam)
+        self.scal = (self.lam, 0.0)
+
+
+class LeastSquares:
+    """f(x) = lam/2 |A x - b|^2 with a dense A (m x n, 1 <= m <= n, m <= 46 000; rank-deficient and zero rows allowed), lam > 0.  The prox
+    y = x - A'(A A' + I/lam)^-1 (A x - b) runs on the factored form of IndAffine with the diagonal of A A' shifted (fos_feas_set_least_squares): two passes
+    over A per prox, a fixed number of launches.  factor = "cholesky" | "newton" builds the inverse.  m > n, m > 46 000 or a sparse A: pass an object with
+    a prox(y, x) method instead (the host-callback path)."""
+
+    MAX_M = 46000
+
+    def __init__(self, A, b, lam=1.0, factor="cholesky"):
+        self.lam = _finite_scalar("LeastSquares: lam", lam)
+        if not self.lam > 0.0:
+            raise ValueError("LeastSquares: lam > 0 is required")
+        direct_factor_code(factor)
+        self.factor = factor
+        if sp.issparse(A):
+            raise ValueError("LeastSquares: A must be dense (a sparse A: an object with a prox(y, x) method, evaluated on the host)")
+        self.A = np.ascontiguousarray(np.asarray(A, dtype=np.float64))
+        self.b = np.ascontiguousarray(np.asarray(b, dtype=np.float64))
+        if self.A.ndim != 2 or self.A.shape[0] < 1 or self.b.shape != (self.A.shape[0],):
+            raise ValueError("LeastSquares(A, b): A must be m x n and b of length m")
+        if not (np.all(np.isfinite(self.A)) and np.all(np.isfinite(self.b))):
+            raise ValueError("LeastSquares(A, b): A and b must be finite")
+
+
 class SeparableSum:
     """The analogue of ProximalOperators.SlicedSeparableSum over index ranges, in the style of ConeProduct: blocks = [(set, length), ...], contiguous, in
-    order, together covering 1..n.  A set is one of IndBallL2, IndBallL1, IndSimplex, IndHalfspace, IndHyperslab, IndPoint, IndFree or an IndBox with
-    scalar bounds (cones stay in ConeProduct).  A bare set used as S1 or S2 is the one-block case of length n."""
+    order, together covering 1..n.  A set is one of IndBallL2, IndBallL1, IndSimplex, IndHalfspace, IndHyperslab, IndPoint, IndFree, an IndBox with
+    scalar bounds (cones stay in ConeProduct), or one of the functions NormL1, SqrNormL2, ElasticNet, Linear, NormL2, HuberLoss, NormLinf, whose block
+    is their prox; sets and functions mix freely.  A bare set or function used as S1 or S2 is the one-block case of length n."""
 
     def __init__(self, blocks):
         self.blocks = []
@@ -1048,7 +1155,7 @@ class SeparableSum:
                 if not S.lo <= S.hi:
                     raise ValueError("SeparableSum: block %d: IndBox needs lo <= hi" % (len(self.blocks) + 1))
             elif not isinstance(S, _VectorSet):
-                raise ValueError("SeparableSum: block %d is %s: not one of the vector sets of the device path" % (len(self.blocks) + 1, type(S).__name__))
+                raise ValueError("SeparableSum: block %d is %s: not one of the vector sets or functions of the device path" % (len(self.blocks) + 1, type(S).__name__))
             else:
                 S._block(length)                                       # (the length of its vector)
             self.blocks.append((S, length))
@@ -1080,7 +1187,9 @@ PROX_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C
 
 class Feasibility:
     """struct Feasibility{T1,T2}(S1, S2, n)   Feasibility.jl:2-6.  S1, S2: IndAffine, IndBox, ConeProduct, a vector set (IndBallL2, IndBallL1,
-    IndSimplex, IndHalfspace, IndHyperslab, IndPoint, IndFree) or a SeparableSum of them (all device resident), or any
+    IndSimplex, IndHalfspace, IndHyperslab, IndPoint, IndFree), a separable function (NormL1, SqrNormL2, ElasticNet, Linear, NormL2, HuberLoss,
+    NormLinf) or a SeparableSum of them, LeastSquares(A, b, lam) with a dense A (all device resident: Feasibility(LeastSquares(A, b, lam), NormL1(mu), n)
+    under DR is the lasso, with no host round trip), or any
     object with a `prox(y, x)` method filling y = prox_S(x) in place (the ProximableFunction protocol; evaluated on the host)."""
 
     def __init__(self, S1, S2, n):
@@ -1118,8 +1227,12 @@ class HipFeasibility:
                 self.set_set(which, S)
 
     def set_set(self, which, S):
-        """set `which` (1 | 2) becomes S: an IndAffine, IndBox, ConeProduct or an object with a prox(y, x) method; replaces what was there"""
-        if isinstance(S, IndAffine):
+        """set `which` (1 | 2) becomes S: an IndAffine, LeastSquares, IndBox, ConeProduct or an object with a prox(y, x) method; replaces what was there"""
+        if isinstance(S, LeastSquares):
+            if S.A.shape[1] != self.n:
+                raise ValueError("LeastSquares: A has %d columns, the problem has n = %d" % (S.A.shape[1], self.n))
+            _lib.check(self._lib.fos_feas_set_least_squares(self._h, which, S.A.shape[0], _lib.dptr(S.A), _lib.dptr(S.b), S.lam, direct_factor_code(S.factor)))
+        elif isinstance(S, IndAffine):
             if S.A.shape[1] != self.n:
                 raise ValueError("IndAffine: A has %d columns, the problem has n = %d" % (S.A.shape[1], self.n))
             if S.form == "factored":
@@ -1283,7 +1396,7 @@ class HipFeasibility:
                 "last_rounding_level": o[5], "nnz": int(o[6]), "lanes_per_row": (int(o[7]) // 1000, int(o[7]) % 1000)}
 
     def affine_factored_stats(self, which):
-        """the factored IndAffine's set-up record and the split of its two passes (fos_feas_affine_factored_stats, fos_feas_affine_factored_plan)"""
+        """the factored IndAffine's (or LeastSquares') set-up record and the split of its two passes (fos_feas_affine_factored_stats, fos_feas_affine_factored_plan)"""
         o, p = np.zeros(8), np.zeros(6, dtype=np.int64)
         _lib.check(self._lib.fos_feas_affine_factored_stats(self._h, which, _lib.dptr(o)))
         _lib.check(self._lib.fos_feas_affine_factored_plan(self._h, which, p.ctypes.data_as(C.POINTER(C.c_int64))))

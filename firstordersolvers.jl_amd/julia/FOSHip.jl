@@ -321,8 +321,9 @@ end
 
 # ---- Feasibility form [problemforms/Feasibility/Feasibility.jl, FeasibilityStatus.jl]: solve!(Feasibility(S1, S2, n), alg; gpu=true)
 #      with S1, S2 among ProximalOperators.IndAffine (dense A), IndBox -- the sets of test/testfeasibility.jl -- and
-#      FirstOrderSolvers.ConeProduct on the device, as are IndBallL2, IndBallL1, IndSimplex, IndHalfspace, IndHyperslab, IndPoint and IndFree
-#      (fos_feas_set_blocks); any other ProximableFunction through a host callback (fos_feas_set_callback).
+#      FirstOrderSolvers.ConeProduct on the device, as are IndBallL2, IndBallL1, IndSimplex, IndHalfspace, IndHyperslab, IndPoint and IndFree,
+#      the functions NormL1, SqrNormL2, ElasticNet, Linear, NormL2, HuberLoss, NormLinf (fos_feas_set_blocks) and LeastSquares over a dense A
+#      (fos_feas_set_least_squares); any other ProximableFunction through a host callback (fos_feas_set_callback).
 #      init_algorithm! returns a HipFeasData; iterate dispatches on it; FeasibilityModel, populate_solution and the printed table
 #      stay the reference's own code.
 import ..FirstOrderSolvers: FeasibilityModel, FeasibilityStatus
@@ -349,7 +350,22 @@ const FOS_SET_HALFSPACE = Int32(4)
 const FOS_SET_HYPERSLAB = Int32(5)
 const FOS_SET_POINT = Int32(6)
 const FOS_SET_BOX = Int32(7)
+# proximable functions that are not indicators: further kinds of the same entry (prox with step 1)
+const FOS_FN_NORM_L1 = Int32(32)
+const FOS_FN_SQR_NORM_L2 = Int32(33)
+const FOS_FN_ELASTIC_NET = Int32(34)
+const FOS_FN_LINEAR = Int32(35)
+const FOS_FN_NORM_L2 = Int32(36)
+const FOS_FN_HUBER = Int32(37)
+const FOS_FN_NORM_LINF = Int32(38)
 vectorset_block(S) = nothing
+vectorset_block(S::ProximalOperators.NormL1{<:Real}) = (FOS_FN_NORM_L1, Float64(S.lambda), 0.0, nothing)
+vectorset_block(S::ProximalOperators.SqrNormL2{<:Real}) = (FOS_FN_SQR_NORM_L2, Float64(S.lambda), 0.0, nothing)
+vectorset_block(S::ProximalOperators.ElasticNet) = (FOS_FN_ELASTIC_NET, Float64(S.mu), Float64(S.lambda), nothing)
+vectorset_block(S::ProximalOperators.Linear) = (FOS_FN_LINEAR, 0.0, 0.0, Vector{Float64}(vec(S.c)))
+vectorset_block(S::ProximalOperators.NormL2) = (FOS_FN_NORM_L2, Float64(S.lambda), 0.0, nothing)
+vectorset_block(S::ProximalOperators.HuberLoss) = (FOS_FN_HUBER, Float64(S.rho), Float64(S.mu), nothing)
+vectorset_block(S::ProximalOperators.Conjugate{<:ProximalOperators.IndBallL1}) = (FOS_FN_NORM_LINF, Float64(S.f.r), 0.0, nothing)      # NormLinf(lambda)
 vectorset_block(S::ProximalOperators.IndFree) = (FOS_SET_FREE, 0.0, 0.0, nothing)
 vectorset_block(S::ProximalOperators.IndBallL2) = (FOS_SET_BALL_L2, Float64(S.r), 0.0, nothing)
 vectorset_block(S::ProximalOperators.IndBallL1) = (FOS_SET_BALL_L1, Float64(S.r), 0.0, nothing)
@@ -393,6 +409,21 @@ function feas_affine_sparse_factored_stats(handle::Ptr{Cvoid}, which::Integer)
     return (m = Int(out[1]), n = Int(out[2]), refine = Int(out[3]), factor = out[4] == 1 ? :cholesky : :newton, fell_back = out[5] != 0, probe_resid = out[6],
             launches = Int(out[7]), bytes = Int(out[8]), nnz = plan[1], gram_order = plan[2], seg = plan[3], items_rows = plan[4], folded_rows = plan[5],
             items_cols = plan[6], folded_cols = plan[7], segments = plan[8])
+end
+# LeastSquares(A, b, lambda) over a dense A (1 <= m <= n, m <= 46 000): the factored form with the diagonal of A A' shifted by 1 / lambda
+function feas_set_least_squares!(handle::Ptr{Cvoid}, which::Integer, A::AbstractMatrix, b::AbstractVector, lambda::Real, factor::Symbol = :cholesky)
+    At = Matrix{Float64}(transpose(A))                      # the C ABI takes A row-major = column-major A'
+    bv = Vector{Float64}(b)
+    GC.@preserve At bv check(ccall((:fos_feas_set_least_squares, libfoship), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Int32),
+                                   handle, Int32(which), Int64(size(A, 1)), At, bv, Float64(lambda), factor == :newton ? Int32(0) : Int32(1)))
+end
+# test entry: the host emulation of the LeastSquares prox (no GPU needed)
+function host_least_squares(A::Matrix{Float64}, b::Vector{Float64}, lambda::Real, x::Vector{Float64})
+    At = Matrix{Float64}(transpose(A))
+    y = similar(x)
+    check(ccall((:fos_host_least_squares, libfoship), Cint, (Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}),
+                Int64(size(A, 1)), Int64(size(A, 2)), At, b, Float64(lambda), x, y))
+    return y
 end
 # test entry: the host emulation of the sparse factored IndAffine (no GPU needed)
 function host_affine_sparse_factored(A::SparseArrays.SparseMatrixCSC{Float64,Int64}, b::Vector{Float64}, refine::Integer, x::Vector{Float64})
@@ -461,7 +492,9 @@ mutable struct HipFeasData <: FOSSolverData
                 GC.@preserve As b check(ccall((:fos_feas_set_affine_sparse, libfoship), Cint,
                                               (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}),
                                               d.handle, which, Int64(size(As, 1)), As.colptr, As.rowval, As.nzval, b))
-            elseif vectorset_block(S) !== nothing           # a ball, simplex, halfspace, hyperslab, point or the free set: one block of length n
+            elseif S isa ProximalOperators.LeastSquares && hasproperty(S, :A) && S.A isa Matrix && hasproperty(S, :lambda) && size(S.A, 1) <= min(size(S.A, 2), 46000)
+                feas_set_least_squares!(d.handle, which, S.A, S.b, S.lambda, get(model.options, :affine_factor, :cholesky))      # wider, taller or sparse A: the callback below
+            elseif vectorset_block(S) !== nothing           # a ball, simplex, halfspace, hyperslab, point, the free set or a separable function: one block of length n
                 feas_set_blocks!(d.handle, which, model.n, [(vectorset_block(S)..., Int64(model.n))])
             else                                            # any other ProximableFunction: prox!(y, S, x) on host vectors [Feasibility.jl:2-6]
                 push!(d.sets, Ref{Any}(S))                  # (rooted: the library keeps a pointer to it)

@@ -496,7 +496,9 @@ int fos_debug_set(fos_handle h, int32_t what, int64_t value);
  *                        loudly (FOS_EINVAL) when that level cannot be reached (A without full row rank).  fos_feas_affine_stats: iteration counts.
  *   fos_feas_set_box     IndBox(lo, hi), scalar bounds (fos_feas_set_box_arrays: array bounds), +-INFINITY allowed;
  *   fos_feas_set_cones   the reference's own ConeProduct (src/cones.jl), any of its nine cone types;
- *   fos_feas_set_blocks  norm balls, simplex, halfspace / hyperslab, point, free and scalar box, alone or as a separable sum of blocks.
+ *   fos_feas_set_blocks  norm balls, simplex, halfspace / hyperslab, point, free and scalar box, and the separable functions NormL1, SqrNormL2, ElasticNet,
+ *                        Linear, NormL2, HuberLoss, NormLinf, alone or as a separable sum of blocks;
+ *   fos_feas_set_least_squares   lambda/2 |A x - b|^2 over a dense A, on the factored form.
  * `which` = 1 | 2 (S1, S2).  Steps: gap.jl:42-87 (GAP / DR / AP), gapa.jl:61-112, fista.jl:28-56, dykstra.jl:25-44; LineSearchWrapper. */
 typedef struct fos_feas* fos_feas_handle;
 int fos_feas_create(int64_t n, int32_t device, fos_feas_handle* out);
@@ -519,6 +521,15 @@ int fos_feas_affine_factored_plan(fos_feas_handle h, int32_t which, int64_t* out
 /* Test-only host emulation of the factored form (no GPU needed): the same scaling, the blocked Cholesky inverse of fos_host_chol_inverse accepted by the same probe,
  * and the two passes with the kernels' split and summation order for this (m, n) on 256 CUs.  x, y: n-vectors. */
 int fos_host_affine_factored(int64_t m, int64_t n, const double* A, const double* b, int32_t refine, const double* x, double* y);
+/* LeastSquares(A, b, lambda): f(x) = lambda/2 |A x - b|^2, A dense m x n ROW-major, 1 <= m <= min(n, 46000), lambda > 0 finite; not an indicator, and the prox
+ * (step 1) is  y = x - A'(A A' + I/lambda)^-1 (A x - b):  the factored IndAffine above with the diagonal of G shifted.  With the rows scaled by D (unit norm; a
+ * zero row is legal here and keeps scale 1) that is  y = x - Ah'(Ah Ah' + D^2/lambda)^-1 (Ah x - D b): one small kernel adds scale[i]^2 / lambda to the diagonal
+ * of G, and the inverse, the two passes, the launch count and the plan are those of fos_feas_set_affine_factored with refine = 0 (the refinement steps assume
+ * A y = b).  The shifted G is positive definite: a rank-deficient A is accepted.  fos_feas_affine_factored_stats / _plan describe the object.  m > n: FOS_EINVAL,
+ * m > 46000: FOS_EUNSUPPORTED (the alternative is a host prox through fos_feas_set_callback). */
+int fos_feas_set_least_squares(fos_feas_handle h, int32_t which, int64_t m, const double* A, const double* b, double lambda, int32_t factor);
+/* Test-only host emulation (no GPU needed): fos_host_affine_factored's steps with the same shift. */
+int fos_host_least_squares(int64_t m, int64_t n, const double* A, const double* b, double lambda, const double* x, double* y);
 /* IndAffine(A, b), A SPARSE m x n (CSC, 1-based, as fos_feas_set_affine_sparse; row indices strictly ascending inside a column), full row rank,
  * 1 <= m <= min(n, 46000), any n: the FACTORED form of the sparse set (opt-in; fos_feas_set_affine_sparse keeps the conjugate gradients).  The rows of [A | b] are
  * scaled to unit norm, A and A' are kept as two CSR matrices, G = A A' (dense, order m rounded up to 64) is formed on the device and inverted once (factor:
@@ -552,7 +563,7 @@ int fos_feas_set_cones(fos_feas_handle h, int32_t which, int64_t ncones, const i
 typedef int32_t (*fos_prox_fn)(void* ctx, int64_t n, const double* x, double* y);
 int fos_feas_set_callback(fos_feas_handle h, int32_t which, fos_prox_fn fn, void* ctx);
 /* Separable sums of convex vector sets on the device (Feasibility.jl:2-6 takes any two ProximableFunctions; these no longer need the callback):
- * nblocks contiguous blocks, in order, covering 1..n (the shape of SlicedSeparableSum); block i is the set kind[i] (FOS_SET_*) on len[i] entries.
+ * nblocks contiguous blocks, in order, covering 1..n (the shape of SlicedSeparableSum); block i is the set kind[i] (FOS_SET_*, or a function FOS_FN_*) on len[i] entries.
  *   scal[2 i], scal[2 i + 1]   r, - (IndBallL2, IndBallL1: |x - c|_2 <= r, |x|_1 <= r, r >= 0) | a, - (IndSimplex: x >= 0, sum x = a, a > 0) |
  *                              b, - (IndHalfspace: <a, x> <= b) | lo, hi (IndHyperslab: lo <= <a, x> <= hi; IndBox: lo <= x <= hi, +-INFINITY allowed)
  *   vec (n entries or NULL)    the centre / normal / point of each block AT THAT BLOCK'S OWN INDICES; ignored where a kind has none; NULL: all centres
@@ -569,6 +580,18 @@ int fos_feas_set_callback(fos_feas_handle h, int32_t which, fos_prox_fn fn, void
 #define FOS_SET_HYPERSLAB  5   /* IndHyperslab(lo, a, hi)  */
 #define FOS_SET_POINT      6   /* IndPoint(p)              */
 #define FOS_SET_BOX        7   /* IndBox(lo, hi), scalars  */
+/* Proximable functions that are not indicators, as further block kinds (numbered from 32; 8..31 are unknown kinds), alone or mixed with FOS_SET_* blocks; the
+ * block's "projection" is prox_f(x) with step 1, as prox!(y, S, x).  Parameters finite and >= 0 (rho > 0), validated like the sets'.
+ *   scal[2 i], scal[2 i + 1]   lambda, - (NormL1, SqrNormL2, NormL2, NormLinf) | mu, lambda (ElasticNet) | rho, mu (HuberLoss) | -, - (Linear: c in vec, required)
+ * Where the definition gives y = x (lambda = 0, c = 0) the result is x bit for bit; where it gives 0, exact zeros.  Launches of a grid-class block: NormL1,
+ * SqrNormL2, ElasticNet, Linear 1; NormL2, HuberLoss 3 (as IndBallL2); NormLinf 3 + 2 x the pass cap (as IndBallL1, whose threshold it shares). */
+#define FOS_FN_NORM_L1     32  /* NormL1(lambda): lambda |x|_1                  y = sign(x) max(|x| - lambda, 0)                               */
+#define FOS_FN_SQR_NORM_L2 33  /* SqrNormL2(lambda): lambda/2 |x|^2             y = x / (1 + lambda)                                           */
+#define FOS_FN_ELASTIC_NET 34  /* ElasticNet(mu, lambda): mu |x|_1 + lambda/2 |x|^2   y = soft(x, mu) / (1 + lambda)                           */
+#define FOS_FN_LINEAR      35  /* Linear(c): <c, x>                             y = x - c                                                      */
+#define FOS_FN_NORM_L2     36  /* NormL2(lambda): lambda |x|_2                  y = max(0, 1 - lambda / |x|) x                                 */
+#define FOS_FN_HUBER       37  /* HuberLoss(rho, mu)                            y = x / (1 + mu) if |x| <= rho (1 + mu), else (1 - rho mu / |x|) x */
+#define FOS_FN_NORM_LINF   38  /* NormLinf(lambda): lambda |x|_inf              y = x - P_{|.|_1 <= lambda}(x) = sign(x) min(|x|, tau)         */
 int fos_feas_set_blocks(fos_feas_handle h, int32_t which, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec);
 /* out8 = blocks, blocks of the wavefront / workgroup / grid class, kernel launches of one projection, threshold passes the last projection needed
  * (IndSimplex, IndBallL1: max over the blocks), the pass cap, candidates per pass.  FOS_EINVAL unless `which` was set by fos_feas_set_blocks. */
