@@ -1,6 +1,6 @@
 // Device side of an equilibrated handle (fos_create3, equil_passes > 0): the handle solves the scaled problem A^ = D A E, b^ = sigma D b,
 // c^ = rho E c; these three kernels are where the caller's units meet it.
-//   eq_status        the six sums of checkstatus (HSDEStatus.jl:34-38,59,61) ON THE CALLER'S A, b, c, formed from the scaled iterate and w = Q^ u^
+//   eq_status        the six sums of checkstatus (HSDEStatus.jl:34-38,59,61) ON THE CALLER'S A, b, c, formed from the scaled iterate and w = Q^ [x^; y^; 0]
 //   eq_interleave    fos_set_iterate / fos_check: plain z in the caller's units -> interleaved scaled iterate
 //   eq_deinterleave  fos_get_iterate / fos_get_checked / fos_getsol: the way back
 // All three are streams over l = n + m + 1 elements.  The sums have a fixed order (lane -> wavefront -> workgroup -> the records in
@@ -16,11 +16,14 @@ namespace fos {
 
 constexpr int EQ_FIN_THREADS = 1024;
 
-// w: plain l-vector, rows 0 .. n+m-1 of Q^ [x^; y^; tau] -- w_x = A^'y^ + c^ tau, w_y = b^ tau - A^ x^ (launch_q1, Q_PLAIN); cb = [c^; b^];
-// inv = [1 ./ E; 1 ./ D].  With x = E x^ / sigma, y = D y^ / rho, r = r^ / (rho E), s = s^ / (sigma D):
-//   A x + s          = D^-1 (b^ tau - w_y + s^) / sigma              A'y               = E^-1 (w_x - c^ tau) / rho
-//   (A x + s)/tau - b = D^-1 (s^ - w_y) / (sigma tau)                 (A'y - r)/tau + c = E^-1 (w_x - r^) / (rho tau)
-// the scalars sigma, rho, tau are applied by the host (solver.cpp eq_status_check).  Records: partials[block][6] in StatusIdx order.
+// w: plain l-vector, rows 0 .. n+m-1 of Q^ [x^; y^; 0] -- w_x = A^'y^, w_y = -A^ x^ (launch_q1, Q_PLAIN_NOTAU: the tau entry taken as zero, so that
+// no c^ tau or b^ tau is added here only to be subtracted again: at a large tau that cost ||A x + s|| and ||A'y|| their digits); cb = [c^; b^];
+// inv = [1 ./ E; 1 ./ D].  With x = E x^ / sigma, y = D y^ / rho, r = r^ / (rho E), s = s^ / (sigma D), b = D^-1 b^ / sigma, c = E^-1 c^ / rho:
+//   A x + s           = D^-1 (s^ - w_y) / sigma                        A'y               = E^-1 w_x / rho
+//   (A x + s)/tau - b = D^-1 ((-w_y / tau + s^ / tau) - b^) / sigma     (A'y - r)/tau + c = E^-1 ((w_x / tau + c^) - r^ / tau) / rho
+// term by term the reference's A x / tau + s / tau - b and A'y / tau + c - r / tau (HSDEStatus.jl:34-35), each row times a positive factor: at tau = 0
+// a row is +-Inf or NaN exactly where the reference's is, so p and d carry its Inf / NaN pattern; tau < 0 enters with its sign, as there.
+// The scalars sigma and rho are applied by the host (solver.cpp eq_status_check).  Records: partials[block][6] in StatusIdx order.
 __global__ __launch_bounds__(EQ_THREADS) void eq_status_kernel(int64_t n, int64_t nm, const d2* __restrict__ z, const double* __restrict__ w,
                                                                const double* __restrict__ cb, const double* __restrict__ inv,
                                                                double* __restrict__ partials) {
@@ -31,14 +34,14 @@ __global__ __launch_bounds__(EQ_THREADS) void eq_status_kernel(int64_t n, int64_
         const d2 zi = z[i];
         const double wi = w[i], c = cb[i], e = inv[i];
         if (i < n) {                       // zi = (x^_i, r^_i), c = c^_i, e = 1 / E_i
-            const double rd = e * (wi - zi.y);
-            const double aty = e * (wi - c * tau);
+            const double rd = e * ((wi / tau + c) - zi.y / tau);
+            const double aty = e * wi;
             acc[ST_RD2] += rd * rd;
             acc[ST_ATY2] += aty * aty;
             acc[ST_CTX] += c * zi.x;
         } else {                           // zi = (y^_j, s^_j), c = b^_j, e = 1 / D_j
-            const double rp = e * (zi.y - wi);
-            const double axs = e * ((c * tau - wi) + zi.y);
+            const double rp = e * ((zi.y / tau - wi / tau) - c);
+            const double axs = e * (zi.y - wi);
             acc[ST_RP2] += rp * rp;
             acc[ST_AXS2] += axs * axs;
             acc[ST_BTY] += c * zi.x;

@@ -536,7 +536,8 @@ bool res_lds_fits(const ResLaunch& rl, int device, std::string* why);
 //   Q_PLAIN : out_plain[i] = sign * (Q v)_i            (rows 0..n+m-1; tau row by q1_finalize)
 //   Q_RHS   : out[i] = (x[i].x - (Q x.y)_i, 0)         (affinepluslinear.jl:94-95 with beta=1, q=0, b=0)
 //   Q_STATUS: residual sums of checkstatus             (HSDEStatus.jl:34-38,59,61)
-enum QMode { Q_PLAIN = 0, Q_RHS = 1, Q_STATUS = 2, Q_VFROMU = 3 };
+//   Q_PLAIN_NOTAU : Q_PLAIN with the tau entry of v taken as zero: out_plain = sign * [A'v_y; -A v_x], no c tau / b tau term (no finalize)
+enum QMode { Q_PLAIN = 0, Q_RHS = 1, Q_STATUS = 2, Q_VFROMU = 3, Q_PLAIN_NOTAU = 4 };
 void launch_q1(const LaunchCtx& c, QMode mode, const double2* v, int comp, double sign, void* out);
 void launch_q1_finalize(const LaunchCtx& c, QMode mode, const double2* v, int comp, double sign, void* out, int from_reduced);
 

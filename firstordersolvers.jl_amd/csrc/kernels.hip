@@ -1410,8 +1410,8 @@ struct EpiQPlain {
     __device__ __forceinline__ void acc_restore(const AccKeep& k) { for (int a = 0; a < 1; ++a) acc[a] = k.v[a]; }
     static constexpr bool FOLDDEF = false;
     __device__ __forceinline__ void park(int, double, double, const d2&) {}     // out_plain[i] = sign * (Q v)_i ; acc[0] = [c;b].v
-    const double* vcomp; double* out; const double* cb; int n; double vt, sign; double acc[1];
-    __device__ __forceinline__ void init(double vtau) { vt = vtau; }
+    const double* vcomp; double* out; const double* cb; int n; double vt, sign; double acc[1]; bool notau;
+    __device__ __forceinline__ void init(double vtau) { vt = notau ? 0.0 : vtau; }       // notau: Q [v_x; v_y; 0], rows A'v_y and -A v_x alone
     __device__ __forceinline__ RowPre pre(int i) const { return RowPre{make_double2(vcomp[2 * (int64_t)i], 0.0), cb[i]}; }
     __device__ __forceinline__ void row(int i, double u, double, const RowPre& pr) {
         const double c = pr.c;
@@ -1579,8 +1579,8 @@ __global__ __launch_bounds__(FIN_THREADS) void status_finalize_kernel(const doub
 void launch_q1(const LaunchCtx& c, QMode mode, const double2* v, int comp, double sign, void* out) {
     const double* vcomp = reinterpret_cast<const double*>(v) + comp;
     const int nm = (int)(c.n + c.m);
-    if (mode == Q_PLAIN) {
-        EpiQPlain e; e.vcomp = vcomp; e.out = (double*)out; e.cb = c.cb; e.n = (int)c.n; e.vt = 0; e.sign = sign;
+    if (mode == Q_PLAIN || mode == Q_PLAIN_NOTAU) {
+        EpiQPlain e; e.vcomp = vcomp; e.out = (double*)out; e.cb = c.cb; e.n = (int)c.n; e.vt = 0; e.sign = sign; e.notau = mode == Q_PLAIN_NOTAU;
         launch_q1_kernels<EpiQPlain, 1>(c, vcomp, e, nm);
     } else if (mode == Q_RHS) {
         EpiQRhs e; e.x = v; e.out = (d2*)out; e.cb = c.cb; e.n = (int)c.n; e.vt = 0;

@@ -546,12 +546,13 @@ static int32_t status_decide(const fos_check_result* res, double eps) {
     return FOS_STATUS_CONTINUE;
 }
 
-// The same on an equilibrated handle, in the CALLER's units: z is the scaled problem's iterate; w = Q^ u^ (rows 0 .. n+m-1; its tau row is not read, so no
-// finalize) feeds one kernel that forms the six sums on the caller's A, b, c (equilibrate.hip), and sigma, rho, tau come in here.
+// The same on an equilibrated handle, in the CALLER's units: z is the scaled problem's iterate; w = Q^ [x^; y^; 0] (rows 0 .. n+m-1; its tau row is not read, so
+// no finalize) feeds one kernel that forms the six sums on the caller's A, b, c (equilibrate.hip), tau included; sigma and rho come in here.  At tau = 0 the
+// sums, hence p, d and g, are Inf / NaN as the reference's divisions leave them.
 static int eq_status_check(fos_solver* h, const d2* z, double eps, fos_check_result* res) {
     RoctxRange range("fos:checkstatus_eq");
     LaunchCtx c = h->ctx();
-    launch_q1(c, Q_PLAIN, z, 0, 1.0, h->eq_w);
+    launch_q1(c, Q_PLAIN_NOTAU, z, 0, 1.0, h->eq_w);
     launch_eq_status(c, z, h->eq_w, h->eq_cb, h->eq_inv, h->partials);
     FOS_TRY(poll_state(h));
     const double* s = h->st_host->stat;
@@ -559,8 +560,8 @@ static int eq_status_check(fos_solver* h, const d2* z, double eps, fos_check_res
     const double tau = s[ST_TAU], kappa = s[ST_KAPPA] / (sg * rho);
     const double nb = h->eq_nb, nc = h->eq_nc;
     const double ctx = s[ST_CTX] / (sg * rho), bty = s[ST_BTY] / (sg * rho);
-    res->p = std::sqrt(s[ST_RP2]) / (sg * std::fabs(tau)) / std::fabs(1 + nb);             // :34
-    res->d = std::sqrt(s[ST_RD2]) / (rho * std::fabs(tau)) / std::fabs(1 + nc);            // :35
+    res->p = std::sqrt(s[ST_RP2]) / sg / std::fabs(1 + nb);                              // :34
+    res->d = std::sqrt(s[ST_RD2]) / rho / std::fabs(1 + nc);                             // :35
     res->ctx = ctx;                                                                      // :36
     res->bty = bty;                                                                      // :37
     res->g = std::fabs(ctx / tau + bty / tau) / (1 + std::fabs(ctx / tau) + std::fabs(bty / tau));   // :38

@@ -127,7 +127,8 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
  * sigma, rho).  What an equilibrated handle speaks at each entry point:
  *   THE CALLER'S UNITS   fos_set_iterate(z != NULL), fos_get_iterate, fos_get_checked, the z_out of fos_getsol, the z of fos_check; every field of
  *                        fos_check_result from fos_step, fos_getsol and fos_check -- p, d, g, ctx, bty, kappa, tau, norm_axs, norm_aty, norm_b, norm_c and the
- *                        status are the quantities of HSDEStatus.jl:34-38,53-63 on the caller's A, b, c (one extra kernel per check, csrc/equilibrate.hip)
+ *                        status are the quantities of HSDEStatus.jl:34-38,53-63 on the caller's A, b, c (one extra kernel per check, csrc/equilibrate.hip);
+ *                        tau < 0 enters with its sign, tau = 0 gives p, d, g the Inf / NaN of the reference's divisions by zero -- as a plain handle does
  *   THE SCALED PROBLEM   fos_set_iterate(NULL) (its own standard start: zeros, tau^ = kappa^ = 1); fos_q_apply, fos_kkt_apply, fos_cg_kkt, fos_prox_*,
  *                        fos_hsdematrix_prox; fos_get/set_affine_state, fos_get/set_alg_state; the logs of the wrappers (fos_linesearch_log, ...)
  *   fos_enable_direct*   receives the CALLER's nzval again and scales it by the stored D, E itself.
