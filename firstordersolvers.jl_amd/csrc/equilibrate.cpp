@@ -34,8 +34,8 @@ int host_equilibrate(int64_t m, int64_t n, const int64_t* colptr, const int64_t*
         return FOS_EINVAL;
     }
     if (passes < 1 || passes > EQ_MAX_PASSES) { set_error("equil_passes = %d: 1 .. %d (0: no equilibration)", passes, EQ_MAX_PASSES); return FOS_EINVAL; }
-    FOS_TRY(validate_cone_table("K1", m, nK1, K1type, K1start, K1len));
-    FOS_TRY(validate_cone_table("K2", n, nK2, K2type, K2start, K2len));
+    FOS_TRY(cone_table_check("K1", m, nK1, K1type, K1start, K1len));
+    FOS_TRY(cone_table_check("K2", n, nK2, K2type, K2start, K2len));
     if (colptr[0] != 1) { set_error("colptr[0] = %lld: the CSC arrays are 1-based", (long long)colptr[0]); return FOS_EINVAL; }
     for (int64_t j = 0; j < n; ++j)
         if (colptr[j + 1] < colptr[j]) { set_error("colptr decreases at column %lld", (long long)j + 1); return FOS_EINVAL; }

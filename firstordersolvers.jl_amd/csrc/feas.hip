@@ -172,15 +172,7 @@ struct FeasSet {
     double *lov = nullptr, *hiv = nullptr;      // [n] array bounds (IndBox with vectors); nullptr: the scalars
     int ns_iters = 0;               // Newton-Schulz steps of the set-up
     double ns_resid = 0.0;          // max |G X - I| it ended with
-    // kind 3: ConeProduct (cones.jl:31-94) on the batched cone kernels of the HSDE path
-    uint8_t* ew_op = nullptr;       // [n] elementwise op per index (EW_SKIP inside SOC / Exp / PSD cones)
-    ConeDesc *soc = nullptr, *expc = nullptr, *psd = nullptr;
-    int nsoc = 0, nexp = 0, npsd = 0, psd_kmin = 0, psd_kmax = 0;
-    double* psd_scratch = nullptr;
-    double* psd_V[2] = {nullptr, nullptr};
-    int psd_cur = 0, psd_have_prev = 0;
-    bool psd_attr_set = false;
-    PsdSign* psd_big = nullptr;     // PSD cones of order > 64 (psd_sign.hip)
+    ConeSet* cones = nullptr;       // kind 3: ConeProduct (cones.jl:31-94) on the batched cone kernels of the HSDE path (cones.cpp)
 };
 
 }  // namespace fos
@@ -260,17 +252,11 @@ int feas_prox(fos_feas* h, int which, double* y, const double* x) {
         if (s.lov) FEAS_K(feas_boxv_kernel, h->n, y, x, (const double*)s.lov, (const double*)s.hiv);
         else FEAS_K(feas_box_kernel, h->n, y, x, s.lo, s.hi);
     } else if (s.kind == 3) {                                             // prox!(y, ::ConeProduct, x)   cones.jl:89-94
-        FeasSet& ms = h->S[which];
         LaunchCtx c = feas_ctx(h, h->n);
-        c.vec_blocks = h->grid; c.cus = h->cus; c.psd_attr_set = &ms.psd_attr_set;
+        c.vec_blocks = h->grid; c.cus = h->cus;
         FEAS_K(feas_to_parts_kernel, h->n, h->zin, x);
-        launch_cones_elementwise(c, h->zout, h->zin, s.ew_op);
-        launch_cones_soc(c, h->zout, h->zin, s.soc, s.nsoc);
-        launch_cones_exp(c, h->zout, h->zin, s.expc, s.nexp);
-        FOS_TRY(launch_cones_psd(c, h->zout, h->zin, s.psd, s.npsd, s.psd_kmin, s.psd_kmax, s.psd_scratch, s.psd_V[s.psd_cur], s.psd_V[1 - s.psd_cur],
-                                 s.psd_have_prev, nullptr, 0));
-        FOS_TRY(launch_cones_psd_sign(c, s.psd_big, h->zout, h->zin));          // cones of order > 64 (psd_sign.hip)
-        if (s.npsd > 0 && s.psd_V[0]) { ms.psd_cur = 1 - ms.psd_cur; ms.psd_have_prev = 1; }      // warm start of the next projection
+        cone_set_project_vector(s.cones, c, h->zout, h->zin);
+        FOS_TRY(cone_set_project_psd(s.cones, c, h->zout, h->zin));             // (the next projection starts warm from this one's basis)
         FEAS_K(feas_from_parts_kernel, h->n, y, (const double2*)h->zout);
     } else if (s.kind == 5) {                                             // IndAffine over a sparse A: CG on the normal equations, exact to the residual's rounding level
         FOS_TRY(sparse_affine_project(s.sa, h->stream, y, x));
@@ -481,7 +467,7 @@ int fos_feas_destroy(fos_feas_handle h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (void* q : h->owned) (void)hipFree(q);
-    for (FeasSet& s : h->S) { if (s.cb_x) (void)hipHostFree(s.cb_x); if (s.cb_y) (void)hipHostFree(s.cb_y); psd_sign_destroy(s.psd_big); sparse_affine_destroy(s.sa); dense_affine_destroy(s.da); sparse_factored_destroy(s.sf); set_blocks_destroy(s.sb); }
+    for (FeasSet& s : h->S) { if (s.cb_x) (void)hipHostFree(s.cb_x); if (s.cb_y) (void)hipHostFree(s.cb_y); cone_set_destroy(s.cones, h->stream); sparse_affine_destroy(s.sa); dense_affine_destroy(s.da); sparse_factored_destroy(s.sf); set_blocks_destroy(s.sb); }
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return FOS_OK;
@@ -681,69 +667,21 @@ int fos_feas_set_cones(fos_feas_handle h, int32_t which, int64_t ncones, const i
     if (!h || which < 1 || which > 2 || ncones < 1 || !type || !len) { set_error("fos_feas_set_cones: bad argument"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
     const int64_t n = h->n;
-    std::vector<uint8_t> ew((size_t)n, 0);
-    std::vector<ConeDesc> soc, psd, expc;
+    std::vector<int64_t> start((size_t)ncones);
     int64_t pos = 0;
-    for (int64_t i = 0; i < ncones; ++i) {
-        if (len[i] < 1 || pos + len[i] > n) { set_error("ConeProduct: cone %lld (length %lld) does not fit the %lld entries (cones.jl:66-72: contiguous, gap-free ranges)", (long long)i + 1, (long long)len[i], (long long)n); return FOS_EINVAL; }
-        uint8_t prim = 0;
-        bool ewise = true;
-        switch (type[i]) {
-            case FOS_CONE_FREE: prim = EW_COPY; break;
-            case FOS_CONE_ZERO: prim = EW_ZERO; break;
-            case FOS_CONE_NONNEG: prim = EW_MAX0; break;
-            case FOS_CONE_NONPOS: prim = EW_MIN0; break;
-            case FOS_CONE_SOC: case FOS_CONE_SOCROT: case FOS_CONE_SDP: case FOS_CONE_EXPPRIMAL: case FOS_CONE_EXPDUAL: ewise = false; break;
-            default: set_error("ConeProduct: unknown cone code %d", type[i]); return FOS_EINVAL;
-        }
-        if (ewise) { for (int64_t k = 0; k < len[i]; ++k) ew[(size_t)(pos + k)] = (uint8_t)(prim | (EW_COPY << 2)); }
-        else {
-            ConeDesc cd;
-            cd.start = pos; cd.len = (int32_t)len[i]; cd.type = type[i]; cd.dual_part = 1; cd.k = 0;      // part 1 (the vector): primal
-            if (type[i] == FOS_CONE_SDP) {
-                const int64_t k = (int64_t)std::floor((std::sqrt(8.0 * (double)len[i] + 1.0) - 1.0) / 2.0 + 0.5);
-                if (k * (k + 1) / 2 != len[i]) { set_error("ConeProduct cone %lld: SDP length %lld is not k(k+1)/2", (long long)i + 1, (long long)len[i]); return FOS_EINVAL; }
-                cd.k = (int32_t)k;
-                psd.push_back(cd);
-            } else if (type[i] == FOS_CONE_EXPPRIMAL || type[i] == FOS_CONE_EXPDUAL) {
-                if (len[i] != 3) { set_error("ConeProduct cone %lld: an exponential cone has exactly 3 entries (got %lld)", (long long)i + 1, (long long)len[i]); return FOS_EINVAL; }
-                expc.push_back(cd);
-            } else {
-                if (type[i] == FOS_CONE_SOCROT && len[i] < 2) { set_error("ConeProduct cone %lld: rotated SOC needs >= 2 entries", (long long)i + 1); return FOS_EINVAL; }
-                soc.push_back(cd);
-            }
-            for (int64_t k = 0; k < len[i]; ++k) ew[(size_t)(pos + k)] = EW_SKIP;
-        }
+    for (int64_t i = 0; i < ncones; ++i) {                 // contiguous from index 1 (cones.jl:66-72): the starts follow from the lengths
+        if (len[i] < 1 || len[i] > n - pos) { set_error("ConeProduct: cone %lld (length %lld) does not fit the %lld entries (cones.jl:66-72: contiguous, gap-free ranges)", (long long)i + 1, (long long)len[i], (long long)n); return FOS_EINVAL; }
+        start[(size_t)i] = pos + 1;
         pos += len[i];
     }
-    if (pos != n) { set_error("ConeProduct: the cones cover %lld of the %lld entries", (long long)pos, (long long)n); return FOS_EINVAL; }
+    FOS_TRY(cone_table_check("ConeProduct", n, ncones, type, start.data(), len));
+    ConeTable table;
+    table.ew.assign((size_t)n, 0);
+    cone_table_add(table, 0, CONE_PRIMAL, ncones, type, start.data(), len);
     FeasSet& s = h->S[which - 1];
-    auto upload = [&](auto** dst, const auto& v) -> int {
-        using T = typename std::remove_reference<decltype(v)>::type::value_type;
-        if (v.empty()) { *dst = nullptr; return FOS_OK; }
-        void* q = nullptr;
-        if (hipMalloc(&q, sizeof(T) * v.size()) != hipSuccess) { set_error("ConeProduct: hipMalloc failed"); return FOS_ENOMEM; }
-        h->owned.push_back(q);
-        if (hipMemcpy(q, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice) != hipSuccess) { set_error("ConeProduct: upload failed"); return FOS_EHIP; }
-        *dst = static_cast<T*>(q);
-        return FOS_OK;
-    };
-    FOS_TRY(upload(&s.ew_op, ew));
-    FOS_TRY(upload(&s.soc, soc));
-    FOS_TRY(upload(&s.expc, expc));
-    psd_sign_destroy(s.psd_big); s.psd_big = nullptr;
-    FOS_TRY(psd_sign_setup(psd, &s.psd_big));
-    FOS_TRY(upload(&s.psd, psd));
-    s.nsoc = (int)soc.size(); s.nexp = (int)expc.size(); s.npsd = (int)psd.size();
-    s.psd_kmax = 0;
-    for (auto& cd : psd) s.psd_kmax = std::max(s.psd_kmax, cd.k);
-    s.psd_kmin = s.psd_kmax;
-    for (auto& cd : psd) s.psd_kmin = std::min(s.psd_kmin, cd.k);
-    const size_t sb = psd_scratch_bytes(s.psd_kmax, s.npsd);
-    if (sb) FOS_TRY(feas_alloc(h, &s.psd_scratch, sb / sizeof(double)));
-    const size_t vb = psd_basis_doubles(s.psd_kmax, s.npsd);
-    if (vb) { FOS_TRY(feas_alloc(h, &s.psd_V[0], vb)); FOS_TRY(feas_alloc(h, &s.psd_V[1], vb)); }
-    s.psd_cur = 0; s.psd_have_prev = 0;
+    cone_set_destroy(s.cones, h->stream); s.cones = nullptr;      // a set defined again: what it held goes before the new state is built
+    if (s.kind == 3) s.kind = 0;
+    FOS_TRY(cone_set_build(table, n, ConeSetOptions{}, PsdTuning{}, &s.cones));
     if (!h->zin) {
         double* q = nullptr;
         FOS_TRY(feas_alloc(h, &q, 2 * (size_t)n)); h->zin = reinterpret_cast<double2*>(q);
@@ -878,7 +816,7 @@ int fos_feas_set_iterate(fos_feas_handle h, const double* x0) {
     FOS_HIP(hipMemcpyAsync(h->a12, &two, sizeof(double), hipMemcpyHostToDevice, h->stream));
     FOS_HIP(hipStreamSynchronize(h->stream));
     h->fista_t = 1.0; h->status = FOS_STATUS_CONTINUE; h->checked = 0; h->err = NAN;
-    for (FeasSet& s : h->S) { s.psd_cur = 0; s.psd_have_prev = 0; sparse_affine_reset(s.sa, h->stream); }        // a new solve starts its PSD projections cold, the sparse IndAffine's multipliers at zero
+    for (FeasSet& s : h->S) { if (s.cones) s.cones->start_cold(); sparse_affine_reset(s.sa, h->stream); }        // a new solve starts its PSD projections cold, the sparse IndAffine's multipliers at zero
     return feas_check_launch("fos_feas_set_iterate");
 }
 

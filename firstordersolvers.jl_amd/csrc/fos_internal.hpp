@@ -345,16 +345,8 @@ struct LaunchCtx {
     void* between_arg;
     double* pre = nullptr;           // 3 x 16 doubles + 16 flags: the producer workgroups' sums of the sweep records (cg_update_kernel)
     const int32_t* gate = nullptr;   // non-null: the relaxation / cone kernels run only if *gate != 0 (DevState.done: enqueued behind a CG batch)
-    // batched PSD projection: the handle's device and switches (read once at fos_create)
+    // batched PSD projection: the launch environment (the cones' own state and switches: ConeSet below)
     int32_t cus = 0;                 // compute units of the handle's device
-    int32_t psd_wave = -1;           // FOS_PSD_WAVE: -1 decide from the batch size, 0 / 1 force the workgroup / wavefront kernel at order 64
-    bool psd_narrow = false, psd_wide = false;
-    int32_t psd_wide_threads = 512;
-    bool* psd_attr_set = nullptr;    // the handle's "LDS opt-in done" flag
-    bool* psd_attr_set_r = nullptr;  // the same for the refinement kernel
-    int32_t psd_refine = -1;         // FOS_PSD_REFINE: -1 by batch size, 0 / 1 never / always (order 64, warm)
-    bool psd_extrapolate = true;     // FOS_PSD_EXTRAPOLATE=0: the refinement starts from the previous basis only
-    double psd_theta = 0.0;          // FOS_PSD_THETA: rotation threshold of the refinement (0: the built-in value)
     int32_t psd_refine_max_mats = 0; // > 0: peer ranks share THIS device (tests): the refinement kernel only for batches this small (psd.hip)
     int32_t count_repl;         // 1: this rank counts the replicated entries in scalar sums (always 1 when not row-sharded)
     int64_t n_repl;             // replicated leading entries of every vector (0 when not row-sharded)
@@ -663,7 +655,6 @@ struct EqScaling {                               // host
 int host_equilibrate(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, const double* c,
                      int64_t nK1, const int32_t* K1type, const int64_t* K1start, const int64_t* K1len,
                      int64_t nK2, const int32_t* K2type, const int64_t* K2start, const int64_t* K2len, int passes, EqScaling* out);
-int validate_cone_table(const char* which, int64_t total, int64_t nK, const int32_t* type, const int64_t* start, const int64_t* len);   // solver.cpp
 void launch_eq_status(const LaunchCtx& c, const double2* z, const double* w, const double* cb, const double* inv, double* partials);
 void launch_eq_interleave(const LaunchCtx& c, double2* out, const double* plain, const double2* up);
 void launch_eq_deinterleave(const LaunchCtx& c, double* plain, const double2* in, const double2* up);
@@ -684,10 +675,6 @@ struct PsdFuse {
     double a1, alpha, alpha2;
     const uint8_t* ew_op; int64_t l; int nmat;           // elementwise entries: workgroups nmat.. of the grid
 };
-bool psd_fuse_possible(const LaunchCtx& c, int ncones, int kmin, int kmax, const double* vin, const double* vout, int have_prev, const int32_t* redo, int phase_limit);
-int  launch_cones_psd(const LaunchCtx& c, double2* out, const double2* in, const ConeDesc* cones, int ncones,
-                      int kmin, int kmax, double* gscratch, const double* vin, double* vout, int have_prev, int* stats, int phase_limit,
-                      int32_t* redo = nullptr, const PsdFuse* fuse = nullptr);
 // PSD cones of order > 64: the projection by matrix products only, P = (M + M sign(M)) / 2 with sign(M) from an inverse-free polynomial iteration on the fp64
 // matrix cores (psd_sign.hip).  psd_sign_setup takes those cones OUT of `psd` (what stays goes to the kernels of psd.hip) and allocates their workspace.
 struct PsdSign;
@@ -695,6 +682,59 @@ int psd_sign_setup(std::vector<ConeDesc>& psd, PsdSign** out);
 void psd_sign_destroy(PsdSign* p);
 int psd_sign_count(const PsdSign* p);
 int launch_cones_psd_sign(const LaunchCtx& c, PsdSign* p, double2* out, const double2* in);
+
+// ---- a product of cones, projected (cones.cpp): the HSDE handle's DualConeProduct and the Feasibility form's ConeProduct are both one ConeSet.
+// The host table: built once per product by the one validator and the one classifier of cone codes
+struct ConeTable { std::vector<uint8_t> ew; std::vector<ConeDesc> soc, psd, expc; };      // ew: one op per stacked index (sized by the caller); the batched cones
+enum ConeRole { CONE_K2, CONE_K1, CONE_PRIMAL };     // K2 on [x | r]: part 1 primal, part 2 dual; K1 on [y | s]: the other way round; a ConeProduct set: part 1 primal, part 2 copied
+int psd_order(int64_t len);                          // k with k (k + 1) / 2 == len, or -1
+// ranges 1-based, contiguous, ordered and covering 1..total (cones.jl:66-72); FOS_EINVAL / FOS_EUNSUPPORTED with a message naming `which`
+int cone_table_check(const char* which, int64_t total, int64_t nK, const int32_t* type, const int64_t* start, const int64_t* len);
+void cone_table_add(ConeTable& t, int64_t offset, ConeRole role, int64_t nK, const int32_t* type, const int64_t* start, const int64_t* len);
+struct PsdTuning {                   // the FOS_PSD_* switches of a handle
+    int wave = -1;                   // FOS_PSD_WAVE: -1 decide from the batch size, 0 / 1 force the workgroup / wavefront kernel at order 64
+    int refine = -1;                 // FOS_PSD_REFINE: -1 by batch size, 0 / 1 never / always (order 64, warm)
+    bool extrapolate = true;         // FOS_PSD_EXTRAPOLATE=0: the refinement starts from the previous basis only
+    double theta = 0.0;              // FOS_PSD_THETA: rotation threshold of the refinement (0: the built-in value)
+    bool narrow = false, wide = false;      // FOS_PSD_NARROW / FOS_PSD_WIDE
+    int wide_threads = 512;          // FOS_PSD_THREADS
+    static PsdTuning from_env();
+};
+struct ConeSetOptions {
+    bool warm = true;                // keep the two warm-start bases (orders <= 64)
+    bool refine_records = false;     // allocate the refinement kernel's records when every order is 64 (without them that kernel never runs)
+    bool debug_rec = false;          // FOS_PSD_DEBUG_REC: the records' diagnostics switch
+};
+// The device state: the uploaded table, the PSD workspaces and warm-start bases, the switches.  It owns every buffer it names.
+struct ConeSet {
+    uint8_t* ew_op = nullptr;                  // [l] elementwise op per index (EW_SKIP inside SOC / Exp / PSD cones)
+    ConeDesc *soc = nullptr, *expc = nullptr, *psd = nullptr;      // psd: orders <= 64 (psd.hip)
+    int nsoc = 0, nexp = 0, npsd = 0, kmin = 0, kmax = 0;
+    PsdSign* big = nullptr;                    // PSD cones of order > 64 (psd_sign.hip)
+    double* scratch = nullptr;
+    double* V[2] = {nullptr, nullptr};         // warm-start eigenvector bases (ping-pong): the last projection's is V[cur]
+    int cur = 0, have_prev = 0;                // have_prev: projections behind the basis, capped at 2
+    int32_t* redo = nullptr;                   // per (cone, copy): 1 = the refinement kernel left the matrix to the Jacobi kernel
+    int* stats = nullptr;                      // Jacobi sweeps of the last projection, per (cone, copy)  (fos_psd_debug)
+    int phase_limit = 0;                       // diagnostic: stop the PSD kernel after a phase (wrong results!)
+    bool attr_set = false, attr_set_r = false; // the "LDS opt-in done" flags of psd_kernel / psd64_refine_kernel
+    PsdTuning tune;
+    int64_t fused_steps = 0;                   // projections taken through the fused launch (host count; fos_psd_fused_steps)
+    std::vector<void*> owned;
+    // the host-side state a projection advances: what a caller that enqueues projections speculatively takes back (affine_then)
+    struct Mark { int cur, have_prev; int64_t fused_steps; };
+    Mark mark() const { return {cur, have_prev, fused_steps}; }
+    void rewind(const Mark& k) { cur = k.cur; have_prev = k.have_prev; fused_steps = k.fused_steps; }
+    void start_cold() { cur = 0; have_prev = 0; }
+};
+int cone_set_build(const ConeTable& t, int64_t l, const ConeSetOptions& o, const PsdTuning& tune, ConeSet** out);      // on the current device
+void cone_set_destroy(ConeSet* cs, hipStream_t stream);      // waits for `stream` (the projections in flight) before it frees; nullptr: nothing to do
+// prox!(out, K, in) in two parts: elementwise (unless ew_done: the kernel that wrote `in` projected them), SOC and Exp cones; then the PSD cones, orders <= 64
+// before orders > 64, and the warm-start advance.  fuse: the step's relaxation and last pass ride on the PSD launch (cone_set_can_fuse says when that is possible)
+void cone_set_project_vector(ConeSet* cs, const LaunchCtx& c, double2* out, const double2* in, bool ew_done = false);
+int cone_set_project_psd(ConeSet* cs, const LaunchCtx& c, double2* out, const double2* in, const PsdFuse* fuse = nullptr);
+bool cone_set_can_fuse(const ConeSet& cs, const LaunchCtx& c);      // psd.hip: the next projection would take the refinement kernel
+int launch_cones_psd(const LaunchCtx& c, ConeSet& cs, double2* out, const double2* in, const PsdFuse* fuse);
 // IndAffine(A, b) with a sparse A (affine_sparse.hip): exact projection by warm-started CG on the row-scaled normal equations, the true residual re-checked
 struct SparseAffine;
 struct SparseRows {                              // host: what sparse_affine_rows leaves -- the scaled A (rp / ci / va) and A' (trp / tci / tva) in CSR, the scaled b

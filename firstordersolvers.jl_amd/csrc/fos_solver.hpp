@@ -1,4 +1,4 @@
-// struct fos_solver (the handle behind fos_handle) and the helpers that solver.cpp, direct.cpp and transport.cpp share.  Private: not part of the ABI.
+// struct fos_solver (the handle behind fos_handle) and the helpers that solver.cpp, cones.cpp, direct.cpp and transport.cpp share.  Private: not part of the ABI.
 #pragma once
 
 #include <rccl/rccl.h>
@@ -81,27 +81,11 @@ struct fos_solver {
     d2 *SOL2 = nullptr;                                     // HSDEMatrix.cgdata.xinit
     double* plain = nullptr;                                // 2l doubles: ABI staging
 
-    // cones
-    uint8_t* ew_op = nullptr;
-    fos::ConeDesc* soc = nullptr; int nsoc = 0;
-    fos::ConeDesc* expc = nullptr; int nexp = 0;
-    fos::ConeDesc* psd = nullptr; int npsd = 0; int psd_kmax = 0, psd_kmin = 0;       // PSD cones of order <= 64 (psd.hip)
-    fos::PsdSign* psd_big = nullptr;                // ... of order > 64: projected by matrix products (psd_sign.hip)
-    double* psd_scratch = nullptr;
-    double* psd_V[2] = {nullptr, nullptr};     // warm-start eigenvector bases (ping-pong), orders <= 64
-    int psd_cur = 0, psd_have_prev = 0;
-    int* psd_stats = nullptr;                  // Jacobi sweeps of the last projection, per (cone, copy)  (fos_psd_debug)
-    int psd_phase_limit = 0;                   // diagnostic: stop the PSD kernel after a phase (wrong results!)
+    // cones: S2 = DualConeProduct, its table, workspaces and warm-start state (cones.cpp)
+    fos::ConeSet* cones = nullptr;
     int cus = 256;                             // compute units of `device`
-    int psd_wave = -1; bool psd_narrow = false, psd_wide = false; int psd_wide_threads = 512;      // FOS_PSD_* (read at fos_create)
-    mutable bool psd_attr_set = false, psd_attr_set_r = false;
-    int32_t* psd_redo = nullptr;               // per (cone, copy): 1 = the refinement kernel left the matrix to the Jacobi kernel
-    int psd_refine = -1;                       // FOS_PSD_REFINE
-    bool psd_extrapolate = true;               // FOS_PSD_EXTRAPOLATE
-    double psd_theta = 0.0;                    // FOS_PSD_THETA
     bool psd_fuse = true;                      // FOS_PSD_FUSE=0: relaxation, projection and the step's last pass stay separate launches
     bool relax_ew = true;                      // FOS_RELAX_EW=0: the relaxation does not project the elementwise cones in the same pass
-    int64_t psd_fused_steps = 0;               // steps taken through the fused launch (host count; fos_psd_fused_steps)
 
     // scalars
     fos::DevState* st = nullptr;
@@ -241,8 +225,7 @@ struct fos_solver {
         c.def_mask = def_mask;
         c.pre = pre_on ? pre_sums : nullptr;
         c.between = nullptr; c.between_arg = nullptr;
-        c.cus = cus; c.psd_wave = psd_wave; c.psd_narrow = psd_narrow; c.psd_wide = psd_wide; c.psd_wide_threads = psd_wide_threads;
-        c.psd_attr_set = &psd_attr_set; c.psd_attr_set_r = &psd_attr_set_r; c.psd_refine = psd_refine; c.psd_extrapolate = psd_extrapolate; c.psd_theta = psd_theta;
+        c.cus = cus;
         c.psd_refine_max_mats = (tr.peer_same_device && nranks > 1) ? std::max(1, cus / nranks) : 0;
         c.count_repl = (!row_sharded || rank == 0) ? 1 : 0;
         c.n_repl = row_sharded ? n : 0;
@@ -320,8 +303,9 @@ struct DenseOpts {
 int dense_spd_inverse(const DenseWork& k, const DenseOpts& o, double** Xout, DenseInv* st);
 void direct_test_vector(int64_t k, int which, std::vector<double>& v);      // the four fixed vectors of the probe (which = 0: also the power iteration's start)
 
-template <class T>
-int dev_alloc(fos_solver* h, T** p, size_t count) {
+// (Owner: the handle, or a state with its own `owned` list -- ConeSet)
+template <class Owner, class T>
+int dev_alloc(Owner* h, T** p, size_t count) {
     void* q = nullptr;
     size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
     hipError_t e = hipMalloc(&q, bytes);
@@ -340,8 +324,8 @@ void dev_release(fos_solver* h, T** p) {          // frees a dev_alloc'd buffer 
     *p = nullptr;
 }
 
-template <class T>
-int dev_upload(fos_solver* h, T** p, const std::vector<T>& v) {
+template <class Owner, class T>
+int dev_upload(Owner* h, T** p, const std::vector<T>& v) {
     FOS_TRY(dev_alloc(h, p, v.size()));
     if (!v.empty()) FOS_HIP(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return FOS_OK;

@@ -1417,24 +1417,31 @@ size_t psd_basis_doubles(int kmax, int ncones) {       // one warm-start basis b
     return (size_t)2 * ncones * (size_t)kmax * kmax;
 }
 
-// whether launch_cones_psd would take the refinement kernel (the only one the step fusion is built into)
 // Whether a warm order-64 batch goes to the refinement kernel (FOS_PSD_REFINE=0 / 1 switches it off / on for every batch size; by default it
 // runs at every size: 128 / 256 / 512 / 1024 matrices 55 / 58 / 89 / 146 us against 121 / 128 / 178 / 201 for Jacobi).  One exception: when peer
 // ranks share THIS device (several ranks on one GPU: tests only) a workgroup of it -- a whole CU's registers and 100 KB of LDS -- finds no CU
 // while a peer's CG kernel is resident there SPINNING for this rank's mailbox words, which this rank writes only after its projection:
 // two ranks of the full C4 on one GPU dead-locked until the exchange timed out.  Then only batches small enough to fit beside everything.
-static bool psd_refine_chosen(const LaunchCtx& c, int ncones) {
-    if (c.psd_refine == 0 || (c.psd_refine < 0 && c.psd_wave == 1)) return false;
+static bool psd_refine_chosen(const LaunchCtx& c, const PsdTuning& t, int ncones) {
+    if (t.refine == 0 || (t.refine < 0 && t.wave == 1)) return false;
     if (c.psd_refine_max_mats > 0 && 2 * ncones > c.psd_refine_max_mats) return false;
     return true;
 }
-bool psd_fuse_possible(const LaunchCtx& c, int ncones, int kmin, int kmax, const double* vin, const double* vout, int have_prev, const int32_t* redo, int phase_limit) {
-    const bool refine_ok = ncones > 0 && kmin == 64 && kmax == 64 && vin && vout && have_prev && redo && phase_limit == 0;
-    return refine_ok && psd_refine_chosen(c, ncones);
+// whether launch_cones_psd would take the refinement kernel for ALL of the set's batched cones (the only kernel the step fusion is built into)
+bool cone_set_can_fuse(const ConeSet& cs, const LaunchCtx& c) {
+    const bool refine_ok = cs.nsoc == 0 && cs.nexp == 0 && !cs.big && cs.npsd > 0 && cs.kmin == 64 && cs.kmax == 64 && cs.V[0] && cs.have_prev && cs.redo && cs.phase_limit == 0;
+    return refine_ok && psd_refine_chosen(c, cs.tune, cs.npsd);
 }
 
-int launch_cones_psd(const LaunchCtx& c, double2* out, const double2* in, const ConeDesc* cones, int ncones, int kmin, int kmax, double* gscratch,
-                     const double* vin, double* vout, int have_prev, int* stats, int phase_limit, int32_t* redo, const PsdFuse* fuse) {
+int launch_cones_psd(const LaunchCtx& c, ConeSet& cs, double2* out, const double2* in, const PsdFuse* fuse) {
+    const ConeDesc* cones = cs.psd;
+    const int ncones = cs.npsd, kmin = cs.kmin, kmax = cs.kmax, have_prev = cs.have_prev, phase_limit = cs.phase_limit;
+    double* gscratch = cs.scratch;
+    const double* vin = cs.V[cs.cur];
+    double* vout = cs.V[1 - cs.cur];
+    int* stats = cs.stats;
+    int32_t* redo = cs.redo;
+    const PsdTuning& tune = cs.tune;
     if (ncones <= 0) return fuse ? FOS_EINVAL : FOS_OK;
     // per-handle configuration (fos_create reads the device's CU count and the FOS_PSD_* switches ONCE: two host threads driving
     // handles on different devices share nothing here, and the kernel choice cannot change between a speculative enqueue and its re-run)
@@ -1443,24 +1450,24 @@ int launch_cones_psd(const LaunchCtx& c, double2* out, const double2* in, const 
     // (every SIMD then has a wavefront of its own: 1024 matrices 195 us against 288), one WORKGROUP of four wavefronts per matrix
     // (psd_kernel<.., 256>, jacobi64_regs) below that (a shard of a multi-GPU run; 128 / 256 / 512 matrices: 118 / 127 / 179 us
     // against 173 / 182 / 190).  FOS_PSD_WAVE=0 / 1 forces the workgroup / the wavefront form.
-    const int wave_env = c.psd_wave;
+    const int wave_env = tune.wave;
     // warm, every cone of order 64, a basis from the previous projection: refinement by matrix products (psd64_refine_kernel) with the
     // Jacobi code in the same workgroup for the matrices it flags (psd_refine_chosen above: when)
     const bool refine_ok = kmin == 64 && kmax == 64 && vin && vout && have_prev && redo && (phase_limit == 0 || phase_limit >= 11);
-    if (refine_ok && psd_refine_chosen(c, ncones)) {
+    if (refine_ok && psd_refine_chosen(c, tune, ncones)) {
         const size_t rl1 = psd64r_lds_bytes(1), rl2 = psd64r_lds_bytes(2);
-        if (!*c.psd_attr_set_r) {
+        if (!cs.attr_set_r) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(psd64_refine_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl1);
             if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(psd64_refine_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl2);
             if (e != hipSuccess) { set_error("hipFuncSetAttribute(psd64_refine_kernel): %s", hipGetErrorString(e)); return FOS_EHIP; }
-            *c.psd_attr_set_r = true;
+            cs.attr_set_r = true;
         }
         // more matrices than CUs: two workgroups per CU (256 registers per lane), so that one's vector phases run beside the other's products
         PsdFuse fz{};
         int grid = 2 * ncones;
         if (fuse) { fz = *fuse; fz.on = 1; fz.nmat = 2 * ncones; grid += std::max(16, std::min(256, (int)((fz.l + 16383) / 16384))); }
-        const int have = c.psd_extrapolate ? have_prev : 1;
-        const double theta = c.psd_theta > 0.0 ? c.psd_theta : RF_THETA;
+        const int have = tune.extrapolate ? have_prev : 1;
+        const double theta = tune.theta > 0.0 ? tune.theta : RF_THETA;
         if (2 * ncones > cus)
             hipLaunchKernelGGL(psd64_refine_kernel<2>, dim3(grid), dim3(256), rl2, c.stream, out, in, cones, vin, vout, have, stats, redo, phase_limit, c.gate, theta, fz);
         else
@@ -1487,18 +1494,18 @@ int launch_cones_psd(const LaunchCtx& c, double2* out, const double2* in, const 
     // (order 64 with EIGHT wavefronts per matrix, four rows of the two columns per lane -- psd_kernel<.., 512> through jacobi64_regs<8>,
     //  FOS_PSD_WIDE=1 -- was measured on 128 matrices: 145 us against 118 for four wavefronts; the barrier across eight wavefronts
     //  per step costs more than the halved arithmetic saves)
-    const bool wide = (warm && !all64 && (2 * ncones <= 2 * cus) && !c.psd_narrow) || (warm && c.psd_wide);
-    if (use_lds && !*c.psd_attr_set) {        // hipFuncSetAttribute acts on the CURRENT device; once per handle
+    const bool wide = (warm && !all64 && (2 * ncones <= 2 * cus) && !tune.narrow) || (warm && tune.wide);
+    if (use_lds && !cs.attr_set) {        // hipFuncSetAttribute acts on the CURRENT device; once per handle
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(psd_kernel<true, false, PSD_THREADS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(psd_kernel<true, true, PSD_THREADS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(psd_kernel<true, true, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(psd_kernel<true, true, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
         if (e != hipSuccess) { set_error("hipFuncSetAttribute(psd_kernel): %s", hipGetErrorString(e)); return FOS_EHIP; }
-        *c.psd_attr_set = true;
+        cs.attr_set = true;
     }
     const size_t stride = (size_t)(kmax * psd_ld(kmax) + 2 * kmax + 16);
     const size_t vstride = (size_t)kmax * kmax;
-    const int wide_threads = c.psd_wide_threads;
+    const int wide_threads = tune.wide_threads;
     if (warm && wide && wide_threads == 512)
         hipLaunchKernelGGL((psd_kernel<true, true, 512>), dim3(2 * ncones), dim3(512), lds, c.stream, out, in, cones, gscratch, stride, vin, vout, vstride, have_prev, stats, phase_limit, c.gate);
     else if (warm && wide && wide_threads == 1024)

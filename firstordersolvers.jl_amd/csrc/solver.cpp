@@ -45,12 +45,6 @@ static bool roctx_on() {
 RoctxRange::RoctxRange(const char* name) : on(roctx_on()) { if (on) g_roctx.push(name); }
 RoctxRange::~RoctxRange() { if (on) g_roctx.pop(); }
 
-static int psd_order(int64_t len) {
-    int64_t k = (int64_t)std::llround(std::sqrt(0.25 + 2.0 * (double)len) - 0.5);
-    if (k * (k + 1) / 2 != len) return -1;
-    return (int)k;
-}
-
 // a kernel launch that the runtime rejected (bad configuration, missing attribute) is only reported by hipGetLastError
 int check_launch(const char* where) {
     const hipError_t e = hipGetLastError();
@@ -520,18 +514,13 @@ int prox_cones(fos_solver* h, d2* out, const d2* in, const int32_t* gate = nullp
     RoctxRange range("fos:prox_cones (elementwise + SOC + Exp + batched PSD)");
     LaunchCtx c = h->ctx();
     c.gate = gate;
-    const int po = (!ew_done || h->nsoc > 0 || h->nexp > 0) ? prof_begin_other(h, gate ? 1 : 0) : -1;
-    if (!ew_done) launch_cones_elementwise(c, out, in, h->ew_op);
-    launch_cones_soc(c, out, in, h->soc, h->nsoc);
-    launch_cones_exp(c, out, in, h->expc, h->nexp);
+    ConeSet* cs = h->cones;
+    const int po = (!ew_done || cs->nsoc > 0 || cs->nexp > 0) ? prof_begin_other(h, gate ? 1 : 0) : -1;
+    cone_set_project_vector(cs, c, out, in, ew_done);
     prof_end(h, po);
-    const int pe = (h->npsd > 0 || h->psd_big) ? prof_begin(h, FOS_PROF_PSD, 0, h->prof_seen[FOS_PROF_PSD]++) : -1;
-    FOS_TRY(launch_cones_psd(c, out, in, h->psd, h->npsd, h->psd_kmin, h->psd_kmax, h->psd_scratch,
-                             h->psd_V[h->psd_cur], h->psd_V[1 - h->psd_cur], h->psd_have_prev, h->psd_stats, h->psd_phase_limit, h->psd_redo));
-    FOS_TRY(launch_cones_psd_sign(c, h->psd_big, out, in));                  // cones of order > 64
+    const int pe = (cs->npsd > 0 || cs->big) ? prof_begin(h, FOS_PROF_PSD, 0, h->prof_seen[FOS_PROF_PSD]++) : -1;
+    FOS_TRY(cone_set_project_psd(cs, c, out, in));
     prof_end(h, pe);
-    // (a diagnostic launch truncated before the basis store leaves the previous basis current)
-    if (h->npsd > 0 && h->psd_V[0] && (h->psd_phase_limit == 0 || (h->psd_phase_limit >= 4 && h->psd_phase_limit < 11))) { h->psd_cur = 1 - h->psd_cur; h->psd_have_prev = std::min(h->psd_have_prev + 1, 2); }
     return check_launch("cone projection");
 }
 
@@ -846,15 +835,14 @@ int long_finish(fos_solver* h, int64_t i) {
 // batch, gated, so that the GPU does not wait for the host to learn the iteration count (cg_solve); if the batch did not
 // suffice the gated launches were no-ops: the host-side state they advanced is rolled back and `post` runs again, ungated.
 int affine_then(fos_solver* h, const LaunchCtx& c, const d2* in, const PostFn& post) {
-    const int psd_cur = h->psd_cur, psd_have_prev = h->psd_have_prev;
-    const int64_t psd_fused_steps = h->psd_fused_steps;
+    const ConeSet::Mark cones = h->cones->mark();
     const size_t prof_used = h->prof_used;
     const int64_t psd_seen = h->prof_seen[FOS_PROF_PSD];
     const double fista_t = h->fista_t;
     bool ran = false;
     FOS_TRY(prox_affine(h, in, &post, &ran));
     if (!ran) {
-        h->psd_cur = psd_cur; h->psd_have_prev = psd_have_prev; h->psd_fused_steps = psd_fused_steps; h->prof_seen[FOS_PROF_PSD] = psd_seen; h->fista_t = fista_t;
+        h->cones->rewind(cones); h->prof_seen[FOS_PROF_PSD] = psd_seen; h->fista_t = fista_t;
         // (event pairs recorded around no-op launches: forget them; the CG records of this solve stay)
         for (size_t k = prof_used; k < h->prof_used; ++k)
             if (h->prof_recs[k].cls == FOS_PROF_PSD || (h->prof_recs[k].cls == FOS_PROF_OTHER && h->prof_recs[k].j == 1)) h->prof_recs[k].cls = -1;
@@ -887,28 +875,23 @@ int step_once(fos_solver* h, int64_t i, const d2** check_on, bool will_check, bo
                 const bool fuse_ew = h->relax_ew, fuse_psd = h->psd_fuse;          // (per handle: read at fos_create)
                 // GAP / DR, no status check in this step, every non-elementwise cone a PSD(64) cone with a basis from the last projection:
                 // relaxation, projection and the step's last pass are ONE launch (PsdFuse, fos_internal.hpp)
-                if (fuse_psd && !gapa && !will_check && h->nsoc == 0 && h->nexp == 0 && !h->psd_big && !h->ls_interval && !h->gapp_iproj && !h->lp.interval &&
-                    psd_fuse_possible(cg, h->npsd, h->psd_kmin, h->psd_kmax, h->psd_V[h->psd_cur], h->psd_V[1 - h->psd_cur], h->psd_have_prev, h->psd_redo,
-                                      h->psd_phase_limit)) {
+                if (fuse_psd && !gapa && !will_check && !h->ls_interval && !h->gapp_iproj && !h->lp.interval && cone_set_can_fuse(*h->cones, cg)) {
                     RoctxRange range("fos:relaxation + PSD projection + final pass (one launch)");
                     const bool sh = h->in_step && h->shift_fuse && !h->direct_exact();
                     PsdFuse fz{};
                     fz.sol = h->SOL; fz.xv = h->X; fz.shift = sh ? h->RHS : nullptr;
                     fz.a1 = h->alpha1; fz.alpha = h->alpha; fz.alpha2 = h->alpha2;
-                    fz.ew_op = h->ew_op; fz.l = h->l;
+                    fz.ew_op = h->cones->ew_op; fz.l = h->l;
                     const int pe = prof_begin(h, FOS_PROF_PSD, 0, h->prof_seen[FOS_PROF_PSD]++);
-                    FOS_TRY(launch_cones_psd(cg, h->T2, h->T1, h->psd, h->npsd, h->psd_kmin, h->psd_kmax, h->psd_scratch, h->psd_V[h->psd_cur],
-                                             h->psd_V[1 - h->psd_cur], h->psd_have_prev, h->psd_stats, 0, h->psd_redo, &fz));
+                    FOS_TRY(cone_set_project_psd(h->cones, cg, h->T2, h->T1, &fz));
                     prof_end(h, pe);
-                    h->psd_cur = 1 - h->psd_cur; h->psd_have_prev = std::min(h->psd_have_prev + 1, 2);
-                    h->psd_fused_steps += 1;
                     h->shift_ready = sh;
                     return check_launch("fused relaxation + PSD projection + final pass");
                 }
                 const int pg = cg.gate ? 1 : 0;
                 int po = prof_begin_other(h, pg);
                 if (fuse_ew) {                       // the relaxation and the elementwise cones of S2! in one pass
-                    launch_relax_ew(cg, h->T1, h->T2, h->SOL, h->X, h->alpha1, gapa, h->ew_op);
+                    launch_relax_ew(cg, h->T1, h->T2, h->SOL, h->X, h->alpha1, gapa, h->cones->ew_op);
                     prof_end(h, po);
                     FOS_TRY(prox_cones(h, h->T2, h->T1, cg.gate, true));
                 } else {
@@ -1036,69 +1019,9 @@ int download_caller(fos_solver* h, double* z, const d2* src) {
     return FOS_OK;
 }
 
-int validate_cones(const char* which, int64_t total, int64_t nK, const int32_t* type, const int64_t* start, const int64_t* len) {
-    int64_t prev_end = 0;                                   // cones.jl:66-72
-    for (int64_t i = 0; i < nK; ++i) {
-        if (start[i] != prev_end + 1) { set_error("%s cone %lld: range starts at %lld, expected %lld (ranges must be contiguous and ordered)", which, (long long)i + 1, (long long)start[i], (long long)prev_end + 1); return FOS_EINVAL; }
-        if (len[i] < 1) { set_error("%s cone %lld: empty range", which, (long long)i + 1); return FOS_EINVAL; }
-        if (len[i] > (int64_t)INT32_MAX) { set_error("%s cone %lld: %lld entries exceed the int32 cone descriptor", which, (long long)i + 1, (long long)len[i]); return FOS_EUNSUPPORTED; }
-        prev_end = start[i] + len[i] - 1;
-        switch (type[i]) {
-            case FOS_CONE_FREE: case FOS_CONE_ZERO: case FOS_CONE_NONNEG: case FOS_CONE_NONPOS: case FOS_CONE_SOC: break;
-            case FOS_CONE_SOCROT:
-                if (len[i] < 2) { set_error("%s cone %lld: rotated SOC needs >= 2 entries", which, (long long)i + 1); return FOS_EINVAL; }
-                break;
-            case FOS_CONE_SDP:
-                if (psd_order(len[i]) < 0) { set_error("%s cone %lld: SDP length %lld is not k(k+1)/2", which, (long long)i + 1, (long long)len[i]); return FOS_EINVAL; }
-                break;
-            case FOS_CONE_EXPPRIMAL: case FOS_CONE_EXPDUAL:
-                if (len[i] != 3) { set_error("%s cone %lld: an exponential cone has exactly 3 entries (got %lld)", which, (long long)i + 1, (long long)len[i]); return FOS_EINVAL; }
-                break;
-            default:
-                set_error("%s cone %lld: unknown cone code %d", which, (long long)i + 1, (int)type[i]);
-                return FOS_EINVAL;
-        }
-    }
-    if (prev_end != total) { set_error("%s cones cover 1..%lld, expected 1..%lld", which, (long long)prev_end, (long long)total); return FOS_EINVAL; }
-    return FOS_OK;
-}
-
-void add_cones(int64_t offset, bool is_K1, int64_t nK, const int32_t* type, const int64_t* start, const int64_t* len,
-               std::vector<uint8_t>& ew, std::vector<ConeDesc>& soc, std::vector<ConeDesc>& psd, std::vector<ConeDesc>& expc) {
-    // K2 cone on [x | r]: part1 primal, part2 dual.   K1 cone on [y | s]: part1 dual, part2 primal.   cones.jl:136-140
-    for (int64_t i = 0; i < nK; ++i) {
-        const int64_t s0 = offset + start[i] - 1;
-        uint8_t prim = 0, dual = 0;
-        bool ewise = true;
-        switch (type[i]) {
-            case FOS_CONE_FREE: prim = EW_COPY; dual = EW_ZERO; break;      // cones.jl:100
-            case FOS_CONE_ZERO: prim = EW_ZERO; dual = EW_COPY; break;      // cones.jl:98
-            case FOS_CONE_NONNEG: prim = dual = EW_MAX0; break;             // cones.jl:101
-            case FOS_CONE_NONPOS: prim = dual = EW_MIN0; break;             // cones.jl:102
-            default: ewise = false;
-        }
-        if (ewise) {
-            const uint8_t op = is_K1 ? (uint8_t)(dual | (prim << 2)) : (uint8_t)(prim | (dual << 2));
-            for (int64_t k = 0; k < len[i]; ++k) ew[s0 + k] = op;
-        } else {
-            for (int64_t k = 0; k < len[i]; ++k) ew[s0 + k] = EW_SKIP;
-            ConeDesc cd;
-            cd.start = s0; cd.len = (int32_t)len[i]; cd.type = type[i];
-            cd.dual_part = is_K1 ? 0 : 1;
-            cd.k = type[i] == FOS_CONE_SDP ? psd_order(len[i]) : 0;
-            if (type[i] == FOS_CONE_SDP) psd.push_back(cd);
-            else if (type[i] == FOS_CONE_EXPPRIMAL || type[i] == FOS_CONE_EXPDUAL) expc.push_back(cd);
-            else soc.push_back(cd);
-        }
-    }
-}
-
 }  // namespace
 
 namespace fos {
-int validate_cone_table(const char* which, int64_t total, int64_t nK, const int32_t* type, const int64_t* start, const int64_t* len) {
-    return validate_cones(which, total, nK, type, start, len);
-}
 int long_project_planes(const LaunchCtx& c, LongPlanes& lp, d2* X, int64_t i) {
     const int K = (int)(2 * (lp.nsave + 1)), neq = (int)(lp.nsave + 1), nin = K - neq;
     const int nb = c.vec_blocks;
@@ -1253,8 +1176,8 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     int ndev = 0;
     FOS_TRY(fos_device_count(&ndev));
     if (device < 0 || device >= ndev) { set_error("device %d out of range (0..%d)", device, ndev - 1); return FOS_EINVAL; }
-    FOS_TRY(validate_cones("K1", m, nK1, K1type, K1start, K1len));
-    FOS_TRY(validate_cones("K2", n, nK2, K2type, K2start, K2len));
+    FOS_TRY(cone_table_check("K1", m, nK1, K1type, K1start, K1len));
+    FOS_TRY(cone_table_check("K2", n, nK2, K2type, K2start, K2len));
     FOS_HIP(hipSetDevice(device));
 
     struct Guard {                       // frees everything on an early error return
@@ -1275,15 +1198,9 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     FOS_HIP(hipGetDeviceProperties(&prop, device));
     const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     h->cus = cus;
-    if (const char* e = getenv("FOS_PSD_WAVE")) h->psd_wave = atoi(e);
-    if (const char* e = getenv("FOS_PSD_REFINE")) h->psd_refine = atoi(e);
-    if (const char* e = getenv("FOS_PSD_EXTRAPOLATE")) h->psd_extrapolate = atoi(e) != 0;
-    if (const char* e = getenv("FOS_PSD_THETA")) h->psd_theta = atof(e);
+    const PsdTuning psd_tuning = PsdTuning::from_env();
     h->psd_fuse = !(getenv("FOS_PSD_FUSE") && atoi(getenv("FOS_PSD_FUSE")) == 0);
     h->relax_ew = !(getenv("FOS_RELAX_EW") && atoi(getenv("FOS_RELAX_EW")) == 0);
-    h->psd_narrow = getenv("FOS_PSD_NARROW") != nullptr;
-    h->psd_wide = getenv("FOS_PSD_WIDE") != nullptr;
-    if (const char* e = getenv("FOS_PSD_THREADS")) h->psd_wide_threads = atoi(e);
     if (const char* e = getenv("FOS_SPMV_WG")) h->nwg_target = std::max(1, std::min(16384, atoi(e)));
     else h->nwg_target = cus * 12;      // ~1.7x the resident workgroups (7/CU): measured best for the KKT sweep (dynamic balance)
 
@@ -1488,33 +1405,16 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     h->cg_blocks = std::min(h->cg_blocks, 1024);         // (cg_close_iteration adds at most 1024 r.r records per wavefront)
 
     // ---- cones
-    std::vector<uint8_t> ew(l, 0);
-    std::vector<ConeDesc> soc, psd, expc;
-    add_cones(0, false, nK2, K2type, K2start, K2len, ew, soc, psd, expc);
-    add_cones(n, true, nK1, K1type, K1start, K1len, ew, soc, psd, expc);
-    h->nexp = (int)expc.size();
-    FOS_TRY(dev_upload(h, &h->expc, expc));
-    ew[l - 1] = (uint8_t)(EW_MAX0 | (EW_MAX0 << 2));            // tau, kappa  cones.jl:138,141
-    FOS_TRY(dev_upload(h, &h->ew_op, ew));
-    h->nsoc = (int)soc.size();
-    FOS_TRY(psd_sign_setup(psd, &h->psd_big));            // (orders > 64 leave the list: projected by matrix products)
-    h->npsd = (int)psd.size();
-    FOS_TRY(dev_upload(h, &h->soc, soc));
-    for (auto& cd : psd) h->psd_kmax = std::max(h->psd_kmax, cd.k);
-    h->psd_kmin = h->psd_kmax;
-    for (auto& cd : psd) h->psd_kmin = std::min(h->psd_kmin, cd.k);
-    FOS_TRY(dev_upload(h, &h->psd, psd));
-    size_t sb = psd_scratch_bytes(h->psd_kmax, h->npsd);
-    if (sb) FOS_TRY(dev_alloc(h, &h->psd_scratch, sb / sizeof(double)));
-    if (!getenv("FOS_PSD_COLD")) {
-        const size_t vb = psd_basis_doubles(h->psd_kmax, h->npsd);
-        if (vb) { FOS_TRY(dev_alloc(h, &h->psd_V[0], vb)); FOS_TRY(dev_alloc(h, &h->psd_V[1], vb)); }
-        if (vb && h->psd_kmin == 64 && h->psd_kmax == 64) {
-            FOS_TRY(dev_alloc(h, &h->psd_redo, (size_t)8 * h->npsd + 16));     // code [2 npsd] + 64-bit column mask [2 npsd] + a diagnostics switch
-            FOS_HIP(hipMemset(h->psd_redo, 0, sizeof(int32_t) * (8 * h->npsd + 16)));
-            if (getenv("FOS_PSD_DEBUG_REC")) { const int32_t v = 77; FOS_HIP(hipMemcpy(h->psd_redo + 8 * h->npsd, &v, sizeof(v), hipMemcpyHostToDevice)); }
-        }
-    }
+    ConeTable table;
+    table.ew.assign(l, 0);
+    cone_table_add(table, 0, CONE_K2, nK2, K2type, K2start, K2len);
+    cone_table_add(table, n, CONE_K1, nK1, K1type, K1start, K1len);
+    table.ew[l - 1] = (uint8_t)(EW_MAX0 | (EW_MAX0 << 2));      // tau, kappa  cones.jl:138,141
+    ConeSetOptions cone_opts;
+    cone_opts.warm = !getenv("FOS_PSD_COLD");
+    cone_opts.refine_records = true;
+    cone_opts.debug_rec = getenv("FOS_PSD_DEBUG_REC") != nullptr;
+    FOS_TRY(cone_set_build(table, (int64_t)l, cone_opts, psd_tuning, &h->cones));
 
     // ---- scalars
     FOS_TRY(dev_alloc(h, &h->st, 1));
@@ -1616,7 +1516,7 @@ int fos_destroy(fos_handle h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     transport_teardown(h, true);
     for (auto& r : h->prof_recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    psd_sign_destroy(h->psd_big);
+    cone_set_destroy(h->cones, h->stream);
     for (void* p : h->pooled) uncached_release(p);
     for (void* p : h->owned) (void)hipFree(p);
     if (h->st_host) (void)hipHostFree(h->st_host);
@@ -2059,34 +1959,6 @@ int fos_bench_kkt(fos_handle h, int32_t reps, double* total_ms) {
     if (total_ms) *total_ms = ms;
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    return FOS_OK;
-}
-
-int fos_psd_debug(fos_handle h, int32_t collect_stats, int32_t phase_limit) {
-    if (!h) { set_error("NULL handle"); return FOS_EINVAL; }
-    FOS_HIP(hipSetDevice(h->device));
-    if (collect_stats && !h->psd_stats && h->npsd > 0) {
-        FOS_TRY(dev_alloc(h, &h->psd_stats, (size_t)2 * h->npsd));
-        FOS_HIP(hipMemset(h->psd_stats, 0, sizeof(int) * 2 * h->npsd));
-    }
-    h->psd_phase_limit = phase_limit;
-    return FOS_OK;
-}
-
-int fos_psd_stats(fos_handle h, int32_t* sweeps, int64_t cap, int64_t* count) {
-    if (!h || !count) { set_error("NULL argument"); return FOS_EINVAL; }
-    FOS_HIP(hipSetDevice(h->device));
-    *count = h->psd_stats ? 2 * (int64_t)h->npsd : 0;
-    if (sweeps && h->psd_stats) {
-        FOS_HIP(hipStreamSynchronize(h->stream));
-        FOS_HIP(hipMemcpy(sweeps, h->psd_stats, sizeof(int32_t) * (size_t)std::min<int64_t>(cap, *count), hipMemcpyDeviceToHost));
-    }
-    return FOS_OK;
-}
-
-int fos_psd_fused_steps(fos_handle h, int64_t* count) {
-    if (!h || !count) { set_error("NULL argument"); return FOS_EINVAL; }
-    *count = h->psd_fused_steps;
     return FOS_OK;
 }
 

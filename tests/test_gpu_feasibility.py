@@ -192,6 +192,45 @@ def test_cone_product_set_matches_oracle(pkg, oracle):
             pkg.HipFeasibility(pkg.Feasibility(pkg.ConeProduct(bad), pkg.IndBox(0.0, 1.0), n))
 
 
+def test_cone_product_set_with_a_psd_cone_of_order_65(pkg, oracle):
+    """The orders > 64 branch of the shared cone projection (the matrix sign function, csrc/psd_sign.hip) through the Feasibility form, beside a
+    NonNeg and a SOC block: three projections in a row, cold and then warm twice (only orders <= 64 keep a basis: order 65 must not care)."""
+    orc = oracle
+    cones = [("NonNeg", 5), ("SDP", 65 * 66 // 2), ("SOC", 7)]
+    n = sum(l for _, l in cones)
+    K = orc.ConeProduct.from_lengths([(orc.CONE_CODES[k], l) for k, l in cones])
+    d = pkg.HipFeasibility(pkg.Feasibility(pkg.ConeProduct(cones), pkg.IndBox(-np.inf, np.inf), n))
+    rng = np.random.default_rng(65)
+    x = rng.standard_normal(n)
+    y = np.empty(n)
+    for rep in range(3):
+        K.prox(y, x)
+        yd = d.prox(1, x)
+        assert np.linalg.norm(yd - y) <= 5e-13 * max(1.0, np.linalg.norm(x)), rep          # (the bound of test_gpu_psd_orders.py at order 65)
+        x = x + 1e-3 * rng.standard_normal(n)
+
+
+def test_cone_product_set_defined_twice_on_one_handle(pkg, oracle):
+    """fos_feas_set_cones twice on the same slot of a live handle: the second ConeProduct (other kinds, other PSD orders, the same n) replaces
+    the first one's tables, workspaces and warm-start bases; both project like the oracle."""
+    orc = oracle
+    n = sum(l for _, l in MIXED_CONES)
+    other = [("SDP", 36), ("SOC", n - 36 - 1275 - 9), ("SDP", 1275), ("NonPos", 3), ("ExpDual", 3), ("Zero", 3)]
+    assert sum(l for _, l in other) == n
+    d = pkg.HipFeasibility(pkg.Feasibility(pkg.ConeProduct(MIXED_CONES), pkg.IndBox(-np.inf, np.inf), n))
+    rng = np.random.default_rng(4)
+    y = np.empty(n)
+    for cones in (MIXED_CONES, other):
+        if cones is other:
+            d.set_set(1, pkg.ConeProduct(other))
+        K = orc.ConeProduct.from_lengths([(orc.CONE_CODES[k], l) for k, l in cones])
+        x = rng.standard_normal(n)
+        for rep in range(2):                                   # cold, then warm from this table's own basis
+            K.prox(y, x)
+            assert np.abs(d.prox(1, x) - y).max() <= 5e-12 * max(1.0, np.abs(x).max()), (cones is other, rep)
+            x = x + 1e-3 * rng.standard_normal(n)
+
+
 @pytest.mark.parametrize("algname", ["DR", "GAPA", "FISTA", "Dykstra"])
 def test_affine_cone_feasibility_matches_oracle(pkg, oracle, algname):
     """find x in {A x = b} n K, K a product of all cone types (the conic feasibility problem the reference's form is made for):
