@@ -11,6 +11,6 @@ from . import workloads            # noqa: F401
 from .interface import (AP, DR, FISTA, GAP, GAPA, GAPP, Dykstra, FOSAlgorithm, FOSMathProgModel, HipHSDE, HSDEStatus,  # noqa: F401
                         LineSearchWrapper, LongstepWrapper, Solution, solve, HEADER_CG, HEADER_DIRECT,
                         ConeProduct, Feasibility, FeasibilityModel, FeasibilitySolution, HipFeasibility, IndAffine, IndBox, IndBallL2, IndBallL1, IndSimplex, IndHalfspace,
-                        IndHyperslab, IndPoint, IndFree, SeparableSum, NormL1, SqrNormL2, ElasticNet, Linear, NormL2, HuberLoss, NormLinf, LeastSquares, solve_feasibility, direct_factor_code, DIRECT_FACTOR_NAMES,
+                        IndHyperslab, IndPoint, IndFree, SeparableSum, NormL1, SqrNormL2, ElasticNet, Linear, NormL2, HuberLoss, NormLinf, LeastSquares, Quadratic, solve_feasibility, direct_factor_code, DIRECT_FACTOR_NAMES,
                         host_equilibrate, equilibrate_passes)
 from . import sharding             # noqa: F401

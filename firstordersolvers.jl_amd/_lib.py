@@ -16,6 +16,7 @@ CONE_CODES = {"Free": 0, "Zero": 1, "NonNeg": 2, "NonPos": 3, "SOC": 4, "SOCRota
               "ExpPrimal": 7, "ExpDual": 8}
 SET_CODES = {"IndFree": 0, "IndBallL2": 1, "IndBallL1": 2, "IndSimplex": 3, "IndHalfspace": 4, "IndHyperslab": 5, "IndPoint": 6, "IndBox": 7}      # FOS_SET_*
 FN_CODES = {"NormL1": 32, "SqrNormL2": 33, "ElasticNet": 34, "Linear": 35, "NormL2": 36, "HuberLoss": 37, "NormLinf": 38}      # FOS_FN_*: further kinds of fos_feas_set_blocks
+LS_FORM_CODES = {"sparse_factored": 0, "normal": 1}      # FOS_LS_FORM_*
 ALG_GAP, ALG_GAPA, ALG_FISTA, ALG_DYKSTRA = 0, 1, 2, 3
 CG_REFERENCE, CG_FUSED_P, CG_MERGED_SWEEP, CG_MERGED_UPDATE, CG_RESIDENT = 0, 1, 2, 3, 4
 DEBUG_PUPDATE_DELAY = 1
@@ -143,6 +144,15 @@ PROTOTYPES = {
     "fos_feas_affine_sparse_factored_stats": (C.c_int, [_h, C.c_int32, _dp]),
     "fos_feas_affine_sparse_factored_plan": (C.c_int, [_h, C.c_int32, _i64p]),
     "fos_host_affine_sparse_factored": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _dp, _dp, C.c_int32, _dp, _dp]),
+    "fos_feas_set_quadratic": (C.c_int, [_h, C.c_int32, _dp, _dp, C.c_int32]),
+    "fos_feas_set_least_squares_normal": (C.c_int, [_h, C.c_int32, C.c_int64, _dp, _dp, C.c_double, C.c_int32]),
+    "fos_feas_set_least_squares_sparse": (C.c_int, [_h, C.c_int32, C.c_int64, _i64p, _i64p, _dp, _dp, C.c_double, C.c_int32, C.c_int32]),
+    "fos_feas_nspace_stats": (C.c_int, [_h, C.c_int32, _dp]),
+    "fos_host_quadratic": (C.c_int, [C.c_int64, _dp, _dp, _dp, _dp]),
+    "fos_host_least_squares_normal": (C.c_int, [C.c_int64, C.c_int64, _dp, _dp, C.c_double, _dp, _dp]),
+    "fos_host_least_squares_sparse": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _dp, _dp, C.c_double, C.c_int32, _dp, _dp]),
+    "fos_host_symv_packed": (C.c_int, [C.c_int64, _dp, _dp, _dp, _i32p]),
+    "fos_bench_symv_packed": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, _dp]),
     "fos_feas_set_box": (C.c_int, [_h, C.c_int32, C.c_double, C.c_double]),
     "fos_feas_set_box_arrays": (C.c_int, [_h, C.c_int32, _dp, _dp]),
     "fos_feas_set_cones": (C.c_int, [_h, C.c_int32, C.c_int64, _i32p, _i64p]),

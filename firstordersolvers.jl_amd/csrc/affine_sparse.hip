@@ -199,7 +199,8 @@ void sparse_affine_destroy(SparseAffine* a) {
 
 // The host half of every sparse IndAffine set-up (this file and affine_sparse_factored.hip).  A: m x n CSC, 1-based (Julia SparseMatrixCSC{Float64,Int64}); b[m]:
 // validated, the rows of [A | b] scaled to unit norm, A and A' as two CSR matrices.  `what` names the caller in the messages.
-int sparse_affine_rows(const char* what, int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, SparseRows* out) {
+int sparse_affine_rows(const char* what, int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, SparseRows* out,
+                       bool zero_rows) {
     if (m < 1 || n < 1 || !colptr || !rowval || !nzval || !b) { set_error("%s: bad argument", what); return FOS_EINVAL; }
     if (colptr[0] != 1) { set_error("%s: colptr must be 1-based (colptr[0] = %lld)", what, (long long)colptr[0]); return FOS_EINVAL; }
     const int64_t nnz = colptr[n] - 1;
@@ -217,13 +218,14 @@ int sparse_affine_rows(const char* what, int64_t m, int64_t n, const int64_t* co
             rcount[(size_t)i + 1]++;
         }
     }
-    std::vector<double> scale((size_t)m);
+    std::vector<double>& scale = out->scale;
+    scale.resize((size_t)m);
     std::vector<double>& bs = out->bs;
     bs.resize((size_t)m);
     for (int64_t i = 0; i < m; ++i) {
-        if (!(rn2[(size_t)i] > 0.0)) { set_error("%s: row %lld of A is zero (A must have full row rank)", what, (long long)i + 1); return FOS_EINVAL; }
+        if (!(rn2[(size_t)i] > 0.0) && !zero_rows) { set_error("%s: row %lld of A is zero (A must have full row rank)", what, (long long)i + 1); return FOS_EINVAL; }
         if (!(b[i] == b[i]) || std::fabs(b[i]) > 1e300) { set_error("%s: b has non-finite entries", what); return FOS_EINVAL; }
-        scale[(size_t)i] = 1.0 / std::sqrt(rn2[(size_t)i]);
+        scale[(size_t)i] = rn2[(size_t)i] > 0.0 ? 1.0 / std::sqrt(rn2[(size_t)i]) : 1.0;
         bs[(size_t)i] = b[i] * scale[(size_t)i];
     }
     // A' in CSR = the CSC arrays as they are (0-based, scaled); A in CSR by a counting pass (columns ascending inside a row)

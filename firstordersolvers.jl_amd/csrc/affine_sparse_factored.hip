@@ -14,6 +14,10 @@
 //     writes its result itself (r_j = s - b_j / y_i = x_i - s; an empty row of A': y_i = x_i); sf_fold_kernel adds a cut row's partials in segment order and
 //     applies the same epilogue.
 //   Nothing is atomic and every sum has a fixed order: the same input gives the same bits, from run to run and from handle to handle.
+//
+// LeastSquares(A, b, lambda) with a sparse wide A is the same object with a shifted G, as in affine_dense.hip: prox_f(x) = x - A'(A A' + I/lambda)^-1 (A x - b), with
+// the rows scaled by D:  x - Ah'(Ah Ah' + D^2/lambda)^-1 (Ah x - D b).  The set-up adds scale[i]^2 / lambda to the diagonal of G (sf_shift_diag_kernel) and everything
+// after it is unchanged; refine is 0, a zero row keeps scale 1 and dependent rows are accepted (the shifted G is positive definite).  lambda = 0 is IndAffine, to the bit.
 #include "fos_solver.hpp"
 #include "dev_common.hpp"
 
@@ -98,6 +102,11 @@ __global__ __launch_bounds__(SF_T) void sf_gram_kernel(int64_t m, int64_t L, con
     }
 }
 
+// set-up of LeastSquares: G[i, i] += scale[i]^2 / lambda  (da_shift_diag_kernel of affine_dense.hip)
+__global__ __launch_bounds__(SF_T) void sf_shift_diag_kernel(int64_t m, int64_t L, double* __restrict__ G, const double* __restrict__ scale, double inv_lambda) {
+    for (int64_t i = blockIdx.x * (int64_t)SF_T + threadIdx.x; i < m; i += (int64_t)gridDim.x * SF_T) G[i + i * L] += scale[i] * scale[i] * inv_lambda;
+}
+
 int sf_lanes(int len) {                                  // the fewest lanes (a power of two, at most 64) that leave a lane at most SF_LANE_ENTRIES entries of a row
     int g = 1;
     while (g < 64 && g * SF_LANE_ENTRIES < len) g <<= 1;
@@ -149,12 +158,14 @@ int sf_segment_length(int* seg) {
 }
 
 // what both the device set-up and the host emulation refuse, and the scaled rows
-int sf_rows(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int refine, SparseRows* R) {
-    const char* what = "IndAffine (sparse, factored)";
+const char* sf_name(double lambda) { return lambda > 0.0 ? "LeastSquares (sparse, factored)" : "IndAffine (sparse, factored)"; }
+int sf_rows(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int refine, SparseRows* R) {
+    const char* what = sf_name(lambda);
+    if (!(lambda >= 0.0) || lambda > 1e300) { set_error("LeastSquares: lambda must be finite and > 0"); return FOS_EINVAL; }
     if (m < 1 || n < 1 || m > n) { set_error("%s: bad argument (1 <= m <= n)", what); return FOS_EINVAL; }
     if (m > 46000) { set_error("%s: the inverse of A A' has order m = %lld: supported up to m = 46000", what, (long long)m); return FOS_EUNSUPPORTED; }
     if (refine < 0 || refine > 2) { set_error("%s: refine = %d (0, 1 or 2 refinement steps per projection)", what, refine); return FOS_EINVAL; }
-    FOS_TRY(sparse_affine_rows(what, m, n, colptr, rowval, nzval, b, R));
+    FOS_TRY(sparse_affine_rows(what, m, n, colptr, rowval, nzval, b, R, lambda > 0.0));
     for (int64_t j = 0; j < n; ++j)                                                   // (sf_gram_kernel adds a column's entries side by side)
         for (int32_t e = R->trp[(size_t)j] + 1; e < R->trp[(size_t)j + 1]; ++e)
             if (R->tci[(size_t)e] <= R->tci[(size_t)e - 1]) {
@@ -216,14 +227,15 @@ int sf_hip(const char* call, hipError_t e) {
 }  // namespace
 
 // A: m x n CSC, 1-based; b[m]; factor: FOS_DIRECT_FACTOR_*; refine: 0..2 refinement steps per projection.  Synchronises `stream`.
-int sparse_factored_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int factor, int refine,
-                          hipStream_t stream, SparseFactored** out) {
+int sparse_factored_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int factor,
+                          int refine, hipStream_t stream, SparseFactored** out) {
     if (factor != FOS_DIRECT_FACTOR_NEWTON && factor != FOS_DIRECT_FACTOR_CHOLESKY) {
-        set_error("IndAffine (sparse, factored): factor must be FOS_DIRECT_FACTOR_NEWTON or FOS_DIRECT_FACTOR_CHOLESKY");
+        set_error("%s: factor must be FOS_DIRECT_FACTOR_NEWTON or FOS_DIRECT_FACTOR_CHOLESKY", sf_name(lambda));
         return FOS_EINVAL;
     }
+    if (lambda > 0.0) refine = 0;
     SparseRows R;
-    FOS_TRY(sf_rows(m, n, colptr, rowval, nzval, b, refine, &R));
+    FOS_TRY(sf_rows(m, n, colptr, rowval, nzval, b, lambda, refine, &R));
     int seg = 0;
     FOS_TRY(sf_segment_length(&seg));
     SfPass P1, P2;
@@ -251,6 +263,10 @@ int sparse_factored_setup(int64_t m, int64_t n, const int64_t* colptr, const int
     SF_HIP(hipMemsetAsync(a->G, 0, sizeof(double) * L2, stream));
     hipLaunchKernelGGL(sf_gram_kernel, dim3((unsigned)std::min<int64_t>(a->L, 65536)), dim3(SF_T), 0, stream, m, a->L, (const int32_t*)a->rp, (const int32_t*)a->ci,
                        (const double*)a->va, (const int32_t*)a->trp, (const int32_t*)a->tci, (const double*)a->tva, a->G);
+    if (lambda > 0.0) {                                    // (a->e holds the row scales until the first projection overwrites it)
+        SF_HIP(hipMemcpyAsync(a->e, R.scale.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(sf_shift_diag_kernel, dim3((unsigned)std::min<int64_t>(256, (m + SF_T - 1) / SF_T)), dim3(SF_T), 0, stream, m, a->L, a->G, (const double*)a->e, 1.0 / lambda);
+    }
     {   // X = G^-1; the square work buffers go at the end of this block
         DenseWork w;
         w.c.stream = stream; w.c.l = m; w.L = a->L; w.G = a->G;
@@ -258,10 +274,10 @@ int sparse_factored_setup(int64_t m, int64_t n, const int64_t* colptr, const int
         w.fill(s);
         if (s.err != hipSuccess) { (void)hipGetLastError(); set_error("IndAffine (sparse, factored): hipMalloc of the set-up buffers (3 x %zu bytes) failed: %s", L2 * 8, hipGetErrorString(s.err)); return fail(FOS_ENOMEM); }
         double* X = nullptr;
-        DenseOpts o{"IndAffine (sparse, factored)", "A A'", factor, false};
+        DenseOpts o{sf_name(lambda), lambda > 0.0 ? "A A' + I/lambda" : "A A'", factor, false};
         o.bar = SF_BAR; o.newton_extra = 40;
         rc = dense_spd_inverse(w, o, &X, &a->inv);
-        if (rc == FOS_EINVAL) {
+        if (rc == FOS_EINVAL && !(lambda > 0.0)) {
             const std::string why = fos_last_error();
             set_error("IndAffine (sparse, factored): the inverse of A A' (rows scaled to unit norm) was not accepted: A needs full row rank  [%s]", why.c_str());
         }
@@ -274,6 +290,13 @@ int sparse_factored_setup(int64_t m, int64_t n, const int64_t* colptr, const int
     if (e != hipSuccess) { set_error("IndAffine (sparse, factored) set-up: a kernel launch failed: %s", hipGetErrorString(e)); return fail(FOS_EHIP); }
     *out = a;
     return FOS_OK;
+}
+
+// G = B B' (+ identity on the padding m .. L-1) for a sparse B of m rows: its CSR (rp / ci / va) and the CSR of B' (trp / tci / tva), column indices strictly
+// ascending in every row of B'; G: L x L column-major, zeroed by the caller (sf_gram_kernel; nspace.hip forms A'A with it)
+void launch_sf_gram(hipStream_t stream, int64_t m, int64_t L, const int32_t* rp, const int32_t* ci, const double* va, const int32_t* trp, const int32_t* tci,
+                    const double* tva, double* G) {
+    hipLaunchKernelGGL(sf_gram_kernel, dim3((unsigned)std::min<int64_t>(L, 65536)), dim3(SF_T), 0, stream, m, L, rp, ci, va, trp, tci, tva, G);
 }
 
 namespace {
@@ -360,11 +383,12 @@ void sf_host_pass(int pass, const SfPass& P, const std::vector<int32_t>& rp, con
 
 // the same validation and scaling, G in sf_gram_kernel's order, host_da_inverse for X, the segment tables of this matrix (FOS_SF_SEG honoured; the tables do not depend on
 // the device) and both passes, the folds and the m-space products in the kernels' summation order
-int host_affine_sparse_factored(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int refine, const double* x,
-                                double* y) {
-    if (!x || !y) { set_error("IndAffine (sparse, factored): bad argument"); return FOS_EINVAL; }
+int host_affine_sparse_factored(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int refine,
+                                const double* x, double* y) {
+    if (!x || !y) { set_error("%s: bad argument", sf_name(lambda)); return FOS_EINVAL; }
+    if (lambda > 0.0) refine = 0;
     SparseRows R;
-    FOS_TRY(sf_rows(m, n, colptr, rowval, nzval, b, refine, &R));
+    FOS_TRY(sf_rows(m, n, colptr, rowval, nzval, b, lambda, refine, &R));
     int seg = 0;
     FOS_TRY(sf_segment_length(&seg));
     SfPass P1, P2;
@@ -376,7 +400,9 @@ int host_affine_sparse_factored(int64_t m, int64_t n, const int64_t* colptr, con
             const int32_t c = R.ci[(size_t)e];
             for (int32_t t = R.trp[(size_t)c]; t < R.trp[(size_t)c + 1]; ++t) G[(size_t)(R.tci[(size_t)t] + i * m)] += R.va[(size_t)e] * R.tva[(size_t)t];
         }
-    FOS_TRY(host_da_inverse("IndAffine (sparse, factored)", m, G.data(), X.data()));
+    if (lambda > 0.0)
+        for (int64_t i = 0; i < m; ++i) G[(size_t)(i + i * m)] += R.scale[(size_t)i] * R.scale[(size_t)i] * (1.0 / lambda);
+    FOS_TRY(host_da_inverse(sf_name(lambda), m, G.data(), X.data()));
     std::vector<double> r((size_t)m), d((size_t)m), e((size_t)m);
     sf_host_pass(1, P1, R.rp, R.ci, R.va, x, R.bs.data(), r.data());
     host_da_symv(m, m, X.data(), r.data(), nullptr, 1.0, d.data());

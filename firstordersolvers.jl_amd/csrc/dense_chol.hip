@@ -276,8 +276,11 @@ void launch_dense_spd_inverse_chol(const LaunchCtx& c, int64_t L, const double* 
 }
 
 // The same blocking and block order on the host (tests): K is k x k column-major, X its inverse (full, exactly symmetric).  Returns the first bad pivot's
-// column (0-based) or -1.
-int64_t host_chol_inverse(int64_t k, const double* K, double* X) {
+// column (0-based) or -1.  fused: every multiply-add is one fused operation, k ascending, as the device's matrix-core products and contracted scalar code round them
+// (the n-space forms' emulation, nspace.hip); otherwise product and sum round separately, as this emulation always did.
+int64_t host_chol_inverse(int64_t k, const double* K, double* X, bool fused) {
+    auto mad = [fused](double a, double b, double c) { return fused ? std::fma(a, b, c) : c + a * b; };      // c + a b
+    auto msub = [fused](double a, double b, double c) { return fused ? std::fma(-a, b, c) : c - a * b; };    // c - a b
     const int64_t L = (k + CH_B - 1) / CH_B * CH_B, nb = L / CH_B;
     const size_t L2 = (size_t)L * (size_t)L;
     std::vector<double> G(L2, 0.0), Lw(L2, 0.0), Ww(L2, 0.0), Xf(L2, 0.0);
@@ -291,7 +294,7 @@ int64_t host_chol_inverse(int64_t k, const double* K, double* X) {
             for (int cc = 0; cc < CH_B; ++cc)
                 for (int r = 0; r < CH_B; ++r) {
                     double acc = 0.0;
-                    for (int64_t kk = 0; kk < j * CH_B; ++kk) acc += Lw[(i * CH_B + r) + kk * L] * Lw[(j * CH_B + cc) + kk * L];
+                    for (int64_t kk = 0; kk < j * CH_B; ++kk) acc = mad(Lw[(i * CH_B + r) + kk * L], Lw[(j * CH_B + cc) + kk * L], acc);
                     at(Lw, i, j, r, cc) = at(G, i, j, r, cc) - acc;
                 }
         for (int cc = 0; cc < CH_B; ++cc) {                                 // (2)
@@ -300,20 +303,20 @@ int64_t host_chol_inverse(int64_t k, const double* K, double* X) {
             const double rt = std::sqrt(d);
             for (int r = cc; r < CH_B; ++r) at(Lw, j, j, r, cc) = r == cc ? rt : at(Lw, j, j, r, cc) / rt;
             for (int jj = cc + 1; jj < CH_B; ++jj)
-                for (int r = jj; r < CH_B; ++r) at(Lw, j, j, r, jj) -= at(Lw, j, j, r, cc) * at(Lw, j, j, jj, cc);
+                for (int r = jj; r < CH_B; ++r) at(Lw, j, j, r, jj) = msub(at(Lw, j, j, r, cc), at(Lw, j, j, jj, cc), at(Lw, j, j, r, jj));
         }
         for (int cc = 0; cc < CH_B; ++cc)
             for (int r = 0; r < CH_B; ++r) {
                 if (r < cc) at(Lw, j, j, r, cc) = 0.0;
                 double s = r == cc ? 1.0 : 0.0;
-                for (int p = cc; p < r; ++p) s -= at(Lw, j, j, r, p) * at(Ww, j, j, p, cc);
+                for (int p = cc; p < r; ++p) s = msub(at(Lw, j, j, r, p), at(Ww, j, j, p, cc), s);
                 at(Ww, j, j, r, cc) = r < cc ? 0.0 : s / at(Lw, j, j, r, r);
             }
         for (int64_t i = j + 1; i < nb; ++i) {                              // (3)
             for (int cc = 0; cc < CH_B; ++cc)
                 for (int r = 0; r < CH_B; ++r) {
                     double acc = 0.0;
-                    for (int kk = 0; kk < CH_B; ++kk) acc += at(Lw, i, j, r, kk) * at(Ww, j, j, cc, kk);
+                    for (int kk = 0; kk < CH_B; ++kk) acc = mad(at(Lw, i, j, r, kk), at(Ww, j, j, cc, kk), acc);
                     S[r][cc] = acc;
                 }
             for (int cc = 0; cc < CH_B; ++cc)
@@ -325,13 +328,13 @@ int64_t host_chol_inverse(int64_t k, const double* K, double* X) {
             for (int cc = 0; cc < CH_B; ++cc)
                 for (int r = 0; r < CH_B; ++r) {
                     double acc = 0.0;
-                    for (int64_t kk = j * CH_B; kk < i * CH_B; ++kk) acc += Lw[(i * CH_B + r) + kk * L] * Ww[kk + (j * CH_B + cc) * L];
+                    for (int64_t kk = j * CH_B; kk < i * CH_B; ++kk) acc = mad(Lw[(i * CH_B + r) + kk * L], Ww[kk + (j * CH_B + cc) * L], acc);
                     S[r][cc] = acc;
                 }
             for (int cc = 0; cc < CH_B; ++cc)
                 for (int r = 0; r < CH_B; ++r) {
                     double acc = 0.0;
-                    for (int kk = 0; kk < CH_B; ++kk) acc += at(Ww, i, i, r, kk) * S[kk][cc];
+                    for (int kk = 0; kk < CH_B; ++kk) acc = mad(at(Ww, i, i, r, kk), S[kk][cc], acc);
                     at(Ww, i, j, r, cc) = -acc;
                 }
         }
@@ -341,7 +344,7 @@ int64_t host_chol_inverse(int64_t k, const double* K, double* X) {
                 for (int r = 0; r < CH_B; ++r) {
                     if (i == j && r < cc) continue;
                     double acc = 0.0;
-                    for (int64_t kk = i * CH_B; kk < L; ++kk) acc += Ww[kk + (i * CH_B + r) * L] * Ww[kk + (j * CH_B + cc) * L];
+                    for (int64_t kk = i * CH_B; kk < L; ++kk) acc = mad(Ww[kk + (i * CH_B + r) * L], Ww[kk + (j * CH_B + cc) * L], acc);
                     at(Xf, i, j, r, cc) = acc;
                     Xf[(j * CH_B + cc) + (i * CH_B + r) * L] = acc;
                 }

@@ -158,11 +158,12 @@ __global__ __launch_bounds__(FEAS_THREADS) void feas_pad_identity_kernel(int64_t
 }
 
 struct FeasSet {
-    int kind = 0;                   // 0 unset, 1 IndAffine (dense), 2 IndBox, 3 ConeProduct, 4 host callback, 5 IndAffine (sparse A), 6 separable sum of sets, 7 IndAffine (dense, factored), 8 IndAffine (sparse A, factored)
+    int kind = 0;                   // 0 unset, 1 IndAffine (dense), 2 IndBox, 3 ConeProduct, 4 host callback, 5 IndAffine (sparse A), 6 separable sum of sets, 7 IndAffine (dense, factored), 8 IndAffine (sparse A, factored), 9 Quadratic / LeastSquares in the n-space
     SparseAffine* sa = nullptr;     // kind 5 (affine_sparse.hip)
     DenseAffine* da = nullptr;      // kind 7 (affine_dense.hip)
     SparseFactored* sf = nullptr;   // kind 8 (affine_sparse_factored.hip)
     SetBlocks* sb = nullptr;        // kind 6 (sets.hip)
+    NSpace* ns = nullptr;           // kind 9 (nspace.hip)
     fos_prox_fn cb = nullptr;       // kind 4: prox!(y, S, x) evaluated by the caller on pinned host vectors
     void* cb_ctx = nullptr;
     double *cb_x = nullptr, *cb_y = nullptr;
@@ -264,6 +265,8 @@ int feas_prox(fos_feas* h, int which, double* y, const double* x) {
         FOS_TRY(dense_affine_project(s.da, h->stream, y, x));
     } else if (s.kind == 8) {                                             // IndAffine over a sparse A, factored: two segmented sparse passes and the dense inverse of A A', a fixed number of launches
         FOS_TRY(sparse_factored_project(s.sf, h->stream, y, x));
+    } else if (s.kind == 9) {                                             // Quadratic, LeastSquares (normal equations): three one-rhs tile products over the packed M and M^-1, six launches
+        FOS_TRY(nspace_prox(s.ns, h->stream, y, x));
     } else if (s.kind == 6) {                                             // balls, simplex, halfspaces ... in contiguous blocks: a fixed number of launches, no copy
         FOS_TRY(set_blocks_project(s.sb, h->stream, y, x));
     } else if (s.kind == 4) {                                             // any other ProximableFunction: the caller's prox! on host vectors
@@ -467,7 +470,7 @@ int fos_feas_destroy(fos_feas_handle h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (void* q : h->owned) (void)hipFree(q);
-    for (FeasSet& s : h->S) { if (s.cb_x) (void)hipHostFree(s.cb_x); if (s.cb_y) (void)hipHostFree(s.cb_y); cone_set_destroy(s.cones, h->stream); sparse_affine_destroy(s.sa); dense_affine_destroy(s.da); sparse_factored_destroy(s.sf); set_blocks_destroy(s.sb); }
+    for (FeasSet& s : h->S) { if (s.cb_x) (void)hipHostFree(s.cb_x); if (s.cb_y) (void)hipHostFree(s.cb_y); cone_set_destroy(s.cones, h->stream); sparse_affine_destroy(s.sa); dense_affine_destroy(s.da); sparse_factored_destroy(s.sf); set_blocks_destroy(s.sb); nspace_destroy(s.ns); }
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return FOS_OK;
@@ -619,7 +622,7 @@ int fos_feas_set_affine_sparse_factored(fos_feas_handle h, int32_t which, int64_
     if (!h || which < 1 || which > 2 || m < 1) { set_error("fos_feas_set_affine_sparse_factored: bad argument (m >= 1, which = 1 | 2)"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
     SparseFactored* sf = nullptr;
-    FOS_TRY(sparse_factored_setup(m, h->n, colptr, rowval, nzval, b, factor, refine, h->stream, &sf));   // (synchronises the stream: no projection onto the set being replaced runs any more)
+    FOS_TRY(sparse_factored_setup(m, h->n, colptr, rowval, nzval, b, 0.0, factor, refine, h->stream, &sf));   // (synchronises the stream: no projection onto the set being replaced runs any more)
     FeasSet& s = h->S[which - 1];
     sparse_factored_destroy(s.sf);
     s.sf = sf; s.kind = 8;
@@ -638,7 +641,80 @@ int fos_feas_affine_sparse_factored_plan(fos_feas_handle h, int32_t which, int64
 // test-only, host: the sparse factored form's scaling, inverse, segment tables and two passes in the kernels' order (affine_sparse_factored.hip)
 int fos_host_affine_sparse_factored(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int32_t refine,
                                     const double* x, double* y) {
-    return host_affine_sparse_factored(m, n, colptr, rowval, nzval, b, refine, x, y);
+    return host_affine_sparse_factored(m, n, colptr, rowval, nzval, b, 0.0, refine, x, y);
+}
+
+// ---- the n-space forms (nspace.hip) and the sparse wide LeastSquares (affine_sparse_factored.hip with a shifted diagonal).  Every object is built first, so that
+// a refused call leaves the set as it was
+namespace {
+int feas_install_nspace(fos_feas* h, int32_t which, NSpace* ns) {                  // (the set-up synchronised the stream: no prox of the set being replaced runs any more)
+    FeasSet& s = h->S[which - 1];
+    nspace_destroy(s.ns);
+    s.ns = ns; s.kind = 9;
+    return FOS_OK;
+}
+}  // namespace
+int fos_feas_set_quadratic(fos_feas_handle h, int32_t which, const double* Q, const double* q, int32_t factor) {
+    if (!h || which < 1 || which > 2) { set_error("fos_feas_set_quadratic: NULL handle or which not in {1, 2}"); return FOS_EINVAL; }
+    FOS_HIP(hipSetDevice(h->device));
+    NSpace* ns = nullptr;
+    FOS_TRY(nspace_setup_quadratic(h->n, Q, q, factor, h->stream, &ns));
+    return feas_install_nspace(h, which, ns);
+}
+int fos_feas_set_least_squares_normal(fos_feas_handle h, int32_t which, int64_t m, const double* A, const double* b, double lambda, int32_t factor) {
+    if (!h || which < 1 || which > 2) { set_error("fos_feas_set_least_squares_normal: NULL handle or which not in {1, 2}"); return FOS_EINVAL; }
+    FOS_HIP(hipSetDevice(h->device));
+    NSpace* ns = nullptr;
+    FOS_TRY(nspace_setup_ls_dense(m, h->n, A, b, lambda, factor, h->stream, &ns));
+    return feas_install_nspace(h, which, ns);
+}
+int fos_feas_set_least_squares_sparse(fos_feas_handle h, int32_t which, int64_t m, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b,
+                                      double lambda, int32_t form, int32_t factor) {
+    if (!h || which < 1 || which > 2) { set_error("fos_feas_set_least_squares_sparse: NULL handle or which not in {1, 2}"); return FOS_EINVAL; }
+    if (!(lambda > 0.0) || lambda > 1e300) { set_error("LeastSquares: lambda must be finite and > 0"); return FOS_EINVAL; }
+    FOS_HIP(hipSetDevice(h->device));
+    if (form == FOS_LS_FORM_NORMAL) {
+        NSpace* ns = nullptr;
+        FOS_TRY(nspace_setup_ls_sparse(m, h->n, colptr, rowval, nzval, b, lambda, factor, h->stream, &ns));
+        return feas_install_nspace(h, which, ns);
+    }
+    if (form != FOS_LS_FORM_SPARSE_FACTORED) { set_error("LeastSquares (sparse): form must be FOS_LS_FORM_SPARSE_FACTORED or FOS_LS_FORM_NORMAL"); return FOS_EINVAL; }
+    SparseFactored* sf = nullptr;
+    FOS_TRY(sparse_factored_setup(m, h->n, colptr, rowval, nzval, b, lambda, factor, 0, h->stream, &sf));
+    FeasSet& s = h->S[which - 1];
+    sparse_factored_destroy(s.sf);
+    s.sf = sf; s.kind = 8;
+    return FOS_OK;
+}
+int fos_feas_nspace_stats(fos_feas_handle h, int32_t which, double* out8) {
+    if (!h || !out8 || which < 1 || which > 2 || h->S[which - 1].kind != 9) { set_error("fos_feas_nspace_stats: set %d is not a Quadratic or a LeastSquares in the normal-equations form", (int)which); return FOS_EINVAL; }
+    nspace_stats(h->S[which - 1].ns, out8);
+    return FOS_OK;
+}
+// test-only, host: the n-space forms' scaling, inverse, packing and three tile products in the kernels' order (nspace.hip)
+int fos_host_quadratic(int64_t n, const double* Q, const double* q, const double* x, double* y) { return host_nspace_quadratic(n, Q, q, x, y); }
+int fos_host_least_squares_normal(int64_t m, int64_t n, const double* A, const double* b, double lambda, const double* x, double* y) {
+    return host_nspace_ls_dense(m, n, A, b, lambda, x, y);
+}
+int fos_host_least_squares_sparse(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int32_t form,
+                                  const double* x, double* y) {
+    if (!(lambda > 0.0) || lambda > 1e300) { set_error("LeastSquares: lambda must be finite and > 0"); return FOS_EINVAL; }
+    if (form == FOS_LS_FORM_NORMAL) return host_nspace_ls_sparse(m, n, colptr, rowval, nzval, b, lambda, x, y);
+    if (form != FOS_LS_FORM_SPARSE_FACTORED) { set_error("LeastSquares (sparse): form must be FOS_LS_FORM_SPARSE_FACTORED or FOS_LS_FORM_NORMAL"); return FOS_EINVAL; }
+    return host_affine_sparse_factored(m, n, colptr, rowval, nzval, b, lambda, 0, x, y);
+}
+int fos_host_symv_packed(int64_t k, const double* X, const double* v, double* y, int32_t* count) { return host_nspace_symv_packed(k, X, v, y, count); }
+// measurement: the one-rhs tile product against red_symm_kernel on the same tiles (nspace.hip); out4 = ms per product of each, bytes of the stream, max |difference|
+int fos_bench_symv_packed(int32_t device, int64_t k, int32_t reps, double* out4) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { set_error("no HIP device is visible: the HIP path has no CPU fallback"); return FOS_ENODEVICE; }
+    if (device < 0 || device >= ndev) { set_error("device %d out of range (0..%d)", device, ndev - 1); return FOS_EINVAL; }
+    FOS_HIP(hipSetDevice(device));
+    hipStream_t stream = nullptr;
+    FOS_HIP(hipStreamCreate(&stream));
+    const int rc = nspace_bench_symv(k, reps, stream, out4);
+    (void)hipStreamDestroy(stream);
+    return rc;
 }
 
 int fos_feas_set_box(fos_feas_handle h, int32_t which, double lo, double hi) {

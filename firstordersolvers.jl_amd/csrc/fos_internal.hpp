@@ -583,7 +583,7 @@ void launch_dense_scale_identity(const LaunchCtx& c, int64_t L, double* X, doubl
 void launch_dense_symv(const LaunchCtx& c, int64_t ld, const double* G, const double* t, double* w);
 // the inverse of a dense symmetric positive definite matrix through a blocked Cholesky factorisation (dense_chol.hip); the same blocking on the host (tests)
 void launch_dense_spd_inverse_chol(const LaunchCtx& c, int64_t L, const double* G, double* X, double* Lw, double* Ww, int32_t* info);
-int64_t host_chol_inverse(int64_t k, const double* K, double* X);
+int64_t host_chol_inverse(int64_t k, const double* K, double* X, bool fused = false);      // fused: one rounding per multiply-add, as the device rounds
 // G = A A' + (identity on the padding m .. L-1) for a ROW-major m x ld matrix A (ld % 64 == 0): L x L column-major, exactly symmetric, fixed summation order (dense_chol.hip)
 void launch_dense_gram_rows(const LaunchCtx& c, int64_t m, int64_t ld, const double* A, int64_t L, double* G);
 void launch_direct_rhs(const LaunchCtx& c, const double2* W, const double2* x, double* t);
@@ -741,8 +741,11 @@ struct SparseRows {                              // host: what sparse_affine_row
     int64_t m = 0, n = 0, nnz = 0;
     std::vector<int32_t> rp, ci, trp, tci;
     std::vector<double> va, tva, bs;
+    std::vector<double> scale;                   // the row factors (1 for a zero row)
 };
-int sparse_affine_rows(const char* what, int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, SparseRows* out);
+// zero_rows: a zero row is accepted and keeps scale 1 (the sparse LeastSquares); otherwise it is FOS_EINVAL
+int sparse_affine_rows(const char* what, int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, SparseRows* out,
+                       bool zero_rows = false);
 int sparse_affine_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int cus, SparseAffine** out);
 int sparse_affine_project(SparseAffine* a, hipStream_t stream, double* y, const double* x);      // y, x: device vectors of length n, y must not alias x
 void sparse_affine_reset(SparseAffine* a, hipStream_t stream);                                   // a new solve: lambda = 0
@@ -764,14 +767,34 @@ double host_da_wave(const double* lane64);
 int host_da_inverse(const char* what, int64_t m, const double* G, double* X);
 // IndAffine(A, b) with a sparse A, factored form (affine_sparse_factored.hip): A and A' kept as CSR, (A A')^-1 of order m dense, two segmented sparse passes per projection
 struct SparseFactored;
-int sparse_factored_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int factor, int refine,
-                          hipStream_t stream, SparseFactored** out);
+// lambda: 0: IndAffine(A, b), > 0: LeastSquares(A, b, lambda) (refine is then 0, zero and dependent rows are accepted)
+int sparse_factored_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int factor,
+                          int refine, hipStream_t stream, SparseFactored** out);
+void launch_sf_gram(hipStream_t stream, int64_t m, int64_t L, const int32_t* rp, const int32_t* ci, const double* va, const int32_t* trp, const int32_t* tci,
+                    const double* tva, double* G);
 int sparse_factored_project(SparseFactored* a, hipStream_t stream, double* y, const double* x);  // y, x: device vectors of length n, y must not alias x
 void sparse_factored_stats(const SparseFactored* a, double* out8);
 void sparse_factored_plan(const SparseFactored* a, int64_t* out8);
 void sparse_factored_destroy(SparseFactored* a);
-int host_affine_sparse_factored(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int refine, const double* x,
-                                double* y);
+int host_affine_sparse_factored(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int refine,
+                                const double* x, double* y);
+// Quadratic(Q, q) and LeastSquares in the normal-equations form (nspace.hip): y = M^-1 (x + c), M and its inverse kept as packed lower-triangle tile streams,
+// three one-right-hand-side tile products per prox
+struct NSpace;
+int nspace_setup_quadratic(int64_t n, const double* Q, const double* q, int factor, hipStream_t stream, NSpace** out);
+int nspace_setup_ls_dense(int64_t m, int64_t n, const double* A, const double* b, double lambda, int factor, hipStream_t stream, NSpace** out);
+int nspace_setup_ls_sparse(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int factor,
+                           hipStream_t stream, NSpace** out);
+int nspace_prox(NSpace* a, hipStream_t stream, double* y, const double* x);                       // y, x: device vectors of at least n doubles
+void nspace_stats(const NSpace* a, double* out8);
+void nspace_destroy(NSpace* a);
+int nspace_bench_symv(int64_t k, int reps, hipStream_t stream, double* out4);
+void host_nspace_symv(const RedPlan& P, const std::vector<double>& tiles, const double* v, double* y);
+int host_nspace_quadratic(int64_t n, const double* Q, const double* q, const double* x, double* y);
+int host_nspace_ls_dense(int64_t m, int64_t n, const double* A, const double* b, double lambda, const double* x, double* y);
+int host_nspace_ls_sparse(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, const double* x,
+                          double* y);
+int host_nspace_symv_packed(int64_t k, const double* X, const double* v, double* y, int32_t* count);
 // Separable sums of convex vector sets (sets.hip): norm balls, simplex, halfspace / hyperslab, point, free, scalar box -- contiguous blocks covering 1..n
 struct SetBlocks;
 int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec, SetBlocks** out);

@@ -1117,16 +1117,41 @@ class LeastSquares:
     """f(x) = lam/2 |A x - b|^2 with a dense A (m x n, 1 <= m <= n, m <= 46 000; rank-deficient and zero rows allowed), lam > 0.  The prox
     y = x - A'(A A' + I/lam)^-1 (A x - b) runs on the factored form of IndAffine with the diagonal of A A' shifted (fos_feas_set_least_squares): two passes
     over A per prox, a fixed number of launches.  factor = "cholesky" | "newton" builds the inverse.  m > n, m > 46 000 or a sparse A: pass an object with
-    a prox(y, x) method instead (the host-callback path)."""
+    a prox(y, x) method instead (the host-callback path), or opt in to one of the forms below (form=None keeps all of the above to the letter).
+    form="normal": the normal-equations form in the n-space, y = (I + lam A'A)^-1 (x + lam A'b), for a dense or scipy-sparse A of ANY m with n <= 46 000
+    (fos_feas_set_least_squares_normal / _sparse): I + lam A'A and its inverse are kept as packed triangles, a prox is three tile products, six launches.
+    form="sparse_factored": a scipy-sparse A with m <= min(n, 46 000) stays sparse, with the dense inverse of A A' + I/lam (fos_feas_set_least_squares_sparse): the
+    sparse factored IndAffine with a shifted diagonal; zero and dependent rows are accepted."""
 
     MAX_M = 46000
+    MAX_N = 46000
 
-    def __init__(self, A, b, lam=1.0, factor="cholesky"):
+    def __init__(self, A, b, lam=1.0, factor="cholesky", form=None):
         self.lam = _finite_scalar("LeastSquares: lam", lam)
         if not self.lam > 0.0:
             raise ValueError("LeastSquares: lam > 0 is required")
         direct_factor_code(factor)
         self.factor = factor
+        if form not in (None, "normal", "sparse_factored"):
+            raise ValueError("LeastSquares: form must be None, 'normal' or 'sparse_factored', not %r" % (form,))
+        self.form = form
+        self.sparse = form is not None and bool(sp.issparse(A))
+        if form == "sparse_factored" and not self.sparse:
+            raise ValueError("LeastSquares: form='sparse_factored' keeps a scipy.sparse A")
+        if self.sparse:
+            self.A = sp.csc_matrix(A, dtype=np.float64)
+            self.A.sum_duplicates(); self.A.sort_indices()
+            self.b = np.ascontiguousarray(np.asarray(b, dtype=np.float64))
+            m, n = self.A.shape
+            if m < 1 or n < 1 or self.b.shape != (m,):
+                raise ValueError("LeastSquares(A, b): A must be m x n and b of length m")
+            if not (np.all(np.isfinite(self.A.data)) and np.all(np.isfinite(self.b))):
+                raise ValueError("LeastSquares(A, b): A and b must be finite")
+            if form == "normal" and n > self.MAX_N:
+                raise ValueError("LeastSquares(form='normal'): n = %d, the inverse of I + lam A'A is supported up to n = %d" % (n, self.MAX_N))
+            if form == "sparse_factored" and (m > n or m > self.MAX_M):
+                raise ValueError("LeastSquares(form='sparse_factored'): m = %d, n = %d: 1 <= m <= min(n, %d) is required" % (m, n, self.MAX_M))
+            return
         if sp.issparse(A):
             raise ValueError("LeastSquares: A must be dense (a sparse A: an object with a prox(y, x) method, evaluated on the host)")
         self.A = np.ascontiguousarray(np.asarray(A, dtype=np.float64))
@@ -1135,6 +1160,32 @@ class LeastSquares:
             raise ValueError("LeastSquares(A, b): A must be m x n and b of length m")
         if not (np.all(np.isfinite(self.A)) and np.all(np.isfinite(self.b))):
             raise ValueError("LeastSquares(A, b): A and b must be finite")
+        if form == "normal" and self.A.shape[1] > self.MAX_N:
+            raise ValueError("LeastSquares(form='normal'): n = %d, the inverse of I + lam A'A is supported up to n = %d" % (self.A.shape[1], self.MAX_N))
+
+
+class Quadratic:
+    """ProximalOperators.Quadratic(Q, q): f(x) = 1/2 x'Qx + q'x with a dense symmetric positive semidefinite Q of order n <= 46 000.  The prox
+    y = (I + Q)^-1 (x - q) runs in the n-space (fos_feas_set_quadratic): I + Q, scaled to a unit diagonal, and its inverse are kept as packed triangles and a prox is
+    three tile products, six launches.  ONLY THE LOWER TRIANGLE of Q is read (Q[i, j], i >= j): there is no symmetry test.  factor = "cholesky" | "newton" builds
+    the inverse; a Q that is not positive semidefinite is refused at set-up with the column of the failed pivot.  Feasibility(Quadratic(Q, q), IndBox(lo, hi), n)
+    under DR is the box-constrained QP."""
+
+    MAX_N = 46000
+
+    def __init__(self, Q, q, factor="cholesky"):
+        direct_factor_code(factor)
+        self.factor = factor
+        if sp.issparse(Q):
+            raise ValueError("Quadratic: Q must be dense")
+        self.Q = np.ascontiguousarray(np.asarray(Q, dtype=np.float64))
+        self.q = np.ascontiguousarray(np.asarray(q, dtype=np.float64))
+        if self.Q.ndim != 2 or self.Q.shape[0] < 1 or self.Q.shape[0] != self.Q.shape[1] or self.q.shape != (self.Q.shape[0],):
+            raise ValueError("Quadratic(Q, q): Q must be n x n and q of length n")
+        if self.Q.shape[0] > self.MAX_N:
+            raise ValueError("Quadratic: n = %d, the inverse of I + Q is supported up to n = %d" % (self.Q.shape[0], self.MAX_N))
+        if not (np.all(np.isfinite(np.tril(self.Q))) and np.all(np.isfinite(self.q))):
+            raise ValueError("Quadratic(Q, q): Q and q must be finite")
 
 
 class SeparableSum:
@@ -1188,7 +1239,7 @@ PROX_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C
 class Feasibility:
     """struct Feasibility{T1,T2}(S1, S2, n)   Feasibility.jl:2-6.  S1, S2: IndAffine, IndBox, ConeProduct, a vector set (IndBallL2, IndBallL1,
     IndSimplex, IndHalfspace, IndHyperslab, IndPoint, IndFree), a separable function (NormL1, SqrNormL2, ElasticNet, Linear, NormL2, HuberLoss,
-    NormLinf) or a SeparableSum of them, LeastSquares(A, b, lam) with a dense A (all device resident: Feasibility(LeastSquares(A, b, lam), NormL1(mu), n)
+    NormLinf) or a SeparableSum of them, LeastSquares(A, b, lam) with a dense A, Quadratic(Q, q), LeastSquares(form="normal" | "sparse_factored") for a tall or sparse A (all device resident: Feasibility(LeastSquares(A, b, lam), NormL1(mu), n)
     under DR is the lasso, with no host round trip), or any
     object with a `prox(y, x)` method filling y = prox_S(x) in place (the ProximableFunction protocol; evaluated on the host)."""
 
@@ -1227,8 +1278,24 @@ class HipFeasibility:
                 self.set_set(which, S)
 
     def set_set(self, which, S):
-        """set `which` (1 | 2) becomes S: an IndAffine, LeastSquares, IndBox, ConeProduct or an object with a prox(y, x) method; replaces what was there"""
-        if isinstance(S, LeastSquares):
+        """set `which` (1 | 2) becomes S: an IndAffine, LeastSquares, Quadratic, IndBox, ConeProduct or an object with a prox(y, x) method; replaces what was there"""
+        if isinstance(S, Quadratic):
+            if S.Q.shape[0] != self.n:
+                raise ValueError("Quadratic: Q has order %d, the problem has n = %d" % (S.Q.shape[0], self.n))
+            _lib.check(self._lib.fos_feas_set_quadratic(self._h, which, _lib.dptr(S.Q), _lib.dptr(S.q), direct_factor_code(S.factor)))
+        elif isinstance(S, LeastSquares) and S.form is not None:
+            if S.A.shape[1] != self.n:
+                raise ValueError("LeastSquares: A has %d columns, the problem has n = %d" % (S.A.shape[1], self.n))
+            if S.sparse:
+                i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+                colptr = np.ascontiguousarray(S.A.indptr, dtype=np.int64) + 1          # Julia 1-based
+                rowval = np.ascontiguousarray(S.A.indices, dtype=np.int64) + 1
+                nzval = np.ascontiguousarray(S.A.data, dtype=np.float64)
+                _lib.check(self._lib.fos_feas_set_least_squares_sparse(self._h, which, S.A.shape[0], i64(colptr), i64(rowval), _lib.dptr(nzval), _lib.dptr(S.b), S.lam,
+                                                                       _lib.LS_FORM_CODES[S.form], direct_factor_code(S.factor)))
+            else:
+                _lib.check(self._lib.fos_feas_set_least_squares_normal(self._h, which, S.A.shape[0], _lib.dptr(S.A), _lib.dptr(S.b), S.lam, direct_factor_code(S.factor)))
+        elif isinstance(S, LeastSquares):
             if S.A.shape[1] != self.n:
                 raise ValueError("LeastSquares: A has %d columns, the problem has n = %d" % (S.A.shape[1], self.n))
             _lib.check(self._lib.fos_feas_set_least_squares(self._h, which, S.A.shape[0], _lib.dptr(S.A), _lib.dptr(S.b), S.lam, direct_factor_code(S.factor)))
@@ -1404,8 +1471,15 @@ class HipFeasibility:
                 "launches": int(o[6]), "bytes": int(o[7]), "ld": int(p[0]), "gram_order": int(p[1]), "span_cols": int(p[2]), "spans": int(p[3]),
                 "rows_per_block": int(p[4]), "row_blocks": int(p[5])}
 
+    def nspace_stats(self, which):
+        """the set-up record of a Quadratic or a LeastSquares(form="normal") (fos_feas_nspace_stats)"""
+        o = np.zeros(8)
+        _lib.check(self._lib.fos_feas_nspace_stats(self._h, which, _lib.dptr(o)))
+        return {"n": int(o[0]), "m": int(o[1]), "factor": DIRECT_FACTOR_NAMES[int(o[2])], "fell_back": int(o[3]), "probe_resid": float(o[4]), "launches": int(o[5]),
+                "bytes": int(o[6]), "tiles": int(o[7])}
+
     def affine_sparse_factored_stats(self, which):
-        """the sparse factored IndAffine's set-up record and the segment tables of its two passes (fos_feas_affine_sparse_factored_stats, ..._plan)"""
+        """the sparse factored IndAffine's (or sparse wide LeastSquares') set-up record and the segment tables of its two passes (fos_feas_affine_sparse_factored_stats, ..._plan)"""
         o, p = np.zeros(8), np.zeros(8, dtype=np.int64)
         _lib.check(self._lib.fos_feas_affine_sparse_factored_stats(self._h, which, _lib.dptr(o)))
         _lib.check(self._lib.fos_feas_affine_sparse_factored_plan(self._h, which, p.ctypes.data_as(C.POINTER(C.c_int64))))

@@ -323,7 +323,8 @@ end
 #      with S1, S2 among ProximalOperators.IndAffine (dense A), IndBox -- the sets of test/testfeasibility.jl -- and
 #      FirstOrderSolvers.ConeProduct on the device, as are IndBallL2, IndBallL1, IndSimplex, IndHalfspace, IndHyperslab, IndPoint and IndFree,
 #      the functions NormL1, SqrNormL2, ElasticNet, Linear, NormL2, HuberLoss, NormLinf (fos_feas_set_blocks) and LeastSquares over a dense A
-#      (fos_feas_set_least_squares); any other ProximableFunction through a host callback (fos_feas_set_callback).
+#      (fos_feas_set_least_squares), a tall or sparse LeastSquares and a dense Quadratic in the n-space (fos_feas_set_least_squares_normal, _sparse,
+#      fos_feas_set_quadratic); any other ProximableFunction through a host callback (fos_feas_set_callback).
 #      init_algorithm! returns a HipFeasData; iterate dispatches on it; FeasibilityModel, populate_solution and the printed table
 #      stay the reference's own code.
 import ..FirstOrderSolvers: FeasibilityModel, FeasibilityStatus
@@ -425,6 +426,67 @@ function host_least_squares(A::Matrix{Float64}, b::Vector{Float64}, lambda::Real
                 Int64(size(A, 1)), Int64(size(A, 2)), At, b, Float64(lambda), x, y))
     return y
 end
+# The n-space forms (csrc/nspace.hip): y = M^-1 (x + c) with M and its inverse kept as packed triangles, three tile products per prox, n <= 46 000.
+# Quadratic(Q, q): M = I + Q (only the lower triangle of Q is read: the transposed copy's lower triangle is the caller's upper one, the same matrix when Q is symmetric)
+const FOS_LS_FORM_SPARSE_FACTORED = Int32(0)
+const FOS_LS_FORM_NORMAL = Int32(1)
+function feas_set_quadratic!(handle::Ptr{Cvoid}, which::Integer, Q::AbstractMatrix, q::AbstractVector, factor::Symbol = :cholesky)
+    Qt = Matrix{Float64}(transpose(Q))                      # row-major for the C ABI
+    qv = Vector{Float64}(q)
+    GC.@preserve Qt qv check(ccall((:fos_feas_set_quadratic, libfoship), Cint, (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Int32),
+                                   handle, Int32(which), Qt, qv, factor == :newton ? Int32(0) : Int32(1)))
+end
+# LeastSquares(A, b, lambda) in the normal-equations form, M = I + lambda A'A: a dense A of any m (the tall A that fos_feas_set_least_squares refuses)
+function feas_set_least_squares_normal!(handle::Ptr{Cvoid}, which::Integer, A::AbstractMatrix, b::AbstractVector, lambda::Real, factor::Symbol = :cholesky)
+    At = Matrix{Float64}(transpose(A))
+    bv = Vector{Float64}(b)
+    GC.@preserve At bv check(ccall((:fos_feas_set_least_squares_normal, libfoship), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Int32),
+                                   handle, Int32(which), Int64(size(A, 1)), At, bv, Float64(lambda), factor == :newton ? Int32(0) : Int32(1)))
+end
+# ... over a sparse A: form = :normal (any m, n <= 46 000) or :sparse_factored (m <= min(n, 46 000): the sparse factored IndAffine with a shifted diagonal)
+function feas_set_least_squares_sparse!(handle::Ptr{Cvoid}, which::Integer, A::SparseArrays.SparseMatrixCSC, b::AbstractVector, lambda::Real, form::Symbol,
+                                        factor::Symbol = :cholesky)
+    As = SparseArrays.SparseMatrixCSC{Float64,Int64}(A)
+    bv = Vector{Float64}(b)
+    GC.@preserve As bv check(ccall((:fos_feas_set_least_squares_sparse, libfoship), Cint,
+                                   (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Int32, Int32),
+                                   handle, Int32(which), Int64(size(As, 1)), As.colptr, As.rowval, As.nzval, bv, Float64(lambda),
+                                   form == :normal ? FOS_LS_FORM_NORMAL : FOS_LS_FORM_SPARSE_FACTORED, factor == :newton ? Int32(0) : Int32(1)))
+end
+function feas_nspace_stats(handle::Ptr{Cvoid}, which::Integer)
+    out = zeros(Float64, 8)
+    check(ccall((:fos_feas_nspace_stats, libfoship), Cint, (Ptr{Cvoid}, Int32, Ptr{Cdouble}), handle, Int32(which), out))
+    return (n = Int(out[1]), m = Int(out[2]), factor = out[3] == 1 ? :cholesky : :newton, fell_back = out[4] != 0, probe_resid = out[5], launches = Int(out[6]),
+            bytes = Int(out[7]), tiles = Int(out[8]))
+end
+# test entries: the host emulations of the n-space forms and of the one-right-hand-side tile product (no GPU needed)
+function host_quadratic(Q::Matrix{Float64}, q::Vector{Float64}, x::Vector{Float64})
+    Qt = Matrix{Float64}(transpose(Q))
+    y = similar(x)
+    check(ccall((:fos_host_quadratic, libfoship), Cint, (Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}), Int64(length(x)), Qt, q, x, y))
+    return y
+end
+function host_least_squares_normal(A::Matrix{Float64}, b::Vector{Float64}, lambda::Real, x::Vector{Float64})
+    At = Matrix{Float64}(transpose(A))
+    y = similar(x)
+    check(ccall((:fos_host_least_squares_normal, libfoship), Cint, (Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}),
+                Int64(size(A, 1)), Int64(size(A, 2)), At, b, Float64(lambda), x, y))
+    return y
+end
+function host_least_squares_sparse(A::SparseArrays.SparseMatrixCSC{Float64,Int64}, b::Vector{Float64}, lambda::Real, form::Symbol, x::Vector{Float64})
+    y = similar(x)
+    check(ccall((:fos_host_least_squares_sparse, libfoship), Cint,
+                (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Int32, Ptr{Cdouble}, Ptr{Cdouble}),
+                Int64(size(A, 1)), Int64(size(A, 2)), A.colptr, A.rowval, A.nzval, b, Float64(lambda),
+                form == :normal ? FOS_LS_FORM_NORMAL : FOS_LS_FORM_SPARSE_FACTORED, x, y))
+    return y
+end
+function host_symv_packed(X::Matrix{Float64}, v::Vector{Float64})
+    y = similar(v)
+    count = zeros(Int32, size(X))
+    check(ccall((:fos_host_symv_packed, libfoship), Cint, (Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}), Int64(length(v)), X, v, y, count))
+    return y, count
+end
 # test entry: the host emulation of the sparse factored IndAffine (no GPU needed)
 function host_affine_sparse_factored(A::SparseArrays.SparseMatrixCSC{Float64,Int64}, b::Vector{Float64}, refine::Integer, x::Vector{Float64})
     y = similar(x)
@@ -493,7 +555,17 @@ mutable struct HipFeasData <: FOSSolverData
                                               (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}),
                                               d.handle, which, Int64(size(As, 1)), As.colptr, As.rowval, As.nzval, b))
             elseif S isa ProximalOperators.LeastSquares && hasproperty(S, :A) && S.A isa Matrix && hasproperty(S, :lambda) && size(S.A, 1) <= min(size(S.A, 2), 46000)
-                feas_set_least_squares!(d.handle, which, S.A, S.b, S.lambda, get(model.options, :affine_factor, :cholesky))      # wider, taller or sparse A: the callback below
+                feas_set_least_squares!(d.handle, which, S.A, S.b, S.lambda, get(model.options, :affine_factor, :cholesky))
+            elseif S isa ProximalOperators.LeastSquares && hasproperty(S, :A) && S.A isa Matrix && hasproperty(S, :lambda) && size(S.A, 2) <= 46000
+                # a tall dense A (or m > 46 000): the normal-equations form in the n-space
+                feas_set_least_squares_normal!(d.handle, which, S.A, S.b, S.lambda, get(model.options, :affine_factor, :cholesky))
+            elseif S isa ProximalOperators.LeastSquares && hasproperty(S, :A) && S.A isa SparseArrays.SparseMatrixCSC && hasproperty(S, :lambda) &&
+                   (size(S.A, 1) <= min(size(S.A, 2), 46000) || size(S.A, 2) <= 46000)
+                # a sparse A: wide, it stays sparse with the dense inverse of A A' + I/lambda; tall, the normal-equations form
+                feas_set_least_squares_sparse!(d.handle, which, S.A, S.b, S.lambda, size(S.A, 1) <= min(size(S.A, 2), 46000) ? :sparse_factored : :normal,
+                                               get(model.options, :affine_factor, :cholesky))
+            elseif S isa ProximalOperators.Quadratic && hasproperty(S, :Q) && S.Q isa Matrix && size(S.Q, 1) <= 46000
+                feas_set_quadratic!(d.handle, which, S.Q, S.q, get(model.options, :affine_factor, :cholesky))      # a dense Q: the n-space form
             elseif vectorset_block(S) !== nothing           # a ball, simplex, halfspace, hyperslab, point, the free set or a separable function: one block of length n
                 feas_set_blocks!(d.handle, which, model.n, [(vectorset_block(S)..., Int64(model.n))])
             else                                            # any other ProximableFunction: prox!(y, S, x) on host vectors [Feasibility.jl:2-6]

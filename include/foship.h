@@ -552,6 +552,42 @@ int fos_feas_affine_sparse_factored_plan(fos_feas_handle h, int32_t which, int64
  * summation order.  x, y: n-vectors. */
 int fos_host_affine_sparse_factored(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b,
                                     int32_t refine, const double* x, double* y);
+/* The N-SPACE forms (csrc/nspace.hip): functions whose prox (step 1) is  y = M^-1 (x + c)  for a symmetric positive definite M of order n <= 46000 with
+ * lambda_min(M) >= 1.  They replace the host callback (fos_feas_set_callback) that a Quadratic, a tall LeastSquares (m > n) and a sparse LeastSquares needed --
+ * ProximalOperators.Quadratic and the LeastSquares it factors in the n-space.  Set-up: M is formed on the device, Jacobi-scaled to a unit diagonal (Mt = D M D),
+ * inverted once (factor: FOS_DIRECT_FACTOR_*; accepted at a probe residual of 1e-7, which the prox squares), and BOTH Mt and its inverse K are kept as packed
+ * lower-triangle tile streams (4 L^2 bytes each, L = n rounded up to 64).  A prox, with w = D x + c~:  z = K w,  z += K (w - Mt z),  y = D z: three
+ * one-right-hand-side tile products and their folds, six launches whatever n, no host synchronise, nothing atomic, the same bits from run to run.
+ *   fos_feas_set_quadratic             Quadratic(Q, q): f(x) = 1/2 x'Qx + q'x, M = I + Q, c = -q.  Q: n x n, ONLY ITS LOWER TRIANGLE is read (Q[i * n + j], i >= j;
+ *                                      no symmetry test); q: n.  Q not positive semidefinite (a pivot fails): FOS_EINVAL naming the column.
+ *   fos_feas_set_least_squares_normal  LeastSquares(A, b, lambda), normal equations: M = I + lambda A'A, c = lambda A'b; A dense m x n ROW-major, ANY m >= 1
+ *                                      (fos_feas_set_least_squares refuses m > n), lambda > 0 finite.
+ *   fos_feas_set_least_squares_sparse  LeastSquares over a SPARSE A (CSC, 1-based, row indices strictly ascending inside a column, as
+ *                                      fos_feas_set_affine_sparse_factored takes it).  form = FOS_LS_FORM_NORMAL: the n-space form above, any m, n <= 46000;
+ *                                      form = FOS_LS_FORM_SPARSE_FACTORED: fos_feas_set_affine_sparse_factored's object with scale[i]^2 / lambda added to the diagonal
+ *                                      of G (as fos_feas_set_least_squares does for a dense A): 1 <= m <= min(n, 46000), refine 0, zero and dependent rows accepted;
+ *                                      fos_feas_affine_sparse_factored_stats / _plan describe it.
+ * n > 46000: FOS_EUNSUPPORTED; lambda <= 0 or not finite, non-finite data, an unknown form or factor: FOS_EINVAL.  A refused call leaves the set as it was. */
+#define FOS_LS_FORM_SPARSE_FACTORED 0
+#define FOS_LS_FORM_NORMAL 1
+int fos_feas_set_quadratic(fos_feas_handle h, int32_t which, const double* Q, const double* q, int32_t factor);
+int fos_feas_set_least_squares_normal(fos_feas_handle h, int32_t which, int64_t m, const double* A, const double* b, double lambda, int32_t factor);
+int fos_feas_set_least_squares_sparse(fos_feas_handle h, int32_t which, int64_t m, const int64_t* colptr, const int64_t* rowval, const double* nzval,
+                                      const double* b, double lambda, int32_t form, int32_t factor);
+/* out8 = n, m (0: Quadratic), factor that produced the accepted inverse, fell_back, probe residual, kernel launches per prox (6), bytes kept, tiles of one stream */
+int fos_feas_nspace_stats(fos_feas_handle h, int32_t which, double* out8);
+/* Test-only host emulations (no GPU needed): the same validation and scaling, the blocked Cholesky inverse of fos_host_chol_inverse accepted by the same probe, the
+ * packing and the three tile products with their epilogues in the kernels' summation order.  x, y: n-vectors.  fos_host_least_squares_sparse: both forms
+ * (sparse_factored: fos_host_affine_sparse_factored's steps with the shift).  fos_host_symv_packed: the packing of the symmetric column-major k x k matrix X plus
+ * ONE one-right-hand-side tile product, y = X v; count (k x k int32, zeroed by the caller, may be NULL) receives how many tile slots hold each entry. */
+int fos_host_quadratic(int64_t n, const double* Q, const double* q, const double* x, double* y);
+int fos_host_least_squares_normal(int64_t m, int64_t n, const double* A, const double* b, double lambda, const double* x, double* y);
+int fos_host_least_squares_sparse(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda,
+                                  int32_t form, const double* x, double* y);
+int fos_host_symv_packed(int64_t k, const double* X, const double* v, double* y, int32_t* count);
+/* Measurement: the one-right-hand-side tile product against the two-right-hand-side kernel of direct = true's reduced form on the SAME tiles (second right-hand side
+ * zero), `reps` products each on a generated symmetric matrix of order k.  out4 = milliseconds per product (one rhs), (two rhs), bytes of the stream, max |difference|. */
+int fos_bench_symv_packed(int32_t device, int64_t k, int32_t reps, double* out4);
 int fos_feas_set_box(fos_feas_handle h, int32_t which, double lo, double hi);
 int fos_feas_set_box_arrays(fos_feas_handle h, int32_t which, const double* lo, const double* hi);     /* IndBox with array bounds (n each) */
 /* ConeProduct (src/cones.jl:31-94): ncones cones of type[i] (FOS_CONE_*) and len[i] entries, in order, contiguous, covering all n entries;
