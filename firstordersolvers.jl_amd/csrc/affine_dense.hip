@@ -178,10 +178,6 @@ DaPlan da_plan(int64_t m, int64_t n, int cus) {
     return p;
 }
 
-int da_hip(const char* call, hipError_t e) {
-    if (e != hipSuccess) { set_error("IndAffine (factored) set-up: %s -> %s", call, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? FOS_ENOMEM : FOS_EHIP; }
-    return FOS_OK;
-}
 const char* da_name(double lambda) { return lambda > 0.0 ? "LeastSquares" : "IndAffine (factored)"; }
 // the argument checks both objects share; lambda = 0: IndAffine
 int da_check_shape(int64_t m, int64_t n, bool ptrs, double lambda) {
@@ -224,39 +220,44 @@ int da_scaling(int64_t m, int64_t n, const double* A, const double* b, double la
 
 }  // namespace
 
-struct DenseAffine {
+struct DenseAffine : ProxObject, DevOwned {
+    DenseAffine() : ProxObject(FEAS_AFFINE_FACTORED) {}
+    int prox(hipStream_t stream, double* y, const double* x) override;
     int64_t m = 0, n = 0;
     DaPlan p;
     int refine = 0;
     double *A = nullptr, *G = nullptr, *X = nullptr, *b = nullptr;       // A: m x ld row-major (scaled); G, X: Lm x Lm column-major; b: scaled
     double *r = nullptr, *d = nullptr, *e = nullptr, *t = nullptr;       // m-space vectors (Lm)
     double *part1 = nullptr, *part2 = nullptr;                           // [nspan][Lm], [nrb][ld] (nrb > 1)
-    std::vector<void*> owned;
     DenseInv inv;
-    size_t bytes = 0;
 };
 
-void dense_affine_destroy(DenseAffine* a) {
-    if (!a) return;
-    for (void* q : a->owned) (void)hipFree(q);
-    delete a;
+// X = G^-1 for a factored form (this file and affine_sparse_factored.hip): G of order m, L x L column-major with the identity on its padding, X: L x L, both the
+// caller's.  The work-set comes from a scratch that lives to the end of the call; the inverse is accepted at `bar`; a refusal of IndAffine (lambda == 0) names
+// the full row rank it needs.  Synchronises `stream`.
+int factored_inverse(const DevOwned& own, double lambda, int factor, double bar, hipStream_t stream, int64_t m, int64_t L, double* G, double* Xout, DenseInv* inv) {
+    const size_t L2 = (size_t)L * (size_t)L;
+    DenseWork w;
+    w.c.stream = stream; w.c.l = m; w.L = L; w.G = G;
+    Scratch s;
+    w.fill(s);
+    if (s.err != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipMalloc of the set-up buffers (3 x %zu bytes) failed: %s", own.what, L2 * 8, hipGetErrorString(s.err)); return FOS_ENOMEM; }
+    double* X = nullptr;
+    DenseOpts o{own.what, lambda > 0.0 ? "A A' + I/lambda" : "A A'", factor, false};
+    o.bar = bar; o.newton_extra = 40;                      // cond(A A') up to ~1e8: ceil(log2 cond) + 7 steps at most, each of the extra ones checked
+    const int rc = dense_spd_inverse(w, o, &X, inv);
+    if (rc == FOS_EINVAL && !(lambda > 0.0)) {
+        const std::string why = fos_last_error();
+        set_error("%s: the inverse of A A' (rows scaled to unit norm) was not accepted: A needs full row rank  [%s]", own.what, why.c_str());
+    }
+    FOS_TRY(rc);
+    FOS_TRY(own.hip("hipMemcpyAsync", hipMemcpyAsync(Xout, X, sizeof(double) * L2, hipMemcpyDeviceToDevice, stream)));
+    return own.hip("hipStreamSynchronize", hipStreamSynchronize(stream));
 }
-
-namespace {
-int da_alloc(DenseAffine* a, double** out, size_t count) {
-    void* q = nullptr;
-    const size_t bytes = sizeof(double) * std::max<size_t>(count, 1);
-    const hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); set_error("IndAffine (factored): hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e)); return FOS_ENOMEM; }
-    a->owned.push_back(q); a->bytes += bytes;
-    *out = static_cast<double*>(q);
-    return FOS_OK;
-}
-}  // namespace
 
 // A: m x n ROW-major, b[m]; lambda: 0: IndAffine(A, b), > 0: LeastSquares(A, b, lambda) (refine is then 0); factor: FOS_DIRECT_FACTOR_*; refine: 0..2 refinement
 // steps per projection.  Synchronises `stream`.
-int dense_affine_setup(int64_t m, int64_t n, const double* A, const double* b, double lambda, int factor, int refine, int cus, hipStream_t stream, DenseAffine** out) {
+int dense_affine_setup(int64_t m, int64_t n, const double* A, const double* b, double lambda, int factor, int refine, int cus, hipStream_t stream, ProxObject** out) {
     FOS_TRY(da_check_shape(m, n, A && b, lambda));
     if (lambda > 0.0) refine = 0;
     if (refine < 0 || refine > 2) { set_error("IndAffine (factored): refine = %d (0, 1 or 2 refinement steps per projection)", refine); return FOS_EINVAL; }
@@ -264,45 +265,28 @@ int dense_affine_setup(int64_t m, int64_t n, const double* A, const double* b, d
     std::vector<double> scale, bs;
     FOS_TRY(da_scaling(m, n, A, b, lambda, scale, bs));
     DenseAffine* a = new DenseAffine();
+    a->what = da_name(lambda);
     a->m = m; a->n = n; a->refine = refine; a->p = da_plan(m, n, cus);
     const DaPlan& p = a->p;
     const size_t L2 = (size_t)p.Lm * (size_t)p.Lm;
-    auto fail = [&](int code) { (void)hipStreamSynchronize(stream); dense_affine_destroy(a); return code; };
+    auto fail = [&](int code) { (void)hipStreamSynchronize(stream); delete a; return code; };
     int rc = FOS_OK;
-    if ((rc = da_alloc(a, &a->A, (size_t)m * (size_t)p.ld)) != FOS_OK || (rc = da_alloc(a, &a->G, L2)) != FOS_OK || (rc = da_alloc(a, &a->X, L2)) != FOS_OK ||
-        (rc = da_alloc(a, &a->part1, (size_t)p.nspan * (size_t)p.Lm)) != FOS_OK || (p.nrb > 1 && (rc = da_alloc(a, &a->part2, (size_t)p.nrb * (size_t)p.ld)) != FOS_OK))
+    if ((rc = a->alloc(&a->A, (size_t)m * (size_t)p.ld)) != FOS_OK || (rc = a->alloc(&a->G, L2)) != FOS_OK || (rc = a->alloc(&a->X, L2)) != FOS_OK ||
+        (rc = a->alloc(&a->part1, (size_t)p.nspan * (size_t)p.Lm)) != FOS_OK || (p.nrb > 1 && (rc = a->alloc(&a->part2, (size_t)p.nrb * (size_t)p.ld)) != FOS_OK))
         return fail(rc);
-    for (double** v : {&a->b, &a->r, &a->d, &a->e, &a->t}) if ((rc = da_alloc(a, v, (size_t)p.Lm)) != FOS_OK) return fail(rc);
-#define DA_HIP(expr) do { const int _r = da_hip(#expr, (expr)); if (_r != FOS_OK) return fail(_r); } while (0)
-    for (double* v : {a->b, a->r, a->d, a->e, a->t}) DA_HIP(hipMemsetAsync(v, 0, sizeof(double) * (size_t)p.Lm, stream));
-    DA_HIP(hipMemsetAsync(a->A, 0, sizeof(double) * (size_t)m * (size_t)p.ld, stream));
-    DA_HIP(hipMemcpy2DAsync(a->A, sizeof(double) * (size_t)p.ld, A, sizeof(double) * (size_t)n, sizeof(double) * (size_t)n, (size_t)m, hipMemcpyHostToDevice, stream));
-    DA_HIP(hipMemcpyAsync(a->b, bs.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
-    DA_HIP(hipMemcpyAsync(a->t, scale.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
+    for (double** v : {&a->b, &a->r, &a->d, &a->e, &a->t}) if ((rc = a->zeros(v, (size_t)p.Lm, stream)) != FOS_OK) return fail(rc);
+    DEV_HIP(a, hipMemsetAsync(a->A, 0, sizeof(double) * (size_t)m * (size_t)p.ld, stream));
+    DEV_HIP(a, hipMemcpy2DAsync(a->A, sizeof(double) * (size_t)p.ld, A, sizeof(double) * (size_t)n, sizeof(double) * (size_t)n, (size_t)m, hipMemcpyHostToDevice, stream));
+    DEV_HIP(a, hipMemcpyAsync(a->b, bs.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
+    DEV_HIP(a, hipMemcpyAsync(a->t, scale.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(da_scale_rows_kernel, dim3(1024), dim3(DA_T), 0, stream, m, p.ld, a->A, (const double*)a->t);
-    {   // G = A A' (+ identity on the padding) and its inverse; the square work buffers go at the end of this block
-        DenseWork w;
-        w.c.stream = stream; w.c.l = m; w.L = p.Lm; w.G = a->G;
-        launch_dense_gram_rows(w.c, m, p.ld, a->A, p.Lm, a->G);
-        if (lambda > 0.0)                                      // (the row scales are still in a->t)
-            hipLaunchKernelGGL(da_shift_diag_kernel, dim3((unsigned)std::min<int64_t>(256, (m + DA_T - 1) / DA_T)), dim3(DA_T), 0, stream, m, p.Lm, a->G, (const double*)a->t, 1.0 / lambda);
-        Scratch s;
-        w.fill(s);
-        if (s.err != hipSuccess) { (void)hipGetLastError(); set_error("IndAffine (factored): hipMalloc of the set-up buffers (3 x %zu bytes) failed: %s", L2 * 8, hipGetErrorString(s.err)); return fail(FOS_ENOMEM); }
-        double* X = nullptr;
-        DenseOpts o{da_name(lambda), lambda > 0.0 ? "A A' + I/lambda" : "A A'", factor, false};
-        o.bar = DA_BAR; o.newton_extra = 40;               // cond(A A') up to ~1e8: ceil(log2 cond) + 7 steps at most, each of the extra ones checked
-        rc = dense_spd_inverse(w, o, &X, &a->inv);
-        if (rc == FOS_EINVAL && !(lambda > 0.0)) {
-            const std::string why = fos_last_error();
-            set_error("IndAffine (factored): the inverse of A A' (rows scaled to unit norm) was not accepted: A needs full row rank  [%s]", why.c_str());
-        }
-        if (rc != FOS_OK) return fail(rc);
-        DA_HIP(hipMemcpyAsync(a->X, X, sizeof(double) * L2, hipMemcpyDeviceToDevice, stream));
-        DA_HIP(hipMemsetAsync(a->t, 0, sizeof(double) * (size_t)p.Lm, stream));
-        DA_HIP(hipStreamSynchronize(stream));
-    }
-#undef DA_HIP
+    LaunchCtx c{};
+    c.stream = stream; c.l = m;
+    launch_dense_gram_rows(c, m, p.ld, a->A, p.Lm, a->G);      // G = A A' (+ identity on the padding)
+    if (lambda > 0.0)                                          // (the row scales are still in a->t)
+        hipLaunchKernelGGL(da_shift_diag_kernel, dim3((unsigned)std::min<int64_t>(256, (m + DA_T - 1) / DA_T)), dim3(DA_T), 0, stream, m, p.Lm, a->G, (const double*)a->t, 1.0 / lambda);
+    DEV_HIP(a, hipMemsetAsync(a->t, 0, sizeof(double) * (size_t)p.Lm, stream));
+    if ((rc = factored_inverse(*a, lambda, factor, DA_BAR, stream, m, p.Lm, a->G, a->X, &a->inv)) != FOS_OK) return fail(rc);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("IndAffine (factored) set-up: a kernel launch failed: %s", hipGetErrorString(e)); return fail(FOS_EHIP); }
     *out = a;
@@ -312,6 +296,11 @@ int dense_affine_setup(int64_t m, int64_t n, const double* A, const double* b, d
 // the m-space product for the factored forms (this file and affine_sparse_factored.hip)
 void launch_da_symv(hipStream_t s, int64_t l, int64_t ld, const double* M, const double* v, const double* add, double sign, double* out) {
     hipLaunchKernelGGL(da_symv_kernel, dim3((unsigned)((l + DA_T / 64 - 1) / (DA_T / 64))), dim3(DA_T), 0, s, l, ld, M, v, add, sign, out);
+}
+void mspace_correct(hipStream_t s, int64_t m, int64_t L, const double* X, const double* G, const double* r, double* d, double* e) {
+    launch_da_symv(s, m, L, X, r, nullptr, 1.0, d);                  // d = X r
+    launch_da_symv(s, m, L, G, d, r, -1.0, e);                       // e = r - G d
+    launch_da_symv(s, m, L, X, e, d, 1.0, d);                        // d += X e
 }
 
 namespace {
@@ -323,9 +312,6 @@ void da_residual(const DenseAffine* a, hipStream_t s, const double* v) {
                        (const double*)a->A, v, a->part1);
     hipLaunchKernelGGL(da_rows_fold_kernel, dim3((unsigned)std::min<int64_t>(256, (a->m + DA_T - 1) / DA_T)), dim3(DA_T), 0, s, a->m, p.Lm, p.nspan, (const double*)a->part1,
                        (const double*)a->b, a->r);
-}
-void da_symv(const DenseAffine* a, hipStream_t s, const double* M, const double* v, const double* add, double sign, double* out) {
-    launch_da_symv(s, a->m, a->p.Lm, M, v, add, sign, out);
 }
 // y = x - A'd
 void da_correct(const DenseAffine* a, hipStream_t s, double* y, const double* x) {
@@ -339,29 +325,30 @@ int da_launches(const DenseAffine* a) { return (2 + 3 + 1 + (a->p.nrb > 1 ? 1 : 
 }  // namespace
 
 // y = the projection of x onto {A x = b} (device vectors of length n, y must not alias x), on `stream`: da_launches(a) launches, nothing else
-int dense_affine_project(DenseAffine* a, hipStream_t stream, double* y, const double* x) {
+int DenseAffine::prox(hipStream_t stream, double* y, const double* x) {
+    const DenseAffine* a = this;
     da_residual(a, stream, x);                                       // r = A x - b
-    da_symv(a, stream, a->X, a->r, nullptr, 1.0, a->d);              // d = X r
-    da_symv(a, stream, a->G, a->d, a->r, -1.0, a->e);                // e = r - G d
-    da_symv(a, stream, a->X, a->e, a->d, 1.0, a->d);                 // d += X e
+    mspace_correct(stream, m, p.Lm, X, G, r, d, e);                  // d = X r, corrected once
     da_correct(a, stream, y, x);                                     // y = x - A'd
-    for (int k = 0; k < a->refine; ++k) {
+    for (int k = 0; k < refine; ++k) {
         da_residual(a, stream, y);                                   // r = A y - b
-        da_symv(a, stream, a->X, a->r, nullptr, 1.0, a->d);          // d = X r
+        launch_da_symv(stream, m, p.Lm, X, r, nullptr, 1.0, d);      // d = X r
         da_correct(a, stream, y, y);                                 // y -= A'd
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("IndAffine (factored): a kernel launch failed: %s", hipGetErrorString(e)); return FOS_EHIP; }
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) { set_error("IndAffine (factored): a kernel launch failed: %s", hipGetErrorString(err)); return FOS_EHIP; }
     return FOS_OK;
 }
 
 // out8 = m, n, refine, factor that produced the accepted inverse, fell_back, probe residual, kernel launches per projection, bytes kept
-void dense_affine_stats(const DenseAffine* a, double* out8) {
+void dense_affine_stats(const ProxObject* obj, double* out8) {
+    const DenseAffine* a = static_cast<const DenseAffine*>(obj);
     out8[0] = (double)a->m; out8[1] = (double)a->n; out8[2] = (double)a->refine; out8[3] = (double)a->inv.used; out8[4] = a->inv.fell_back ? 1.0 : 0.0;
     out8[5] = a->inv.probe; out8[6] = (double)da_launches(a); out8[7] = (double)a->bytes;
 }
 // out6 = leading dimension of A, padded order of A A', pass 1: columns per span, spans; pass 2: rows per row block, row blocks
-void dense_affine_plan(const DenseAffine* a, int64_t* out6) {
+void dense_affine_plan(const ProxObject* obj, int64_t* out6) {
+    const DenseAffine* a = static_cast<const DenseAffine*>(obj);
     out6[0] = a->p.ld; out6[1] = a->p.Lm; out6[2] = a->p.span; out6[3] = a->p.nspan; out6[4] = a->p.rows_blk; out6[5] = a->p.nrb;
 }
 
@@ -387,6 +374,11 @@ void da_host_symv(int64_t l, int64_t ld, const double* M, const double* v, const
 }  // namespace
 
 void host_da_symv(int64_t l, int64_t ld, const double* M, const double* v, const double* add, double sign, double* out) { da_host_symv(l, ld, M, v, add, sign, out); }
+void host_mspace_correct(int64_t m, const double* X, const double* G, const double* r, double* d, double* e) {
+    da_host_symv(m, m, X, r, nullptr, 1.0, d);
+    da_host_symv(m, m, G, d, r, -1.0, e);
+    da_host_symv(m, m, X, e, d, 1.0, d);
+}
 double host_da_wave(const double* lane64) {
     double lane[64];
     for (int i = 0; i < 64; ++i) lane[i] = lane64[i];
@@ -465,9 +457,7 @@ int host_affine_factored(int64_t m, int64_t n, const double* A, const double* b,
         }
     };
     residual(x);
-    da_host_symv(m, m, X.data(), r.data(), nullptr, 1.0, d.data());
-    da_host_symv(m, m, G.data(), d.data(), r.data(), -1.0, e.data());
-    da_host_symv(m, m, X.data(), e.data(), d.data(), 1.0, d.data());
+    host_mspace_correct(m, X.data(), G.data(), r.data(), d.data(), e.data());
     correct(y, x);
     for (int k = 0; k < refine; ++k) {
         residual(y);

@@ -146,14 +146,17 @@ int lanes_per_row(int64_t nnz, int64_t rows) {
 
 }  // namespace
 
-struct SparseAffine {
+struct SparseAffine : ProxObject, DevOwned {
+    SparseAffine() : ProxObject(FEAS_AFFINE_SPARSE) { what = "IndAffine (sparse)"; }
+    ~SparseAffine() override { if (st_host) (void)hipHostFree(st_host); }
+    int prox(hipStream_t stream, double* y, const double* x) override;
+    void reset(hipStream_t stream) override { (void)hipMemsetAsync(lam, 0, sizeof(double) * (size_t)m, stream); }      // a new solve starts from lambda = 0
     int64_t m = 0, n = 0, nnz = 0;
     int32_t *rp = nullptr, *ci = nullptr, *trp = nullptr, *tci = nullptr;
     double *va = nullptr, *tva = nullptr;
     double *b = nullptr, *lam = nullptr, *r = nullptr, *p = nullptr, *q = nullptr, *part = nullptr;
     SaState *st = nullptr, *st_host = nullptr;
     int lpr_a = 1, lpr_t = 1, grid_a = 1, grid_t = 1, grid_m = 1;
-    std::vector<void*> owned;
     // statistics (fos_feas_affine_stats)
     int64_t calls = 0, iters_total = 0;
     int last_iters = 0, last_rounds = 0;
@@ -170,32 +173,7 @@ void sa_launch_rows(hipStream_t s, int lpr, int grid, int64_t nrows, const int32
 #undef SA_CASE
 }
 
-template <class T>
-int sa_upload(SparseAffine* a, T** out, const std::vector<T>& v) {
-    void* q = nullptr;
-    FOS_HIP(hipMalloc(&q, sizeof(T) * std::max<size_t>(v.size(), 1)));
-    a->owned.push_back(q);
-    if (!v.empty()) FOS_HIP(hipMemcpy(q, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
-    *out = static_cast<T*>(q);
-    return FOS_OK;
-}
-int sa_zeros(SparseAffine* a, double** out, size_t count) {
-    void* q = nullptr;
-    FOS_HIP(hipMalloc(&q, sizeof(double) * std::max<size_t>(count, 1)));
-    a->owned.push_back(q);
-    FOS_HIP(hipMemset(q, 0, sizeof(double) * std::max<size_t>(count, 1)));
-    *out = static_cast<double*>(q);
-    return FOS_OK;
-}
-
 }  // namespace
-
-void sparse_affine_destroy(SparseAffine* a) {
-    if (!a) return;
-    for (void* q : a->owned) (void)hipFree(q);
-    if (a->st_host) (void)hipHostFree(a->st_host);
-    delete a;
-}
 
 // The host half of every sparse IndAffine set-up (this file and affine_sparse_factored.hip).  A: m x n CSC, 1-based (Julia SparseMatrixCSC{Float64,Int64}); b[m]:
 // validated, the rows of [A | b] scaled to unit norm, A and A' as two CSR matrices.  `what` names the caller in the messages.
@@ -249,25 +227,21 @@ int sparse_affine_rows(const char* what, int64_t m, int64_t n, const int64_t* co
 }
 
 // A: m x n CSC, 1-based; b[m].  Rows of [A | b] scaled to unit norm; A and A' to CSR (sparse_affine_rows); upload.
-int sparse_affine_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int cus, SparseAffine** out) {
+int sparse_affine_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int cus, ProxObject** out) {
     SparseRows R;
     FOS_TRY(sparse_affine_rows("IndAffine (sparse)", m, n, colptr, rowval, nzval, b, &R));
     const int64_t nnz = R.nnz;
-    const std::vector<int32_t>&rp = R.rp, &ci = R.ci, &trp = R.trp, &tci = R.tci;
-    const std::vector<double>&va = R.va, &tva = R.tva, &bs = R.bs;
     SparseAffine* a = new SparseAffine();
     a->m = m; a->n = n; a->nnz = nnz;
     int rc = FOS_OK;
-    auto fail = [&](int code) { sparse_affine_destroy(a); return code; };
-    if ((rc = sa_upload(a, &a->rp, rp)) != FOS_OK || (rc = sa_upload(a, &a->ci, ci)) != FOS_OK || (rc = sa_upload(a, &a->va, va)) != FOS_OK ||
-        (rc = sa_upload(a, &a->trp, trp)) != FOS_OK || (rc = sa_upload(a, &a->tci, tci)) != FOS_OK || (rc = sa_upload(a, &a->tva, tva)) != FOS_OK ||
-        (rc = sa_upload(a, &a->b, bs)) != FOS_OK || (rc = sa_zeros(a, &a->lam, (size_t)m)) != FOS_OK || (rc = sa_zeros(a, &a->r, (size_t)m)) != FOS_OK ||
-        (rc = sa_zeros(a, &a->p, (size_t)m)) != FOS_OK || (rc = sa_zeros(a, &a->q, (size_t)n)) != FOS_OK || (rc = sa_zeros(a, &a->part, 3 * SA_PARTS_MAX)) != FOS_OK)
+    auto fail = [&](int code) { delete a; return code; };
+    const hipStream_t sync = nullptr;                        // (this set-up has no stream: blocking copies)
+    if ((rc = a->upload(&a->rp, R.rp, sync)) != FOS_OK || (rc = a->upload(&a->ci, R.ci, sync)) != FOS_OK || (rc = a->upload(&a->va, R.va, sync)) != FOS_OK ||
+        (rc = a->upload(&a->trp, R.trp, sync)) != FOS_OK || (rc = a->upload(&a->tci, R.tci, sync)) != FOS_OK || (rc = a->upload(&a->tva, R.tva, sync)) != FOS_OK ||
+        (rc = a->upload(&a->b, R.bs, sync)) != FOS_OK || (rc = a->zeros(&a->lam, (size_t)m, sync)) != FOS_OK || (rc = a->zeros(&a->r, (size_t)m, sync)) != FOS_OK ||
+        (rc = a->zeros(&a->p, (size_t)m, sync)) != FOS_OK || (rc = a->zeros(&a->q, (size_t)n, sync)) != FOS_OK || (rc = a->zeros(&a->part, 3 * SA_PARTS_MAX, sync)) != FOS_OK ||
+        (rc = a->zeros(&a->st, 1, sync)) != FOS_OK)
         return fail(rc);
-    void* q = nullptr;
-    if (hipMalloc(&q, sizeof(SaState)) != hipSuccess) { set_error("IndAffine (sparse): hipMalloc failed"); return fail(FOS_ENOMEM); }
-    a->owned.push_back(q); a->st = static_cast<SaState*>(q);
-    if (hipMemset(q, 0, sizeof(SaState)) != hipSuccess) { set_error("IndAffine (sparse): hipMemset failed"); return fail(FOS_EHIP); }
     if (hipHostMalloc((void**)&a->st_host, sizeof(SaState), hipHostMallocDefault) != hipSuccess) { set_error("IndAffine (sparse): hipHostMalloc failed"); return fail(FOS_ENOMEM); }
     a->lpr_a = lanes_per_row(nnz, m); a->lpr_t = lanes_per_row(nnz, n);
     const int wg_max = std::min(SA_PARTS_MAX, 4 * std::max(1, cus));
@@ -279,7 +253,8 @@ int sparse_affine_setup(int64_t m, int64_t n, const int64_t* colptr, const int64
 }
 
 // y = the projection of x onto {A x = b} (device vectors of length n, y must not alias x), on `stream`
-int sparse_affine_project(SparseAffine* a, hipStream_t stream, double* y, const double* x) {
+int SparseAffine::prox(hipStream_t stream, double* y, const double* x) {
+    SparseAffine* a = this;
     constexpr double TOL_FACTOR = 16.0 * 2.220446049250313e-16;
     constexpr int BATCH = 24, ROUNDS_MAX = 6;
     const int maxit = (int)std::min<int64_t>(20000, 2 * a->m + 100);
@@ -320,11 +295,8 @@ int sparse_affine_project(SparseAffine* a, hipStream_t stream, double* y, const 
     return FOS_OK;
 }
 
-void sparse_affine_reset(SparseAffine* a, hipStream_t stream) {           // a new solve starts from lambda = 0
-    if (a) (void)hipMemsetAsync(a->lam, 0, sizeof(double) * (size_t)a->m, stream);
-}
-
-void sparse_affine_stats(const SparseAffine* a, double* out8) {
+void sparse_affine_stats(const ProxObject* obj, double* out8) {
+    const SparseAffine* a = static_cast<const SparseAffine*>(obj);
     out8[0] = (double)a->calls; out8[1] = (double)a->iters_total; out8[2] = (double)a->last_iters; out8[3] = (double)a->last_rounds;
     out8[4] = a->last_resid; out8[5] = a->last_level; out8[6] = (double)a->nnz; out8[7] = (double)(a->lpr_a * 1000 + a->lpr_t);
 }

@@ -177,7 +177,9 @@ int sf_rows(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, 
 
 }  // namespace
 
-struct SparseFactored {
+struct SparseFactored : ProxObject, DevOwned {
+    SparseFactored() : ProxObject(FEAS_SPARSE_FACTORED) {}
+    int prox(hipStream_t stream, double* y, const double* x) override;
     int64_t m = 0, n = 0, nnz = 0, L = 0;
     int refine = 0, seg = 0;
     int32_t *rp = nullptr, *ci = nullptr, *trp = nullptr, *tci = nullptr;
@@ -189,46 +191,12 @@ struct SparseFactored {
     double *part1 = nullptr, *part2 = nullptr;
     int nitems1 = 0, nitems2 = 0, nfold1 = 0, nfold2 = 0;
     int64_t nparts1 = 0, nparts2 = 0;
-    std::vector<void*> owned;
     DenseInv inv;
-    size_t bytes = 0;
 };
-
-void sparse_factored_destroy(SparseFactored* a) {
-    if (!a) return;
-    for (void* q : a->owned) (void)hipFree(q);
-    delete a;
-}
-
-namespace {
-template <class T>
-int sf_alloc(SparseFactored* a, T** out, size_t count) {
-    void* q = nullptr;
-    const size_t bytes = sizeof(T) * std::max<size_t>(count, 1);
-    const hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); set_error("IndAffine (sparse, factored): hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e)); return FOS_ENOMEM; }
-    a->owned.push_back(q); a->bytes += bytes;
-    *out = static_cast<T*>(q);
-    return FOS_OK;
-}
-template <class T>
-int sf_upload(SparseFactored* a, T** out, const std::vector<T>& v, hipStream_t s) {
-    FOS_TRY(sf_alloc(a, out, v.size()));
-    if (!v.empty()) {
-        const hipError_t e = hipMemcpyAsync(*out, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) { set_error("IndAffine (sparse, factored) set-up: hipMemcpyAsync -> %s", hipGetErrorString(e)); return FOS_EHIP; }
-    }
-    return FOS_OK;
-}
-int sf_hip(const char* call, hipError_t e) {
-    if (e != hipSuccess) { set_error("IndAffine (sparse, factored) set-up: %s -> %s", call, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? FOS_ENOMEM : FOS_EHIP; }
-    return FOS_OK;
-}
-}  // namespace
 
 // A: m x n CSC, 1-based; b[m]; factor: FOS_DIRECT_FACTOR_*; refine: 0..2 refinement steps per projection.  Synchronises `stream`.
 int sparse_factored_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int factor,
-                          int refine, hipStream_t stream, SparseFactored** out) {
+                          int refine, hipStream_t stream, ProxObject** out) {
     if (factor != FOS_DIRECT_FACTOR_NEWTON && factor != FOS_DIRECT_FACTOR_CHOLESKY) {
         set_error("%s: factor must be FOS_DIRECT_FACTOR_NEWTON or FOS_DIRECT_FACTOR_CHOLESKY", sf_name(lambda));
         return FOS_EINVAL;
@@ -242,50 +210,29 @@ int sparse_factored_setup(int64_t m, int64_t n, const int64_t* colptr, const int
     sf_plan_pass(m, R.rp.data(), seg, &P1);
     sf_plan_pass(n, R.trp.data(), seg, &P2);
     SparseFactored* a = new SparseFactored();
+    a->what = sf_name(lambda);
     a->m = m; a->n = n; a->nnz = R.nnz; a->L = (m + 63) / 64 * 64; a->refine = refine; a->seg = seg;
     a->nitems1 = (int)P1.items.size(); a->nitems2 = (int)P2.items.size(); a->nfold1 = (int)P1.frow.size(); a->nfold2 = (int)P2.frow.size();
     a->nparts1 = P1.nparts; a->nparts2 = P2.nparts;
     const size_t L = (size_t)a->L, L2 = L * L;
-    auto fail = [&](int code) { (void)hipStreamSynchronize(stream); sparse_factored_destroy(a); return code; };
+    auto fail = [&](int code) { (void)hipStreamSynchronize(stream); delete a; return code; };
     int rc = FOS_OK;
-    if ((rc = sf_upload(a, &a->rp, R.rp, stream)) != FOS_OK || (rc = sf_upload(a, &a->ci, R.ci, stream)) != FOS_OK || (rc = sf_upload(a, &a->va, R.va, stream)) != FOS_OK ||
-        (rc = sf_upload(a, &a->trp, R.trp, stream)) != FOS_OK || (rc = sf_upload(a, &a->tci, R.tci, stream)) != FOS_OK || (rc = sf_upload(a, &a->tva, R.tva, stream)) != FOS_OK ||
-        (rc = sf_upload(a, &a->items1, P1.items, stream)) != FOS_OK || (rc = sf_upload(a, &a->items2, P2.items, stream)) != FOS_OK ||
-        (rc = sf_upload(a, &a->frow1, P1.frow, stream)) != FOS_OK || (rc = sf_upload(a, &a->fptr1, P1.fptr, stream)) != FOS_OK ||
-        (rc = sf_upload(a, &a->frow2, P2.frow, stream)) != FOS_OK || (rc = sf_upload(a, &a->fptr2, P2.fptr, stream)) != FOS_OK ||
-        (rc = sf_alloc(a, &a->part1, (size_t)P1.nparts)) != FOS_OK || (rc = sf_alloc(a, &a->part2, (size_t)P2.nparts)) != FOS_OK ||
-        (rc = sf_alloc(a, &a->G, L2)) != FOS_OK || (rc = sf_alloc(a, &a->X, L2)) != FOS_OK)
+    if ((rc = a->upload(&a->rp, R.rp, stream)) != FOS_OK || (rc = a->upload(&a->ci, R.ci, stream)) != FOS_OK || (rc = a->upload(&a->va, R.va, stream)) != FOS_OK ||
+        (rc = a->upload(&a->trp, R.trp, stream)) != FOS_OK || (rc = a->upload(&a->tci, R.tci, stream)) != FOS_OK || (rc = a->upload(&a->tva, R.tva, stream)) != FOS_OK ||
+        (rc = a->upload(&a->items1, P1.items, stream)) != FOS_OK || (rc = a->upload(&a->items2, P2.items, stream)) != FOS_OK ||
+        (rc = a->upload(&a->frow1, P1.frow, stream)) != FOS_OK || (rc = a->upload(&a->fptr1, P1.fptr, stream)) != FOS_OK ||
+        (rc = a->upload(&a->frow2, P2.frow, stream)) != FOS_OK || (rc = a->upload(&a->fptr2, P2.fptr, stream)) != FOS_OK ||
+        (rc = a->alloc(&a->part1, (size_t)P1.nparts)) != FOS_OK || (rc = a->alloc(&a->part2, (size_t)P2.nparts)) != FOS_OK ||
+        (rc = a->zeros(&a->G, L2, stream)) != FOS_OK || (rc = a->alloc(&a->X, L2)) != FOS_OK)
         return fail(rc);
-    for (double** v : {&a->b, &a->r, &a->d, &a->e}) if ((rc = sf_alloc(a, v, L)) != FOS_OK) return fail(rc);
-#define SF_HIP(expr) do { const int _r = sf_hip(#expr, (expr)); if (_r != FOS_OK) return fail(_r); } while (0)
-    for (double* v : {a->b, a->r, a->d, a->e}) SF_HIP(hipMemsetAsync(v, 0, sizeof(double) * L, stream));
-    SF_HIP(hipMemcpyAsync(a->b, R.bs.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
-    SF_HIP(hipMemsetAsync(a->G, 0, sizeof(double) * L2, stream));
-    hipLaunchKernelGGL(sf_gram_kernel, dim3((unsigned)std::min<int64_t>(a->L, 65536)), dim3(SF_T), 0, stream, m, a->L, (const int32_t*)a->rp, (const int32_t*)a->ci,
-                       (const double*)a->va, (const int32_t*)a->trp, (const int32_t*)a->tci, (const double*)a->tva, a->G);
+    for (double** v : {&a->b, &a->r, &a->d, &a->e}) if ((rc = a->zeros(v, L, stream)) != FOS_OK) return fail(rc);
+    DEV_HIP(a, hipMemcpyAsync(a->b, R.bs.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
+    launch_sf_gram(stream, m, a->L, a->rp, a->ci, a->va, a->trp, a->tci, a->tva, a->G);
     if (lambda > 0.0) {                                    // (a->e holds the row scales until the first projection overwrites it)
-        SF_HIP(hipMemcpyAsync(a->e, R.scale.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
+        DEV_HIP(a, hipMemcpyAsync(a->e, R.scale.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
         hipLaunchKernelGGL(sf_shift_diag_kernel, dim3((unsigned)std::min<int64_t>(256, (m + SF_T - 1) / SF_T)), dim3(SF_T), 0, stream, m, a->L, a->G, (const double*)a->e, 1.0 / lambda);
     }
-    {   // X = G^-1; the square work buffers go at the end of this block
-        DenseWork w;
-        w.c.stream = stream; w.c.l = m; w.L = a->L; w.G = a->G;
-        Scratch s;
-        w.fill(s);
-        if (s.err != hipSuccess) { (void)hipGetLastError(); set_error("IndAffine (sparse, factored): hipMalloc of the set-up buffers (3 x %zu bytes) failed: %s", L2 * 8, hipGetErrorString(s.err)); return fail(FOS_ENOMEM); }
-        double* X = nullptr;
-        DenseOpts o{sf_name(lambda), lambda > 0.0 ? "A A' + I/lambda" : "A A'", factor, false};
-        o.bar = SF_BAR; o.newton_extra = 40;
-        rc = dense_spd_inverse(w, o, &X, &a->inv);
-        if (rc == FOS_EINVAL && !(lambda > 0.0)) {
-            const std::string why = fos_last_error();
-            set_error("IndAffine (sparse, factored): the inverse of A A' (rows scaled to unit norm) was not accepted: A needs full row rank  [%s]", why.c_str());
-        }
-        if (rc != FOS_OK) return fail(rc);
-        SF_HIP(hipMemcpyAsync(a->X, X, sizeof(double) * L2, hipMemcpyDeviceToDevice, stream));
-        SF_HIP(hipStreamSynchronize(stream));
-    }
-#undef SF_HIP
+    if ((rc = factored_inverse(*a, lambda, factor, SF_BAR, stream, m, a->L, a->G, a->X, &a->inv)) != FOS_OK) return fail(rc);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("IndAffine (sparse, factored) set-up: a kernel launch failed: %s", hipGetErrorString(e)); return fail(FOS_EHIP); }
     *out = a;
@@ -324,29 +271,30 @@ int sf_launches(const SparseFactored* a) {
 }  // namespace
 
 // y = the projection of x onto {A x = b} (device vectors of length n, y must not alias x), on `stream`: sf_launches(a) launches, nothing else
-int sparse_factored_project(SparseFactored* a, hipStream_t stream, double* y, const double* x) {
+int SparseFactored::prox(hipStream_t stream, double* y, const double* x) {
+    const SparseFactored* a = this;
     sf_residual(a, stream, x);                                                   // r = A x - b
-    launch_da_symv(stream, a->m, a->L, a->X, a->r, nullptr, 1.0, a->d);          // d = X r
-    launch_da_symv(stream, a->m, a->L, a->G, a->d, a->r, -1.0, a->e);            // e = r - G d
-    launch_da_symv(stream, a->m, a->L, a->X, a->e, a->d, 1.0, a->d);             // d += X e
+    mspace_correct(stream, m, L, X, G, r, d, e);                                 // d = X r, corrected once
     sf_correct(a, stream, y, x);                                                 // y = x - A'd
-    for (int k = 0; k < a->refine; ++k) {
+    for (int k = 0; k < refine; ++k) {
         sf_residual(a, stream, y);                                               // r = A y - b
-        launch_da_symv(stream, a->m, a->L, a->X, a->r, nullptr, 1.0, a->d);      // d = X r
+        launch_da_symv(stream, m, L, X, r, nullptr, 1.0, d);                     // d = X r
         sf_correct(a, stream, y, y);                                             // y -= A'd
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("IndAffine (sparse, factored): a kernel launch failed: %s", hipGetErrorString(e)); return FOS_EHIP; }
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) { set_error("IndAffine (sparse, factored): a kernel launch failed: %s", hipGetErrorString(err)); return FOS_EHIP; }
     return FOS_OK;
 }
 
 // out8 = m, n, refine, factor that produced the accepted inverse, fell_back, probe residual, kernel launches per projection, bytes kept
-void sparse_factored_stats(const SparseFactored* a, double* out8) {
+void sparse_factored_stats(const ProxObject* obj, double* out8) {
+    const SparseFactored* a = static_cast<const SparseFactored*>(obj);
     out8[0] = (double)a->m; out8[1] = (double)a->n; out8[2] = (double)a->refine; out8[3] = (double)a->inv.used; out8[4] = a->inv.fell_back ? 1.0 : 0.0;
     out8[5] = a->inv.probe; out8[6] = (double)sf_launches(a); out8[7] = (double)a->bytes;
 }
 // out8 = stored entries, padded order of A A', SEG in force, pass 1: work items, rows cut (folded); pass 2: work items, rows cut; segments of the cut rows of both passes
-void sparse_factored_plan(const SparseFactored* a, int64_t* out8) {
+void sparse_factored_plan(const ProxObject* obj, int64_t* out8) {
+    const SparseFactored* a = static_cast<const SparseFactored*>(obj);
     out8[0] = a->nnz; out8[1] = a->L; out8[2] = a->seg; out8[3] = a->nitems1; out8[4] = a->nfold1; out8[5] = a->nitems2; out8[6] = a->nfold2;
     out8[7] = a->nparts1 + a->nparts2;
 }
@@ -405,9 +353,7 @@ int host_affine_sparse_factored(int64_t m, int64_t n, const int64_t* colptr, con
     FOS_TRY(host_da_inverse(sf_name(lambda), m, G.data(), X.data()));
     std::vector<double> r((size_t)m), d((size_t)m), e((size_t)m);
     sf_host_pass(1, P1, R.rp, R.ci, R.va, x, R.bs.data(), r.data());
-    host_da_symv(m, m, X.data(), r.data(), nullptr, 1.0, d.data());
-    host_da_symv(m, m, G.data(), d.data(), r.data(), -1.0, e.data());
-    host_da_symv(m, m, X.data(), e.data(), d.data(), 1.0, d.data());
+    host_mspace_correct(m, X.data(), G.data(), r.data(), d.data(), e.data());
     sf_host_pass(2, P2, R.trp, R.tci, R.tva, d.data(), x, y);
     for (int k = 0; k < refine; ++k) {
         sf_host_pass(1, P1, R.rp, R.ci, R.va, y, R.bs.data(), r.data());

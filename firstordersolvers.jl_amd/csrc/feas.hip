@@ -2,18 +2,18 @@
 //   reference: src/problemforms/Feasibility/Feasibility.jl (model, zeros(n) start, populate_solution),
 //              src/problemforms/Feasibility/FeasibilityStatus.jl:32-72 (err = norm(prev - z) every checki-th iteration),
 //              src/solvers/{gap,gapa,fista,dykstra}.jl (the steps: the same files the HSDE path follows).
-// The reference takes ANY two ProximalOperators objects (host callbacks); here the two sets are device objects, the two its own
-// test uses (test/testfeasibility.jl:9-10): IndAffine(A, b) -- dense A with full row rank, an exact projection through a one-time
-// inverse of A A' (Newton-Schulz on the fp64 MFMA GEMM of vecops.hip, as fos_enable_direct does for the HSDE) -- and
-// IndBox(lo, hi).  Vectors are plain n-vectors in HBM; every iteration is a handful of streaming kernels plus, for IndAffine,
-// one dense symmetric matrix-vector product (n^2 x 8 bytes: the kernel that bounds the path, HBM).  No CPU fallback.
+// The reference takes ANY two ProximalOperators objects (host callbacks); here a set is a device object behind one interface (ProxObject, fos_internal.hpp): the
+// handle owns one per slot and calls its prox.  The objects live in feas_objects.hip (dense IndAffine projector, IndBox, ConeProduct, host callback) and in the
+// back-ends' own files (affine_sparse.hip, affine_dense.hip, affine_sparse_factored.hip, nspace.hip, sets.hip).  This file keeps the algorithms, the status check,
+// the wrappers and the ABI.  Every fos_feas_set_* entry does three things: validate, build, feas_install -- the object is built first, so that a refused call
+// leaves the set as it was, and the install frees what the slot held.  Vectors are plain n-vectors in HBM, zero padded to L.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <type_traits>
+#include <memory>
 #include <vector>
 
 #include "dev_common.hpp"
@@ -21,27 +21,10 @@
 
 namespace fos {
 
-constexpr int FEAS_THREADS = 256;
 constexpr int FEAS_PARTS = 256;               // partial sums per reduction (fixed: results do not depend on the device)
-
-#define FEAS_STRIDE(i, n) for (int64_t i = blockIdx.x * (int64_t)FEAS_THREADS + threadIdx.x; i < (n); i += (int64_t)gridDim.x * FEAS_THREADS)
 
 __global__ __launch_bounds__(FEAS_THREADS) void feas_fill_kernel(int64_t n, double* __restrict__ y, double v) { FEAS_STRIDE(i, n) y[i] = v; }
 __global__ __launch_bounds__(FEAS_THREADS) void feas_copy_kernel(int64_t n, double* __restrict__ y, const double* __restrict__ x) { FEAS_STRIDE(i, n) y[i] = x[i]; }
-// y = x - P x + q      IndAffine: x - A'(A A')^-1 (A x - b) with P = A'(A A')^-1 A, q = A'(A A')^-1 b
-__global__ __launch_bounds__(FEAS_THREADS) void feas_affine_finish_kernel(int64_t n, double* __restrict__ y, const double* __restrict__ x,
-                                                                          const double* __restrict__ Px, const double* __restrict__ q) {
-    FEAS_STRIDE(i, n) y[i] = (x[i] - Px[i]) + q[i];
-}
-// y = clamp(x, lo, hi)      IndBox
-__global__ __launch_bounds__(FEAS_THREADS) void feas_box_kernel(int64_t n, double* __restrict__ y, const double* __restrict__ x, double lo, double hi) {
-    FEAS_STRIDE(i, n) y[i] = fmin(fmax(x[i], lo), hi);
-}
-// y = clamp(x, lo[i], hi[i])      IndBox with array bounds
-__global__ __launch_bounds__(FEAS_THREADS) void feas_boxv_kernel(int64_t n, double* __restrict__ y, const double* __restrict__ x,
-                                                                 const double* __restrict__ lo, const double* __restrict__ hi) {
-    FEAS_STRIDE(i, n) y[i] = fmin(fmax(x[i], lo[i]), hi[i]);
-}
 // y = a y + (1 - a) x       gap.jl:48,58 ; gapa.jl:67,77 (a = alpha12, a device scalar) ; fista.jl:37
 __global__ __launch_bounds__(FEAS_THREADS) void feas_relax_kernel(int64_t n, double* __restrict__ y, const double* __restrict__ x, double a,
                                                                   const double* __restrict__ a_dev) {
@@ -135,62 +118,21 @@ __global__ __launch_bounds__(FEAS_THREADS) void feas_gap_tail_kernel(int64_t n, 
 __global__ __launch_bounds__(FEAS_THREADS) void feas_combine_kernel(int64_t n, double* __restrict__ x, const double* __restrict__ t2, double alpha) {
     FEAS_STRIDE(i, n) x[i] = alpha * t2[i] + (1.0 - alpha) * x[i];
 }
-// plain vector <-> the two-part layout of the cone kernels (part 1 = the vector, part 2 = zeros: its dual projections are of zero)
-__global__ __launch_bounds__(FEAS_THREADS) void feas_to_parts_kernel(int64_t n, double2* __restrict__ z, const double* __restrict__ x) {
-    FEAS_STRIDE(i, n) z[i] = make_double2(x[i], 0.0);
-}
-__global__ __launch_bounds__(FEAS_THREADS) void feas_from_parts_kernel(int64_t n, double* __restrict__ y, const double2* __restrict__ z) {
-    FEAS_STRIDE(i, n) y[i] = z[i].x;
-}
-// set-up: the row-major m x n matrix A as a column-major L x L array (rows 0..m-1, zero padded) and its transpose
-__global__ __launch_bounds__(FEAS_THREADS) void feas_spread_kernel(int64_t m, int64_t n, int64_t L, const double* __restrict__ A,
-                                                                   double* __restrict__ Ah, double* __restrict__ At) {
-    FEAS_STRIDE(e, m * n) {
-        const int64_t i = e / n, j = e % n;
-        const double v = A[e];
-        Ah[i + j * L] = v;
-        At[j + i * L] = v;
-    }
-}
-// set-up: E[i + i L] = 1 for i >= m (the padding of G = A A' + E keeps it positive definite)
-__global__ __launch_bounds__(FEAS_THREADS) void feas_pad_identity_kernel(int64_t L, int64_t m, double* __restrict__ E) {
-    FEAS_STRIDE(i, L) if (i >= m) E[i + i * L] = 1.0;
-}
-
-struct FeasSet {
-    int kind = 0;                   // 0 unset, 1 IndAffine (dense), 2 IndBox, 3 ConeProduct, 4 host callback, 5 IndAffine (sparse A), 6 separable sum of sets, 7 IndAffine (dense, factored), 8 IndAffine (sparse A, factored), 9 Quadratic / LeastSquares in the n-space
-    SparseAffine* sa = nullptr;     // kind 5 (affine_sparse.hip)
-    DenseAffine* da = nullptr;      // kind 7 (affine_dense.hip)
-    SparseFactored* sf = nullptr;   // kind 8 (affine_sparse_factored.hip)
-    SetBlocks* sb = nullptr;        // kind 6 (sets.hip)
-    NSpace* ns = nullptr;           // kind 9 (nspace.hip)
-    fos_prox_fn cb = nullptr;       // kind 4: prox!(y, S, x) evaluated by the caller on pinned host vectors
-    void* cb_ctx = nullptr;
-    double *cb_x = nullptr, *cb_y = nullptr;
-    double* P = nullptr;            // [L x L] A'(A A')^-1 A, column-major
-    double* q = nullptr;            // [L]     A'(A A')^-1 b
-    double lo = 0.0, hi = 0.0;
-    double *lov = nullptr, *hiv = nullptr;      // [n] array bounds (IndBox with vectors); nullptr: the scalars
-    int ns_iters = 0;               // Newton-Schulz steps of the set-up
-    double ns_resid = 0.0;          // max |G X - I| it ended with
-    ConeSet* cones = nullptr;       // kind 3: ConeProduct (cones.jl:31-94) on the batched cone kernels of the HSDE path (cones.cpp)
-};
-
 }  // namespace fos
 
 using namespace fos;
 
-struct fos_feas {
+struct fos_feas : DevOwned {                      // (owns the vectors below; the sets own theirs)
+    fos_feas() { what = "feasibility form"; }
     int device = 0;
     hipStream_t stream = nullptr;
     int64_t n = 0, L = 0;
-    FeasSet S[2];
+    std::unique_ptr<ProxObject> S[2];      // the two sets: nullptr until defined
     int alg = FOS_ALG_GAP;
     double alpha = 0.8, alpha1 = 1.8, alpha2 = 1.8, beta = 0.0;
     double fista_t = 1.0;
     // vectors of length L (zero padded)
-    double *x = nullptr, *t1 = nullptr, *t2 = nullptr, *y = nullptr, *xold = nullptr, *p = nullptr, *q = nullptr, *prev = nullptr, *tmp = nullptr, *px = nullptr;
-    double2 *zin = nullptr, *zout = nullptr;      // [n] two-part scratch of the cone kernels (allocated with the first ConeProduct set)
+    double *x = nullptr, *t1 = nullptr, *t2 = nullptr, *y = nullptr, *xold = nullptr, *p = nullptr, *q = nullptr, *prev = nullptr, *tmp = nullptr;
     int cus = 256;
     double* partials = nullptr;     // [3 x FEAS_PARTS]
     double* a12 = nullptr;          // device scalar alpha12 (GAPA)
@@ -203,7 +145,6 @@ struct fos_feas {
     LongPlanes lp;                  // LongstepWrapper (wrappers/longstep.jl): planes saved in the last nsave + 1 iterations of every interval (vectors viewed as L/2 double2)
     int64_t gapp_iproj = 100;       // GAPP (solvers/gapproj.jl): every iproj-th iteration is a projected search
     double gapp_log[23] = {0};      // 21 test norms, alpha_best, iteration
-    std::vector<void*> owned;
 };
 
 namespace {
@@ -211,16 +152,6 @@ namespace {
 int feas_check_launch(const char* where) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("%s: a kernel launch failed: %s", where, hipGetErrorString(e)); return FOS_EHIP; }
-    return FOS_OK;
-}
-
-int feas_alloc(fos_feas* h, double** out, size_t count) {
-    void* q = nullptr;
-    const hipError_t e = hipMalloc(&q, sizeof(double) * std::max<size_t>(count, 1));
-    if (e != hipSuccess) { set_error("feasibility form: hipMalloc of %zu doubles failed: %s", count, hipGetErrorString(e)); return FOS_ENOMEM; }
-    if (hipMemsetAsync(q, 0, sizeof(double) * std::max<size_t>(count, 1), h->stream) != hipSuccess) { (void)hipFree(q); set_error("hipMemsetAsync failed"); return FOS_EHIP; }
-    h->owned.push_back(q);
-    *out = static_cast<double*>(q);
     return FOS_OK;
 }
 
@@ -245,37 +176,24 @@ inline void feas_long_save(fos_feas* h, int which, const double* y, const double
 
 // prox!(y, S, x): the projection onto set `which`; y must not alias x
 int feas_prox(fos_feas* h, int which, double* y, const double* x) {
-    const FeasSet& s = h->S[which];
-    if (s.kind == 1) {
-        launch_dense_symv(feas_ctx(h, h->n), h->L, s.P, x, h->px);        // P is symmetric: column dots = P x
-        FEAS_K(feas_affine_finish_kernel, h->n, y, x, h->px, s.q);
-    } else if (s.kind == 2) {
-        if (s.lov) FEAS_K(feas_boxv_kernel, h->n, y, x, (const double*)s.lov, (const double*)s.hiv);
-        else FEAS_K(feas_box_kernel, h->n, y, x, s.lo, s.hi);
-    } else if (s.kind == 3) {                                             // prox!(y, ::ConeProduct, x)   cones.jl:89-94
-        LaunchCtx c = feas_ctx(h, h->n);
-        c.vec_blocks = h->grid; c.cus = h->cus;
-        FEAS_K(feas_to_parts_kernel, h->n, h->zin, x);
-        cone_set_project_vector(s.cones, c, h->zout, h->zin);
-        FOS_TRY(cone_set_project_psd(s.cones, c, h->zout, h->zin));             // (the next projection starts warm from this one's basis)
-        FEAS_K(feas_from_parts_kernel, h->n, y, (const double2*)h->zout);
-    } else if (s.kind == 5) {                                             // IndAffine over a sparse A: CG on the normal equations, exact to the residual's rounding level
-        FOS_TRY(sparse_affine_project(s.sa, h->stream, y, x));
-    } else if (s.kind == 7) {                                             // IndAffine over a dense A, factored: two passes over A and the inverse of A A', a fixed number of launches
-        FOS_TRY(dense_affine_project(s.da, h->stream, y, x));
-    } else if (s.kind == 8) {                                             // IndAffine over a sparse A, factored: two segmented sparse passes and the dense inverse of A A', a fixed number of launches
-        FOS_TRY(sparse_factored_project(s.sf, h->stream, y, x));
-    } else if (s.kind == 9) {                                             // Quadratic, LeastSquares (normal equations): three one-rhs tile products over the packed M and M^-1, six launches
-        FOS_TRY(nspace_prox(s.ns, h->stream, y, x));
-    } else if (s.kind == 6) {                                             // balls, simplex, halfspaces ... in contiguous blocks: a fixed number of launches, no copy
-        FOS_TRY(set_blocks_project(s.sb, h->stream, y, x));
-    } else if (s.kind == 4) {                                             // any other ProximableFunction: the caller's prox! on host vectors
-        FOS_HIP(hipMemcpyAsync(s.cb_x, x, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
-        FOS_HIP(hipStreamSynchronize(h->stream));
-        const int32_t rc = s.cb(s.cb_ctx, h->n, s.cb_x, s.cb_y);
-        if (rc != 0) { set_error("feasibility form: the prox callback of set %d returned %d", which + 1, (int)rc); return FOS_EINVAL; }
-        FOS_HIP(hipMemcpyAsync(y, s.cb_y, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
-    } else { set_error("feasibility form: set %d has not been defined", which + 1); return FOS_EINVAL; }
+    if (!h->S[which]) { set_error("feasibility form: set %d has not been defined", which + 1); return FOS_EINVAL; }
+    return h->S[which]->prox(h->stream, y, x);
+}
+
+FeasEnv feas_env(const fos_feas* h) { return FeasEnv{h->stream, h->n, h->L, h->grid, h->cus, h->partials}; }
+
+// the one way a set enters a slot (which = 1 | 2): `fresh` was built first, so a refused call never gets here and leaves the set as it was; no prox of the object
+// being replaced runs any more once the stream is idle, and what it owned goes with it, whatever its kind
+int feas_install(fos_feas* h, int32_t which, ProxObject* fresh) {
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { delete fresh; set_error("feasibility form: hipStreamSynchronize -> %s", hipGetErrorString(e)); return FOS_EHIP; }
+    h->S[which - 1].reset(fresh);
+    return FOS_OK;
+}
+// the object of slot `which` when it is of `kind`, for the accessors; otherwise FOS_EINVAL with "<fn>: set <which> <is_not>"
+int feas_object(fos_feas* h, int32_t which, const void* out, int kind, const char* fn, const char* is_not, const ProxObject** obj) {
+    if (!h || !out || which < 1 || which > 2 || !h->S[which - 1] || h->S[which - 1]->kind != kind) { set_error("%s: set %d %s", fn, (int)which, is_not); return FOS_EINVAL; }
+    *obj = h->S[which - 1].get();
     return FOS_OK;
 }
 
@@ -456,10 +374,10 @@ int fos_feas_create(int64_t n, int32_t device, fos_feas_handle* out) {
     if (hipStreamCreate(&h->stream) != hipSuccess) { delete h; set_error("hipStreamCreate failed"); return FOS_EHIP; }
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) h->cus = prop.multiProcessorCount; }
     int rc = FOS_OK;
-    double** vecs[] = {&h->x, &h->t1, &h->t2, &h->y, &h->xold, &h->p, &h->q, &h->prev, &h->tmp, &h->px};
-    for (double** v : vecs) { rc = feas_alloc(h, v, (size_t)h->L); if (rc != FOS_OK) break; }
-    if (rc == FOS_OK) rc = feas_alloc(h, &h->partials, 3 * (size_t)FEAS_PARTS);
-    if (rc == FOS_OK) rc = feas_alloc(h, &h->a12, 8);
+    double** vecs[] = {&h->x, &h->t1, &h->t2, &h->y, &h->xold, &h->p, &h->q, &h->prev, &h->tmp};
+    for (double** v : vecs) { rc = h->zeros(v, (size_t)h->L, h->stream); if (rc != FOS_OK) break; }
+    if (rc == FOS_OK) rc = h->zeros(&h->partials, 3 * (size_t)FEAS_PARTS, h->stream);
+    if (rc == FOS_OK) rc = h->zeros(&h->a12, 8, h->stream);
     if (rc != FOS_OK) { fos_feas_destroy(h); return rc; }
     *out = h;
     return fos_feas_set_iterate(h, nullptr);
@@ -469,129 +387,58 @@ int fos_feas_destroy(fos_feas_handle h) {
     if (!h) return FOS_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* q : h->owned) (void)hipFree(q);
-    for (FeasSet& s : h->S) { if (s.cb_x) (void)hipHostFree(s.cb_x); if (s.cb_y) (void)hipHostFree(s.cb_y); cone_set_destroy(s.cones, h->stream); sparse_affine_destroy(s.sa); dense_affine_destroy(s.da); sparse_factored_destroy(s.sf); set_blocks_destroy(s.sb); nspace_destroy(s.ns); }
+    for (auto& s : h->S) s.reset();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return FOS_OK;
 }
 
-// IndAffine(A, b): A is m x n, ROW-major (C order), full row rank.  One-time set-up on the device:
-//   G = A A' (+ identity on the padding), X = G^-1 by Newton-Schulz  X <- 2 X - X (G X)  from X_0 = I / (1.25 |A|_F^2),
-//   P = A' X A,  q = A' X b.
+// IndAffine(A, b) as the dense n x n projector (feas_objects.hip): A is m x n, ROW-major (C order), full row rank
 int fos_feas_set_affine(fos_feas_handle h, int32_t which, int64_t m, const double* A, const double* b) {
     if (!h || !A || !b || which < 1 || which > 2 || m < 1 || m > h->n) { set_error("fos_feas_set_affine: bad argument (1 <= m <= n, which = 1 | 2)"); return FOS_EINVAL; }
     if (h->n > 46000) { set_error("IndAffine: the dense projector holds %lld x %lld doubles: supported up to n = 46000", (long long)h->n, (long long)h->n); return FOS_EUNSUPPORTED; }
     FOS_HIP(hipSetDevice(h->device));
-    const int64_t n = h->n, L = h->L;
-    const size_t L2 = (size_t)L * (size_t)L;
-    std::vector<double> bp((size_t)L, 0.0);
-    double fro2 = 0.0;
-    for (int64_t e = 0; e < m * n; ++e) {
-        const double v = A[e];
-        if (!(v == v) || std::fabs(v) > 1e300) { set_error("IndAffine: A has non-finite entries"); return FOS_EINVAL; }
-        fro2 += v * v;
-    }
-    for (int64_t i = 0; i < m; ++i) bp[(size_t)i] = b[i];
-    if (!(fro2 > 0.0)) { set_error("IndAffine: A is zero"); return FOS_EINVAL; }
-    double *dA = nullptr, *dAt = nullptr, *G = nullptr, *B0 = nullptr, *B1 = nullptr, *B2 = nullptr, *db = nullptr, *dt = nullptr, *draw = nullptr;
-    auto cleanup = [&]() { for (double* q : {dA, dAt, G, B0, B1, B2, db, dt, draw}) (void)hipFree(q); };
-    hipError_t e = hipSuccess;
-    for (double** q : {&dA, &dAt, &G, &B0, &B1, &B2}) if (e == hipSuccess) e = hipMalloc((void**)q, sizeof(double) * L2);
-    for (double** q : {&db, &dt}) if (e == hipSuccess) e = hipMalloc((void**)q, sizeof(double) * (size_t)L);
-    if (e == hipSuccess) e = hipMalloc((void**)&draw, sizeof(double) * (size_t)(m * n));
-    if (e != hipSuccess) { cleanup(); set_error("IndAffine set-up: hipMalloc of six %lld x %lld buffers failed: %s", (long long)L, (long long)L, hipGetErrorString(e)); return FOS_ENOMEM; }
-    auto fail = [&](int code) { cleanup(); return code; };
-#define FEAS_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error("IndAffine set-up: %s -> %s", #expr, hipGetErrorString(_e)); return fail(FOS_EHIP); } } while (0)
-    FEAS_HIP(hipMemcpyAsync(draw, A, sizeof(double) * (size_t)(m * n), hipMemcpyHostToDevice, h->stream));
-    FEAS_HIP(hipMemsetAsync(dA, 0, sizeof(double) * L2, h->stream));
-    FEAS_HIP(hipMemsetAsync(dAt, 0, sizeof(double) * L2, h->stream));
-    hipLaunchKernelGGL(feas_spread_kernel, dim3(1024), dim3(FEAS_THREADS), 0, h->stream, m, n, L, (const double*)draw, dA, dAt);
-    FEAS_HIP(hipMemcpyAsync(db, bp.data(), sizeof(double) * (size_t)L, hipMemcpyHostToDevice, h->stream));
-    FEAS_HIP(hipMemsetAsync(B0, 0, sizeof(double) * L2, h->stream));
-    FEAS_HIP(hipMemsetAsync(B1, 0, sizeof(double) * L2, h->stream));
-    const LaunchCtx c = feas_ctx(h, L);
-    FEAS_K(feas_pad_identity_kernel, L, m, B0);                                        // E
-    launch_dense_gemm(c, (int)L, 1.0, dA, dAt, 1.0, B0, G);                            // G = A A' + E   (block diagonal, positive definite)
-    launch_dense_scale_identity(c, L, B1, 1.0 / (1.25 * std::max(fro2, 1.0)));         // X_0: lambda_max(G) <= max(|A|_F^2, 1)
-    double *X = B1, *Xn = B2;
-    std::vector<double> part(256);
-    double resid = 1.0, prev_resid = 2.0;
-    int it = 0;
-    for (; it < 120; ++it) {
-        launch_dense_gemm(c, (int)L, 1.0, G, X, 0.0, nullptr, B0);                     // Y = G X
-        launch_dense_resid(c, L, B0, h->partials, 256);
-        FEAS_HIP(hipMemcpyAsync(part.data(), h->partials, sizeof(double) * 256, hipMemcpyDeviceToHost, h->stream));
-        FEAS_HIP(hipStreamSynchronize(h->stream));
-        resid = 0.0;
-        for (double r : part) resid = (r > resid || r != r) ? r : resid;
-        if (resid != resid) { set_error("IndAffine set-up: the inverse of A A' produced NaN"); return fail(FOS_EINVAL); }
-        if (resid <= 2e-14 || (resid <= 1e-10 && resid >= 0.5 * prev_resid)) break;   // rounding level: the residual no longer squares
-        prev_resid = resid;
-        launch_dense_gemm(c, (int)L, -1.0, X, B0, 2.0, X, Xn);                         // X <- 2 X - X Y
-        std::swap(X, Xn);
-    }
-    if (!(resid <= 1e-10)) {
-        set_error("IndAffine set-up: the inverse of A A' did not converge (max |G X - I| = %.3e after %d Newton-Schulz steps): A needs full row rank and a moderate condition number", resid, it);
-        return fail(FOS_EINVAL);
-    }
-    FeasSet& s = h->S[which - 1];
-    int rc = FOS_OK;
-    if (!s.P) rc = feas_alloc(h, &s.P, L2);
-    if (rc == FOS_OK && !s.q) rc = feas_alloc(h, &s.q, (size_t)L);
-    if (rc != FOS_OK) return fail(rc);
-    launch_dense_gemm(c, (int)L, 1.0, X, dA, 0.0, nullptr, B0);                        // B0 = X A
-    launch_dense_gemm(c, (int)L, 1.0, dAt, B0, 0.0, nullptr, s.P);                     // P = A' X A
-    launch_dense_symv(c, L, X, db, dt);                                                // t = X b   (X symmetric)
-    launch_dense_symv(c, L, dA, dt, s.q);                                              // q[col] = A[:, col] . t = (A' t)[col]
-    FEAS_HIP(hipStreamSynchronize(h->stream));
-#undef FEAS_HIP
-    rc = feas_check_launch("IndAffine set-up");
-    cleanup();
-    if (rc != FOS_OK) return rc;
-    s.kind = 1; s.ns_iters = it; s.ns_resid = resid;
-    return FOS_OK;
+    ProxObject* s = nullptr;
+    FOS_TRY(dense_projector_setup(feas_env(h), m, A, b, &s));
+    return feas_install(h, which, s);
 }
 
 // IndAffine(A, b), A a sparse m x n matrix (CSC, 1-based: Julia's SparseMatrixCSC{Float64,Int64}), full row rank: nothing dense is formed, any n
 int fos_feas_set_affine_sparse(fos_feas_handle h, int32_t which, int64_t m, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b) {
     if (!h || which < 1 || which > 2 || m < 1 || m > h->n) { set_error("fos_feas_set_affine_sparse: bad argument (1 <= m <= n, which = 1 | 2)"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
-    SparseAffine* sa = nullptr;
-    FOS_TRY(sparse_affine_setup(m, h->n, colptr, rowval, nzval, b, h->cus, &sa));
-    FeasSet& s = h->S[which - 1];
-    sparse_affine_destroy(s.sa);
-    s.sa = sa; s.kind = 5;
-    return FOS_OK;
+    ProxObject* s = nullptr;
+    FOS_TRY(sparse_affine_setup(m, h->n, colptr, rowval, nzval, b, h->cus, &s));
+    return feas_install(h, which, s);
 }
 
 // out8: projections so far, CG iterations so far, CG iterations / restarts of the last projection, its |A y - b| and the rounding level | |A||y| + |b| |
 // (rows scaled to unit norm), stored entries, lanes per row of A x 1000 + of A'
 int fos_feas_affine_stats(fos_feas_handle h, int32_t which, double* out8) {
-    if (!h || !out8 || which < 1 || which > 2 || h->S[which - 1].kind != 5) { set_error("fos_feas_affine_stats: set %d is not a sparse IndAffine", (int)which); return FOS_EINVAL; }
-    sparse_affine_stats(h->S[which - 1].sa, out8);
+    const ProxObject* s = nullptr;
+    FOS_TRY(feas_object(h, which, out8, FEAS_AFFINE_SPARSE, "fos_feas_affine_stats", "is not a sparse IndAffine", &s));
+    sparse_affine_stats(s, out8);
     return FOS_OK;
 }
 
-// IndAffine(A, b), A dense m x n ROW-major, factored form (affine_dense.hip): built first, so that a refused call leaves the set as it was
+// IndAffine(A, b), A dense m x n ROW-major, factored form (affine_dense.hip)
 int fos_feas_set_affine_factored(fos_feas_handle h, int32_t which, int64_t m, const double* A, const double* b, int32_t factor, int32_t refine) {
     if (!h || which < 1 || which > 2 || m < 1 || m > h->n) { set_error("fos_feas_set_affine_factored: bad argument (1 <= m <= n, which = 1 | 2)"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
-    DenseAffine* da = nullptr;
-    FOS_TRY(dense_affine_setup(m, h->n, A, b, 0.0, factor, refine, h->cus, h->stream, &da));       // (synchronises the stream: no projection onto the set being replaced runs any more)
-    FeasSet& s = h->S[which - 1];
-    dense_affine_destroy(s.da);
-    s.da = da; s.kind = 7;
-    return FOS_OK;
+    ProxObject* s = nullptr;
+    FOS_TRY(dense_affine_setup(m, h->n, A, b, 0.0, factor, refine, h->cus, h->stream, &s));
+    return feas_install(h, which, s);
 }
 int fos_feas_affine_factored_stats(fos_feas_handle h, int32_t which, double* out8) {
-    if (!h || !out8 || which < 1 || which > 2 || h->S[which - 1].kind != 7) { set_error("fos_feas_affine_factored_stats: set %d is not a factored IndAffine", (int)which); return FOS_EINVAL; }
-    dense_affine_stats(h->S[which - 1].da, out8);
+    const ProxObject* s = nullptr;
+    FOS_TRY(feas_object(h, which, out8, FEAS_AFFINE_FACTORED, "fos_feas_affine_factored_stats", "is not a factored IndAffine", &s));
+    dense_affine_stats(s, out8);
     return FOS_OK;
 }
 int fos_feas_affine_factored_plan(fos_feas_handle h, int32_t which, int64_t* out6) {
-    if (!h || !out6 || which < 1 || which > 2 || h->S[which - 1].kind != 7) { set_error("fos_feas_affine_factored_plan: set %d is not a factored IndAffine", (int)which); return FOS_EINVAL; }
-    dense_affine_plan(h->S[which - 1].da, out6);
+    const ProxObject* s = nullptr;
+    FOS_TRY(feas_object(h, which, out6, FEAS_AFFINE_FACTORED, "fos_feas_affine_factored_plan", "is not a factored IndAffine", &s));
+    dense_affine_plan(s, out6);
     return FOS_OK;
 }
 // test-only, host: the factored form's scaling, inverse and two passes in the kernels' order (affine_dense.hip)
@@ -599,43 +446,39 @@ int fos_host_affine_factored(int64_t m, int64_t n, const double* A, const double
     return host_affine_factored(m, n, A, b, 0.0, refine, x, y);
 }
 // LeastSquares(A, b, lambda), A dense m x n ROW-major: the factored form with the diagonal of A A' shifted by 1 / lambda (affine_dense.hip); the same object
-// kind, so the stats and the plan of the factored form describe it.  Built first, so that a refused call leaves the set as it was
+// kind, so the stats and the plan of the factored form describe it
 int fos_feas_set_least_squares(fos_feas_handle h, int32_t which, int64_t m, const double* A, const double* b, double lambda, int32_t factor) {
     if (!h || which < 1 || which > 2) { set_error("fos_feas_set_least_squares: NULL handle or which not in {1, 2}"); return FOS_EINVAL; }
     if (!(lambda > 0.0) || lambda > 1e300) { set_error("LeastSquares: lambda must be finite and > 0"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
-    DenseAffine* da = nullptr;
-    FOS_TRY(dense_affine_setup(m, h->n, A, b, lambda, factor, 0, h->cus, h->stream, &da));    // (synchronises the stream, as above)
-    FeasSet& s = h->S[which - 1];
-    dense_affine_destroy(s.da);
-    s.da = da; s.kind = 7;
-    return FOS_OK;
+    ProxObject* s = nullptr;
+    FOS_TRY(dense_affine_setup(m, h->n, A, b, lambda, factor, 0, h->cus, h->stream, &s));
+    return feas_install(h, which, s);
 }
 int fos_host_least_squares(int64_t m, int64_t n, const double* A, const double* b, double lambda, const double* x, double* y) {
     if (!(lambda > 0.0) || lambda > 1e300) { set_error("LeastSquares: lambda must be finite and > 0"); return FOS_EINVAL; }
     return host_affine_factored(m, n, A, b, lambda, 0, x, y);
 }
 
-// IndAffine(A, b), A sparse m x n (CSC, 1-based), factored form (affine_sparse_factored.hip): built first, so that a refused call leaves the set as it was
+// IndAffine(A, b), A sparse m x n (CSC, 1-based), factored form (affine_sparse_factored.hip)
 int fos_feas_set_affine_sparse_factored(fos_feas_handle h, int32_t which, int64_t m, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b,
                                         int32_t factor, int32_t refine) {
     if (!h || which < 1 || which > 2 || m < 1) { set_error("fos_feas_set_affine_sparse_factored: bad argument (m >= 1, which = 1 | 2)"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
-    SparseFactored* sf = nullptr;
-    FOS_TRY(sparse_factored_setup(m, h->n, colptr, rowval, nzval, b, 0.0, factor, refine, h->stream, &sf));   // (synchronises the stream: no projection onto the set being replaced runs any more)
-    FeasSet& s = h->S[which - 1];
-    sparse_factored_destroy(s.sf);
-    s.sf = sf; s.kind = 8;
-    return FOS_OK;
+    ProxObject* s = nullptr;
+    FOS_TRY(sparse_factored_setup(m, h->n, colptr, rowval, nzval, b, 0.0, factor, refine, h->stream, &s));
+    return feas_install(h, which, s);
 }
 int fos_feas_affine_sparse_factored_stats(fos_feas_handle h, int32_t which, double* out8) {
-    if (!h || !out8 || which < 1 || which > 2 || h->S[which - 1].kind != 8) { set_error("fos_feas_affine_sparse_factored_stats: set %d is not a sparse factored IndAffine", (int)which); return FOS_EINVAL; }
-    sparse_factored_stats(h->S[which - 1].sf, out8);
+    const ProxObject* s = nullptr;
+    FOS_TRY(feas_object(h, which, out8, FEAS_SPARSE_FACTORED, "fos_feas_affine_sparse_factored_stats", "is not a sparse factored IndAffine", &s));
+    sparse_factored_stats(s, out8);
     return FOS_OK;
 }
 int fos_feas_affine_sparse_factored_plan(fos_feas_handle h, int32_t which, int64_t* out8) {
-    if (!h || !out8 || which < 1 || which > 2 || h->S[which - 1].kind != 8) { set_error("fos_feas_affine_sparse_factored_plan: set %d is not a sparse factored IndAffine", (int)which); return FOS_EINVAL; }
-    sparse_factored_plan(h->S[which - 1].sf, out8);
+    const ProxObject* s = nullptr;
+    FOS_TRY(feas_object(h, which, out8, FEAS_SPARSE_FACTORED, "fos_feas_affine_sparse_factored_plan", "is not a sparse factored IndAffine", &s));
+    sparse_factored_plan(s, out8);
     return FOS_OK;
 }
 // test-only, host: the sparse factored form's scaling, inverse, segment tables and two passes in the kernels' order (affine_sparse_factored.hip)
@@ -644,51 +487,36 @@ int fos_host_affine_sparse_factored(int64_t m, int64_t n, const int64_t* colptr,
     return host_affine_sparse_factored(m, n, colptr, rowval, nzval, b, 0.0, refine, x, y);
 }
 
-// ---- the n-space forms (nspace.hip) and the sparse wide LeastSquares (affine_sparse_factored.hip with a shifted diagonal).  Every object is built first, so that
-// a refused call leaves the set as it was
-namespace {
-int feas_install_nspace(fos_feas* h, int32_t which, NSpace* ns) {                  // (the set-up synchronised the stream: no prox of the set being replaced runs any more)
-    FeasSet& s = h->S[which - 1];
-    nspace_destroy(s.ns);
-    s.ns = ns; s.kind = 9;
-    return FOS_OK;
-}
-}  // namespace
+// ---- the n-space forms (nspace.hip) and the sparse wide LeastSquares (affine_sparse_factored.hip with a shifted diagonal)
 int fos_feas_set_quadratic(fos_feas_handle h, int32_t which, const double* Q, const double* q, int32_t factor) {
     if (!h || which < 1 || which > 2) { set_error("fos_feas_set_quadratic: NULL handle or which not in {1, 2}"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
-    NSpace* ns = nullptr;
-    FOS_TRY(nspace_setup_quadratic(h->n, Q, q, factor, h->stream, &ns));
-    return feas_install_nspace(h, which, ns);
+    ProxObject* s = nullptr;
+    FOS_TRY(nspace_setup_quadratic(h->n, Q, q, factor, h->stream, &s));
+    return feas_install(h, which, s);
 }
 int fos_feas_set_least_squares_normal(fos_feas_handle h, int32_t which, int64_t m, const double* A, const double* b, double lambda, int32_t factor) {
     if (!h || which < 1 || which > 2) { set_error("fos_feas_set_least_squares_normal: NULL handle or which not in {1, 2}"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
-    NSpace* ns = nullptr;
-    FOS_TRY(nspace_setup_ls_dense(m, h->n, A, b, lambda, factor, h->stream, &ns));
-    return feas_install_nspace(h, which, ns);
+    ProxObject* s = nullptr;
+    FOS_TRY(nspace_setup_ls_dense(m, h->n, A, b, lambda, factor, h->stream, &s));
+    return feas_install(h, which, s);
 }
 int fos_feas_set_least_squares_sparse(fos_feas_handle h, int32_t which, int64_t m, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b,
                                       double lambda, int32_t form, int32_t factor) {
     if (!h || which < 1 || which > 2) { set_error("fos_feas_set_least_squares_sparse: NULL handle or which not in {1, 2}"); return FOS_EINVAL; }
     if (!(lambda > 0.0) || lambda > 1e300) { set_error("LeastSquares: lambda must be finite and > 0"); return FOS_EINVAL; }
+    if (form != FOS_LS_FORM_NORMAL && form != FOS_LS_FORM_SPARSE_FACTORED) { set_error("LeastSquares (sparse): form must be FOS_LS_FORM_SPARSE_FACTORED or FOS_LS_FORM_NORMAL"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
-    if (form == FOS_LS_FORM_NORMAL) {
-        NSpace* ns = nullptr;
-        FOS_TRY(nspace_setup_ls_sparse(m, h->n, colptr, rowval, nzval, b, lambda, factor, h->stream, &ns));
-        return feas_install_nspace(h, which, ns);
-    }
-    if (form != FOS_LS_FORM_SPARSE_FACTORED) { set_error("LeastSquares (sparse): form must be FOS_LS_FORM_SPARSE_FACTORED or FOS_LS_FORM_NORMAL"); return FOS_EINVAL; }
-    SparseFactored* sf = nullptr;
-    FOS_TRY(sparse_factored_setup(m, h->n, colptr, rowval, nzval, b, lambda, factor, 0, h->stream, &sf));
-    FeasSet& s = h->S[which - 1];
-    sparse_factored_destroy(s.sf);
-    s.sf = sf; s.kind = 8;
-    return FOS_OK;
+    ProxObject* s = nullptr;
+    if (form == FOS_LS_FORM_NORMAL) FOS_TRY(nspace_setup_ls_sparse(m, h->n, colptr, rowval, nzval, b, lambda, factor, h->stream, &s));
+    else FOS_TRY(sparse_factored_setup(m, h->n, colptr, rowval, nzval, b, lambda, factor, 0, h->stream, &s));
+    return feas_install(h, which, s);
 }
 int fos_feas_nspace_stats(fos_feas_handle h, int32_t which, double* out8) {
-    if (!h || !out8 || which < 1 || which > 2 || h->S[which - 1].kind != 9) { set_error("fos_feas_nspace_stats: set %d is not a Quadratic or a LeastSquares in the normal-equations form", (int)which); return FOS_EINVAL; }
-    nspace_stats(h->S[which - 1].ns, out8);
+    const ProxObject* s = nullptr;
+    FOS_TRY(feas_object(h, which, out8, FEAS_NSPACE, "fos_feas_nspace_stats", "is not a Quadratic or a LeastSquares in the normal-equations form", &s));
+    nspace_stats(s, out8);
     return FOS_OK;
 }
 // test-only, host: the n-space forms' scaling, inverse, packing and three tile products in the kernels' order (nspace.hip)
@@ -719,9 +547,10 @@ int fos_bench_symv_packed(int32_t device, int64_t k, int32_t reps, double* out4)
 
 int fos_feas_set_box(fos_feas_handle h, int32_t which, double lo, double hi) {
     if (!h || which < 1 || which > 2 || !(lo <= hi)) { set_error("fos_feas_set_box: which = 1 | 2 and lo <= hi are required"); return FOS_EINVAL; }
-    FeasSet& s = h->S[which - 1];
-    s.kind = 2; s.lo = lo; s.hi = hi; s.lov = s.hiv = nullptr;
-    return FOS_OK;
+    FOS_HIP(hipSetDevice(h->device));
+    ProxObject* s = nullptr;
+    FOS_TRY(box_setup(feas_env(h), lo, hi, nullptr, nullptr, &s));
+    return feas_install(h, which, s);
 }
 
 // IndBox(lo, hi) with array bounds (n entries each; +-INFINITY allowed)
@@ -729,13 +558,9 @@ int fos_feas_set_box_arrays(fos_feas_handle h, int32_t which, const double* lo, 
     if (!h || which < 1 || which > 2 || !lo || !hi) { set_error("fos_feas_set_box_arrays: bad argument"); return FOS_EINVAL; }
     for (int64_t i = 0; i < h->n; ++i) if (!(lo[i] <= hi[i])) { set_error("IndBox: lo[%lld] <= hi[%lld] is required", (long long)i + 1, (long long)i + 1); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
-    FeasSet& s = h->S[which - 1];
-    if (!s.lov) { FOS_TRY(feas_alloc(h, &s.lov, (size_t)h->n)); FOS_TRY(feas_alloc(h, &s.hiv, (size_t)h->n)); }
-    FOS_HIP(hipMemcpyAsync(s.lov, lo, sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, h->stream));
-    FOS_HIP(hipMemcpyAsync(s.hiv, hi, sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, h->stream));
-    FOS_HIP(hipStreamSynchronize(h->stream));
-    s.kind = 2;
-    return FOS_OK;
+    ProxObject* s = nullptr;
+    FOS_TRY(box_setup(feas_env(h), 0.0, 0.0, lo, hi, &s));
+    return feas_install(h, which, s);
 }
 
 // ConeProduct (cones.jl:31-77): ncones cones in order, contiguous from index 1, together covering all n entries
@@ -754,54 +579,32 @@ int fos_feas_set_cones(fos_feas_handle h, int32_t which, int64_t ncones, const i
     ConeTable table;
     table.ew.assign((size_t)n, 0);
     cone_table_add(table, 0, CONE_PRIMAL, ncones, type, start.data(), len);
-    FeasSet& s = h->S[which - 1];
-    cone_set_destroy(s.cones, h->stream); s.cones = nullptr;      // a set defined again: what it held goes before the new state is built
-    if (s.kind == 3) s.kind = 0;
-    FOS_TRY(cone_set_build(table, n, ConeSetOptions{}, PsdTuning{}, &s.cones));
-    if (!h->zin) {
-        double* q = nullptr;
-        FOS_TRY(feas_alloc(h, &q, 2 * (size_t)n)); h->zin = reinterpret_cast<double2*>(q);
-        FOS_TRY(feas_alloc(h, &q, 2 * (size_t)n)); h->zout = reinterpret_cast<double2*>(q);
-    }
-    FOS_HIP(hipStreamSynchronize(h->stream));
-    s.kind = 3;
-    return FOS_OK;
+    ProxObject* s = nullptr;
+    FOS_TRY(cone_product_setup(feas_env(h), table, &s));
+    return feas_install(h, which, s);
 }
 
 int fos_feas_set_callback(fos_feas_handle h, int32_t which, fos_prox_fn fn, void* ctx) {
     if (!h || (which != 1 && which != 2) || !fn) { set_error("fos_feas_set_callback: NULL handle / callback or which not in {1, 2}"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
-    FeasSet& s = h->S[which - 1];
-    if (!s.cb_x) {
-        void *px = nullptr, *py = nullptr;
-        if (hipHostMalloc(&px, sizeof(double) * std::max<int64_t>(h->n, 1)) != hipSuccess || hipHostMalloc(&py, sizeof(double) * std::max<int64_t>(h->n, 1)) != hipSuccess) {
-            if (px) (void)hipHostFree(px);
-            set_error("fos_feas_set_callback: pinned host buffers of %lld doubles could not be allocated", (long long)h->n);
-            return FOS_ENOMEM;
-        }
-        s.cb_x = static_cast<double*>(px); s.cb_y = static_cast<double*>(py);
-    }
-    s.cb = fn; s.cb_ctx = ctx;
-    s.kind = 4;
-    return FOS_OK;
+    ProxObject* s = nullptr;
+    FOS_TRY(callback_setup(feas_env(h), which, fn, ctx, &s));
+    return feas_install(h, which, s);
 }
 
-// A separable sum of convex vector sets (sets.hip; Feasibility.jl:2-6): validated and built first, so that a refused call leaves the set as it was
+// A separable sum of convex vector sets (sets.hip; Feasibility.jl:2-6)
 int fos_feas_set_blocks(fos_feas_handle h, int32_t which, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec) {
     if (!h || which < 1 || which > 2) { set_error("fos_feas_set_blocks: NULL handle or which not in {1, 2}"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
-    SetBlocks* sb = nullptr;
-    FOS_TRY(set_blocks_setup(h->n, nblocks, kind, len, scal, vec, &sb));
-    FeasSet& s = h->S[which - 1];
-    FOS_HIP(hipStreamSynchronize(h->stream));                          // (a projection onto the set being replaced may still run)
-    set_blocks_destroy(s.sb);
-    s.sb = sb; s.kind = 6;
-    return FOS_OK;
+    ProxObject* s = nullptr;
+    FOS_TRY(set_blocks_setup(h->n, nblocks, kind, len, scal, vec, &s));
+    return feas_install(h, which, s);
 }
 int fos_feas_set_stats(fos_feas_handle h, int32_t which, double* out8) {
-    if (!h || !out8 || which < 1 || which > 2 || h->S[which - 1].kind != 6) { set_error("fos_feas_set_stats: set %d was not defined by fos_feas_set_blocks", (int)which); return FOS_EINVAL; }
+    const ProxObject* s = nullptr;
+    FOS_TRY(feas_object(h, which, out8, FEAS_BLOCKS, "fos_feas_set_stats", "was not defined by fos_feas_set_blocks", &s));
     FOS_HIP(hipSetDevice(h->device));
-    return set_blocks_stats(h->S[which - 1].sb, h->stream, out8);
+    return set_blocks_stats(s, h->stream, out8);
 }
 
 int fos_feas_set_alg(fos_feas_handle h, int32_t alg, double alpha, double alpha1, double alpha2, double beta) {
@@ -858,10 +661,10 @@ int fos_feas_set_longstep(fos_feas_handle h, int64_t longinterval, int64_t nsave
         }
         h->lp.P = nullptr; h->lp.bpart = nullptr; h->lp.dots = nullptr; h->lp.nu = nullptr;
         double* q = nullptr;
-        FOS_TRY(feas_alloc(h, &q, (size_t)K * h->L)); h->lp.P = reinterpret_cast<double2*>(q);
-        FOS_TRY(feas_alloc(h, &h->lp.bpart, (size_t)K * h->grid));
-        FOS_TRY(feas_alloc(h, &h->lp.dots, (size_t)h->grid * 2 * (LONG_KMAX_ROWS + 1)));
-        FOS_TRY(feas_alloc(h, &h->lp.nu, (size_t)2 * K));
+        FOS_TRY(h->zeros(&q, (size_t)K * h->L, h->stream)); h->lp.P = reinterpret_cast<double2*>(q);
+        FOS_TRY(h->zeros(&h->lp.bpart, (size_t)K * h->grid, h->stream));
+        FOS_TRY(h->zeros(&h->lp.dots, (size_t)h->grid * 2 * (LONG_KMAX_ROWS + 1), h->stream));
+        FOS_TRY(h->zeros(&h->lp.nu, (size_t)2 * K, h->stream));
     }
     h->lp.interval = longinterval; h->lp.nsave = nsave; h->lp.savepos = 0; h->lp.now = false;
     h->lp.max_supports = getenv("FOS_LONG_MAX_SUPPORTS") ? atoll(getenv("FOS_LONG_MAX_SUPPORTS")) : 4096;
@@ -885,14 +688,14 @@ int fos_feas_set_iterate(fos_feas_handle h, const double* x0) {
     if (!h) { set_error("NULL handle"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
     const size_t bytes = sizeof(double) * (size_t)h->L;
-    for (double* v : {h->x, h->t1, h->t2, h->y, h->xold, h->p, h->q, h->tmp, h->px}) FOS_HIP(hipMemsetAsync(v, 0, bytes, h->stream));
+    for (double* v : {h->x, h->t1, h->t2, h->y, h->xold, h->p, h->q, h->tmp}) FOS_HIP(hipMemsetAsync(v, 0, bytes, h->stream));
     if (x0) FOS_HIP(hipMemcpyAsync(h->x, x0, sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, h->stream));
     FEAS_K(feas_fill_kernel, h->n, h->prev, (double)NAN);
     const double two = 2.0;
     FOS_HIP(hipMemcpyAsync(h->a12, &two, sizeof(double), hipMemcpyHostToDevice, h->stream));
     FOS_HIP(hipStreamSynchronize(h->stream));
     h->fista_t = 1.0; h->status = FOS_STATUS_CONTINUE; h->checked = 0; h->err = NAN;
-    for (FeasSet& s : h->S) { if (s.cones) s.cones->start_cold(); sparse_affine_reset(s.sa, h->stream); }        // a new solve starts its PSD projections cold, the sparse IndAffine's multipliers at zero
+    for (auto& s : h->S) if (s) s->reset(h->stream);       // a new solve starts its PSD projections cold, the sparse IndAffine's multipliers at zero
     return feas_check_launch("fos_feas_set_iterate");
 }
 
@@ -955,8 +758,11 @@ int fos_feas_info(fos_feas_handle h, double* alpha12, int32_t* ns_iters, double*
     FOS_HIP(hipSetDevice(h->device));
     if (alpha12) { FOS_HIP(hipMemcpyAsync(alpha12, h->a12, sizeof(double), hipMemcpyDeviceToHost, h->stream)); FOS_HIP(hipStreamSynchronize(h->stream)); }
     for (int k = 0; k < 2; ++k) {
-        if (ns_iters) ns_iters[k] = h->S[k].ns_iters;
-        if (ns_resid) ns_resid[k] = h->S[k].ns_resid;
+        int32_t it = 0;
+        double res = 0.0;
+        dense_projector_stats(h->S[k].get(), &it, &res);
+        if (ns_iters) ns_iters[k] = it;
+        if (ns_resid) ns_resid[k] = res;
     }
     return FOS_OK;
 }

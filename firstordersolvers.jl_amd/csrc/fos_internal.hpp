@@ -735,8 +735,81 @@ void cone_set_project_vector(ConeSet* cs, const LaunchCtx& c, double2* out, cons
 int cone_set_project_psd(ConeSet* cs, const LaunchCtx& c, double2* out, const double2* in, const PsdFuse* fuse = nullptr);
 bool cone_set_can_fuse(const ConeSet& cs, const LaunchCtx& c);      // psd.hip: the next projection would take the refinement kernel
 int launch_cones_psd(const LaunchCtx& c, ConeSet& cs, double2* out, const double2* in, const PsdFuse* fuse);
+// ---- the sets of the Feasibility form (feas.hip).  A set is a device object with prox!(y, S, x); the handle owns one per slot and knows nothing else about it.
+// A new kind is one file with a set-up function (build, hand back a ProxObject*) and a prox override, plus an ABI entry: validate, build, feas_install.
+enum FeasKind : int {
+    FEAS_AFFINE_DENSE = 1,           // IndAffine, the dense n x n projector (feas_objects.hip)
+    FEAS_BOX = 2,                    // IndBox, scalar or array bounds (feas_objects.hip)
+    FEAS_CONES = 3,                  // ConeProduct around a ConeSet (feas_objects.hip)
+    FEAS_CALLBACK = 4,               // the caller's prox! on host vectors (feas_objects.hip)
+    FEAS_AFFINE_SPARSE = 5,          // IndAffine over a sparse A, CG (affine_sparse.hip)
+    FEAS_BLOCKS = 6,                 // separable sum of vector sets and functions (sets.hip)
+    FEAS_AFFINE_FACTORED = 7,        // IndAffine / LeastSquares over a dense A, factored (affine_dense.hip)
+    FEAS_SPARSE_FACTORED = 8,        // IndAffine / LeastSquares over a sparse A, factored (affine_sparse_factored.hip)
+    FEAS_NSPACE = 9,                 // Quadratic / LeastSquares in the n-space (nspace.hip)
+};
+struct ProxObject {
+    explicit ProxObject(int k) : kind(k) {}
+    ProxObject(const ProxObject&) = delete;
+    ProxObject& operator=(const ProxObject&) = delete;
+    virtual ~ProxObject() = default;                                       // frees what the object owns; the caller has synchronised the stream its prox ran on
+    virtual int prox(hipStream_t stream, double* y, const double* x) = 0;  // y, x: device vectors of length n (zero padded to a multiple of 64), y must not alias x
+    virtual void reset(hipStream_t) {}                                     // a new solve (fos_feas_set_iterate): cold PSD bases, zero multipliers
+    const int kind;                                                        // FeasKind: the ABI accessors check it before they downcast
+};
+// The device memory an object owns, with the three helpers every set-up needs.  `what` names the caller in the messages.
+struct DevOwned {
+    std::vector<void*> owned;
+    size_t bytes = 0;
+    const char* what = "";
+    DevOwned() = default;
+    DevOwned(const DevOwned&) = delete;
+    DevOwned& operator=(const DevOwned&) = delete;
+    ~DevOwned() { for (void* q : owned) (void)hipFree(q); }
+    // FOS_OK, or FOS_ENOMEM / FOS_EHIP with "<what> set-up: <call> -> <error>"
+    int hip(const char* call, hipError_t e) const {
+        if (e != hipSuccess) { set_error("%s set-up: %s -> %s", what, call, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? FOS_ENOMEM : FOS_EHIP; }
+        return FOS_OK;
+    }
+    template <class T> int alloc(T** out, size_t count) {
+        void* q = nullptr;
+        const size_t nb = sizeof(T) * std::max<size_t>(count, 1);
+        const hipError_t e = hipMalloc(&q, nb);
+        if (e != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipMalloc of %zu bytes failed: %s", what, nb, hipGetErrorString(e)); return FOS_ENOMEM; }
+        owned.push_back(q); bytes += nb;
+        *out = static_cast<T*>(q);
+        return FOS_OK;
+    }
+    // stream == nullptr: the blocking calls (a set-up without a stream of its own)
+    template <class T> int zeros(T** out, size_t count, hipStream_t s) {
+        FOS_TRY(alloc(out, count));
+        const size_t nb = sizeof(T) * std::max<size_t>(count, 1);
+        return hip("hipMemset", s ? hipMemsetAsync(*out, 0, nb, s) : hipMemset(*out, 0, nb));
+    }
+    template <class T> int upload(T** out, const T* src, size_t count, hipStream_t s) {
+        FOS_TRY(alloc(out, count));
+        if (count == 0) return FOS_OK;
+        return hip("hipMemcpy", s ? hipMemcpyAsync(*out, src, sizeof(T) * count, hipMemcpyHostToDevice, s) : hipMemcpy(*out, src, sizeof(T) * count, hipMemcpyHostToDevice));
+    }
+    template <class T> int upload(T** out, const std::vector<T>& v, hipStream_t s) { return upload(out, v.data(), v.size(), s); }
+};
+// inside a set-up that defines fail(code) (release the half-built object, hand the code back): a HIP call of owner `a`
+#define DEV_HIP(a, expr) do { const int _r = (a)->hip(#expr, (expr)); if (_r != FOS_OK) return fail(_r); } while (0)
+
+// the element-wise kernels of feas.hip and feas_objects.hip: FEAS_THREADS threads, a grid-stride loop
+constexpr int FEAS_THREADS = 256;
+#define FEAS_STRIDE(i, n) for (int64_t i = blockIdx.x * (int64_t)FEAS_THREADS + threadIdx.x; i < (n); i += (int64_t)gridDim.x * FEAS_THREADS)
+// what a set-up in feas_objects.hip takes from the handle
+struct FeasEnv { hipStream_t stream; int64_t n, L; int grid, cus; double* partials; };
+// feas_objects.hip: the dense projector (A: m x n ROW-major), the box (lov == nullptr: the scalars), the ConeProduct, the host callback (which: 1 | 2, for its message)
+int dense_projector_setup(const FeasEnv& env, int64_t m, const double* A, const double* b, ProxObject** out);
+void dense_projector_stats(const ProxObject* p, int32_t* ns_iters, double* ns_resid);      // 0, 0 when p is no dense projector
+int box_setup(const FeasEnv& env, double lo, double hi, const double* lov, const double* hiv, ProxObject** out);
+int cone_product_setup(const FeasEnv& env, const ConeTable& table, ProxObject** out);
+int callback_setup(const FeasEnv& env, int which, fos_prox_fn fn, void* ctx, ProxObject** out);
+
+// The stats / plan functions below take the object the set-up of the same file built (the caller checked `kind`).
 // IndAffine(A, b) with a sparse A (affine_sparse.hip): exact projection by warm-started CG on the row-scaled normal equations, the true residual re-checked
-struct SparseAffine;
 struct SparseRows {                              // host: what sparse_affine_rows leaves -- the scaled A (rp / ci / va) and A' (trp / tci / tva) in CSR, the scaled b
     int64_t m = 0, n = 0, nnz = 0;
     std::vector<int32_t> rp, ci, trp, tci;
@@ -746,18 +819,12 @@ struct SparseRows {                              // host: what sparse_affine_row
 // zero_rows: a zero row is accepted and keeps scale 1 (the sparse LeastSquares); otherwise it is FOS_EINVAL
 int sparse_affine_rows(const char* what, int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, SparseRows* out,
                        bool zero_rows = false);
-int sparse_affine_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int cus, SparseAffine** out);
-int sparse_affine_project(SparseAffine* a, hipStream_t stream, double* y, const double* x);      // y, x: device vectors of length n, y must not alias x
-void sparse_affine_reset(SparseAffine* a, hipStream_t stream);                                   // a new solve: lambda = 0
-void sparse_affine_stats(const SparseAffine* a, double* out8);
-void sparse_affine_destroy(SparseAffine* a);
+int sparse_affine_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int cus, ProxObject** out);
+void sparse_affine_stats(const ProxObject* a, double* out8);
 // IndAffine(A, b) with a dense A, factored form (affine_dense.hip): A kept once, (A A')^-1 of order m, two passes over A per projection
-struct DenseAffine;
-int dense_affine_setup(int64_t m, int64_t n, const double* A, const double* b, double lambda, int factor, int refine, int cus, hipStream_t stream, DenseAffine** out);
-int dense_affine_project(DenseAffine* a, hipStream_t stream, double* y, const double* x);        // y, x: device vectors of length n, y must not alias x
-void dense_affine_stats(const DenseAffine* a, double* out8);
-void dense_affine_plan(const DenseAffine* a, int64_t* out6);
-void dense_affine_destroy(DenseAffine* a);
+int dense_affine_setup(int64_t m, int64_t n, const double* A, const double* b, double lambda, int factor, int refine, int cus, hipStream_t stream, ProxObject** out);
+void dense_affine_stats(const ProxObject* a, double* out8);
+void dense_affine_plan(const ProxObject* a, int64_t* out6);
 int host_affine_factored(int64_t m, int64_t n, const double* A, const double* b, double lambda, int refine, const double* x, double* y);
 // the m-space product of the factored forms (da_symv_kernel): out = add + sign M v, M symmetric column-major of order l, leading dimension ld (add == nullptr: 0;
 // out may be add); the same on the host in the kernel's order, the host's wave_sum tree, and the host's accepted inverse of G (order m, unpadded; `what` in the message)
@@ -765,29 +832,26 @@ void launch_da_symv(hipStream_t s, int64_t l, int64_t ld, const double* M, const
 void host_da_symv(int64_t l, int64_t ld, const double* M, const double* v, const double* add, double sign, double* out);
 double host_da_wave(const double* lane64);
 int host_da_inverse(const char* what, int64_t m, const double* G, double* X);
+// the m-space step of a factored projection, d = X r corrected once: d = X r; e = r - G d; d += X e (X, G of order m, leading dimension L); its host twin (L = m)
+void mspace_correct(hipStream_t s, int64_t m, int64_t L, const double* X, const double* G, const double* r, double* d, double* e);
+void host_mspace_correct(int64_t m, const double* X, const double* G, const double* r, double* d, double* e);
 // IndAffine(A, b) with a sparse A, factored form (affine_sparse_factored.hip): A and A' kept as CSR, (A A')^-1 of order m dense, two segmented sparse passes per projection
-struct SparseFactored;
 // lambda: 0: IndAffine(A, b), > 0: LeastSquares(A, b, lambda) (refine is then 0, zero and dependent rows are accepted)
 int sparse_factored_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int factor,
-                          int refine, hipStream_t stream, SparseFactored** out);
+                          int refine, hipStream_t stream, ProxObject** out);
 void launch_sf_gram(hipStream_t stream, int64_t m, int64_t L, const int32_t* rp, const int32_t* ci, const double* va, const int32_t* trp, const int32_t* tci,
                     const double* tva, double* G);
-int sparse_factored_project(SparseFactored* a, hipStream_t stream, double* y, const double* x);  // y, x: device vectors of length n, y must not alias x
-void sparse_factored_stats(const SparseFactored* a, double* out8);
-void sparse_factored_plan(const SparseFactored* a, int64_t* out8);
-void sparse_factored_destroy(SparseFactored* a);
+void sparse_factored_stats(const ProxObject* a, double* out8);
+void sparse_factored_plan(const ProxObject* a, int64_t* out8);
 int host_affine_sparse_factored(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int refine,
                                 const double* x, double* y);
 // Quadratic(Q, q) and LeastSquares in the normal-equations form (nspace.hip): y = M^-1 (x + c), M and its inverse kept as packed lower-triangle tile streams,
 // three one-right-hand-side tile products per prox
-struct NSpace;
-int nspace_setup_quadratic(int64_t n, const double* Q, const double* q, int factor, hipStream_t stream, NSpace** out);
-int nspace_setup_ls_dense(int64_t m, int64_t n, const double* A, const double* b, double lambda, int factor, hipStream_t stream, NSpace** out);
+int nspace_setup_quadratic(int64_t n, const double* Q, const double* q, int factor, hipStream_t stream, ProxObject** out);
+int nspace_setup_ls_dense(int64_t m, int64_t n, const double* A, const double* b, double lambda, int factor, hipStream_t stream, ProxObject** out);
 int nspace_setup_ls_sparse(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int factor,
-                           hipStream_t stream, NSpace** out);
-int nspace_prox(NSpace* a, hipStream_t stream, double* y, const double* x);                       // y, x: device vectors of at least n doubles
-void nspace_stats(const NSpace* a, double* out8);
-void nspace_destroy(NSpace* a);
+                           hipStream_t stream, ProxObject** out);
+void nspace_stats(const ProxObject* a, double* out8);
 int nspace_bench_symv(int64_t k, int reps, hipStream_t stream, double* out4);
 void host_nspace_symv(const RedPlan& P, const std::vector<double>& tiles, const double* v, double* y);
 int host_nspace_quadratic(int64_t n, const double* Q, const double* q, const double* x, double* y);
@@ -796,11 +860,8 @@ int host_nspace_ls_sparse(int64_t m, int64_t n, const int64_t* colptr, const int
                           double* y);
 int host_nspace_symv_packed(int64_t k, const double* X, const double* v, double* y, int32_t* count);
 // Separable sums of convex vector sets (sets.hip): norm balls, simplex, halfspace / hyperslab, point, free, scalar box -- contiguous blocks covering 1..n
-struct SetBlocks;
-int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec, SetBlocks** out);
-int set_blocks_project(SetBlocks* p, hipStream_t stream, double* y, const double* x);           // y, x: device vectors of length n, y must not alias x
-int set_blocks_stats(SetBlocks* p, hipStream_t stream, double* out8);
-void set_blocks_destroy(SetBlocks* p);
+int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec, ProxObject** out);
+int set_blocks_stats(const ProxObject* p, hipStream_t stream, double* out8);
 size_t psd_scratch_bytes(int kmax, int ncones);
 size_t psd_basis_doubles(int kmax, int ncones);
 

@@ -302,6 +302,9 @@ struct DenseOpts {
 };
 int dense_spd_inverse(const DenseWork& k, const DenseOpts& o, double** Xout, DenseInv* st);
 void direct_test_vector(int64_t k, int which, std::vector<double>& v);      // the four fixed vectors of the probe (which = 0: also the power iteration's start)
+// affine_dense.hip: X = G^-1 for the factored forms (G of order m, L x L with the identity on its padding; X: L x L, the caller's) through dense_spd_inverse at `bar`,
+// its work-set from a scratch of its own; own.what names the caller; lambda == 0 (IndAffine): a refusal names the full row rank A needs.  Synchronises `stream`.
+int factored_inverse(const DevOwned& own, double lambda, int factor, double bar, hipStream_t stream, int64_t m, int64_t L, double* G, double* Xout, DenseInv* inv);
 
 // (Owner: the handle, or a state with its own `owned` list -- ConeSet)
 template <class Owner, class T>

@@ -214,10 +214,6 @@ __global__ __launch_bounds__(NS_T) void ns_ct_kernel(int64_t L, const double* __
     for (int64_t i = blockIdx.x * (int64_t)NS_T + threadIdx.x; i < L; i += (int64_t)gridDim.x * NS_T) ct[i] = D[i] * c[i];
 }
 
-int ns_hip(const char* what, const char* call, hipError_t e) {
-    if (e != hipSuccess) { set_error("%s set-up: %s -> %s", what, call, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? FOS_ENOMEM : FOS_EHIP; }
-    return FOS_OK;
-}
 int ns_check_common(const char* what, int64_t n, int factor) {
     if (n < 1) { set_error("%s: n >= 1 is required", what); return FOS_EINVAL; }
     if (n > NS_MAX_N) { set_error("%s: the inverse of the n-space matrix has order n = %lld: supported up to n = %lld (beyond that: a host prox through fos_feas_set_callback)", what, (long long)n, (long long)NS_MAX_N); return FOS_EUNSUPPORTED; }
@@ -276,36 +272,19 @@ int ns_sparse_rows(int64_t m, int64_t n, const int64_t* colptr, const int64_t* r
 
 }  // namespace
 
-struct NSpace {
+struct NSpace : ProxObject, DevOwned {
+    NSpace() : ProxObject(FEAS_NSPACE) {}
+    int prox(hipStream_t stream, double* y, const double* x) override;
     int64_t n = 0, m = 0, L = 0;              // m = 0: Quadratic
-    const char* what = "";
     RedPlan plan;
     RedDev rM{}, rK{};                        // the two tile streams over one plan, one set of slots
     RedUnit* units = nullptr; int32_t* strip_u0 = nullptr;
     double *tilesM = nullptr, *tilesK = nullptr, *rowslot = nullptr, *colslot = nullptr;
     double *D = nullptr, *ct = nullptr, *z = nullptr, *r = nullptr;     // L-vectors, zero on the padding
-    std::vector<void*> owned;
     DenseInv inv;
-    size_t bytes = 0;
 };
 
-void nspace_destroy(NSpace* a) {
-    if (!a) return;
-    for (void* q : a->owned) (void)hipFree(q);
-    delete a;
-}
-
 namespace {
-template <class T>
-int ns_alloc(NSpace* a, T** out, size_t count) {
-    void* q = nullptr;
-    const size_t bytes = sizeof(T) * std::max<size_t>(count, 1);
-    const hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipMalloc of %zu bytes failed: %s", a->what, bytes, hipGetErrorString(e)); return FOS_ENOMEM; }
-    a->owned.push_back(q); a->bytes += bytes;
-    *out = static_cast<T*>(q);
-    return FOS_OK;
-}
 int ns_grid(int64_t count) { return (int)std::max<int64_t>(1, std::min<int64_t>((count + NS_T - 1) / NS_T, 4096)); }
 
 // what the three set-ups share.  `form` leaves S (the lower triangle of Q, or of A'A: quad says which) readable until this returns and c (L doubles, zero on
@@ -315,21 +294,19 @@ int ns_build(NSpace* a, int factor, hipStream_t stream, const char* gname, Dense
     const int64_t n = a->n, L = a->L;
     const size_t L2 = (size_t)L * (size_t)L;
     const char* what = a->what;
-#define NS_HIP(expr) FOS_TRY(ns_hip(what, #expr, (expr)))
     hipLaunchKernelGGL(ns_diag_kernel, dim3(ns_grid(L)), dim3(NS_T), 0, stream, n, L, src.quad, src.S, src.lambda, a->D);
     hipLaunchKernelGGL(ns_scale_kernel, dim3(ns_grid((int64_t)L2)), dim3(NS_T), 0, stream, n, L, src.quad, src.S, src.lambda, (const double*)a->D, w.G);
     hipLaunchKernelGGL(ns_ct_kernel, dim3(ns_grid(L)), dim3(NS_T), 0, stream, L, (const double*)a->D, (const double*)a->r, a->ct);
-    NS_HIP(hipMemcpyAsync(a->units, a->plan.units.data(), sizeof(RedUnit) * a->plan.units.size(), hipMemcpyHostToDevice, stream));
-    NS_HIP(hipMemcpyAsync(a->strip_u0, a->plan.strip_u0.data(), sizeof(int32_t) * a->plan.strip_u0.size(), hipMemcpyHostToDevice, stream));
+    FOS_TRY(a->hip("hipMemcpyAsync", hipMemcpyAsync(a->units, a->plan.units.data(), sizeof(RedUnit) * a->plan.units.size(), hipMemcpyHostToDevice, stream)));
+    FOS_TRY(a->hip("hipMemcpyAsync", hipMemcpyAsync(a->strip_u0, a->plan.strip_u0.data(), sizeof(int32_t) * a->plan.strip_u0.size(), hipMemcpyHostToDevice, stream)));
     double* X = nullptr;
     DenseOpts o{what, gname, factor, false};
     o.bar = NS_BAR; o.newton_extra = 40;
     FOS_TRY(dense_spd_inverse(w, o, &X, &a->inv));
     launch_red_pack_tiles(w.c, a->rM, L, w.G);
     launch_red_pack_tiles(w.c, a->rK, L, X);
-    NS_HIP(hipMemsetAsync(a->r, 0, sizeof(double) * (size_t)L, stream));
-    NS_HIP(hipStreamSynchronize(stream));
-#undef NS_HIP
+    FOS_TRY(a->hip("hipMemsetAsync", hipMemsetAsync(a->r, 0, sizeof(double) * (size_t)L, stream)));
+    FOS_TRY(a->hip("hipStreamSynchronize", hipStreamSynchronize(stream)));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("%s set-up: a kernel launch failed: %s", what, hipGetErrorString(e)); return FOS_EHIP; }
     return FOS_OK;
@@ -340,15 +317,14 @@ int ns_prepare(NSpace* a, int64_t n, int64_t m, const char* what, hipStream_t st
     build_reduced_plan(n, &a->plan);
     const RedPlan& P = a->plan;
     const size_t L = (size_t)a->L, L2 = L * L;
-    FOS_TRY(ns_alloc(a, &a->units, P.units.size()));
-    FOS_TRY(ns_alloc(a, &a->strip_u0, P.strip_u0.size()));
-    FOS_TRY(ns_alloc(a, &a->tilesM, (size_t)P.ntiles * RED_TILE));
-    FOS_TRY(ns_alloc(a, &a->tilesK, (size_t)P.ntiles * RED_TILE));
-    FOS_TRY(ns_alloc(a, &a->rowslot, (size_t)P.ntiles * 64));
-    FOS_TRY(ns_alloc(a, &a->colslot, P.units.size() * RED_TC));
+    FOS_TRY(a->alloc(&a->units, P.units.size()));
+    FOS_TRY(a->alloc(&a->strip_u0, P.strip_u0.size()));
+    FOS_TRY(a->alloc(&a->tilesM, (size_t)P.ntiles * RED_TILE));
+    FOS_TRY(a->alloc(&a->tilesK, (size_t)P.ntiles * RED_TILE));
+    FOS_TRY(a->alloc(&a->rowslot, (size_t)P.ntiles * 64));
+    FOS_TRY(a->alloc(&a->colslot, P.units.size() * RED_TC));
     for (double** v : {&a->D, &a->ct, &a->z, &a->r}) {
-        FOS_TRY(ns_alloc(a, v, L));
-        FOS_TRY(ns_hip(what, "hipMemsetAsync", hipMemsetAsync(*v, 0, sizeof(double) * L, stream)));
+        FOS_TRY(a->zeros(v, L, stream));
     }
     RedDev R{};
     R.k = n; R.kpad = a->L; R.nt = P.nt; R.nunits = (int)P.units.size(); R.units = a->units; R.strip_u0 = a->strip_u0;
@@ -363,12 +339,12 @@ int ns_prepare(NSpace* a, int64_t n, int64_t m, const char* what, hipStream_t st
 }  // namespace
 
 // Quadratic(Q, q): Q n x n (its lower triangle is read: Q[i * n + j], i >= j), q[n].  Synchronises `stream`.
-int nspace_setup_quadratic(int64_t n, const double* Q, const double* q, int factor, hipStream_t stream, NSpace** out) {
+int nspace_setup_quadratic(int64_t n, const double* Q, const double* q, int factor, hipStream_t stream, ProxObject** out) {
     const char* what = "Quadratic";
     FOS_TRY(ns_check_common(what, n, factor));
     FOS_TRY(ns_check_quadratic(n, Q, q));
     NSpace* a = new NSpace();
-    auto fail = [&](int code) { (void)hipStreamSynchronize(stream); nspace_destroy(a); return code; };
+    auto fail = [&](int code) { (void)hipStreamSynchronize(stream); delete a; return code; };
     int rc = FOS_OK;
     {
         Scratch s;
@@ -378,9 +354,8 @@ int nspace_setup_quadratic(int64_t n, const double* Q, const double* q, int fact
         if (s.err != hipSuccess) { (void)hipGetLastError(); set_error("Quadratic: hipMalloc of Q (%zu bytes) failed: %s", (size_t)n * (size_t)n * 8, hipGetErrorString(s.err)); return fail(FOS_ENOMEM); }
         std::vector<double> c((size_t)n);
         for (int64_t i = 0; i < n; ++i) c[(size_t)i] = -q[i];
-        if ((rc = ns_hip(what, "hipMemcpyAsync", hipMemcpyAsync(dQ, Q, sizeof(double) * (size_t)n * (size_t)n, hipMemcpyHostToDevice, stream))) != FOS_OK ||
-            (rc = ns_hip(what, "hipMemcpyAsync", hipMemcpyAsync(a->r, c.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, stream))) != FOS_OK)
-            return fail(rc);
+        DEV_HIP(a, hipMemcpyAsync(dQ, Q, sizeof(double) * (size_t)n * (size_t)n, hipMemcpyHostToDevice, stream));
+        DEV_HIP(a, hipMemcpyAsync(a->r, c.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, stream));
         if ((rc = ns_build(a, factor, stream, "I + Q", w, NsSource{1, dQ, 1.0})) != FOS_OK) return fail(rc);
     }
     *out = a;
@@ -388,7 +363,7 @@ int nspace_setup_quadratic(int64_t n, const double* Q, const double* q, int fact
 }
 
 // LeastSquares(A, b, lambda), normal-equations form, A dense m x n ROW-major, any m >= 1.  Synchronises `stream`.
-int nspace_setup_ls_dense(int64_t m, int64_t n, const double* A, const double* b, double lambda, int factor, hipStream_t stream, NSpace** out) {
+int nspace_setup_ls_dense(int64_t m, int64_t n, const double* A, const double* b, double lambda, int factor, hipStream_t stream, ProxObject** out) {
     const char* what = "LeastSquares (normal)";
     FOS_TRY(ns_check_lambda(lambda));
     FOS_TRY(ns_check_common(what, n, factor));
@@ -396,7 +371,7 @@ int nspace_setup_ls_dense(int64_t m, int64_t n, const double* A, const double* b
     if (!ns_finite(A, m * n)) { set_error("%s: A has non-finite entries", what); return FOS_EINVAL; }
     if (!ns_finite(b, m)) { set_error("%s: b has non-finite entries", what); return FOS_EINVAL; }
     NSpace* a = new NSpace();
-    auto fail = [&](int code) { (void)hipStreamSynchronize(stream); nspace_destroy(a); return code; };
+    auto fail = [&](int code) { (void)hipStreamSynchronize(stream); delete a; return code; };
     int rc = FOS_OK;
     {
         Scratch s;
@@ -407,10 +382,9 @@ int nspace_setup_ls_dense(int64_t m, int64_t n, const double* A, const double* b
         double* dAt = s.alloc<double>((size_t)n * (size_t)ld);
         double* db = s.alloc<double>((size_t)m);
         if (s.err != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipMalloc of A and A' (%zu bytes) failed: %s", what, ((size_t)m * n + (size_t)n * ld) * 8, hipGetErrorString(s.err)); return fail(FOS_ENOMEM); }
-        if ((rc = ns_hip(what, "hipMemcpyAsync", hipMemcpyAsync(dA, A, sizeof(double) * (size_t)m * (size_t)n, hipMemcpyHostToDevice, stream))) != FOS_OK ||
-            (rc = ns_hip(what, "hipMemcpyAsync", hipMemcpyAsync(db, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream))) != FOS_OK ||
-            (rc = ns_hip(what, "hipMemsetAsync", hipMemsetAsync(dAt, 0, sizeof(double) * (size_t)n * (size_t)ld, stream))) != FOS_OK)
-            return fail(rc);
+        DEV_HIP(a, hipMemcpyAsync(dA, A, sizeof(double) * (size_t)m * (size_t)n, hipMemcpyHostToDevice, stream));
+        DEV_HIP(a, hipMemcpyAsync(db, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
+        DEV_HIP(a, hipMemsetAsync(dAt, 0, sizeof(double) * (size_t)n * (size_t)ld, stream));
         const int64_t nblk = ((m + 31) / 32) * ((n + 31) / 32);
         hipLaunchKernelGGL(ns_transpose_kernel, dim3((unsigned)std::min<int64_t>(nblk, 65536)), dim3(NS_T), 0, stream, m, n, ld, (const double*)dA, dAt);
         hipLaunchKernelGGL(ns_rowdot_kernel, dim3((unsigned)std::min<int64_t>((n + 3) / 4, 4096)), dim3(NS_T), 0, stream, n, m, ld, (const double*)dAt, (const double*)db, lambda, a->r);
@@ -423,14 +397,14 @@ int nspace_setup_ls_dense(int64_t m, int64_t n, const double* A, const double* b
 
 // the same with a sparse A (CSC, 1-based, strictly ascending row indices per column).  Synchronises `stream`.
 int nspace_setup_ls_sparse(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int factor,
-                           hipStream_t stream, NSpace** out) {
+                           hipStream_t stream, ProxObject** out) {
     const char* what = "LeastSquares (sparse, normal)";
     FOS_TRY(ns_check_lambda(lambda));
     FOS_TRY(ns_check_common(what, n, factor));
     NsSparse S;
     FOS_TRY(ns_sparse_rows(m, n, colptr, rowval, nzval, b, &S));
     NSpace* a = new NSpace();
-    auto fail = [&](int code) { (void)hipStreamSynchronize(stream); nspace_destroy(a); return code; };
+    auto fail = [&](int code) { (void)hipStreamSynchronize(stream); delete a; return code; };
     int rc = FOS_OK;
     {
         Scratch s;
@@ -440,12 +414,11 @@ int nspace_setup_ls_sparse(int64_t m, int64_t n, const int64_t* colptr, const in
         int32_t *dcp = s.alloc<int32_t>((size_t)n + 1), *dri = s.alloc<int32_t>(ne), *drp = s.alloc<int32_t>((size_t)m + 1), *dci = s.alloc<int32_t>(ne);
         double *dva = s.alloc<double>(ne), *drv = s.alloc<double>(ne), *db = s.alloc<double>((size_t)m);
         if (s.err != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipMalloc of the sparse set-up buffers failed: %s", what, hipGetErrorString(s.err)); return fail(FOS_ENOMEM); }
-#define NS_UP(dst, vec) if (!(vec).empty() && (rc = ns_hip(what, "hipMemcpyAsync", hipMemcpyAsync(dst, (vec).data(), sizeof((vec)[0]) * (vec).size(), hipMemcpyHostToDevice, stream))) != FOS_OK) return fail(rc)
+#define NS_UP(dst, vec) if (!(vec).empty()) DEV_HIP(a, hipMemcpyAsync(dst, (vec).data(), sizeof((vec)[0]) * (vec).size(), hipMemcpyHostToDevice, stream))
         NS_UP(dcp, S.cp); NS_UP(dri, S.ri); NS_UP(dva, S.va); NS_UP(drp, S.rp); NS_UP(dci, S.ci); NS_UP(drv, S.rv);
 #undef NS_UP
-        if ((rc = ns_hip(what, "hipMemcpyAsync", hipMemcpyAsync(db, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream))) != FOS_OK ||
-            (rc = ns_hip(what, "hipMemsetAsync", hipMemsetAsync(w.B0, 0, sizeof(double) * (size_t)a->L * (size_t)a->L, stream))) != FOS_OK)
-            return fail(rc);
+        DEV_HIP(a, hipMemcpyAsync(db, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
+        DEV_HIP(a, hipMemsetAsync(w.B0, 0, sizeof(double) * (size_t)a->L * (size_t)a->L, stream));
         hipLaunchKernelGGL(ns_rowdot_csr_kernel, dim3((unsigned)std::min<int64_t>((n + 3) / 4, 4096)), dim3(NS_T), 0, stream, n, (const int32_t*)dcp, (const int32_t*)dri,
                            (const double*)dva, (const double*)db, lambda, a->r);
         launch_sf_gram(stream, n, a->L, dcp, dri, dva, drp, dci, drv, w.B0);       // A'A = B B', B = A': its CSR is A's CSC, the CSR of B' is A's
@@ -465,7 +438,8 @@ void ns_product(const NSpace* a, hipStream_t s, const double* tiles, const NsVec
 }  // namespace
 
 // y = prox_f(x) (device vectors of at least n doubles), on `stream`: NS_LAUNCHES launches, nothing else
-int nspace_prox(NSpace* a, hipStream_t stream, double* y, const double* x) {
+int NSpace::prox(hipStream_t stream, double* y, const double* x) {
+    const NSpace* a = this;
     const NsVec w{x, a->D, a->ct, a->n};
     ns_product(a, stream, a->tilesK, w, 0, w, a->z);                                       // z = K w
     ns_product(a, stream, a->tilesM, NsVec{a->z, nullptr, nullptr, a->L}, 1, w, a->r);     // r = w - Mt z
@@ -476,7 +450,8 @@ int nspace_prox(NSpace* a, hipStream_t stream, double* y, const double* x) {
 }
 
 // out8 = n, m (0: Quadratic), factor that produced the accepted inverse, fell_back, probe residual, kernel launches per prox, bytes kept, tiles of one stream
-void nspace_stats(const NSpace* a, double* out8) {
+void nspace_stats(const ProxObject* obj, double* out8) {
+    const NSpace* a = static_cast<const NSpace*>(obj);
     out8[0] = (double)a->n; out8[1] = (double)a->m; out8[2] = (double)a->inv.used; out8[3] = a->inv.fell_back ? 1.0 : 0.0; out8[4] = a->inv.probe;
     out8[5] = (double)NS_LAUNCHES; out8[6] = (double)a->bytes; out8[7] = (double)a->plan.ntiles;
 }
@@ -511,23 +486,23 @@ int nspace_bench_symv(int64_t k, int reps, hipStream_t stream, double* out4) {
     const size_t L = (size_t)a->L;
     int rc = FOS_OK;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    auto done = [&](int code) { (void)hipStreamSynchronize(stream); for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); nspace_destroy(a); return code; };
+    auto done = [&](int code) { (void)hipStreamSynchronize(stream); for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); delete a; return code; };
     double *X = nullptr, *v = nullptr, *col2 = nullptr, *dd = nullptr;
     double2 *pq = nullptr, *y2 = nullptr, *row2 = nullptr;
-    if ((rc = ns_alloc(a, &a->units, P.units.size())) != FOS_OK || (rc = ns_alloc(a, &a->strip_u0, P.strip_u0.size())) != FOS_OK ||
-        (rc = ns_alloc(a, &a->tilesK, (size_t)P.ntiles * RED_TILE)) != FOS_OK || (rc = ns_alloc(a, &a->rowslot, (size_t)P.ntiles * 64)) != FOS_OK ||
-        (rc = ns_alloc(a, &a->colslot, P.units.size() * RED_TC)) != FOS_OK || (rc = ns_alloc(a, &a->z, L)) != FOS_OK ||
-        (rc = ns_alloc(a, &X, L * L)) != FOS_OK || (rc = ns_alloc(a, &v, L)) != FOS_OK || (rc = ns_alloc(a, &pq, L)) != FOS_OK || (rc = ns_alloc(a, &y2, L)) != FOS_OK ||
-        (rc = ns_alloc(a, &row2, (size_t)P.ntiles * 64)) != FOS_OK || (rc = ns_alloc(a, &col2, P.units.size() * 64)) != FOS_OK || (rc = ns_alloc(a, &dd, 1)) != FOS_OK)
+    if ((rc = a->alloc(&a->units, P.units.size())) != FOS_OK || (rc = a->alloc(&a->strip_u0, P.strip_u0.size())) != FOS_OK ||
+        (rc = a->alloc(&a->tilesK, (size_t)P.ntiles * RED_TILE)) != FOS_OK || (rc = a->alloc(&a->rowslot, (size_t)P.ntiles * 64)) != FOS_OK ||
+        (rc = a->alloc(&a->colslot, P.units.size() * RED_TC)) != FOS_OK || (rc = a->alloc(&a->z, L)) != FOS_OK ||
+        (rc = a->alloc(&X, L * L)) != FOS_OK || (rc = a->alloc(&v, L)) != FOS_OK || (rc = a->alloc(&pq, L)) != FOS_OK || (rc = a->alloc(&y2, L)) != FOS_OK ||
+        (rc = a->alloc(&row2, (size_t)P.ntiles * 64)) != FOS_OK || (rc = a->alloc(&col2, P.units.size() * 64)) != FOS_OK || (rc = a->alloc(&dd, 1)) != FOS_OK)
         return done(rc);
     RedDev R{};
     R.k = k; R.kpad = a->L; R.nt = P.nt; R.nunits = (int)P.units.size(); R.units = a->units; R.strip_u0 = a->strip_u0; R.tiles = a->tilesK;
     R.rowslot = row2; R.colslot = col2;
     a->rK = R;
-    if ((rc = ns_hip(a->what, "hipMemcpyAsync", hipMemcpyAsync(a->units, P.units.data(), sizeof(RedUnit) * P.units.size(), hipMemcpyHostToDevice, stream))) != FOS_OK ||
-        (rc = ns_hip(a->what, "hipMemcpyAsync", hipMemcpyAsync(a->strip_u0, P.strip_u0.data(), sizeof(int32_t) * P.strip_u0.size(), hipMemcpyHostToDevice, stream))) != FOS_OK)
+    if ((rc = a->hip("hipMemcpyAsync", hipMemcpyAsync(a->units, P.units.data(), sizeof(RedUnit) * P.units.size(), hipMemcpyHostToDevice, stream))) != FOS_OK ||
+        (rc = a->hip("hipMemcpyAsync", hipMemcpyAsync(a->strip_u0, P.strip_u0.data(), sizeof(int32_t) * P.strip_u0.size(), hipMemcpyHostToDevice, stream))) != FOS_OK)
         return done(rc);
-    for (hipEvent_t& e : ev) if ((rc = ns_hip(a->what, "hipEventCreate", hipEventCreate(&e))) != FOS_OK) return done(rc);
+    for (hipEvent_t& e : ev) if ((rc = a->hip("hipEventCreate", hipEventCreate(&e))) != FOS_OK) return done(rc);
     LaunchCtx c{};
     c.stream = stream; c.l = k;
     hipLaunchKernelGGL(ns_bench_fill_kernel, dim3(ns_grid((int64_t)(L * L))), dim3(NS_T), 0, stream, k, a->L, X, v, pq);
@@ -542,8 +517,8 @@ int nspace_bench_symv(int64_t k, int reps, hipStream_t stream, double* out4) {
     (void)hipEventRecord(ev[2], stream);
     hipLaunchKernelGGL(ns_bench_diff_kernel, dim3(1), dim3(NS_T), 0, stream, k, (const double*)a->z, (const double2*)y2, dd);
     double diff = 0.0;
-    if ((rc = ns_hip(a->what, "hipMemcpyAsync", hipMemcpyAsync(&diff, dd, sizeof(double), hipMemcpyDeviceToHost, stream))) != FOS_OK ||
-        (rc = ns_hip(a->what, "hipStreamSynchronize", hipStreamSynchronize(stream))) != FOS_OK)
+    if ((rc = a->hip("hipMemcpyAsync", hipMemcpyAsync(&diff, dd, sizeof(double), hipMemcpyDeviceToHost, stream))) != FOS_OK ||
+        (rc = a->hip("hipStreamSynchronize", hipStreamSynchronize(stream))) != FOS_OK)
         return done(rc);
     float ms1 = 0.f, ms2 = 0.f;
     (void)hipEventElapsedTime(&ms1, ev[0], ev[1]);

@@ -407,7 +407,9 @@ __global__ __launch_bounds__(SET_THREADS) void sets_grid_apply_kernel(SetBlock b
 }
 
 // ------------------------------------------------------------------------------------------ host side
-struct SetBlocks {
+struct SetBlocks : ProxObject, DevOwned {
+    SetBlocks() : ProxObject(FEAS_BLOCKS) { what = "fos_feas_set_blocks"; }
+    int prox(hipStream_t stream, double* y, const double* x) override;
     int64_t n = 0;
     std::vector<SetBlock> blocks;
     std::vector<int> grid_ids;                  // grid-class blocks, in order
@@ -502,11 +504,11 @@ double host_combine(const std::vector<double>& lane, int64_t T, int K, int k) {
 
 }  // namespace
 
-int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec, SetBlocks** out) {
+int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec, ProxObject** out) {
     if (!out || n < 1 || nblocks < 1 || !kind || !len || !scal) { set_error("fos_feas_set_blocks: bad argument (nblocks >= 1; kind, len and scal are required)"); return FOS_EINVAL; }
     SetBlocks* p = new SetBlocks();
     p->n = n;
-    auto fail = [&](int code) { set_blocks_destroy(p); return code; };
+    auto fail = [&](int code) { delete p; return code; };
     int64_t pos = 0;
     bool any_vec = false;
     std::vector<int32_t> wave_ids, wg_ids;
@@ -532,21 +534,14 @@ int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int6
     if (pos != n) { set_error("fos_feas_set_blocks: the %lld blocks cover %lld of the %lld entries", (long long)nblocks, (long long)pos, (long long)n); return fail(FOS_EINVAL); }
     p->nwave = (int)wave_ids.size(); p->nwg = (int)wg_ids.size();
     p->launches += (p->nwave > 0) + (p->nwg > 0);
-    auto upload = [&](auto** dst, const auto* src, size_t count) -> int {
-        using T = typename std::remove_pointer<typename std::remove_reference<decltype(*dst)>::type>::type;
-        if (count == 0) return FOS_OK;
-        if (hipMalloc((void**)dst, sizeof(T) * count) != hipSuccess) { *dst = nullptr; set_error("fos_feas_set_blocks: hipMalloc of %zu bytes failed", sizeof(T) * count); return FOS_ENOMEM; }
-        if (src) { if (hipMemcpy(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice) != hipSuccess) { set_error("fos_feas_set_blocks: upload failed"); return FOS_EHIP; } }
-        else if (hipMemset(*dst, 0, sizeof(T) * count) != hipSuccess) { set_error("fos_feas_set_blocks: hipMemset failed"); return FOS_EHIP; }
-        return FOS_OK;
-    };
-    int rc = upload(&p->d_blocks, p->blocks.data(), p->blocks.size());
-    if (rc == FOS_OK) rc = upload(&p->d_wave_ids, wave_ids.data(), wave_ids.size());
-    if (rc == FOS_OK) rc = upload(&p->d_wg_ids, wg_ids.data(), wg_ids.size());
-    if (rc == FOS_OK) rc = upload(&p->d_passes, (const int32_t*)nullptr, p->blocks.size());
-    if (rc == FOS_OK && any_vec && vec) rc = upload(&p->d_vec, vec, (size_t)n);
-    if (rc == FOS_OK && !p->grid_ids.empty()) rc = upload(&p->d_partials, (const double*)nullptr, (size_t)SET_PARTS * THR_NACC);
-    if (rc == FOS_OK && !p->grid_ids.empty()) rc = upload(&p->d_gstate, (const double*)nullptr, p->grid_ids.size() * GS_WORDS);
+    const hipStream_t sync = nullptr;                        // (this set-up has no stream: blocking copies)
+    int rc = p->upload(&p->d_blocks, p->blocks, sync);
+    if (rc == FOS_OK && p->nwave > 0) rc = p->upload(&p->d_wave_ids, wave_ids, sync);
+    if (rc == FOS_OK && p->nwg > 0) rc = p->upload(&p->d_wg_ids, wg_ids, sync);
+    if (rc == FOS_OK) rc = p->zeros(&p->d_passes, p->blocks.size(), sync);
+    if (rc == FOS_OK && any_vec && vec) rc = p->upload(&p->d_vec, vec, (size_t)n, sync);
+    if (rc == FOS_OK && !p->grid_ids.empty()) rc = p->zeros(&p->d_partials, (size_t)SET_PARTS * THR_NACC, sync);
+    if (rc == FOS_OK && !p->grid_ids.empty()) rc = p->zeros(&p->d_gstate, p->grid_ids.size() * GS_WORDS, sync);
     if (rc != FOS_OK) return fail(rc);
     if (p->wg_lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(sets_wg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SET_WG_MAX * (int)sizeof(double)) != hipSuccess) {
         set_error("fos_feas_set_blocks: %d bytes of LDS per workgroup are not available on this device", SET_WG_MAX * (int)sizeof(double));
@@ -556,15 +551,9 @@ int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int6
     return FOS_OK;
 }
 
-void set_blocks_destroy(SetBlocks* p) {
-    if (!p) return;
-    for (void* q : {(void*)p->d_blocks, (void*)p->d_wave_ids, (void*)p->d_wg_ids, (void*)p->d_passes, (void*)p->d_vec, (void*)p->d_partials, (void*)p->d_gstate})
-        if (q) (void)hipFree(q);
-    delete p;
-}
-
 // y = the projection of x onto the product (device vectors of length n, y must not alias x): p->launches launches, nothing else
-int set_blocks_project(SetBlocks* p, hipStream_t stream, double* y, const double* x) {
+int SetBlocks::prox(hipStream_t stream, double* y, const double* x) {
+    const SetBlocks* p = this;
     const double* vec = p->d_vec;
     if (p->nwave > 0)
         hipLaunchKernelGGL(sets_wave_kernel, dim3((p->nwave + 3) / 4), dim3(SET_THREADS), 0, stream, (const SetBlock*)p->d_blocks, (const int32_t*)p->d_wave_ids,
@@ -596,7 +585,8 @@ int set_blocks_project(SetBlocks* p, hipStream_t stream, double* y, const double
 
 // out8: blocks, blocks of the wavefront / workgroup / grid class, launches of one projection, threshold passes of the last projection (max over the
 // blocks), the pass cap, candidates per pass
-int set_blocks_stats(SetBlocks* p, hipStream_t stream, double* out8) {
+int set_blocks_stats(const ProxObject* obj, hipStream_t stream, double* out8) {
+    const SetBlocks* p = static_cast<const SetBlocks*>(obj);
     FOS_HIP(hipStreamSynchronize(stream));
     std::vector<int32_t> passes(p->blocks.size(), 0);
     FOS_HIP(hipMemcpy(passes.data(), p->d_passes, sizeof(int32_t) * passes.size(), hipMemcpyDeviceToHost));

@@ -1254,6 +1254,14 @@ class FeasibilitySolution:
         self.x, self.status = x, status
 
 
+def _csc_one_based(A):
+    """the arrays of a scipy CSC matrix as the sparse fos_feas_set_* entries take them (Julia's SparseMatrixCSC{Float64,Int64}: 1-based), and the int64 pointer cast"""
+    i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+    colptr = np.ascontiguousarray(A.indptr, dtype=np.int64) + 1
+    rowval = np.ascontiguousarray(A.indices, dtype=np.int64) + 1
+    return i64, colptr, rowval, np.ascontiguousarray(A.data, dtype=np.float64)
+
+
 class HipFeasibility:
     """The device handle of a Feasibility problem (fos_feas_*): both sets, the algorithm's vectors and the status state."""
 
@@ -1287,10 +1295,7 @@ class HipFeasibility:
             if S.A.shape[1] != self.n:
                 raise ValueError("LeastSquares: A has %d columns, the problem has n = %d" % (S.A.shape[1], self.n))
             if S.sparse:
-                i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-                colptr = np.ascontiguousarray(S.A.indptr, dtype=np.int64) + 1          # Julia 1-based
-                rowval = np.ascontiguousarray(S.A.indices, dtype=np.int64) + 1
-                nzval = np.ascontiguousarray(S.A.data, dtype=np.float64)
+                i64, colptr, rowval, nzval = _csc_one_based(S.A)
                 _lib.check(self._lib.fos_feas_set_least_squares_sparse(self._h, which, S.A.shape[0], i64(colptr), i64(rowval), _lib.dptr(nzval), _lib.dptr(S.b), S.lam,
                                                                        _lib.LS_FORM_CODES[S.form], direct_factor_code(S.factor)))
             else:
@@ -1305,10 +1310,7 @@ class HipFeasibility:
             if S.form == "factored":
                 _lib.check(self._lib.fos_feas_set_affine_factored(self._h, which, S.A.shape[0], _lib.dptr(S.A), _lib.dptr(S.b), direct_factor_code(S.factor), S.refine))
             elif S.sparse:
-                i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-                colptr = np.ascontiguousarray(S.A.indptr, dtype=np.int64) + 1          # Julia 1-based
-                rowval = np.ascontiguousarray(S.A.indices, dtype=np.int64) + 1
-                nzval = np.ascontiguousarray(S.A.data, dtype=np.float64)
+                i64, colptr, rowval, nzval = _csc_one_based(S.A)
                 if S.form == "sparse_factored":
                     _lib.check(self._lib.fos_feas_set_affine_sparse_factored(self._h, which, S.A.shape[0], i64(colptr), i64(rowval), _lib.dptr(nzval), _lib.dptr(S.b),
                                                                              direct_factor_code(S.factor), S.refine))
