@@ -338,7 +338,7 @@ static int blkdir_setup(fos_solver* h, const int64_t* colptr, const int64_t* row
     FOS_TRY(dev_alloc(h, &h->blk_ctx, (size_t)nblk));
     // (rows of A that the sweep does not finish itself -- rows wider than one tile chunk are slot-spread too -- need the deferred-row kernel behind the third apply)
     h->blk_skip_tail = !(getenv("FOS_BLKDIR_FULL_APPLY") && atoi(getenv("FOS_BLKDIR_FULL_APPLY")) != 0);
-    for (int32_t r : h->hostS.def_rows) if (r >= n) { h->blk_skip_tail = false; break; }
+    for (int32_t r : h->op.host.def_rows) if (r >= n) { h->blk_skip_tail = false; break; }
     FOS_HIP(hipMemset(h->blk_phg, 0, sizeof(d2) * (size_t)l));
     FOS_HIP(hipMemset(h->blk_qphg, 0, sizeof(d2) * (size_t)l));
     // ---- the border: h = [c; b], M h = [A'b; -A c], ph = D^-1 (h; 0), pg = D^-1 (M h; 0) by two runs of the device path without the border terms

@@ -1,4 +1,4 @@
-// struct fos_solver (the handle behind fos_handle) and the helpers that solver.cpp, cones.cpp, direct.cpp and transport.cpp share.  Private: not part of the ABI.
+// struct fos_solver (the handle behind fos_handle) and the helpers that solver.cpp, operator.cpp, cones.cpp, direct.cpp and transport.cpp share.  Private: not part of the ABI.
 #pragma once
 
 #include <rccl/rccl.h>
@@ -55,6 +55,30 @@ struct Transport {
     ReduceVia via() const { return peer_on ? VIA_PEER : (host_fn ? VIA_HOST : (comm ? VIA_RCCL : VIA_NONE)); }
 };
 
+// ------------------------------------------------------------------------------------------------ the stacked operator S = [A'; A] (operator.cpp)
+// Its device arrays are on the handle's `owned` and `pooled` lists like everything else.
+struct Operator {
+    fos::HostBlkCsr host;                      // kept only for re-partitioning (indices freed after upload)
+    fos::DevBlkCsr dev{};                      // what the kernels read (LaunchCtx::S)
+    int32_t* wave_blk0 = nullptr; fos::BlkDesc* wave_first = nullptr;      // dev.wave_blk0 and dev.wave_first, writable: operator_repartition
+    uint32_t* def_mask = nullptr;              // bit i: row i of S is finished from partial slots (dual tiles)
+    int64_t win_stats[4] = {0, 0, 0, 0};       // window panels: panels, (panel, window) segments, 64-row slices, stored entries
+    int nwg_target = 2048;                     // workgroups the row blocks are partitioned for
+    // row-sharded: the slots of the rows of A' summed over the ranks (what dev.slots_rd names; fos_solver::sum_slots_over_ranks fills it)
+    double* slots_rd = nullptr;
+    // row-sharded WITH dual tiles: the sweep fills local slot lists (dev.slots = slots_rd + 2n doubles); between sweep and consumers the
+    // lists of the n rows of A' are added up (cmp_rec / cmp_idx -> cmp_local) and THAT n-vector crosses the ranks into slots_rd[0..n);
+    // the consumers' records (dev.def_rec) name slot j for row j < n and the local lists, shifted by n, for the rows of A
+    fos::DefRow* cmp_rec = nullptr; int32_t* cmp_idx = nullptr; double* cmp_local = nullptr; int cmp_lpr = 1;
+    // FOS_CG_RESIDENT (resident.hip): the plan (which workgroup holds which tiles), its device copy and the workgroups' record arrays
+    fos::ResPlan res_plan;
+    fos::ResLaunch res{};
+    fos::ResWG* res_wg = nullptr;              // res.wg, writable: resident_setup replaces it
+    bool res_ok = false;                       // this handle's operator qualifies (under the current workgroup budget)
+    bool res_all = false;                      // ... and so does every rank's (sharded: the vote of global_setup)
+    int res_gmax = 0;                          // the budget the plan was made for
+};
+
 // ------------------------------------------------------------------------------------------------ the handle
 struct fos_solver {
     int device = 0;
@@ -62,10 +86,7 @@ struct fos_solver {
     int64_t m = 0, n = 0, l = 0, nnz = 0;
     int64_t l_global = 0;                      // == l unless sharded (tolerance floor uses the global size)
 
-    // operator
-    fos::HostBlkCsr hostS;                          // kept only for re-partitioning (indices freed after upload)
-    int64_t win_stats[4] = {0, 0, 0, 0};       // window panels: panels, (panel, window) segments, 64-row slices, stored entries
-    fos::DevBlkCsr S{};
+    Operator op;
     std::vector<void*> owned;                  // every hipMalloc'd pointer
     std::vector<void*> pooled;                 // blocks of the process-wide pool of uncached memory (uncached_acquire): released, never freed
     double* cb = nullptr;
@@ -100,15 +121,8 @@ struct fos_solver {
     double* reduced = nullptr;                 // 16 doubles
     int vec_blocks = 0;
     int cg_blocks = 0;
-    uint32_t* def_mask = nullptr;              // bit i: row i of S is finished from partial slots (dual tiles)
     bool fuse_p = false;                       // the p update of CG rides on the next sweep (2 launches per iteration)
     int cg_variant = -1;                       // FOS_CG_*: -1 = the handle's default (sharded: merged reduction, closing in the update)
-    // FOS_CG_RESIDENT (resident.hip): the plan (which workgroup holds which tiles), its device copy and the workgroups' record arrays
-    fos::ResPlan res_plan;
-    fos::ResLaunch res{};
-    bool res_ok = false;                       // this handle's operator qualifies (under the current workgroup budget)
-    bool res_all = false;                      // ... and so does every rank's (sharded: the vote of global_setup)
-    int res_gmax = 0;                          // the budget the plan was made for
 
     // algorithm (gap.jl:6-21, gapa.jl:9-25, fista.jl:6-18, dykstra.jl:5-17)
     int alg = FOS_ALG_GAP;
@@ -181,7 +195,6 @@ struct fos_solver {
     // row sharding of a non-block-diagonal A: the first n entries (and tau, kappa) of every vector are replicated,
     // the slots of the rows of A' are summed over the ranks (RCCL all-reduce of 2n doubles) between a sweep and its slot-list sums
     bool row_sharded = false;
-    double* slots_rd = nullptr;
 
     // opt-in equilibration (fos_create3): the handle holds the SCALED problem; eq_passes == 0: a plain handle, nothing below is allocated
     int eq_passes = 0;
@@ -194,7 +207,6 @@ struct fos_solver {
 
     // tuning / measurement
     int cg_chunk = 8;
-    int nwg_target = 2048;
     bool prof = false;
     int prof_period = 1;                       // every prof_period-th launch of a class is bracketed by events (1: all)
     int64_t cg_total = 0;                      // CG iterations since fos_create
@@ -208,21 +220,14 @@ struct fos_solver {
     static constexpr size_t PROF_CAP = 16384;
 
     static int sum_slots_over_ranks(void* self);      // transport.cpp
-    // row-sharded WITH dual tiles: the sweep fills local slot lists (S.slots = slots_rd + 2n doubles); between sweep and consumers the
-    // lists of the n rows of A' are added up (cmp_rec / cmp_idx -> cmp_local) and THAT n-vector crosses the ranks into slots_rd[0..n);
-    // the consumers' records (S.def_rec) name slot j for row j < n and the local lists, shifted by n, for the rows of A
-    fos::DefRow* cmp_rec = nullptr;
-    int32_t* cmp_idx = nullptr;
-    double* cmp_local = nullptr;
-    int cmp_lpr = 1;
 
     // mailboxes = true: with the open mailboxes attached although the sums do not go through them (yet): fos_peer_selftest
     fos::LaunchCtx ctx(bool mailboxes = false) const {
         fos::LaunchCtx c;
-        c.stream = stream; c.S = S; c.cb = cb; c.n = n; c.m = m; c.l = l; c.st = st;
+        c.stream = stream; c.S = op.dev; c.cb = cb; c.n = n; c.m = m; c.l = l; c.st = st;
         c.partials = partials; c.reduced = reduced; c.vec_blocks = vec_blocks; c.cg_blocks = cg_blocks;
         c.peer = (tr.peer_on || mailboxes) ? &tr.peer : nullptr;
-        c.def_mask = def_mask;
+        c.def_mask = op.def_mask;
         c.pre = pre_on ? pre_sums : nullptr;
         c.between = nullptr; c.between_arg = nullptr;
         c.cus = cus;
@@ -242,9 +247,8 @@ int allreduce(fos_solver* h, int count);
 int finish_reduce(fos_solver* h, const LaunchCtx& c, int count, int nacc, int gate, int* from_reduced, int off = 0);
 void transport_teardown(fos_solver* h, bool destroy = false);
 bool peer_fold_env(), peer_loopback_env();
-// solver.cpp, for transport.cpp: the sharded set-up, the resident plan and the process-wide pool of uncached memory
+// solver.cpp, for transport.cpp and operator.cpp: the sharded set-up and the process-wide pool of uncached memory
 int global_setup(fos_solver* h);
-int resident_setup(fos_solver* h, int gmax);
 int uncached_acquire(int device, size_t bytes, bool allow_plain, void** out, const char* what);
 struct RoctxRange {                            // a named range for `rocprofv3 --marker-trace` (FOS_ROCTX=1)
     bool on;
@@ -257,6 +261,10 @@ int prof_begin_other(fos_solver* h, int post);
 void prof_end(fos_solver* h, int idx);
 int poll_state(fos_solver* h);
 int kkt_apply_full(fos_solver* h, const LaunchCtx& c, const d2* w, d2* out, bool deferred = true, bool tau_row = true);
+// operator.cpp: the operator of a new handle (h->m, n, cus and row_sharded set), another grid for its sweep (fos_set_tuning), the resident solve's plan
+int operator_setup(fos_solver* h, const int64_t* colptr, const int64_t* rowval, const double* nzval);
+int operator_repartition(fos_solver* h, int nwg);
+int resident_setup(fos_solver* h, int gmax);
 // direct.cpp: prox!(y, S1::IndAffine([Q -I], 0), x) in the handle's exact form, the result left in h->SOL
 int prox_affine_direct(fos_solver* h, const d2* x);
 
@@ -318,6 +326,13 @@ int dev_alloc(Owner* h, T** p, size_t count) {
     return FOS_OK;
 }
 
+template <class Owner, class T>
+int dev_zeros(Owner* h, T** p, size_t count) {    // dev_alloc, zero-filled
+    FOS_TRY(dev_alloc(h, p, count));
+    FOS_HIP(hipMemset(*p, 0, sizeof(T) * count));
+    return FOS_OK;
+}
+
 template <class T>
 void dev_release(fos_solver* h, T** p) {          // frees a dev_alloc'd buffer before the handle's end
     if (!*p) return;
@@ -332,5 +347,12 @@ int dev_upload(Owner* h, T** p, const std::vector<T>& v) {
     FOS_TRY(dev_alloc(h, p, v.size()));
     if (!v.empty()) FOS_HIP(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return FOS_OK;
+}
+
+// sum of squares in index order (norm(b), norm(c): values are O(1)-scaled problem data)
+inline double sum_squares(const double* v, int64_t count) {
+    double s = 0;
+    for (int64_t i = 0; i < count; ++i) s += v[i] * v[i];
+    return s;
 }
 }  // namespace fos

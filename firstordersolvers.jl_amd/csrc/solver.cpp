@@ -146,66 +146,21 @@ static void uncached_release(void* p) {
         if (g_unc_used[i].p == p) { g_unc_free.push_back(g_unc_used[i]); g_unc_used.erase(g_unc_used.begin() + (long)i); return; }
 }
 
-// FOS_CG_RESIDENT: (re)plan the resident solve for at most `gmax` workgroups -- every one of them must be on the device at once, so ranks that
-// share ONE device (the tests' stand-in for a multi-GPU box) share its CUs
-int resident_setup(fos_solver* h, int gmax) {
-    if (const char* e = getenv("FOS_RESIDENT_GMAX")) gmax = std::max(1, std::min(gmax, atoi(e)));      // (tests: several tiles per workgroup on small problems)
-    if (h->res_gmax == gmax) return FOS_OK;
-    h->res_gmax = gmax;
-    h->res_ok = false;
-    ResPlan plan;
-    if (!build_resident_plan(h->hostS, h->m, h->n, gmax, &plan)) { h->res_plan = plan; h->res_all = false; return FOS_OK; }
-    {   // the kernel instance the plan launches must fit the device's LDS (the planner assumed 160 KiB and a static allowance)
-        ResLaunch rl{};
-        rl.G = plan.G; rl.nw = plan.nw; rl.ncomm = plan.ncomm; rl.rpt = plan.rpt; rl.tmax = plan.tmax; rl.stream = plan.stream; rl.nt = plan.nt;
-        rl.tiles_wg_max = plan.tiles_wg_max;
-        std::string why;
-        if (!res_lds_fits(rl, h->device, &why)) {
-            plan.why = why; plan.G = 0; plan.wg.clear();
-            h->res_plan = plan; h->res_all = false;
-            return FOS_OK;
-        }
-    }
-    FOS_HIP(hipStreamSynchronize(h->stream));
-    if (!h->res.grec) {
-        constexpr size_t b1 = sizeof(unsigned long long) * 2 * RES_GMAX * 8, b2 = sizeof(unsigned long long) * 2 * RES_GMAX * 64 * 4;
-        void *q1 = nullptr, *q2 = nullptr;
-        FOS_TRY(uncached_acquire(h->device, b1, true, &q1, "resident CG records"));
-        h->pooled.push_back(q1);
-        FOS_TRY(uncached_acquire(h->device, b2, true, &q2, "resident CG column records"));
-        h->pooled.push_back(q2);
-        FOS_HIP(hipMemset(q1, 0, b1));                           // sequence number 0 is never sent
-        FOS_HIP(hipMemset(q2, 0, b2));
-        h->res.grec = static_cast<unsigned long long*>(q1); h->res.crec = static_cast<unsigned long long*>(q2);
-    }
-    ResWG* dwg = const_cast<ResWG*>(h->res.wg);
-    dev_release(h, &dwg);
-    FOS_TRY(dev_upload(h, &dwg, plan.wg));
-    h->res.wg = dwg; h->res.G = plan.G; h->res.nw = plan.nw; h->res.ncomm = plan.ncomm; h->res.rpt = plan.rpt; h->res.tmax = plan.tmax;
-    h->res.stream = plan.stream; h->res.nt = plan.nt; h->res.tiles_wg_max = plan.tiles_wg_max;
-    static const double res_wait_s = getenv("FOS_RESIDENT_WAIT_S") ? atof(getenv("FOS_RESIDENT_WAIT_S")) : 5.0;
-    h->res.timeout_ticks = (int64_t)(res_wait_s * 1e8);
-    h->res_plan = plan;
-    h->res_ok = true;
-    h->res_all = !h->sharded();
-    return FOS_OK;
-}
-
 // sharded set-up: global problem size and norms (tolerance floor, status normalisation) from the shards'
 int global_setup(fos_solver* h) {
     // the resident CG solve runs on a sharded handle only where EVERY rank's shard qualifies (all ranks must run the same exchanges) and
     // the sums cross the ranks through mailboxes (no collective call can sit inside a kernel): a vote through the handle's transport
     FOS_TRY(resident_setup(h, (h->tr.peer_same_device && h->nranks > 1) ? std::max(1, h->cus / h->nranks) : h->cus));
-    h->res_all = false;
+    h->op.res_all = false;
     if (h->tr.peer_on) {
         LaunchCtx cv = h->ctx();
-        double q = h->res_ok ? 1.0 : 0.0;
+        double q = h->op.res_ok ? 1.0 : 0.0;
         FOS_HIP(hipMemcpyAsync(h->partials, &q, sizeof(q), hipMemcpyHostToDevice, h->stream));
         launch_reduce1(cv, 1, 1, 0);
         FOS_TRY(allreduce(h, 1));
         FOS_HIP(hipMemcpyAsync(&q, h->reduced, sizeof(q), hipMemcpyDeviceToHost, h->stream));
         FOS_TRY(poll_state(h));
-        h->res_all = q == (double)h->nranks;
+        h->op.res_all = q == (double)h->nranks;
     }
     LaunchCtx c = h->ctx();
     const bool cnt = !h->row_sharded || h->rank == 0;     // row-sharded: the n columns and c are replicated, counted by rank 0
@@ -332,7 +287,7 @@ int cg_solve(fos_solver* h, d2* x, const d2* rhs, double tol, int maxit, int64_t
         // the whole solve is ONE launch (resident.hip): nothing to enqueue ahead, nothing to predict; what follows the solve is enqueued behind it
         // (gated on DevState.done, which the launch sets when it ends) and the host reads the iteration count from the mark the launch leaves
         const int pe = prof_begin(h, FOS_PROF_RESIDENT, 1, h->prof_seen[FOS_PROF_RESIDENT]++);
-        const hipError_t le = launch_cg_resident(c, h->res, x, rhs, apply_on ? apply_on : x, tol, maxit, fold ? &h->tr.peer : nullptr, seq_base);
+        const hipError_t le = launch_cg_resident(c, h->op.res, x, rhs, apply_on ? apply_on : x, tol, maxit, fold ? &h->tr.peer : nullptr, seq_base);
         prof_end(h, pe);
         if (le != hipSuccess) { set_error("resident CG launch: %s", hipGetErrorString(le)); return FOS_EHIP; }
         if (spec) {
@@ -1157,6 +1112,11 @@ int fos_device_name(int device, char* buf, int buflen) {
     return FOS_OK;
 }
 
+struct HandleGuard {                     // frees everything on an early error return of a create
+    fos_solver* h;
+    ~HandleGuard() { if (h) fos_destroy(h); }
+};
+
 int fos_create(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval,
                const double* b, const double* c,
                int64_t nK1, const int32_t* K1type, const int64_t* K1start, const int64_t* K1len,
@@ -1180,10 +1140,7 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     FOS_TRY(cone_table_check("K2", n, nK2, K2type, K2start, K2len));
     FOS_HIP(hipSetDevice(device));
 
-    struct Guard {                       // frees everything on an early error return
-        fos_solver* h;
-        ~Guard() { if (h) fos_destroy(h); }
-    } guard{new fos_solver()};
+    HandleGuard guard{new fos_solver()};
     fos_solver* h = guard.h;
     h->device = device;
     h->m = m; h->n = n; h->l = n + m + 1; h->l_global = h->l;
@@ -1201,207 +1158,36 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     const PsdTuning psd_tuning = PsdTuning::from_env();
     h->psd_fuse = !(getenv("FOS_PSD_FUSE") && atoi(getenv("FOS_PSD_FUSE")) == 0);
     h->relax_ew = !(getenv("FOS_RELAX_EW") && atoi(getenv("FOS_RELAX_EW")) == 0);
-    if (const char* e = getenv("FOS_SPMV_WG")) h->nwg_target = std::max(1, std::min(16384, atoi(e)));
-    else h->nwg_target = cus * 12;      // ~1.7x the resident workgroups (7/CU): measured best for the KKT sweep (dynamic balance)
 
-    // ---- operator
-    HostBlkCsr& hs = h->hostS;
+    // ---- operator (operator.cpp)
     h->row_sharded = (flags & FOS_CREATE_ROW_SHARDED) != 0;
-    FOS_TRY(build_stacked_csr(m, n, colptr, rowval, nzval, h->nwg_target, &hs, cus * 28, -1, h->row_sharded, cus * 16));
-    const bool windowed = !hs.wpanel.empty();
-    if (!windowed && !getenv("FOS_SPMV_WG") && hs.ntiles > hs.nblk / 2) {
-        // tile-dominated operator: the blocks are (nearly) equal work units, so give every wavefront the SAME whole number of them
-        // -- one, unless that needs more than 16384 workgroups (C4: 16896 tiles over 12288 wavefronts leaves 3/8 of them with
-        // twice the work: 77 us; 4224 workgroups: 71 us; tall tiles: 8704 blocks over 4096 wavefronts 73 us, one each 64)
-        const int64_t waves_target = (int64_t)h->nwg_target * SPMV_WAVES;
-        int64_t per_wave = std::max<int64_t>(1, (hs.nblk + waves_target / 2) / waves_target);
-        while ((hs.nblk + SPMV_WAVES * per_wave - 1) / (SPMV_WAVES * per_wave) > 16384) ++per_wave;
-        h->nwg_target = (int)((hs.nblk + SPMV_WAVES * per_wave - 1) / (SPMV_WAVES * per_wave));
-        partition_workgroups(&hs, h->nwg_target);
-    } else if (!windowed && !getenv("FOS_SPMV_WG") && hs.nblk / SPMV_WAVES < h->nwg_target) {
-        // small operators: one row block per wavefront up to ONE resident round of workgroups (4 per CU); beyond that a
-        // wavefront walks several blocks rather than queueing a second round behind the first (C3, 11 736 blocks: 2 934
-        // workgroups 38.3 us per CG iteration, 1 024: 32.6, 1 152: 40.7)
-        h->nwg_target = std::min(cus * 4, std::max(cus, (hs.nblk + SPMV_WAVES - 1) / SPMV_WAVES));
-        partition_workgroups(&hs, h->nwg_target);
-    }
-    double* dval; int32_t* dcol; BlkDesc* dblk; uint16_t* drr; int32_t* dwv;
-    FOS_TRY(dev_upload(h, &dval, hs.val));
-    FOS_TRY(dev_upload(h, &dcol, hs.col));
-    FOS_TRY(dev_upload(h, &dblk, hs.blk));
-    FOS_TRY(dev_upload(h, &drr, hs.row_rel));
-    // room for re-partitioning up to 16384 workgroups
-    {
-        std::vector<int32_t> wv(std::max<size_t>(hs.wave_blk0.size(), (size_t)SPMV_WAVES * 16384 + 16), 0);
-        std::copy(hs.wave_blk0.begin(), hs.wave_blk0.end(), wv.begin());
-        FOS_TRY(dev_upload(h, &dwv, wv));
-    }
-    BlkDesc* dwf = nullptr;
-    {
-        std::vector<BlkDesc> wf(std::max<size_t>(hs.wave_first.size(), (size_t)SPMV_WAVES * 16384 + 16), BlkDesc{});
-        std::copy(hs.wave_first.begin(), hs.wave_first.end(), wf.begin());
-        FOS_TRY(dev_upload(h, &dwf, wf));
-    }
-    if (windowed) {
-        // window panels: persistent workgroups, one per CU (96 KB of LDS each), walking the panels (measured on C5: 116 us per
-        // sweep with 256 workgroups, 122 us with one workgroup per panel)
-        int nwg = std::min<int>((int)hs.wpanel.size(), cus * hs.wgeom.wg_per_cu);
-        if (const char* e = getenv("FOS_SPMV_WG")) nwg = std::max(1, std::min<int>(atoi(e), (int)hs.wpanel.size()));
-        // (a multiple of 8 lets xcd_remap give every XCD a contiguous run of panels -- but never at the price of a workgroup walking two
-        //  panels while others walk one: with fewer panels than slots every panel gets its own workgroup, remapped or not)
-        if (nwg >= 8 && (int)hs.wpanel.size() > nwg) nwg -= nwg % 8;
-        hs.nwg = nwg;
-    }
-    h->S.npanel = (int32_t)hs.wpanel.size();
-    h->S.win_tall = hs.wgeom.rows == WinTall::ROWS ? 1 : 0;
-    h->S.wpanel = nullptr; h->S.wwave = nullptr; h->S.wdesc = nullptr; h->S.wval = nullptr; h->S.wcol = nullptr; h->S.wrow = nullptr;
-    if (h->S.npanel > 0) {
-        WinPanel* dp; WinWave* dsg; WinDesc* dsl; double* dwv2; uint16_t *dwc, *dwr;
-        FOS_TRY(dev_upload(h, &dp, hs.wpanel));
-        FOS_TRY(dev_upload(h, &dsg, hs.wwave));
-        FOS_TRY(dev_upload(h, &dsl, hs.wdesc));
-        FOS_TRY(dev_upload(h, &dwv2, hs.wval));
-        FOS_TRY(dev_upload(h, &dwc, hs.wcol));
-        FOS_TRY(dev_upload(h, &dwr, hs.wrow));
-        h->S.wpanel = dp; h->S.wwave = dsg; h->S.wdesc = dsl; h->S.wval = dwv2; h->S.wcol = dwc; h->S.wrow = dwr;
-        h->win_stats[0] = (int64_t)hs.wpanel.size(); h->win_stats[1] = (int64_t)hs.wdesc.size() / hs.wgeom.waves; h->win_stats[2] = hs.wnslice;
-        h->win_stats[3] = (int64_t)hs.wval.size();
-        std::vector<double>().swap(hs.wval);
-        std::vector<uint16_t>().swap(hs.wcol);
-        std::vector<uint16_t>().swap(hs.wrow);
-    }
-    h->S.nrows = hs.nrows; h->S.nnz = hs.nnz; h->S.nnz_padded = hs.nnz_padded;
-    h->S.val = dval; h->S.col = dcol; h->S.blk = dblk;
-    h->S.dbg_flags = getenv("FOS_DBG_FLAGS") ? atoi(getenv("FOS_DBG_FLAGS")) : 0;
-    // an operator whose stored form (with the dozen vectors of the solver beside it) fits the XCDs' L2s / the Infinity Cache is
-    // read with ordinary loads: it then stays on-die from one sweep to the next (FOS_RESIDENT=0/1 forces)
-    {
-        const double op_bytes = 8.0 * (double)hs.nnz_padded + 4.0 * (double)hs.ncol_stored + 48.0 * (double)hs.nblk;
-        // (measured: C3, 12 MB, sweep 22.0 -> 17.1 us; the 64-block shard of C4, 34 MB = 4.3 MB per XCD against 4 MB of L2 each,
-        //  24.5 -> 26.2 us per CG iteration: an operator that does not fit the L2s only evicts the vectors)
-        //  (C3's stored form is 34.4 MB too -- what differs is the access: row blocks that GATHER (explicit column indices, latency
-        //  bound) gain from a cache-resident matrix, a streamed dual-tile operator of that size does not)
-        h->S.resident = (!windowed && hs.ntiles == 0 && op_bytes <= 48e6) ? 1 : 0;
-        if (const char* e = getenv("FOS_RESIDENT")) h->S.resident = atoi(e) != 0 ? 1 : 0;
-    }
-    h->S.row_rel = drr; h->S.wave_blk0 = dwv; h->S.wave_first = dwf; h->S.nblk = hs.nblk; h->S.nwg = hs.nwg; h->S.nwaves = hs.nwaves;
-    // dual tiles: partial-sum slots and the deferred rows' slot lists
-    h->S.slots = nullptr; h->S.slots_rd = nullptr; h->S.row_defer = nullptr; h->S.def_rows = nullptr; h->S.def_ptr = nullptr; h->S.def_idx = nullptr;
-    h->S.def_rec = nullptr;
-    h->S.ndef = (int32_t)hs.def_rows.size();
-    h->S.nwg_def = 0; h->S.def_lpr = 1;
-    if (h->S.ndef > 0) {
-        int32_t *drd, *ddr, *ddp, *ddi;
-        double* dsl;
-        FOS_TRY(dev_upload(h, &drd, hs.row_defer));
-        FOS_TRY(dev_upload(h, &ddr, hs.def_rows));
-        FOS_TRY(dev_upload(h, &ddp, hs.def_ptr));
-        FOS_TRY(dev_upload(h, &ddi, hs.def_idx));
-        DefRow* ddrec = nullptr;
-        double avg_list = (double)hs.def_ptr.back() / (double)h->S.ndef;
-        const bool rs_tiles = h->row_sharded && hs.ntiles > 0;
-        if (!rs_tiles) {
-            FOS_TRY(dev_upload(h, &ddrec, hs.def_rec));
-            h->S.def_rec = ddrec;
-            FOS_TRY(dev_alloc(h, &dsl, (size_t)2 * hs.nslots));
-            FOS_HIP(hipMemset(dsl, 0, sizeof(double) * 2 * hs.nslots));
-            h->S.slots = dsl; h->S.slots_rd = dsl; h->S.row_defer = drd; h->S.def_rows = ddr; h->S.def_ptr = ddp; h->S.def_idx = ddi;
-            if (h->row_sharded) {                      // the all-reduced copy the slot-list sums read
-                FOS_TRY(dev_alloc(h, &h->slots_rd, (size_t)2 * hs.nslots));
-                FOS_HIP(hipMemset(h->slots_rd, 0, sizeof(double) * 2 * hs.nslots));
-                h->S.slots_rd = h->slots_rd;
-            }
-        } else {
-            // Two views of the builder's lists (fos_solver::cmp_rec).  The builder lists the n rows of A' first (rows ascending).
-            const size_t nn = (size_t)h->n;
-            if (hs.def_rows.size() < nn || hs.def_rows[nn - 1] != (int32_t)(nn - 1)) { set_error("internal: row-sharded tile operator without all rows of A' deferred"); return FOS_EINVAL; }
-            // (1) what slots_compact_kernel adds up: the records of rows 0..n-1 as built, over the sweep's slot array
-            std::vector<DefRow> crec(hs.def_rec.begin(), hs.def_rec.begin() + nn);
-            FOS_TRY(dev_upload(h, &h->cmp_rec, crec));
-            h->cmp_idx = ddi;
-            double lsum = 0.0;
-            for (size_t q = 0; q < nn; ++q) lsum += (double)(hs.def_ptr[q + 1] - hs.def_ptr[q]);
-            int clpr = 1;
-            while (clpr < 64 && 4.0 * clpr < lsum / (double)nn) clpr <<= 1;
-            h->cmp_lpr = clpr;
-            FOS_TRY(dev_alloc(h, &h->cmp_local, 2 * nn));
-            FOS_HIP(hipMemset(h->cmp_local, 0, sizeof(double) * 2 * nn));
-            // (2) what the consumers read, over slots_rd = [n summed rows | the sweep's slot array]: row j < n -> the single slot j;
-            //     rows of A spread over column chunks -> their local lists, shifted by n
-            std::vector<DefRow> vrec(hs.def_rec);
-            std::vector<int32_t> vidx(hs.def_idx.size() + nn);
-            for (size_t k = 0; k < hs.def_idx.size(); ++k) vidx[k] = hs.def_idx[k] + (int32_t)nn;
-            for (size_t j = 0; j < nn; ++j) vidx[hs.def_idx.size() + j] = (int32_t)j;
-            for (size_t q = 0; q < vrec.size(); ++q) {
-                DefRow& d = vrec[q];
-                if (q < nn) { d.own = -1; d.count = 1; d.base = (int32_t)q; d.stride = getenv("FOS_DEF_EXPLICIT") ? DEF_EXPLICIT : 0; d.kidx = (int32_t)(hs.def_idx.size() + q); }
-                else { if (d.own >= 0) d.own += (int32_t)nn; d.base += (int32_t)nn; }
-            }
-            FOS_TRY(dev_upload(h, &ddrec, vrec));
-            h->S.def_rec = ddrec;
-            int32_t* dvi = nullptr;
-            FOS_TRY(dev_upload(h, &dvi, vidx));
-            FOS_TRY(dev_alloc(h, &h->slots_rd, 2 * (nn + (size_t)hs.nslots)));
-            FOS_HIP(hipMemset(h->slots_rd, 0, sizeof(double) * 2 * (nn + (size_t)hs.nslots)));
-            h->S.slots_rd = h->slots_rd;
-            h->S.slots = h->slots_rd + 2 * nn;
-            h->S.row_defer = drd; h->S.def_rows = ddr; h->S.def_ptr = ddp; h->S.def_idx = dvi;
-            // consumers: one slot per row of A', the lists of the rows of A
-            avg_list = ((double)nn + ((double)hs.def_ptr.back() - lsum)) / (double)h->S.ndef;
-        }
-        // lanes per deferred row: about a quarter of the average slot-list length (C4: 33 slots -> 8 lanes, dense LP: 80 -> 16)
-        int lpr = 1;
-        while (lpr < 64 && 4.0 * lpr < avg_list) lpr <<= 1;
-        if (getenv("FOS_DEF_LPR")) lpr = std::max(1, std::min(64, atoi(getenv("FOS_DEF_LPR"))));
-        while (lpr & (lpr - 1)) lpr &= lpr - 1;
-        h->S.def_lpr = lpr;
-        h->S.nwg_def = (int32_t)std::min<int64_t>(DEF_MAX_WG, ((int64_t)h->S.ndef * lpr + DEF_THREADS - 1) / DEF_THREADS);
-        // bit mask of the rows finished from partial slots (cg_update_kernel skips them in its streaming pass)
-        std::vector<uint32_t> mask((size_t)(h->l + 31) / 32 + 1, 0u);
-        for (int32_t r : hs.def_rows) mask[(size_t)r >> 5] |= 1u << (r & 31);
-        FOS_TRY(dev_upload(h, &h->def_mask, mask));
-        std::vector<int32_t>().swap(hs.row_defer);
-        std::vector<int32_t>().swap(hs.def_idx);
-    }
+    FOS_TRY(operator_setup(h, colptr, rowval, nzval));
     // The p update of CG can ride on the next sweep (two launches per iteration, launch_kkt2_cg): built and measured -- on
     // MI355X it is SLOWER than the separate launch at every size tried (C4: sweep 59 -> 86 us against a 10 us p update kernel;
     // 64-block shard: 13 -> 20 us against 5 us), so it stays an option (fos_set_tuning / FOS_CG_FUSE_P)
     h->fuse_p = false;
     if (const char* e = getenv("FOS_CG_FUSE_P")) h->fuse_p = atoi(e) != 0;
     if (const char* e = getenv("FOS_CG_VARIANT")) h->cg_variant = std::max(-1, std::min((int)FOS_CG_RESIDENT, atoi(e)));
-    h->S.npart = h->S.nwg_def > 0 ? h->S.nwg_def : h->S.nwg;
-    h->S.part_off = h->S.nwg_def > 0 ? h->S.nwg : 0;
-    // free the big host arrays (keep block table for re-partitioning)
-    std::vector<double>().swap(hs.val);
-    std::vector<int32_t>().swap(hs.col);
-    std::vector<uint16_t>().swap(hs.row_rel);
 
     std::vector<double> cbv((size_t)(n + m));
-    double nb2 = 0, nc2 = 0;
     for (int64_t j = 0; j < n; ++j) { cbv[j] = c[j]; }
     for (int64_t i = 0; i < m; ++i) { cbv[n + i] = b[i]; }
-    // norm(b), norm(c): plain sums of squares (values are O(1)-scaled problem data)
-    for (int64_t j = 0; j < n; ++j) nc2 += c[j] * c[j];
-    for (int64_t i = 0; i < m; ++i) nb2 += b[i] * b[i];
-    h->nb = std::sqrt(nb2); h->nc = std::sqrt(nc2);
+    h->nb = std::sqrt(sum_squares(b, m)); h->nc = std::sqrt(sum_squares(c, n));
     h->nb_local = h->nb; h->nc_local = h->nc;
     FOS_TRY(dev_upload(h, &h->cb, cbv));
 
     // ---- vectors
     const size_t l = (size_t)h->l;
     d2** vecs[] = {&h->X, &h->T1, &h->T2, &h->SOL, &h->RHS, &h->R, &h->PB[0], &h->PB[1], &h->AP, &h->Y, &h->XOLD, &h->W, &h->SOL2};
-    for (d2** v : vecs) {
-        FOS_TRY(dev_alloc(h, v, l));
-        FOS_HIP(hipMemset(*v, 0, sizeof(d2) * l));
-    }
+    for (d2** v : vecs) FOS_TRY(dev_zeros(h, v, l));
     FOS_TRY(dev_alloc(h, &h->plain, 2 * l));
     h->vec_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((h->l + 255) / 256, 1024));
     h->cg_blocks = std::min(h->vec_blocks, getenv("FOS_CG_BLOCKS") ? std::max(1, atoi(getenv("FOS_CG_BLOCKS"))) : 2 * cus);
     // the x,r update kernel also adds the slot lists of the rows spread over dual tiles (`def_lpr` lanes per row): its grid must
     // cover them in ONE pass even when the vectors are short (dense LP C2: 15 000 such rows x 16 lanes against l = 15 001 --
     // sized by l alone the kernel took 105 us instead of 17)
-    if (h->S.ndef > 0)
-        h->cg_blocks = std::max<int>(h->cg_blocks, (int)std::min<int64_t>(1024, ((int64_t)h->S.ndef * h->S.def_lpr + 255) / 256));
+    if (h->op.dev.ndef > 0)
+        h->cg_blocks = std::max<int>(h->cg_blocks, (int)std::min<int64_t>(1024, ((int64_t)h->op.dev.ndef * h->op.dev.def_lpr + 255) / 256));
     h->cg_blocks = std::min(h->cg_blocks, 1024);         // (cg_close_iteration adds at most 1024 r.r records per wavefront)
 
     // ---- cones
@@ -1417,10 +1203,8 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     FOS_TRY(cone_set_build(table, (int64_t)l, cone_opts, psd_tuning, &h->cones));
 
     // ---- scalars
-    FOS_TRY(dev_alloc(h, &h->st, 1));
-    FOS_HIP(hipMemset(h->st, 0, sizeof(DevState)));
-    FOS_TRY(dev_alloc(h, &h->pre_sums, 128));           // 16 producers x 3 sums x 2 self-validating words (sweep_sums3)
-    FOS_HIP(hipMemset(h->pre_sums, 0, sizeof(double) * 128));
+    FOS_TRY(dev_zeros(h, &h->st, 1));
+    FOS_TRY(dev_zeros(h, &h->pre_sums, 128));           // 16 producers x 3 sums x 2 self-validating words (sweep_sums3)
     h->pre_on = !(getenv("FOS_CG_PRE") && atoi(getenv("FOS_CG_PRE")) == 0);
     {
         void* dp = nullptr;
@@ -1431,8 +1215,7 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     FOS_HIP(hipHostMalloc((void**)&h->st_host, sizeof(DevState), hipHostMallocDefault));
     memset(h->st_host, 0, sizeof(DevState));
     FOS_TRY(dev_alloc(h, &h->partials, (size_t)6 * PART_CAP));
-    FOS_TRY(dev_alloc(h, &h->reduced, 16));
-    FOS_HIP(hipMemset(h->reduced, 0, sizeof(double) * 16));
+    FOS_TRY(dev_zeros(h, &h->reduced, 16));
     if (const char* e = getenv("FOS_CG_CHUNK")) h->cg_chunk = std::max(1, atoi(e));
 
     FOS_TRY(resident_setup(h, cus));                      // FOS_CG_RESIDENT: does the operator qualify, and the plan if so
@@ -1463,14 +1246,8 @@ int fos_create3(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     FOS_TRY(host_equilibrate(m, n, colptr, rowval, nzval, b, c, nK1, K1type, K1start, K1len, nK2, K2type, K2start, K2len, equil_passes, &eq));
     fos_handle h = nullptr;
     FOS_TRY(fos_create2(m, n, colptr, rowval, eq.nz.data(), eq.b.data(), eq.c.data(), nK1, K1type, K1start, K1len, nK2, K2type, K2start, K2len, device, flags, &h));
-    struct Guard {
-        fos_solver* h;
-        ~Guard() { if (h) fos_destroy(h); }
-    } guard{h};
-    double nb2 = 0, nc2 = 0;                               // the caller's norms, summed as fos_create2 sums the handle's
-    for (int64_t j = 0; j < n; ++j) nc2 += c[j] * c[j];
-    for (int64_t i = 0; i < m; ++i) nb2 += b[i] * b[i];
-    h->eq_nb = std::sqrt(nb2); h->eq_nc = std::sqrt(nc2);
+    HandleGuard guard{h};
+    h->eq_nb = std::sqrt(sum_squares(b, m)); h->eq_nc = std::sqrt(sum_squares(c, n));      // the caller's norms, summed as the handle's
     h->eq_sigma = eq.sigma; h->eq_rho = eq.rho; h->eq_gamma = eq.gamma;
     const size_t l = (size_t)h->l;
     std::vector<d2> up(l);
@@ -1491,8 +1268,7 @@ int fos_create3(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     FOS_TRY(dev_upload(h, &h->eq_up, up));
     FOS_TRY(dev_upload(h, &h->eq_inv, inv));
     FOS_TRY(dev_upload(h, &h->eq_cb, cbv));
-    FOS_TRY(dev_alloc(h, &h->eq_w, l));
-    FOS_HIP(hipMemset(h->eq_w, 0, sizeof(double) * l));
+    FOS_TRY(dev_zeros(h, &h->eq_w, l));
     h->eq_D.swap(eq.D);
     h->eq_E.swap(eq.E);
     h->eq_passes = equil_passes;
@@ -1671,13 +1447,11 @@ int fos_set_longstep(fos_handle h, int64_t longinterval, int64_t nsave) {
     if (!h->lp.P || h->lp.nsave != nsave) {
         FOS_HIP(hipStreamSynchronize(h->stream));
         dev_release(h, &h->lp.P); dev_release(h, &h->lp.bpart); dev_release(h, &h->lp.dots); dev_release(h, &h->lp.nu);    // (a caller sweeping nsave must not pile buffers up)
-        FOS_TRY(dev_alloc(h, &h->lp.P, (size_t)K * h->l));
-        FOS_TRY(dev_alloc(h, &h->lp.bpart, (size_t)K * h->vec_blocks));
+        // rows a saving window never wrote (fos_step entered in the middle of one) are zero planes, not uninitialised memory
+        FOS_TRY(dev_zeros(h, &h->lp.P, (size_t)K * h->l));
+        FOS_TRY(dev_zeros(h, &h->lp.bpart, (size_t)K * h->vec_blocks));
         FOS_TRY(dev_alloc(h, &h->lp.dots, (size_t)h->vec_blocks * 2 * (LONG_KMAX_ROWS + 1)));
         FOS_TRY(dev_alloc(h, &h->lp.nu, (size_t)2 * K));
-        // rows a saving window never wrote (fos_step entered in the middle of one) are zero planes, not uninitialised memory
-        FOS_HIP(hipMemset(h->lp.P, 0, sizeof(d2) * (size_t)K * h->l));
-        FOS_HIP(hipMemset(h->lp.bpart, 0, sizeof(double) * (size_t)K * h->vec_blocks));
     }
     h->lp.interval = longinterval; h->lp.nsave = nsave; h->lp.savepos = 0; h->lp.now = false;
     h->lp.max_supports = getenv("FOS_LONG_MAX_SUPPORTS") ? atoll(getenv("FOS_LONG_MAX_SUPPORTS")) : 4096;      // (0 tries none: the failure path, tests)
@@ -1922,26 +1696,6 @@ int fos_profile_read(fos_handle h, int64_t* launches, double* total_ms, double* 
     return FOS_OK;
 }
 
-int fos_operator_stats(fos_handle h, int64_t* stats) {
-    if (!h || !stats) { set_error("NULL argument"); return FOS_EINVAL; }
-    const HostBlkCsr& S = h->hostS;
-    int64_t nell = 0, nlds = 0, nlong = 0, nrun = 0;
-    for (const BlkDesc& d : S.blk) {
-        if (d.kind() == BLK_ELL) ++nell; else if (d.kind() == BLK_LDS) ++nlds; else if (d.kind() == BLK_LONG) ++nlong;
-        if (d.run()) ++nrun;
-    }
-    stats[0] = S.nblk; stats[1] = nell; stats[2] = nlds; stats[3] = nlong; stats[4] = nrun;
-    stats[5] = S.nnz_padded; stats[6] = S.ncol_stored; stats[7] = h->S.nwaves;
-    stats[8] = S.ntiles; stats[9] = S.nslots; stats[10] = h->S.ndef; stats[11] = S.tile_values;
-    return FOS_OK;
-}
-
-int fos_window_stats(fos_handle h, int64_t* stats4) {
-    if (!h || !stats4) { set_error("NULL argument"); return FOS_EINVAL; }
-    for (int k = 0; k < 4; ++k) stats4[k] = h->win_stats[k];
-    return FOS_OK;
-}
-
 int fos_bench_kkt(fos_handle h, int32_t reps, double* total_ms) {
     if (!h || reps < 1) { set_error("bad argument"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
@@ -2040,113 +1794,6 @@ int fos_bench_cg_chain(fos_handle h, int32_t iters, int32_t reps, int32_t use_gr
     return FOS_OK;
 }
 
-int fos_host_resident_cg(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, const double* c,
-                         int32_t gmax, double* x, const double* rhs, double tol, int64_t max_iters, int64_t* iters, int64_t* stats8) {
-    if (!colptr || m < 0 || n < 0 || gmax < 1 || (x && (!rhs || !b || !c || max_iters < 1))) { set_error("bad argument"); return FOS_EINVAL; }
-    HostBlkCsr S;
-    const int cus = 256;                       // (the operator as fos_create builds it on a 256-CU device)
-    FOS_TRY(build_stacked_csr(m, n, colptr, rowval, nzval, cus * 12, &S, cus * 28, -1, false, cus * 16));
-    ResPlan P;
-    const bool ok = build_resident_plan(S, m, n, gmax, &P);
-    if (stats8) {
-        stats8[0] = ok ? 1 : 0; stats8[1] = P.G; stats8[2] = P.nw; stats8[3] = P.stream ? -P.nt : P.rpt; stats8[4] = P.units; stats8[5] = P.tiles_wg_max; stats8[6] = P.tmax; stats8[7] = ok ? 1 : 0;
-    }
-    if (!ok) { set_error("FOS_CG_RESIDENT: the operator does not qualify (%s)", P.why.c_str()); return x ? FOS_EUNSUPPORTED : FOS_OK; }
-    if (!x) return FOS_OK;
-    const int64_t l = n + m + 1;
-    std::vector<double> cb((size_t)(n + m));
-    for (int64_t j = 0; j < n; ++j) cb[j] = c[j];
-    for (int64_t i = 0; i < m; ++i) cb[n + i] = b[i];
-    std::vector<double2> xv((size_t)l), rv((size_t)l);
-    for (int64_t i = 0; i < l; ++i) { xv[i] = double2{x[i], x[l + i]}; rv[i] = double2{rhs[i], rhs[l + i]}; }      // plain [part1; part2] -> interleaved
-    std::vector<double2> v0(xv);
-    int it = 0;
-    FOS_TRY(host_resident_cg(S, P, m, n, cb.data(), xv.data(), rv.data(), v0.data(), tol, (int)std::min<int64_t>(max_iters, 1 << 30), &it));
-    for (int64_t i = 0; i < l; ++i) { x[i] = xv[i].x; x[l + i] = xv[i].y; }
-    if (iters) *iters = it;
-    return FOS_OK;
-}
-
-int fos_host_resident_plan(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, int32_t gmax,
-                           int64_t* info8, int32_t* wg7, int64_t wg_cap, int64_t* tile5, int64_t tile_cap) {
-    if (!colptr || !info8 || m < 0 || n < 0 || gmax < 1) { set_error("bad argument"); return FOS_EINVAL; }
-    HostBlkCsr S;
-    const int cus = 256;                       // (as fos_host_resident_cg)
-    FOS_TRY(build_stacked_csr(m, n, colptr, rowval, nzval, cus * 12, &S, cus * 28, -1, false, cus * 16));
-    ResPlan P;
-    const bool ok = build_resident_plan(S, m, n, gmax, &P);
-    int64_t ntiles = 0;
-    for (const ResWG& w : P.wg) ntiles += w.nblk;
-    info8[0] = ok ? (P.stream ? 2 : 1) : 0; info8[1] = P.G; info8[2] = P.nt; info8[3] = P.tmax; info8[4] = P.nw; info8[5] = P.rpt; info8[6] = P.ncomm;
-    info8[7] = ntiles;
-    if (!ok) { set_error("FOS_CG_RESIDENT: the operator does not qualify (%s)", P.why.c_str()); return FOS_OK; }
-    if (wg7 && wg_cap >= P.G)
-        for (int q = 0; q < P.G; ++q) {
-            const ResWG& w = P.wg[q];
-            const int32_t r[7] = {w.blk0, w.nblk, w.c0, w.tc, w.wg0, w.wpu, w.idx};
-            memcpy(wg7 + 7 * (size_t)q, r, sizeof(r));
-        }
-    if (tile5 && tile_cap >= ntiles) {
-        int64_t k = 0;
-        for (const ResWG& w : P.wg)
-            for (int ti = 0; ti < w.nblk; ++ti, ++k) {
-                const BlkDesc& d = S.blk[w.blk0 + ti];
-                int64_t* t = tile5 + 5 * k;
-                t[0] = d.meta[0]; t[1] = d.meta[3]; t[2] = d.steps(); t[3] = d.nrows(); t[4] = d.row0;
-            }
-    }
-    return FOS_OK;
-}
-
-// (not part of the ABI: the CPU test-suite's view of the streamed form's deal -- cnt8 = the tiles each of the eight wavefronts of a workgroup of `tiles`
-//  tiles of at most `steps` steps walks, seven compute wavefronts and then the communication wavefront, consecutive tiles in wavefront order, as the
-//  plan carries them to the kernel; lds_bytes (may be NULL) = the dynamic LDS of the launch)
-extern "C" int fos_debug_resident_deal(int32_t tiles, int32_t steps, int32_t* cnt8, int64_t* lds_bytes) {
-    if (tiles < 0 || steps < 1 || steps > 64 || !cnt8) { set_error("bad argument"); return FOS_EINVAL; }
-    const uint32_t deal = rs_deal(tiles, rs_ntc(steps));
-    for (int w = 0, t0, cnt; w <= RS_NCOMP; ++w) { rs_split(deal, w, t0, cnt); cnt8[w] = cnt; }
-    if (lds_bytes) *lds_bytes = (int64_t)res_stream_lds_bytes(tiles);
-    return FOS_OK;
-}
-
-int fos_host_stacked_spmv(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval,
-                          const double* v, double* out, int32_t spmv_workgroups, int32_t resident_waves, int64_t* stats) {
-    if (!colptr || !v || !out || m < 0 || n < 0) { set_error("bad argument"); return FOS_EINVAL; }
-    HostBlkCsr S;
-    FOS_TRY(build_stacked_csr(m, n, colptr, rowval, nzval, spmv_workgroups > 0 ? spmv_workgroups : 1024, &S, resident_waves));
-    std::string why;
-    int rc = host_stacked_spmv(S, v, out, &why);
-    if (rc != FOS_OK) { set_error("operator format check failed: %s", why.c_str()); return rc; }
-    if (stats) {
-        int64_t nell = 0, nlds = 0, nlong = 0, nrun = 0;
-        for (const BlkDesc& d : S.blk) {
-            if (d.kind() == BLK_ELL) ++nell; else if (d.kind() == BLK_LDS) ++nlds; else if (d.kind() == BLK_LONG) ++nlong;
-            if (d.run()) ++nrun;
-        }
-        stats[0] = S.nblk; stats[1] = nell; stats[2] = nlds; stats[3] = nlong; stats[4] = nrun;
-        stats[5] = S.nnz_padded; stats[6] = S.ncol_stored; stats[7] = S.nwaves;
-        stats[8] = S.ntiles; stats[9] = S.nslots; stats[10] = (int64_t)S.def_rows.size(); stats[11] = S.tile_values;
-    }
-    return FOS_OK;
-}
-
-int fos_host_stacked_spmv_mode(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval,
-                               const double* v, double* out, int32_t window_mode, int64_t* stats16) {
-    if (!colptr || !v || !out || m < 0 || n < 0) { set_error("bad argument"); return FOS_EINVAL; }
-    HostBlkCsr S;
-    const bool rs = getenv("FOS_HOST_SPMV_ROW_SHARDED") && atoi(getenv("FOS_HOST_SPMV_ROW_SHARDED")) != 0;      // (tests: the row-sharded builder)
-    FOS_TRY(build_stacked_csr(m, n, colptr, rowval, nzval, 1024, &S, 0, window_mode, rs));
-    std::string why;
-    int rc = host_stacked_spmv(S, v, out, &why);
-    if (rc != FOS_OK) { set_error("operator format check failed: %s", why.c_str()); return rc; }
-    if (stats16) {
-        for (int k = 0; k < 16; ++k) stats16[k] = 0;
-        stats16[0] = S.nblk; stats16[5] = S.nnz_padded; stats16[6] = S.ncol_stored; stats16[8] = S.ntiles; stats16[9] = S.nslots;
-        stats16[12] = (int64_t)S.wpanel.size(); stats16[13] = (int64_t)S.wdesc.size() / S.wgeom.waves; stats16[14] = S.wnslice; stats16[15] = (int64_t)S.wval.size();
-    }
-    return FOS_OK;
-}
-
 int fos_sync(fos_handle h) {
     if (!h) { set_error("NULL handle"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
@@ -2159,32 +1806,15 @@ int fos_set_tuning(fos_handle h, int32_t spmv_workgroups, int32_t cg_chunk, int3
     FOS_HIP(hipSetDevice(h->device));
     if (fuse_p >= 0) { h->fuse_p = fuse_p != 0; h->cg_variant = -1; }
     if (cg_chunk > 0) h->cg_chunk = cg_chunk;
-    if (spmv_workgroups > 0 && h->S.npanel > 0) {
-        // window panels: the grid is a number of persistent workgroups walking the panels
-        h->S.nwg = std::max(1, std::min<int32_t>(std::min(spmv_workgroups, 16384), h->S.npanel));
-        h->S.npart = h->S.nwg; h->S.part_off = 0;
-    } else if (spmv_workgroups > 0) {
-        if (spmv_workgroups > 16384) spmv_workgroups = 16384;
-        FOS_HIP(hipStreamSynchronize(h->stream));
-        partition_workgroups(&h->hostS, spmv_workgroups);
-        FOS_HIP(hipMemcpy(const_cast<int32_t*>(h->S.wave_blk0), h->hostS.wave_blk0.data(),
-                          h->hostS.wave_blk0.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        FOS_HIP(hipMemcpy(const_cast<BlkDesc*>(h->S.wave_first), h->hostS.wave_first.data(),
-                          h->hostS.wave_first.size() * sizeof(BlkDesc), hipMemcpyHostToDevice));
-        h->S.nwg = h->hostS.nwg;
-        h->S.npart = h->S.nwg_def > 0 ? h->S.nwg_def : h->S.nwg;
-        h->S.part_off = h->S.nwg_def > 0 ? h->S.nwg : 0;
-        h->S.nwaves = h->hostS.nwaves;
-        h->nwg_target = spmv_workgroups;
-    }
+    if (spmv_workgroups > 0) FOS_TRY(operator_repartition(h, spmv_workgroups));
     return FOS_OK;
 }
 
 // which CG recurrence the affine projection runs (FOS_CG_*; -1: the handle's default)
 int fos_set_cg_variant(fos_handle h, int32_t variant) {
     if (!h || variant < -1 || variant > FOS_CG_RESIDENT) { set_error("unknown CG variant %d", (int)variant); return FOS_EINVAL; }
-    if (variant == FOS_CG_RESIDENT && !h->res_ok) {
-        set_error("FOS_CG_RESIDENT: the operator does not qualify (%s)", h->res_plan.why.empty() ? "no plan" : h->res_plan.why.c_str());
+    if (variant == FOS_CG_RESIDENT && !h->op.res_ok) {
+        set_error("FOS_CG_RESIDENT: the operator does not qualify (%s)", h->op.res_plan.why.empty() ? "no plan" : h->op.res_plan.why.c_str());
         return FOS_EUNSUPPORTED;
     }
     h->cg_variant = variant;
@@ -2203,29 +1833,20 @@ int fos_get_cg_variant(fos_handle h, int32_t* variant) {
     // keep the reference's arithmetic).  Same Krylov iterates, same
     // iteration counting and stop test; FOS_CG_VARIANT=0 / fos_set_cg_variant restore the reference recurrence everywhere.
     int v = h->cg_variant >= 0 ? h->cg_variant
-            : (h->fuse_p ? FOS_CG_FUSED_P : ((h->sharded() || (h->S.resident && !h->row_sharded && h->l >= 32768)) ? FOS_CG_MERGED_UPDATE : FOS_CG_REFERENCE));
+            : (h->fuse_p ? FOS_CG_FUSED_P : ((h->sharded() || (h->op.dev.resident && !h->row_sharded && h->l >= 32768)) ? FOS_CG_MERGED_UPDATE : FOS_CG_REFERENCE));
     // the resident solve: on request wherever the operator qualifies; by default on sharded handles whose sums travel through mailboxes and
     // whose shards ALL qualify (FOS_RESIDENT_DEFAULT=0: never by default).  Sharded without mailboxes (RCCL, the caller's collective): a
     // collective call cannot sit inside a kernel -- the launch-per-iteration form of the same recurrence runs instead.
     const bool res_default = !(getenv("FOS_RESIDENT_DEFAULT") && atoi(getenv("FOS_RESIDENT_DEFAULT")) == 0);      // (read at every call: bench.py turns it off after a failed warm-up)
-    const bool res_usable = h->res_ok && !h->row_sharded && (!h->sharded() || (h->tr.peer_on && fold_env && h->res_all));
+    const bool res_usable = h->op.res_ok && !h->row_sharded && (!h->sharded() || (h->tr.peer_on && fold_env && h->op.res_all));
     if (h->cg_variant < 0 && !h->fuse_p && h->sharded() && res_usable && res_default) v = FOS_CG_RESIDENT;
     // one GPU: the STREAMED form where it fills at least half of the chip (C4: 66.3 us per CG iteration against 89 for three launches); operators
     // small enough for the register form keep the reference's arithmetic by default
-    if (h->cg_variant < 0 && !h->fuse_p && !h->sharded() && res_usable && res_default && h->res_plan.stream && 2 * h->res_plan.G >= h->cus) v = FOS_CG_RESIDENT;
+    if (h->cg_variant < 0 && !h->fuse_p && !h->sharded() && res_usable && res_default && h->op.res_plan.stream && 2 * h->op.res_plan.G >= h->cus) v = FOS_CG_RESIDENT;
     if (v == FOS_CG_RESIDENT && !res_usable) v = FOS_CG_MERGED_UPDATE;
     if (v == FOS_CG_MERGED_SWEEP && h->sharded()) v = FOS_CG_MERGED_UPDATE;
     if (v == FOS_CG_MERGED_UPDATE && h->tr.peer_on && !fold_env) v = FOS_CG_REFERENCE;
     *variant = v;
-    return FOS_OK;
-}
-
-int fos_resident_stats(fos_handle h, int64_t* stats8) {
-    if (!h || !stats8) { set_error("NULL argument"); return FOS_EINVAL; }
-    const ResPlan& p = h->res_plan;
-    stats8[0] = h->res_ok ? 1 : 0; stats8[1] = p.G; stats8[2] = p.nw; stats8[3] = p.stream ? -p.nt : p.rpt; stats8[4] = p.units; stats8[5] = p.tiles_wg_max;
-    stats8[6] = p.tmax; stats8[7] = (h->sharded() ? h->res_all : h->res_ok) ? 1 : 0;
-    if (!h->res_ok) set_error("FOS_CG_RESIDENT: %s", p.why.empty() ? "no plan" : p.why.c_str());
     return FOS_OK;
 }
 

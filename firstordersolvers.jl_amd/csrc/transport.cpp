@@ -277,23 +277,23 @@ using namespace fos;
 int fos_solver::sum_slots_over_ranks(void* self) {
     fos_solver* h = static_cast<fos_solver*>(self);
     Transport& t = h->tr;
-    const double* src = h->S.slots;            // one slot per row of A' ...
-    if (h->cmp_local) {                        // ... or, with dual tiles, the rows' local slot lists added up first
-        launch_slots_compact(h->ctx(), (int)h->n, h->cmp_rec, h->cmp_idx, h->cmp_lpr, h->S.slots, h->cmp_local);
-        src = h->cmp_local;
+    const double* src = h->op.dev.slots;       // one slot per row of A' ...
+    if (h->op.cmp_local) {                     // ... or, with dual tiles, the rows' local slot lists added up first
+        launch_slots_compact(h->ctx(), (int)h->n, h->op.cmp_rec, h->op.cmp_idx, h->op.cmp_lpr, h->op.dev.slots, h->op.cmp_local);
+        src = h->op.cmp_local;
     }
     const size_t n2 = (size_t)2 * (size_t)h->n;
     switch (t.via()) {
-    case VIA_HOST: return host_allreduce(h, src, h->slots_rd, n2);
+    case VIA_HOST: return host_allreduce(h, src, h->op.slots_rd, n2);
     case VIA_PEER:             // peer-mapped memory: push + sum, in stream, no library call
-        if (t.vec.buf) { launch_vec_exchange(h->ctx(), t.vec, ++t.vec_seq, src, h->slots_rd); return FOS_OK; }
+        if (t.vec.buf) { launch_vec_exchange(h->ctx(), t.vec, ++t.vec_seq, src, h->op.slots_rd); return FOS_OK; }
         [[fallthrough]];
     case VIA_RCCL:
-        if (t.comm) return nccl_ok("AllReduce", g_rccl.AllReduce(src, h->slots_rd, n2, ncclDouble, ncclSum, t.comm, h->stream));
+        if (t.comm) return nccl_ok("AllReduce", g_rccl.AllReduce(src, h->op.slots_rd, n2, ncclDouble, ncclSum, t.comm, h->stream));
         [[fallthrough]];
     case VIA_NONE: break;      // no communicator yet (set-up calls before fos_comm_init, or a single process): the sum is the copy
     }
-    return hipMemcpyAsync(h->slots_rd, src, sizeof(double) * n2, hipMemcpyDeviceToDevice, h->stream) == hipSuccess ? FOS_OK : FOS_EHIP;
+    return hipMemcpyAsync(h->op.slots_rd, src, sizeof(double) * n2, hipMemcpyDeviceToDevice, h->stream) == hipSuccess ? FOS_OK : FOS_EHIP;
 }
 
 extern "C" {
