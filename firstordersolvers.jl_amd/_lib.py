@@ -152,6 +152,11 @@ PROTOTYPES = {
     "fos_host_least_squares_normal": (C.c_int, [C.c_int64, C.c_int64, _dp, _dp, C.c_double, _dp, _dp]),
     "fos_host_least_squares_sparse": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _dp, _dp, C.c_double, C.c_int32, _dp, _dp]),
     "fos_host_symv_packed": (C.c_int, [C.c_int64, _dp, _dp, _dp, _i32p]),
+    "fos_feas_set_quadratic_sparse": (C.c_int, [_h, C.c_int32, _i64p, _i64p, _dp, _dp, C.c_double]),
+    "fos_feas_set_least_squares_cg": (C.c_int, [_h, C.c_int32, C.c_int64, _i64p, _i64p, _dp, _dp, C.c_double, C.c_double]),
+    "fos_feas_nspace_cg_stats": (C.c_int, [_h, C.c_int32, _dp]),
+    "fos_host_quadratic_cg": (C.c_int, [C.c_int64, _i64p, _i64p, _dp, _dp, C.c_double, _dp, _dp, _i32p]),
+    "fos_host_least_squares_cg": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _dp, _dp, C.c_double, C.c_double, _dp, _dp, _i32p]),
     "fos_bench_symv_packed": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, _dp]),
     "fos_feas_set_box": (C.c_int, [_h, C.c_int32, C.c_double, C.c_double]),
     "fos_feas_set_box_arrays": (C.c_int, [_h, C.c_int32, _dp, _dp]),

@@ -32,14 +32,8 @@ namespace fos {
 namespace {
 
 constexpr int SF_T = 256;                     // threads per workgroup: four work items
-constexpr int SF_SEG_DEFAULT = 2048;          // stored entries per segment (FOS_SF_SEG: a multiple of 64 from 64 up to this)
 constexpr int SF_LANE_ENTRIES = 4;            // packed rows: entries per lane of the packet's longest row, while g < 64
 constexpr double SF_BAR = 1e-7;               // the inverse of A A' is accepted at this probe residual (as affine_dense.hip)
-
-// a work item (16 bytes, read wave-uniformly):
-//   segment: a = row, b = first entry, c = entries (> 0), d = slot of part[] (-1: the row's only segment, never built: such rows are packed)
-//   packet:  a = first row, b = rows (<= 64 / g), c = -g (lanes per row, a power of two), d unused
-struct SfItem { int32_t a, b, c, d; };
 
 // PASS 1 (the CSR of A):  s = A[row, segment] in  ->  out[row] = s - aux[row]          (in = x or y, aux = b, out = r)
 // PASS 2 (the CSR of A'): s = A'[row, segment] in ->  out[row] = aux[row] - s          (in = d, aux = x or y, out = y; out may be aux: same lane reads and writes)
@@ -113,12 +107,9 @@ int sf_lanes(int len) {                                  // the fewest lanes (a 
     return g;
 }
 
-// the work items of one pass, from the row pointers and SEG alone
-struct SfPass {
-    std::vector<SfItem> items;
-    std::vector<int32_t> frow, fptr;                     // cut rows and their slots of part[]: fptr[k] .. fptr[k + 1] - 1, in segment order
-    int64_t nparts = 0;
-};
+}  // namespace
+
+// the work items of one pass, from the row pointers and SEG alone (SfItem, SfPass: fos_internal.hpp; nspace_cg.hip plans its passes with it too)
 void sf_plan_pass(int64_t nrows, const int32_t* rp, int seg, SfPass* P) {
     P->items.clear(); P->frow.clear(); P->fptr.assign(1, 0); P->nparts = 0;
     auto len = [&](int64_t r) { return rp[r + 1] - rp[r]; };
@@ -141,6 +132,8 @@ void sf_plan_pass(int64_t nrows, const int32_t* rp, int seg, SfPass* P) {
         r += cnt;
     }
 }
+
+namespace {
 
 // FOS_SF_SEG (read at every set-up: per handle): a multiple of 64 from 64 up to the default
 int sf_segment_length(int* seg) {

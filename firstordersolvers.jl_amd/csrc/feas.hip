@@ -532,6 +532,37 @@ int fos_host_least_squares_sparse(int64_t m, int64_t n, const int64_t* colptr, c
     return host_affine_sparse_factored(m, n, colptr, rowval, nzval, b, lambda, 0, x, y);
 }
 int fos_host_symv_packed(int64_t k, const double* X, const double* v, double* y, int32_t* count) { return host_nspace_symv_packed(k, X, v, y, count); }
+// ---- the n-space forms by CG (nspace_cg.hip): a sparse Q or A of any size
+int fos_feas_set_quadratic_sparse(fos_feas_handle h, int32_t which, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* q, double tol) {
+    if (!h || which < 1 || which > 2) { set_error("fos_feas_set_quadratic_sparse: NULL handle or which not in {1, 2}"); return FOS_EINVAL; }
+    FOS_HIP(hipSetDevice(h->device));
+    ProxObject* s = nullptr;
+    FOS_TRY(nspace_cg_setup_quadratic(h->n, colptr, rowval, nzval, q, tol, h->stream, &s));
+    return feas_install(h, which, s);
+}
+int fos_feas_set_least_squares_cg(fos_feas_handle h, int32_t which, int64_t m, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b,
+                                  double lambda, double tol) {
+    if (!h || which < 1 || which > 2) { set_error("fos_feas_set_least_squares_cg: NULL handle or which not in {1, 2}"); return FOS_EINVAL; }
+    FOS_HIP(hipSetDevice(h->device));
+    ProxObject* s = nullptr;
+    FOS_TRY(nspace_cg_setup_ls(m, h->n, colptr, rowval, nzval, b, lambda, tol, h->stream, &s));
+    return feas_install(h, which, s);
+}
+int fos_feas_nspace_cg_stats(fos_feas_handle h, int32_t which, double* out8) {
+    const ProxObject* s = nullptr;
+    FOS_TRY(feas_object(h, which, out8, FEAS_NSPACE_CG, "fos_feas_nspace_cg_stats", "is not a Quadratic or a LeastSquares in the cg form", &s));
+    nspace_cg_stats(s, out8);
+    return FOS_OK;
+}
+// test-only, host: the cg forms' matrices, work items, recurrence and sums in the kernels' order (nspace_cg.hip)
+int fos_host_quadratic_cg(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* q, double tol, const double* x, double* y,
+                          int32_t* iters) {
+    return host_nspace_cg_quadratic(n, colptr, rowval, nzval, q, tol, x, y, iters);
+}
+int fos_host_least_squares_cg(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, double tol,
+                              const double* x, double* y, int32_t* iters) {
+    return host_nspace_cg_ls(m, n, colptr, rowval, nzval, b, lambda, tol, x, y, iters);
+}
 // measurement: the one-rhs tile product against red_symm_kernel on the same tiles (nspace.hip); out4 = ms per product of each, bytes of the stream, max |difference|
 int fos_bench_symv_packed(int32_t device, int64_t k, int32_t reps, double* out4) {
     int ndev = 0;

@@ -747,6 +747,7 @@ enum FeasKind : int {
     FEAS_AFFINE_FACTORED = 7,        // IndAffine / LeastSquares over a dense A, factored (affine_dense.hip)
     FEAS_SPARSE_FACTORED = 8,        // IndAffine / LeastSquares over a sparse A, factored (affine_sparse_factored.hip)
     FEAS_NSPACE = 9,                 // Quadratic / LeastSquares in the n-space (nspace.hip)
+    FEAS_NSPACE_CG = 10,             // Quadratic / LeastSquares over a sparse Q / A of any size, CG in the n-space (nspace_cg.hip)
 };
 struct ProxObject {
     explicit ProxObject(int k) : kind(k) {}
@@ -839,6 +840,17 @@ void host_mspace_correct(int64_t m, const double* X, const double* G, const doub
 // lambda: 0: IndAffine(A, b), > 0: LeastSquares(A, b, lambda) (refine is then 0, zero and dependent rows are accepted)
 int sparse_factored_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int factor,
                           int refine, hipStream_t stream, ProxObject** out);
+// a work item of a segmented sparse pass (16 bytes, read wave-uniformly), one wavefront each:
+//   segment: a = row, b = first entry, c = entries (> 0), d = slot of part[] (-1: the row's only segment, never built: such rows are packed)
+//   packet:  a = first row, b = rows (<= 64 / g), c = -g (lanes per row, a power of two), d unused
+struct SfItem { int32_t a, b, c, d; };
+struct SfPass {
+    std::vector<SfItem> items;
+    std::vector<int32_t> frow, fptr;                     // cut rows and their slots of part[]: fptr[k] .. fptr[k + 1] - 1, in segment order
+    int64_t nparts = 0;
+};
+constexpr int SF_SEG_DEFAULT = 2048;          // stored entries per segment (FOS_SF_SEG: a multiple of 64 from 64 up to this)
+void sf_plan_pass(int64_t nrows, const int32_t* rp, int seg, SfPass* P);
 void launch_sf_gram(hipStream_t stream, int64_t m, int64_t L, const int32_t* rp, const int32_t* ci, const double* va, const int32_t* trp, const int32_t* tci,
                     const double* tva, double* G);
 void sparse_factored_stats(const ProxObject* a, double* out8);
@@ -859,6 +871,17 @@ int host_nspace_ls_dense(int64_t m, int64_t n, const double* A, const double* b,
 int host_nspace_ls_sparse(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, const double* x,
                           double* y);
 int host_nspace_symv_packed(int64_t k, const double* X, const double* v, double* y, int32_t* count);
+// Quadratic(Q, q) with a sparse Q and LeastSquares(A, b, lambda) with a sparse A of any size (nspace_cg.hip): y = M^-1 (x + c) by warm-started Jacobi-preconditioned CG,
+// nothing dense.  Q, A: CSC, 1-based, row indices strictly ascending in a column; of Q only the entries i >= j are read.  tol: relative stop (0: the rounding level)
+int nspace_cg_setup_quadratic(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* q, double tol, hipStream_t stream,
+                              ProxObject** out);
+int nspace_cg_setup_ls(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, double tol,
+                       hipStream_t stream, ProxObject** out);
+void nspace_cg_stats(const ProxObject* a, double* out8);
+int host_nspace_cg_quadratic(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* q, double tol, const double* x, double* y,
+                             int32_t* iters);
+int host_nspace_cg_ls(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, double tol,
+                      const double* x, double* y, int32_t* iters);
 // Separable sums of convex vector sets (sets.hip): norm balls, simplex, halfspace / hyperslab, point, free, scalar box -- contiguous blocks covering 1..n
 int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec, ProxObject** out);
 int set_blocks_stats(const ProxObject* p, hipStream_t stream, double* out8);

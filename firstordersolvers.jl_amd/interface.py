@@ -1113,6 +1113,16 @@ class NormLinf(_ProxFunction):
         self.scal = (self.lam, 0.0)
 
 
+def _cg_tol(name, tol, form):
+    """the relative stop of form="cg": a number in [0, 1); any other form takes none"""
+    tol = _finite_scalar(name + ": tol", tol)
+    if not 0.0 <= tol < 1.0:
+        raise ValueError("%s: tol must be in [0, 1)" % name)
+    if tol != 0.0 and form != "cg":
+        raise ValueError("%s: tol belongs to form='cg'" % name)
+    return tol
+
+
 class LeastSquares:
     """f(x) = lam/2 |A x - b|^2 with a dense A (m x n, 1 <= m <= n, m <= 46 000; rank-deficient and zero rows allowed), lam > 0.  The prox
     y = x - A'(A A' + I/lam)^-1 (A x - b) runs on the factored form of IndAffine with the diagonal of A A' shifted (fos_feas_set_least_squares): two passes
@@ -1121,20 +1131,25 @@ class LeastSquares:
     form="normal": the normal-equations form in the n-space, y = (I + lam A'A)^-1 (x + lam A'b), for a dense or scipy-sparse A of ANY m with n <= 46 000
     (fos_feas_set_least_squares_normal / _sparse): I + lam A'A and its inverse are kept as packed triangles, a prox is three tile products, six launches.
     form="sparse_factored": a scipy-sparse A with m <= min(n, 46 000) stays sparse, with the dense inverse of A A' + I/lam (fos_feas_set_least_squares_sparse): the
-    sparse factored IndAffine with a shifted diagonal; zero and dependent rows are accepted."""
+    sparse factored IndAffine with a shifted diagonal; zero and dependent rows are accepted.
+    form="cg": a scipy-sparse A (a dense A is converted) of ANY m and n, nothing dense kept: y = (I + lam A'A)^-1 (x + lam A'b) by warm-started Jacobi-preconditioned
+    CG on the device (fos_feas_set_least_squares_cg), three launches per iteration, ended on the recomputed residual at max(tol |x + lam A'b|, its rounding level)."""
 
     MAX_M = 46000
     MAX_N = 46000
 
-    def __init__(self, A, b, lam=1.0, factor="cholesky", form=None):
+    def __init__(self, A, b, lam=1.0, factor="cholesky", form=None, tol=0.0):
         self.lam = _finite_scalar("LeastSquares: lam", lam)
         if not self.lam > 0.0:
             raise ValueError("LeastSquares: lam > 0 is required")
         direct_factor_code(factor)
         self.factor = factor
-        if form not in (None, "normal", "sparse_factored"):
-            raise ValueError("LeastSquares: form must be None, 'normal' or 'sparse_factored', not %r" % (form,))
+        if form not in (None, "normal", "sparse_factored", "cg"):
+            raise ValueError("LeastSquares: form must be None, 'normal', 'sparse_factored' or 'cg', not %r" % (form,))
         self.form = form
+        self.tol = _cg_tol("LeastSquares", tol, form)
+        if form == "cg" and not sp.issparse(A):
+            A = sp.csc_matrix(np.atleast_2d(np.asarray(A, dtype=np.float64)))
         self.sparse = form is not None and bool(sp.issparse(A))
         if form == "sparse_factored" and not self.sparse:
             raise ValueError("LeastSquares: form='sparse_factored' keeps a scipy.sparse A")
@@ -1169,13 +1184,29 @@ class Quadratic:
     y = (I + Q)^-1 (x - q) runs in the n-space (fos_feas_set_quadratic): I + Q, scaled to a unit diagonal, and its inverse are kept as packed triangles and a prox is
     three tile products, six launches.  ONLY THE LOWER TRIANGLE of Q is read (Q[i, j], i >= j): there is no symmetry test.  factor = "cholesky" | "newton" builds
     the inverse; a Q that is not positive semidefinite is refused at set-up with the column of the failed pivot.  Feasibility(Quadratic(Q, q), IndBox(lo, hi), n)
-    under DR is the box-constrained QP."""
+    under DR is the box-constrained QP.
+    form="cg": a scipy-sparse Q (a dense Q is converted) of ANY order, nothing dense kept: y = (I + Q)^-1 (x - q) by warm-started Jacobi-preconditioned CG on the device
+    (fos_feas_set_quadratic_sparse), two launches per iteration, ended on the recomputed residual at max(tol |x - q|, its rounding level).  Only the entries i >= j are
+    read; a Q that is not positive semidefinite is refused at set-up (1 + Q[i, i] <= 0) or by the prox that meets p'(I + Q)p <= 0."""
 
     MAX_N = 46000
 
-    def __init__(self, Q, q, factor="cholesky"):
+    def __init__(self, Q, q, factor="cholesky", form=None, tol=0.0):
         direct_factor_code(factor)
         self.factor = factor
+        if form not in (None, "cg"):
+            raise ValueError("Quadratic: form must be None or 'cg', not %r" % (form,))
+        self.form = form
+        self.tol = _cg_tol("Quadratic", tol, form)
+        if form == "cg":
+            self.Q = sp.csc_matrix(Q if sp.issparse(Q) else np.atleast_2d(np.asarray(Q, dtype=np.float64)), dtype=np.float64)
+            self.Q.sum_duplicates(); self.Q.sort_indices()
+            self.q = np.ascontiguousarray(np.asarray(q, dtype=np.float64))
+            if self.Q.shape[0] < 1 or self.Q.shape[0] != self.Q.shape[1] or self.q.shape != (self.Q.shape[0],):
+                raise ValueError("Quadratic(Q, q): Q must be n x n and q of length n")
+            if not (np.all(np.isfinite(self.Q.data)) and np.all(np.isfinite(self.q))):
+                raise ValueError("Quadratic(Q, q): Q and q must be finite")
+            return
         if sp.issparse(Q):
             raise ValueError("Quadratic: Q must be dense")
         self.Q = np.ascontiguousarray(np.asarray(Q, dtype=np.float64))
@@ -1239,7 +1270,7 @@ PROX_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C
 class Feasibility:
     """struct Feasibility{T1,T2}(S1, S2, n)   Feasibility.jl:2-6.  S1, S2: IndAffine, IndBox, ConeProduct, a vector set (IndBallL2, IndBallL1,
     IndSimplex, IndHalfspace, IndHyperslab, IndPoint, IndFree), a separable function (NormL1, SqrNormL2, ElasticNet, Linear, NormL2, HuberLoss,
-    NormLinf) or a SeparableSum of them, LeastSquares(A, b, lam) with a dense A, Quadratic(Q, q), LeastSquares(form="normal" | "sparse_factored") for a tall or sparse A (all device resident: Feasibility(LeastSquares(A, b, lam), NormL1(mu), n)
+    NormLinf) or a SeparableSum of them, LeastSquares(A, b, lam) with a dense A, Quadratic(Q, q), LeastSquares(form="normal" | "sparse_factored") for a tall or sparse A, Quadratic / LeastSquares(form="cg") for a sparse Q / A of any size (all device resident: Feasibility(LeastSquares(A, b, lam), NormL1(mu), n)
     under DR is the lasso, with no host round trip), or any
     object with a `prox(y, x)` method filling y = prox_S(x) in place (the ProximableFunction protocol; evaluated on the host)."""
 
@@ -1286,15 +1317,23 @@ class HipFeasibility:
                 self.set_set(which, S)
 
     def set_set(self, which, S):
-        """set `which` (1 | 2) becomes S: an IndAffine, LeastSquares, Quadratic, IndBox, ConeProduct or an object with a prox(y, x) method; replaces what was there"""
-        if isinstance(S, Quadratic):
+        """set `which` (1 | 2) becomes S: an IndAffine, LeastSquares, Quadratic (any form), IndBox, ConeProduct or an object with a prox(y, x) method; replaces what was there"""
+        if isinstance(S, Quadratic) and S.form == "cg":
+            if S.Q.shape[0] != self.n:
+                raise ValueError("Quadratic: Q has order %d, the problem has n = %d" % (S.Q.shape[0], self.n))
+            i64, colptr, rowval, nzval = _csc_one_based(S.Q)
+            _lib.check(self._lib.fos_feas_set_quadratic_sparse(self._h, which, i64(colptr), i64(rowval), _lib.dptr(nzval), _lib.dptr(S.q), S.tol))
+        elif isinstance(S, Quadratic):
             if S.Q.shape[0] != self.n:
                 raise ValueError("Quadratic: Q has order %d, the problem has n = %d" % (S.Q.shape[0], self.n))
             _lib.check(self._lib.fos_feas_set_quadratic(self._h, which, _lib.dptr(S.Q), _lib.dptr(S.q), direct_factor_code(S.factor)))
         elif isinstance(S, LeastSquares) and S.form is not None:
             if S.A.shape[1] != self.n:
                 raise ValueError("LeastSquares: A has %d columns, the problem has n = %d" % (S.A.shape[1], self.n))
-            if S.sparse:
+            if S.form == "cg":
+                i64, colptr, rowval, nzval = _csc_one_based(S.A)
+                _lib.check(self._lib.fos_feas_set_least_squares_cg(self._h, which, S.A.shape[0], i64(colptr), i64(rowval), _lib.dptr(nzval), _lib.dptr(S.b), S.lam, S.tol))
+            elif S.sparse:
                 i64, colptr, rowval, nzval = _csc_one_based(S.A)
                 _lib.check(self._lib.fos_feas_set_least_squares_sparse(self._h, which, S.A.shape[0], i64(colptr), i64(rowval), _lib.dptr(nzval), _lib.dptr(S.b), S.lam,
                                                                        _lib.LS_FORM_CODES[S.form], direct_factor_code(S.factor)))
@@ -1479,6 +1518,13 @@ class HipFeasibility:
         _lib.check(self._lib.fos_feas_nspace_stats(self._h, which, _lib.dptr(o)))
         return {"n": int(o[0]), "m": int(o[1]), "factor": DIRECT_FACTOR_NAMES[int(o[2])], "fell_back": int(o[3]), "probe_resid": float(o[4]), "launches": int(o[5]),
                 "bytes": int(o[6]), "tiles": int(o[7])}
+
+    def nspace_cg_stats(self, which):
+        """the CG record of a Quadratic(form="cg") or a LeastSquares(form="cg") (fos_feas_nspace_cg_stats)"""
+        o = np.zeros(8)
+        _lib.check(self._lib.fos_feas_nspace_cg_stats(self._h, which, _lib.dptr(o)))
+        return {"calls": int(o[0]), "iters_total": int(o[1]), "last_iters": int(o[2]), "last_restarts": int(o[3]), "last_resid": float(o[4]),
+                "last_level": float(o[5]), "stored": int(o[6]), "launches_per_iter": int(o[7])}
 
     def affine_sparse_factored_stats(self, which):
         """the sparse factored IndAffine's (or sparse wide LeastSquares') set-up record and the segment tables of its two passes (fos_feas_affine_sparse_factored_stats, ..._plan)"""

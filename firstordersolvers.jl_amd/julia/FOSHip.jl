@@ -487,6 +487,43 @@ function host_symv_packed(X::Matrix{Float64}, v::Vector{Float64})
     check(ccall((:fos_host_symv_packed, libfoship), Cint, (Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}), Int64(length(v)), X, v, y, count))
     return y, count
 end
+# The n-space forms by conjugate gradients (csrc/nspace_cg.hip): a SPARSE Q or A of any size, nothing dense kept; warm-started Jacobi-preconditioned CG ended on the
+# recomputed residual at max(tol |x + c|, its rounding level).  Quadratic: only the entries i >= j of Q are read.
+function feas_set_quadratic_sparse!(handle::Ptr{Cvoid}, which::Integer, Q::SparseArrays.SparseMatrixCSC, q::AbstractVector, tol::Real = 0.0)
+    Qs = SparseArrays.SparseMatrixCSC{Float64,Int64}(Q)
+    qv = Vector{Float64}(q)
+    GC.@preserve Qs qv check(ccall((:fos_feas_set_quadratic_sparse, libfoship), Cint, (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble),
+                                   handle, Int32(which), Qs.colptr, Qs.rowval, Qs.nzval, qv, Float64(tol)))
+end
+function feas_set_least_squares_cg!(handle::Ptr{Cvoid}, which::Integer, A::SparseArrays.SparseMatrixCSC, b::AbstractVector, lambda::Real, tol::Real = 0.0)
+    As = SparseArrays.SparseMatrixCSC{Float64,Int64}(A)
+    bv = Vector{Float64}(b)
+    GC.@preserve As bv check(ccall((:fos_feas_set_least_squares_cg, libfoship), Cint,
+                                   (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble),
+                                   handle, Int32(which), Int64(size(As, 1)), As.colptr, As.rowval, As.nzval, bv, Float64(lambda), Float64(tol)))
+end
+function feas_nspace_cg_stats(handle::Ptr{Cvoid}, which::Integer)
+    out = zeros(Float64, 8)
+    check(ccall((:fos_feas_nspace_cg_stats, libfoship), Cint, (Ptr{Cvoid}, Int32, Ptr{Cdouble}), handle, Int32(which), out))
+    return (calls = Int(out[1]), iters_total = Int(out[2]), last_iters = Int(out[3]), last_restarts = Int(out[4]), last_resid = out[5], last_level = out[6],
+            stored = Int(out[7]), launches_per_iter = Int(out[8]))
+end
+# test entries: the host emulations of the cg forms (no GPU needed) -> y and the CG iterations taken
+function host_quadratic_cg(Q::SparseArrays.SparseMatrixCSC{Float64,Int64}, q::Vector{Float64}, tol::Real, x::Vector{Float64})
+    y = similar(x)
+    iters = Ref{Int32}(0)
+    check(ccall((:fos_host_quadratic_cg, libfoship), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Int32}),
+                Int64(length(x)), Q.colptr, Q.rowval, Q.nzval, q, Float64(tol), x, y, iters))
+    return y, Int(iters[])
+end
+function host_least_squares_cg(A::SparseArrays.SparseMatrixCSC{Float64,Int64}, b::Vector{Float64}, lambda::Real, tol::Real, x::Vector{Float64})
+    y = similar(x)
+    iters = Ref{Int32}(0)
+    check(ccall((:fos_host_least_squares_cg, libfoship), Cint,
+                (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Int32}),
+                Int64(size(A, 1)), Int64(size(A, 2)), A.colptr, A.rowval, A.nzval, b, Float64(lambda), Float64(tol), x, y, iters))
+    return y, Int(iters[])
+end
 # test entry: the host emulation of the sparse factored IndAffine (no GPU needed)
 function host_affine_sparse_factored(A::SparseArrays.SparseMatrixCSC{Float64,Int64}, b::Vector{Float64}, refine::Integer, x::Vector{Float64})
     y = similar(x)
@@ -566,6 +603,11 @@ mutable struct HipFeasData <: FOSSolverData
                                                get(model.options, :affine_factor, :cholesky))
             elseif S isa ProximalOperators.Quadratic && hasproperty(S, :Q) && S.Q isa Matrix && size(S.Q, 1) <= 46000
                 feas_set_quadratic!(d.handle, which, S.Q, S.q, get(model.options, :affine_factor, :cholesky))      # a dense Q: the n-space form
+            elseif S isa ProximalOperators.Quadratic && hasproperty(S, :Q) && S.Q isa SparseArrays.SparseMatrixCSC
+                feas_set_quadratic_sparse!(d.handle, which, S.Q, S.q, get(model.options, :cg_tol, 0.0))      # a sparse Q of any order: CG in the n-space
+            elseif S isa ProximalOperators.LeastSquares && hasproperty(S, :A) && S.A isa SparseArrays.SparseMatrixCSC && hasproperty(S, :lambda)
+                # a sparse A beyond both kept-inverse forms (n > 46 000 and m > min(n, 46 000)): CG in the n-space, nothing dense
+                feas_set_least_squares_cg!(d.handle, which, S.A, S.b, S.lambda, get(model.options, :cg_tol, 0.0))
             elseif vectorset_block(S) !== nothing           # a ball, simplex, halfspace, hyperslab, point, the free set or a separable function: one block of length n
                 feas_set_blocks!(d.handle, which, model.n, [(vectorset_block(S)..., Int64(model.n))])
             else                                            # any other ProximableFunction: prox!(y, S, x) on host vectors [Feasibility.jl:2-6]

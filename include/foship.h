@@ -585,6 +585,30 @@ int fos_host_least_squares_normal(int64_t m, int64_t n, const double* A, const d
 int fos_host_least_squares_sparse(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda,
                                   int32_t form, const double* x, double* y);
 int fos_host_symv_packed(int64_t k, const double* X, const double* v, double* y, int32_t* count);
+/* The N-SPACE forms BY CONJUGATE GRADIENTS (csrc/nspace_cg.hip): the same prox  y = M^-1 (x + c)  for a SPARSE Q or A of ANY size -- nothing dense is kept, no bound
+ * on m or n but the 2e9 stored entries of every sparse entry of this ABI.  The counterpart of ProximalOperators' iterative = true for Quadratic and LeastSquares, two of
+ * the ProximableFunctions Feasibility.jl:2-6 takes as either set.  Jacobi-preconditioned CG on the device, warm-started from the previous answer
+ * (fos_feas_set_iterate: the next prox starts from D^-1 (x + c)); the TRUE residual x + c - M y is recomputed before and after CG and the prox ends at
+ * |r|_2 <= max(tol |x + c|_2, 16 eps | |M||y| + |x + c| |_2)  (tol = 0: the rounding level alone; LeastSquares: |M| read as I + lambda |A'||A|).  Two launches per CG
+ * iteration (Quadratic), three (LeastSquares); every sum in a fixed order: a prox repeats bit for bit.
+ *   fos_feas_set_quadratic_sparse      Quadratic(Q, q), Q: n x n CSC, 1-based, row indices strictly ascending inside a column; ONLY THE ENTRIES i >= j are read (as
+ *                                      fos_feas_set_quadratic reads the lower triangle) and mirrored; empty rows and columns are fine.  1 + Q[i, i] not a positive
+ *                                      finite number: FOS_EINVAL naming the column.  A Q that is not positive semidefinite is found by CG (p'(I + Q)p <= 0): the PROX
+ *                                      then returns FOS_EINVAL.
+ *   fos_feas_set_least_squares_cg      LeastSquares(A, b, lambda), A: m x n CSC as above, ANY m, n >= 1; zero rows, zero columns and dependent rows are fine.
+ * tol in [0, 1).  0-based or decreasing colptr, an index out of range, non-finite data, lambda <= 0 or not finite, a bad tol: FOS_EINVAL; the set stays as it was. */
+int fos_feas_set_quadratic_sparse(fos_feas_handle h, int32_t which, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* q, double tol);
+int fos_feas_set_least_squares_cg(fos_feas_handle h, int32_t which, int64_t m, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b,
+                                  double lambda, double tol);
+/* out8 = prox calls so far, CG iterations so far, CG iterations / restarts of the last prox, its |x + c - M y|_2 and rounding level | |M||y| + |x + c| |_2, stored
+ * entries (of I + Q mirrored; of A and A' together), kernel launches per CG iteration (2 | 3).  Another kind of set: FOS_EINVAL. */
+int fos_feas_nspace_cg_stats(fos_feas_handle h, int32_t which, double* out8);
+/* Test-only host emulations (no GPU needed): the same validation, matrices, work items, recurrence, stop rule and summation order as the kernels, from a cold start.
+ * x, y: n-vectors; iters (may be NULL) receives the CG iterations taken. */
+int fos_host_quadratic_cg(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* q, double tol, const double* x, double* y,
+                          int32_t* iters);
+int fos_host_least_squares_cg(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, double tol,
+                              const double* x, double* y, int32_t* iters);
 /* Measurement: the one-right-hand-side tile product against the two-right-hand-side kernel of direct = true's reduced form on the SAME tiles (second right-hand side
  * zero), `reps` products each on a generated symmetric matrix of order k.  out4 = milliseconds per product (one rhs), (two rhs), bytes of the stream, max |difference|. */
 int fos_bench_symv_packed(int32_t device, int64_t k, int32_t reps, double* out4);
