@@ -1727,7 +1727,8 @@ int fos_bench_cg_chain(fos_handle h, int32_t iters, int32_t reps, int32_t use_gr
     FOS_TRY(kkt_apply_full(h, c, h->W, h->AP));
     launch_cg_init(c, h->RHS, h->AP, h->R, h->PB[1]);
     launch_cg_init_finalize(c, h->R, -1.0, INT32_MAX, 0);
-    const int variant = h->cg_variant >= 0 ? h->cg_variant : (h->fuse_p ? FOS_CG_FUSED_P : FOS_CG_REFERENCE);
+    int variant = h->cg_variant >= 0 ? h->cg_variant : (h->fuse_p ? FOS_CG_FUSED_P : FOS_CG_REFERENCE);
+    if (variant == FOS_CG_FUSED_P && h->op.dev.npanel > 0) variant = FOS_CG_REFERENCE;      // (as fos_get_cg_variant resolves it)
     const bool merged = variant == FOS_CG_MERGED_SWEEP || variant == FOS_CG_MERGED_UPDATE;
     // (the producer flags of the update kernels carry the launch's sequence number: a replayed graph would present the SAME
     //  numbers again and the consumers would not wait -- the graph runs without the producers)
@@ -1801,9 +1802,18 @@ int fos_sync(fos_handle h) {
     return FOS_OK;
 }
 
+// FOS_CG_FUSED_P closes the previous iteration and builds p on the fly inside kkt2_kernel; the window-panel sweeps (kkt2_win_kernel) have no such
+// form -- they would apply M to the PREVIOUS p and leave the iteration unclosed -- so the variant is refused where the operator is stored that way
+static int refuse_fused_p_on_window_panels(const fos_solver* h) {
+    if (h->op.dev.npanel == 0) return FOS_OK;
+    set_error("FOS_CG_FUSED_P: the operator is stored in window panels, whose sweeps cannot build p on the fly (row-block and tile storage only)");
+    return FOS_EUNSUPPORTED;
+}
+
 int fos_set_tuning(fos_handle h, int32_t spmv_workgroups, int32_t cg_chunk, int32_t fuse_p) {
     if (!h) { set_error("NULL handle"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
+    if (fuse_p > 0) FOS_TRY(refuse_fused_p_on_window_panels(h));
     if (fuse_p >= 0) { h->fuse_p = fuse_p != 0; h->cg_variant = -1; }
     if (cg_chunk > 0) h->cg_chunk = cg_chunk;
     if (spmv_workgroups > 0) FOS_TRY(operator_repartition(h, spmv_workgroups));
@@ -1817,6 +1827,7 @@ int fos_set_cg_variant(fos_handle h, int32_t variant) {
         set_error("FOS_CG_RESIDENT: the operator does not qualify (%s)", h->op.res_plan.why.empty() ? "no plan" : h->op.res_plan.why.c_str());
         return FOS_EUNSUPPORTED;
     }
+    if (variant == FOS_CG_FUSED_P) FOS_TRY(refuse_fused_p_on_window_panels(h));
     h->cg_variant = variant;
     if (variant >= 0) h->fuse_p = variant == FOS_CG_FUSED_P;
     h->last_cg_pred = 0; h->cg_same_run = 0;
@@ -1844,6 +1855,7 @@ int fos_get_cg_variant(fos_handle h, int32_t* variant) {
     // small enough for the register form keep the reference's arithmetic by default
     if (h->cg_variant < 0 && !h->fuse_p && !h->sharded() && res_usable && res_default && h->op.res_plan.stream && 2 * h->op.res_plan.G >= h->cus) v = FOS_CG_RESIDENT;
     if (v == FOS_CG_RESIDENT && !res_usable) v = FOS_CG_MERGED_UPDATE;
+    if (v == FOS_CG_FUSED_P && h->op.dev.npanel > 0) v = FOS_CG_REFERENCE;      // (FOS_CG_FUSE_P is set for the whole process: window-panel handles keep three launches)
     if (v == FOS_CG_MERGED_SWEEP && h->sharded()) v = FOS_CG_MERGED_UPDATE;
     if (v == FOS_CG_MERGED_UPDATE && h->tr.peer_on && !fold_env) v = FOS_CG_REFERENCE;
     *variant = v;

@@ -513,12 +513,14 @@ class HipHSDE:
                 "factor": DIRECT_FACTOR_NAMES[int(out[4])], "invert_s": float(out[5]), "probe_resid": float(out[6]), "fell_back": int(out[7])}
 
     def set_tuning(self, spmv_workgroups=0, cg_chunk=0, fuse_p=-1):
-        """fuse_p: -1 keeps the library's choice, 0 / 1 force the three- / two-launch CG iteration."""
+        """fuse_p: -1 keeps the library's choice, 0 / 1 force the three- / two-launch CG iteration (1 on an operator stored in window panels:
+        FosError(FOS_EUNSUPPORTED), nothing changes)."""
         _lib.check(self._lib.fos_set_tuning(self._h, spmv_workgroups, cg_chunk, fuse_p))
 
     def set_cg_variant(self, variant):
         """which CG recurrence the affine projection runs: 'reference' | 'fused_p' | 'merged_sweep' | 'merged_update' | 'resident' | None (default).
-        'resident' (one launch per solve, operator and vectors in registers) raises FosError(FOS_EUNSUPPORTED) when the operator does not qualify."""
+        'resident' (one launch per solve, operator and vectors in registers) raises FosError(FOS_EUNSUPPORTED) when the operator does not qualify,
+        'fused_p' when the operator is stored in window panels (their sweeps cannot build p on the fly)."""
         codes = {None: -1, "default": -1, "reference": _lib.CG_REFERENCE, "fused_p": _lib.CG_FUSED_P,
                  "merged_sweep": _lib.CG_MERGED_SWEEP, "merged_update": _lib.CG_MERGED_UPDATE, "resident": _lib.CG_RESIDENT}
         _lib.check(self._lib.fos_set_cg_variant(self._h, codes[variant] if not isinstance(variant, int) else variant))

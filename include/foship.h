@@ -439,7 +439,8 @@ int fos_host_stacked_spmv_mode(int64_t m, int64_t n, const int64_t* colptr, cons
                                const double* v, double* out, int32_t window_mode, int64_t* stats16);
 
 /* tuning knobs (0 keeps the default): workgroups of the SpMV grid, CG iterations enqueued per host poll;
- * fuse_p: -1 keeps the choice made at fos_create, 0 / 1 force the three- / two-launch CG iteration (see fos_bench_cg_chain) */
+ * fuse_p: -1 keeps the choice made at fos_create, 0 / 1 force the three- / two-launch CG iteration (see fos_bench_cg_chain);
+ * fuse_p = 1 on an operator stored in window panels: FOS_EUNSUPPORTED, nothing is changed (see FOS_CG_FUSED_P) */
 int fos_set_tuning(fos_handle h, int32_t spmv_workgroups, int32_t cg_chunk, int32_t fuse_p);
 
 /* Which recurrence conjugategradient! (src/utilities/conjugategradients.jl:31-55) runs in.  All four produce the same Krylov
@@ -447,6 +448,8 @@ int fos_set_tuning(fos_handle h, int32_t spmv_workgroups, int32_t cg_chunk, int3
  * max_iters) to the same recursively updated residual; they differ in launches and reduction points per iteration:
  *   FOS_CG_REFERENCE      the reference's recurrence: sweep Ap = M p -> alpha, x, r update -> beta, p update   (3 launches, 2 reduction points)
  *   FOS_CG_FUSED_P        the p update rides on the next sweep                                                (2 launches, 2 reduction points; measured slower)
+ *                         Row-block and tile storage only: fos_set_cg_variant returns FOS_EUNSUPPORTED on an operator stored in window panels, whose
+ *                         sweeps cannot build p on the fly; FOS_CG_FUSE_P in the environment leaves such handles on the reference recurrence.
  *   FOS_CG_MERGED_SWEEP   merged-reduction (Chronopoulos-Gear) recurrence: s = M p by recurrence from w = M r, one
  *                         reduction point carrying r.r and w.r; the sweep closes the iteration            (2 launches, single GPU only)
  *   FOS_CG_MERGED_UPDATE  the same, the update kernel closes the iteration: ONE exchange of four doubles per iteration
