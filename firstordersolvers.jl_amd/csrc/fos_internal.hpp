@@ -516,7 +516,13 @@ struct ResLaunch {
     unsigned long long* grec;        // [2][G][4][2] words: the workgroups' records of the four sums
     unsigned long long* crec;        // [2][G][tmax][2][2] words: the workgroups' column sums (units of more than one workgroup)
     int64_t timeout_ticks;
+    // the fp32 walk of the streamed form (resident.hip, rs_lowp_decide; all zero: none): the tile values as float at val's offsets, delta >= |A - fl32(A)|_2,
+    // eta = the share of a solve's stop tolerance the walk may cost, mode 1: by the rule, 2: every sweep behind the start (tests), and the device
+    // record of the last solve {fp32 sweeps, reverted, bound}
+    const float* val32; double lowp_delta, lowp_eta; int lowp_mode; double* lowp_out;
 };
+// rounds `nvals` tile values to val32 and leaves, per workgroup of the streamed plan, its bound of |A - fl32(A)|_2 in part[G] (the maximum is delta)
+hipError_t launch_rs_lowp_setup(hipStream_t stream, const BlkDesc* blk, const double* val, int64_t nvals, const ResWG* wg, int G, float* val32, double* part);
 // x (in: the start iterate, out: the solution), r_0 = rhs - M v; fold != nullptr: the sums cross the ranks through the mailboxes
 // (hipSuccess, or the error of the LDS opt-in: a plan that does not fit is refused by resident_setup before it gets here)
 hipError_t launch_cg_resident(const LaunchCtx& c, const ResLaunch& rl, double2* x, const double2* rhs, const double2* v, double tol, int maxit,

@@ -77,6 +77,10 @@ struct Operator {
     bool res_ok = false;                       // this handle's operator qualifies (under the current workgroup budget)
     bool res_all = false;                      // ... and so does every rank's (sharded: the vote of global_setup)
     int res_gmax = 0;                          // the budget the plan was made for
+    // the streamed form's fp32 walk (resident_lowp_ensure; res.val32 / res.lowp_out name them): the tile values as float, the last solve's record
+    float* res_val32 = nullptr;
+    bool res_lowp_pending = false;             // the plan in force has not been given its float copy and delta yet (resident_lowp_ensure)
+    double* res_lowp_out = nullptr;
 };
 
 // ------------------------------------------------------------------------------------------------ the handle
@@ -107,6 +111,8 @@ struct fos_solver {
     int cus = 256;                             // compute units of `device`
     bool psd_fuse = true;                      // FOS_PSD_FUSE=0: relaxation, projection and the step's last pass stay separate launches
     bool relax_ew = true;                      // FOS_RELAX_EW=0: the relaxation does not project the elementwise cones in the same pass
+    int rs_lowp = 1;                           // FOS_RS_LOWP: 0 the streamed CG solve reads doubles only, 1 fp32 tiles by the rule (default), 2 on every sweep behind the start (tests)
+    double rs_lowp_eta = 0.1;                  // FOS_RS_LOWP_ETA: the share of min(a solve's tolerance, the schedule's floor l eps) the fp32 sweeps may cost
 
     // scalars
     fos::DevState* st = nullptr;
@@ -265,6 +271,7 @@ int kkt_apply_full(fos_solver* h, const LaunchCtx& c, const d2* w, d2* out, bool
 int operator_setup(fos_solver* h, const int64_t* colptr, const int64_t* rowval, const double* nzval);
 int operator_repartition(fos_solver* h, int nwg);
 int resident_setup(fos_solver* h, int gmax);
+int resident_lowp_ensure(fos_solver* h);    // the streamed plan's float copy and delta, once per plan: before a resident solve
 // direct.cpp: prox!(y, S1::IndAffine([Q -I], 0), x) in the handle's exact form, the result left in h->SOL
 int prox_affine_direct(fos_solver* h, const d2* x);
 

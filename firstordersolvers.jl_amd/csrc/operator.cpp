@@ -226,6 +226,36 @@ static void plan_stats8(const ResPlan& p, bool ok, bool all, int64_t* stats8) {
     stats8[6] = p.tmax; stats8[7] = all ? 1 : 0;
 }
 
+// The streamed form's fp32 walk (resident.hip, rs_lowp_decide), for the plan in force: val32 = the tile values rounded to float, at val's offsets and
+// from the same allocator (+4 bytes per stored value), and delta >= |A - fl32(A)|_2 from the workgroups' Gram bounds (rs_lowp_delta_kernel; widened by
+// 2^-20, far more than the rounding of the Gram sums themselves).  delta == 0: every value is a float already.  An operator whose values do not round to
+// finite floats keeps the doubles.  Built when the resident solve is what the handle runs -- at fos_create where it is the default, else in front of the
+// first resident solve (cg_solve): a handle that never runs it never pays the bytes.  A new plan (resident_setup) asks for it again.
+int resident_lowp_ensure(fos_solver* h) {
+    Operator& o = h->op;
+    if (!o.res_lowp_pending) return FOS_OK;
+    o.res_lowp_pending = false;
+    if (!o.res_ok || !o.res_plan.stream || h->rs_lowp == 0 || h->sharded() || o.dev.nnz_padded <= 0) return FOS_OK;
+    const int G = o.res_plan.G;
+    if (!o.res_val32) {
+        FOS_TRY(dev_alloc(h, &o.res_val32, (size_t)o.dev.nnz_padded));
+        FOS_TRY(dev_zeros(h, &o.res_lowp_out, 4));
+    }
+    double* part = nullptr;
+    FOS_TRY(dev_alloc(h, &part, (size_t)G));
+    std::vector<double> hp((size_t)G);
+    hipError_t e = launch_rs_lowp_setup(h->stream, o.dev.blk, o.dev.val, o.dev.nnz_padded, o.res_wg, G, o.res_val32, part);
+    if (e == hipSuccess) e = hipMemcpyAsync(hp.data(), part, sizeof(double) * hp.size(), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    dev_release(h, &part);                                             // (on every path)
+    FOS_HIP(e);
+    double delta = 0.0;
+    for (double v : hp) delta = (v > delta || v != v) ? v : delta;
+    if (!(delta < std::numeric_limits<double>::infinity())) return FOS_OK;
+    o.res.val32 = o.res_val32; o.res.lowp_out = o.res_lowp_out; o.res.lowp_delta = delta * (1.0 + 0x1p-20); o.res.lowp_mode = h->rs_lowp;
+    return FOS_OK;
+}
+
 // FOS_CG_RESIDENT: (re)plan the resident solve for at most `gmax` workgroups -- every one of them must be on the device at once, so ranks that
 // share ONE device (the tests' stand-in for a multi-GPU box) share its CUs
 int resident_setup(fos_solver* h, int gmax) {
@@ -259,6 +289,8 @@ int resident_setup(fos_solver* h, int gmax) {
     o.res = plan_launch(plan, o.res);
     static const double res_wait_s = getenv("FOS_RESIDENT_WAIT_S") ? atof(getenv("FOS_RESIDENT_WAIT_S")) : 5.0;
     o.res.timeout_ticks = (int64_t)(res_wait_s * 1e8);
+    o.res.val32 = nullptr; o.res.lowp_out = nullptr; o.res.lowp_delta = 0.0; o.res.lowp_eta = h->rs_lowp_eta; o.res.lowp_mode = 0;
+    o.res_lowp_pending = true;                             // (resident_lowp_ensure, in front of the first resident solve on this plan)
     o.res_plan = plan; o.res_ok = true; o.res_all = !h->sharded();
     return FOS_OK;
 }
@@ -300,6 +332,19 @@ int fos_resident_stats(fos_handle h, int64_t* stats8) {
     const Operator& o = h->op;
     plan_stats8(o.res_plan, o.res_ok, h->sharded() ? o.res_all : o.res_ok, stats8);
     if (!o.res_ok) set_error("FOS_CG_RESIDENT: %s", o.res_plan.why.empty() ? "no plan" : o.res_plan.why.c_str());
+    return FOS_OK;
+}
+
+int fos_resident_lowp_stats(fos_handle h, double* stats8) {
+    if (!h || !stats8) { set_error("NULL argument"); return FOS_EINVAL; }
+    const Operator& o = h->op;
+    for (int k = 0; k < 8; ++k) stats8[k] = 0.0;
+    if (!o.res_ok || !o.res.val32) return FOS_OK;
+    double rec[4];
+    FOS_HIP(hipStreamSynchronize(h->stream));
+    FOS_HIP(hipMemcpy(rec, o.res.lowp_out, sizeof(rec), hipMemcpyDeviceToHost));
+    stats8[0] = o.res.lowp_delta; stats8[1] = rec[0]; stats8[2] = rec[1]; stats8[3] = rec[2];
+    stats8[4] = 4.0 * (double)o.dev.nnz_padded; stats8[5] = (double)o.res.lowp_mode; stats8[6] = o.res.lowp_eta;
     return FOS_OK;
 }
 

@@ -37,6 +37,7 @@ struct ResArgs {
     DevState* st;
     const BlkDesc* blk;
     const double* val;
+    const float* val32;        // streamed form: the same values as float, same offsets (nullptr: every sweep reads val -- see rs_lowp_decide)
     const ResWG* wg;
     int G;
     unsigned long long* grec;
@@ -49,6 +50,10 @@ struct ResArgs {
     PeerBox pb;
     uint32_t seq_base;
     long long timeout_ticks;
+    // the fp32 walk of the streamed form (val32 != nullptr): delta >= |A - fl32(A)|_2, the residual norm from which sweeps read val32, the error budget
+    // the guard holds them to (eta tol / 2; negative: no guard), and where the last solve's record goes: {fp32 sweeps, reverted, bound B}
+    double lowp_delta, lowp_theta, lowp_budget;
+    double* lowp_out;
 };
 
 __device__ __forceinline__ void res_st_word(unsigned long long* p, unsigned long long w) { __hip_atomic_store(p, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -122,7 +127,7 @@ __device__ long long g_res_stamps[4 * 16 * 64 * 16];
 #endif
 
 // what the communication wavefronts hand to the compute wavefronts through LDS at the end of an exchange
-enum ResCtl { RC_ALPHA = 0, RC_BETA, RC_GTX, RC_GTY, RC_STOP, RC_NEAR, RC_COUNT };     // RC_STOP: 0 go on, 1 CG has stopped, 2 an exchange failed
+enum ResCtl { RC_ALPHA = 0, RC_BETA, RC_GTX, RC_GTY, RC_STOP, RC_NEAR, RC_LOWP, RC_COUNT };     // RC_STOP: 0 go on, 1 CG has stopped, 2 an exchange failed; RC_LOWP: the next sweep reads the float values (streamed form)
 
 // The exchange of the four sums across the GPUs by ONE wavefront (the words, slots and sequence numbers of peer_fold_sum, dev_common.hpp --
 // the launch-per-iteration kernels and this one speak the same protocol): lane = (rank r, value v, half hh), two rounds cover 16 ranks.
@@ -621,7 +626,8 @@ __global__ __launch_bounds__(LB) void cg_resident_kernel(ResArgs a) {
 #ifndef RS_XC
 #define RS_XC 2
 #endif
-__device__ __forceinline__ void res_tile_plain(const double (&val)[TILE_GROUP], const d2 g, const d2* __restrict__ gcol, d2& u, double (&a1)[TILE_GROUP],
+template <class VT>
+__device__ __forceinline__ void res_tile_plain(const VT (&val)[TILE_GROUP], const d2 g, const d2* __restrict__ gcol, d2& u, double (&a1)[TILE_GROUP],
                                                double (&a2)[TILE_GROUP]) {
 #pragma unroll
     for (int h = 0; h < TILE_GROUP / RS_XC; ++h) {                   // (RS_XC column elements in flight at a time: four registers each)
@@ -630,7 +636,7 @@ __device__ __forceinline__ void res_tile_plain(const double (&val)[TILE_GROUP], 
         for (int k = 0; k < RS_XC; ++k) xc[k] = gcol[RS_XC * h + k];
 #pragma unroll
         for (int k = 0; k < RS_XC; ++k) {
-            const double v = val[RS_XC * h + k];
+            const double v = (double)val[RS_XC * h + k];             // (float values: widened as they are consumed, the same FMAs in the same order)
             u.x += v * xc[k].x; u.y += v * xc[k].y;
             a1[RS_XC * h + k] += v * g.x; a2[RS_XC * h + k] += v * g.y;
         }
@@ -656,10 +662,15 @@ __device__ __forceinline__ BlkDesc rs_desc(const BlkDesc* blk, int i) {
 // requests chunk `grp` of tile `blk`.  ALWAYS eight loads: for a tile without that group (a narrower unit; the group behind the walk's last) they all read
 // the tile's first value, one address for the wavefront, and are never consumed -- a request that is there on one path and not on another leaves the
 // compiler no count of the loads in flight behind a chunk, and every chunk then waits for ALL requests (s_waitcnt vmcnt(0)): the ring held one chunk
-__device__ __forceinline__ void rs_request(const ResArgs& a, int blk, int grp, int lane, double (&val)[TILE_GROUP]) {
+// (VT = float: the same chunk of val32 -- same offsets, half the bytes; the ring is then twice as deep, rs_walk)
+template <class VT> __device__ __forceinline__ const VT* rs_values(const ResArgs& a);
+template <> __device__ __forceinline__ const double* rs_values<double>(const ResArgs& a) { return a.val; }
+template <> __device__ __forceinline__ const float* rs_values<float>(const ResArgs& a) { return a.val32; }
+template <class VT>
+__device__ __forceinline__ void rs_request(const ResArgs& a, int blk, int grp, int lane, VT (&val)[TILE_GROUP]) {
     const BlkDesc d = rs_desc(a.blk, blk);
     const bool live = TILE_GROUP * grp < d.steps();                  // wave-uniform
-    const double* __restrict__ vp = a.val + d.nnz0 + (live ? 64 * TILE_GROUP * grp : 0) + (live ? lane : 0);
+    const VT* __restrict__ vp = rs_values<VT>(a) + d.nnz0 + (live ? 64 * TILE_GROUP * grp : 0) + (live ? lane : 0);
 #pragma unroll
     for (int t = 0; t < TILE_GROUP; ++t) val[t] = __builtin_nontemporal_load(vp + 64 * t);      // (zero-padded storage beyond the tile's rows and columns)
 }
@@ -694,9 +705,9 @@ __device__ __forceinline__ void rs_rows_store(const ResArgs& a, int blk_first, i
 
 // one column group of a wavefront's tiles Q, Q + 1, ...: the tiles NEST (tile Q + 1 inside tile Q's branch), so the paths of wavefronts with fewer tiles
 // leave the group and do not meet the others again inside it
-template <int Q, int NT, int D>
+template <int Q, int NT, int D, class VT>
 __device__ __forceinline__ void rs_group(const ResArgs& a, int bf, int cnt, int grp, int c0, int lane, const d2* __restrict__ s_gcol, d2* __restrict__ mycol,
-                                         RsRows<NT>& R, double (&val)[D][TILE_GROUP], double (&a1)[TILE_GROUP], double (&a2)[TILE_GROUP]) {
+                                         RsRows<NT>& R, VT (&val)[D][TILE_GROUP], double (&a1)[TILE_GROUP], double (&a2)[TILE_GROUP]) {
     if constexpr (Q < NT) {
         if (Q < cnt) {                             // wave-uniform
             const BlkDesc d = rs_desc(a.blk, bf + Q);
@@ -715,7 +726,7 @@ __device__ __forceinline__ void rs_group(const ResArgs& a, int bf, int cnt, int 
 #pragma unroll
                 for (int u = 0; u < TILE_GROUP; ++u) a1[u] = a2[u] = 0.0;
             }
-            rs_group<Q + 1, NT, D>(a, bf, cnt, grp, c0, lane, s_gcol, mycol, R, val, a1, a2);
+            rs_group<Q + 1, NT, D, VT>(a, bf, cnt, grp, c0, lane, s_gcol, mycol, R, val, a1, a2);
         }
     }
 }
@@ -730,35 +741,50 @@ __device__ __forceinline__ void rs_group(const ResArgs& a, int bf, int cnt, int 
 // is eight loads (rs_request) and the tiles of a group nest, so behind a group's first chunk the waits are exact counts (rs_group).
 // Column sums: per lane over the segment's tiles in tile order, then tile_colsum8's lane order, STORED (a unit is one segment per wavefront: no
 // read-modify-write); the wavefronts are added in wavefront order by the communication wavefront.
+// THE FP32 WALK (VT = float, a sweep whose s_ctl[RC_LOWP] is set: rs_lowp_decide): the same chunks of val32, widened to double as they are consumed --
+// every FMA, accumulator and summation order is the fp64 walk's.  A chunk is 2 KB there, so the ring is twice as deep in the same 32 registers: a
+// wavefront keeps its 8 KB in flight.
 #ifndef RS_RING
 #define RS_RING 2
 #endif
-template <int TMAX, int NT>
+template <int TMAX, int NT, class VT>
+__device__ __forceinline__ void rs_walk(const ResArgs& a, int blk_first, int cnt, int c0, int lane, const d2* __restrict__ s_gcol, d2* __restrict__ mycol,
+                                        RsRows<NT>& R) {
+    constexpr int RING = RS_RING * (int)(sizeof(double) / sizeof(VT));
+    constexpr int D = NT < RING ? NT : RING;
+    int tw = 0;                                // the wavefront's longest tile: its groups bound the walk
+#pragma unroll
+    for (int q = 0; q < NT; ++q) { const int t = rs_desc(a.blk, blk_first + (q < cnt ? q : cnt - 1)).steps(); tw = t > tw ? t : tw; }
+    const int ngrp = ((tw < TMAX ? tw : TMAX) + TILE_GROUP - 1) / TILE_GROUP;
+    VT val[D][TILE_GROUP];
+    double a1[TILE_GROUP], a2[TILE_GROUP];
+#pragma unroll
+    for (int s = 0; s < D; ++s) if (s < cnt) rs_request<VT>(a, blk_first + s, 0, lane, val[s]);
+#pragma unroll
+    for (int q = 0; q < NT; ++q) R.ww[q] = make_double2(0.0, 0.0);
+#pragma unroll
+    for (int u = 0; u < TILE_GROUP; ++u) a1[u] = a2[u] = 0.0;
+    for (int grp = 0; grp < ngrp; ++grp) {
+        int bf = blk_first;
+        asm volatile("" : "+s"(bf));           // (opaque per group: the descriptor loads stay in the loop, see above)
+        rs_group<0, NT, D, VT>(a, bf, cnt, grp, c0, lane, s_gcol, mycol, R, val, a1, a2);
+    }
+}
+template <int TMAX, int NT, bool LOWP>
 __device__ __forceinline__ void rs_sweep(const ResArgs& a, int blk_first, int cnt, int c0, int lane, const d2* __restrict__ s_gcol, const double* s_ctl,
                                          d2* __restrict__ mycol, RsRows<NT>& R, double (&acc)[4], bool early = false,
                                          const double* __restrict__ cbh = nullptr) {
-    constexpr int D = NT < RS_RING ? NT : RS_RING;
     // (early: an exchange round that carries r.r alone -- no tile is walked, the other three sums are zero)
     if (early) cnt = 0;
     mycol[lane] = make_double2(0.0, 0.0);
     acc[0] = acc[1] = acc[2] = acc[3] = 0.0;
     if (cnt > 0) {                                 // wave-uniform
-        int tw = 0;                                // the wavefront's longest tile: its groups bound the walk
-#pragma unroll
-        for (int q = 0; q < NT; ++q) { const int t = rs_desc(a.blk, blk_first + (q < cnt ? q : cnt - 1)).steps(); tw = t > tw ? t : tw; }
-        const int ngrp = ((tw < TMAX ? tw : TMAX) + TILE_GROUP - 1) / TILE_GROUP;
-        double val[D][TILE_GROUP], a1[TILE_GROUP], a2[TILE_GROUP];
-#pragma unroll
-        for (int s = 0; s < D; ++s) if (s < cnt) rs_request(a, blk_first + s, 0, lane, val[s]);
-#pragma unroll
-        for (int q = 0; q < NT; ++q) R.ww[q] = make_double2(0.0, 0.0);
-#pragma unroll
-        for (int u = 0; u < TILE_GROUP; ++u) a1[u] = a2[u] = 0.0;
-        for (int grp = 0; grp < ngrp; ++grp) {
-            int bf = blk_first;
-            asm volatile("" : "+s"(bf));           // (opaque per group: the descriptor loads stay in the loop, see above)
-            rs_group<0, NT, D>(a, bf, cnt, grp, c0, lane, s_gcol, mycol, R, val, a1, a2);
-        }
+        // which values this sweep reads: one decision per sweep, the same in every wavefront of the grid (wave-uniform, outside the group loop)
+        // (LOWP: the kernel instance of a plan with a float copy; the other instance is the fp64 walk alone, as it was before there was a second one)
+        bool lowp = false;
+        if constexpr (LOWP) lowp = __builtin_amdgcn_readfirstlane((int)(s_ctl[RC_LOWP] != 0.0)) != 0;
+        if (lowp) rs_walk<TMAX, NT, float>(a, blk_first, cnt, c0, lane, s_gcol, mycol, R);
+        else rs_walk<TMAX, NT, double>(a, blk_first, cnt, c0, lane, s_gcol, mycol, R);
         // the rows' epilogue: [c; b] from the caller's registers (cbh), or of all tiles requested together
         double cb[NT];
 #pragma unroll
@@ -879,7 +905,32 @@ __device__ __forceinline__ bool rs_poll(const ResArgs& a, const ResWG& me, unsig
     return !bad;
 }
 
-template <int TMAX, int NT>
+// WHICH SWEEPS TAKE THE FP32 WALK: decided by the first communication wavefront behind the totals, from scalars that are the same bits in every workgroup
+// (gam = |r_i|^2, alpha_i, beta_i), so every workgroup takes the same walk.  With M~ = M + dM in the sweeps from iteration s on (|dM|_2 <= delta: A rounded
+// to float; the identity parts, [c; b] and the tau row are exact), linearity of the merged recurrence gives s_i - M p_i = dM (the part of p_i built from
+// r_j, j >= s), so the true residual leaves the recursive one by at most delta sum_i |alpha_i| |p~_i|, where |p~_i|^2 = pi_i = gam_i + beta_i^2 pi_{i-1}
+// (residuals orthogonal; pi = 0 before s, and gam_i is left out again for an iteration whose sweep read the doubles).
+//   trigger: the first iteration with sqrt(gam_i) <= theta = eta tol / (K delta) -- the sweeps from r_{i+1} on read val32 (delta == 0: from r_0 on);
+//   guard:   B += delta |alpha_i| sqrt(pi_i) at every iteration; B > eta tol / 2 sends the remaining sweeps of the solve back to the doubles, for good
+//            (the part of p already built keeps decaying through beta, and keeps being counted in B).
+// Returns RC_LOWP of the next sweep.  start: the round of r_0 = rhs - M v (no scalars yet); cur: the sweep of this iteration read val32.
+enum ResLowp { LP_STATE = 0, LP_PI, LP_BOUND, LP_SWEEPS, LP_COUNT };         // LP_STATE: 0 doubles so far, 1 floats, 2 back on doubles; LP_SWEEPS: fp32 sweeps that entered an update
+__device__ __forceinline__ double rs_lowp_decide(const ResArgs& a, double* s_lowp, int lane, bool start, bool cur, double gam, double alpha, double beta) {
+    if (a.val32 == nullptr) return 0.0;
+    double state = s_lowp[LP_STATE], pi = s_lowp[LP_PI], bound = s_lowp[LP_BOUND], sweeps = s_lowp[LP_SWEEPS];
+    if (start) { if (a.lowp_theta == INFINITY) state = 1.0; }
+    else {
+        if (cur) sweeps += 1.0;
+        pi = (cur ? gam : 0.0) + beta * beta * pi;
+        bound += a.lowp_delta * fabs(alpha) * sqrt(pi);
+        if (state == 1.0 && a.lowp_budget >= 0.0 && bound > a.lowp_budget) state = 2.0;
+        else if (state == 0.0 && sqrt(gam) <= a.lowp_theta) state = 1.0;
+    }
+    if (lane == 0) { s_lowp[LP_STATE] = state; s_lowp[LP_PI] = pi; s_lowp[LP_BOUND] = bound; s_lowp[LP_SWEEPS] = sweeps; }
+    return state == 1.0 ? 1.0 : 0.0;
+}
+
+template <int TMAX, int NT, bool LOWP>
 __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs a) {
     __shared__ __attribute__((aligned(16))) d2 s_gcol[64];                   // the workgroup's column elements of the vector being swept (v, then r)
     __shared__ double s_red[16][4];
@@ -889,6 +940,7 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
     // the tau element's x, p, s and the last iteration's scalars: the communication wavefront needs them between the totals and barrier (B) alone, and
     // PARKS them here -- live across its sweep, 20 registers of wavefront-uniform values were what its six tiles' rows did not fit beside
     __shared__ double s_tau[9];
+    __shared__ double s_lowp[LP_COUNT];                                       // the fp32 walk's rule, parked the same way (rs_lowp_decide)
     extern __shared__ __attribute__((aligned(16))) double s_dyn[];
     d2* const s_colpart = reinterpret_cast<d2*>(s_dyn);                       // [RS_NCOMP + 1][64]: a wavefront's column sums of a sweep
     double* const s_all = reinterpret_cast<double*>(s_colpart + (RS_NCOMP + 1) * 64);      // [4][RS_GMAX], zero beyond G
@@ -945,7 +997,7 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
         bool early = false;
         for (int i = -1, xr = 0;; ++xr) {
             double acc[4];
-            rs_sweep<TMAX, NT>(a, me.blk0 + t0, cnt, c0, lane, s_gcol, s_ctl, mycol, R, acc, early, HOLD_CB ? cbh : nullptr);
+            rs_sweep<TMAX, NT, LOWP>(a, me.blk0 + t0, cnt, c0, lane, s_gcol, s_ctl, mycol, R, acc, early, HOLD_CB ? cbh : nullptr);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const double v = wave_sum(acc[k]);
@@ -996,7 +1048,8 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
         if (lane < tc) { cr = a.v[c0 + lane]; cx = a.x[c0 + lane]; cc = a.cb[c0 + lane]; }
         s_gcol[lane] = cr;
         const d2 gt = a.v[nm], xt = a.x[nm];
-        if (lane == 0) { s_ctl[RC_GTX] = gt.x; s_ctl[RC_GTY] = gt.y; s_ctl[RC_STOP] = 0.0; }      // (the compute wavefronts read the tau element here, from the start)
+        if (lane == 0) { s_ctl[RC_GTX] = gt.x; s_ctl[RC_GTY] = gt.y; s_ctl[RC_STOP] = 0.0; if (LOWP) s_ctl[RC_LOWP] = 0.0; }      // (the compute wavefronts read the tau element here, from the start)
+        if (LOWP && lane == 0) { s_lowp[LP_STATE] = 0.0; s_lowp[LP_PI] = 0.0; s_lowp[LP_BOUND] = 0.0; s_lowp[LP_SWEEPS] = 0.0; }
         if (lane == 0) { s_tau[0] = xt.x; s_tau[1] = xt.y; s_tau[2] = s_tau[3] = s_tau[4] = s_tau[5] = s_tau[6] = s_tau[7] = s_tau[8] = 0.0; }
         if (blockIdx.x == 0 && lane == 0) { st->tol = a.tol; st->maxit = a.maxit; st->hit_max = 0; st->rn_old = 0.0; }
     }
@@ -1012,7 +1065,7 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
         nx += 1;
         if (c0wave) {
             double racc[4];
-            rs_sweep<TMAX, NTC>(a, me.blk0 + t0, cnt, c0, lane, s_gcol, s_ctl, mycol, R, racc, early);
+            rs_sweep<TMAX, NTC, LOWP>(a, me.blk0 + t0, cnt, c0, lane, s_gcol, s_ctl, mycol, R, racc, early);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const double v = wave_sum(racc[k]);
@@ -1137,7 +1190,7 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
             const double q1 = ctot.x + gt.x * cc, q2 = ctot.y + gt.y * cc;
             const d2 cwv = make_double2(cr.x - q2, q1 - cr.y);
             const d2 wt = make_double2(gt.x + tot[3], -tot[2] - gt.y);
-            double stopf = failed ? 2.0 : 0.0, alpha = 0.0, beta = 0.0, near = 0.0;
+            double stopf = failed ? 2.0 : 0.0, alpha = 0.0, beta = 0.0, near = 0.0, lowp = 0.0;
             if (!failed && early) {
                 gam = tot[0] + (gt.x * gt.x + gt.y * gt.y);                              // |r_i|^2 of the residual the last update left: the sum the sweep would form
                 if (i > 0 && (sqrt(gam) <= a.tol || i >= a.maxit)) { iter = i; stopf = 1.0; }       // conjugategradients.jl:42 for iteration i, without its sweep
@@ -1145,6 +1198,7 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
                 if (i < 0) {
                     cr = make_double2(crhs.x - cwv.x, crhs.y - cwv.y);                  // r_0 = rhs - M v      conjugategradients.jl:32-36
                     gt = make_double2(rhst.x - wt.x, rhst.y - wt.y);
+                    if constexpr (LOWP) lowp = rs_lowp_decide(a, s_lowp, lane, true, false, 0.0, 0.0, 0.0);
                 } else {
                     gam = tot[0] + (gt.x * gt.x + gt.y * gt.y);
                     if (i > 0 && (sqrt(gam) <= a.tol || i >= a.maxit)) { iter = i; stopf = 1.0; }       // conjugategradients.jl:42 for iteration i
@@ -1156,6 +1210,7 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
                             alpha = gam / (delta - beta * gam / a_prev);
                         }
                         g_prev = gam; a_prev = alpha;
+                        if constexpr (LOWP) lowp = rs_lowp_decide(a, s_lowp, lane, false, s_ctl[RC_LOWP] != 0.0, gam, alpha, beta);
                         auto upd = [&](const d2 wi, d2& ri, d2& pi, d2& si, d2& xi) {
                             if (i == 0) { pi = ri; si = wi; }
                             else {
@@ -1175,7 +1230,7 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
             }
             if (stopf == 0.0 && !early) s_gcol[lane] = lane < tc ? cr : make_double2(0.0, 0.0);
             if (lane == 0) {
-                if (!early) { s_ctl[RC_ALPHA] = alpha; s_ctl[RC_BETA] = beta; s_ctl[RC_GTX] = gt.x; s_ctl[RC_GTY] = gt.y; s_ctl[RC_NEAR] = near; }
+                if (!early) { s_ctl[RC_ALPHA] = alpha; s_ctl[RC_BETA] = beta; s_ctl[RC_GTX] = gt.x; s_ctl[RC_GTY] = gt.y; s_ctl[RC_NEAR] = near; if (LOWP) s_ctl[RC_LOWP] = lowp; }
                 s_ctl[RC_STOP] = stopf;
                 s_tau[0] = xt.x; s_tau[1] = xt.y; s_tau[2] = pt.x; s_tau[3] = pt.y; s_tau[4] = stt.x; s_tau[5] = stt.y; s_tau[6] = g_prev; s_tau[7] = a_prev; s_tau[8] = gam;
             }
@@ -1198,6 +1253,8 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
         if (ok) rs_rows_store<NTC>(a, me.blk0 + t0, cnt, lane, R);
         if (ok && leader && lane < tc) a.x[c0 + lane] = cx;
         if (blockIdx.x == 0 && lane == 0) {
+            // (the fp32 walk's record of THIS solve, however it ended: a failed exchange does not leave the last solve's behind)
+            if (LOWP && a.lowp_out) { a.lowp_out[0] = s_lowp[LP_SWEEPS]; a.lowp_out[1] = s_lowp[LP_STATE] == 2.0 ? 1.0 : 0.0; a.lowp_out[2] = s_lowp[LP_BOUND]; }
             if (ok) {
                 a.x[nm] = make_double2(s_tau[0], s_tau[1]);
                 const double gam = s_tau[8];
@@ -1213,18 +1270,18 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
 
 // The kernel instance a plan launches, with its block and its dynamic LDS (res_stream_lds_bytes / res_reg_lds_bytes, fos_internal.hpp: the planner's formula)
 struct ResKernel { const void* fn; int threads; size_t lds; };
-static ResKernel res_kernel(const ResLaunch& rl) {
+static ResKernel res_kernel(const ResLaunch& rl, bool lowp = false) {
     auto k = [](auto kern, int threads, size_t lds) { return ResKernel{reinterpret_cast<const void*>(kern), threads, lds}; };
     if (rl.stream) {
         // (the compute wavefronts' sums land in s_red[wv]: RS_NCOMP rows, the others zeroed once)
         const int thr = 64 * (RS_NCOMP + 1);
         const size_t lds = res_stream_lds_bytes(rl.tiles_wg_max);
-        if (rl.tmax > 32 && rl.nt <= 3) return k(cg_stream_kernel<64, 3>, thr, lds);
-        if (rl.tmax > 32) return k(cg_stream_kernel<64, 5>, thr, lds);
-        if (rl.nt <= 3) return k(cg_stream_kernel<32, 3>, thr, lds);
-        if (rl.nt <= 5) return k(cg_stream_kernel<32, 5>, thr, lds);
-        if (rl.nt <= 9) return k(cg_stream_kernel<32, 9>, thr, lds);
-        return k(cg_stream_kernel<32, 10>, thr, lds);
+        if (rl.tmax > 32 && rl.nt <= 3) return lowp ? k(cg_stream_kernel<64, 3, true>, thr, lds) : k(cg_stream_kernel<64, 3, false>, thr, lds);
+        if (rl.tmax > 32) return lowp ? k(cg_stream_kernel<64, 5, true>, thr, lds) : k(cg_stream_kernel<64, 5, false>, thr, lds);
+        if (rl.nt <= 3) return lowp ? k(cg_stream_kernel<32, 3, true>, thr, lds) : k(cg_stream_kernel<32, 3, false>, thr, lds);
+        if (rl.nt <= 5) return lowp ? k(cg_stream_kernel<32, 5, true>, thr, lds) : k(cg_stream_kernel<32, 5, false>, thr, lds);
+        if (rl.nt <= 9) return lowp ? k(cg_stream_kernel<32, 9, true>, thr, lds) : k(cg_stream_kernel<32, 9, false>, thr, lds);
+        return lowp ? k(cg_stream_kernel<32, 10, true>, thr, lds) : k(cg_stream_kernel<32, 10, false>, thr, lds);
     }
     const int thr = 64 * (rl.nw + rl.ncomm);
     if (rl.tmax <= 32 && rl.rpt == 1) return k(cg_resident_kernel<32, 1, 768>, thr, res_reg_lds_bytes(12, 32));
@@ -1233,6 +1290,7 @@ static ResKernel res_kernel(const ResLaunch& rl) {
     return k(cg_resident_kernel<64, 1, 512>, thr, res_reg_lds_bytes(8, 64));
 }
 
+static bool res_lds_fits_instance(const ResKernel& k, int device, std::string* why);
 // dynamic LDS above the default limit needs an opt-in per kernel (a table update)
 static hipError_t res_lds_optin(const ResKernel& k) {
     if (k.lds > 48 * 1024) return hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
@@ -1240,7 +1298,10 @@ static hipError_t res_lds_optin(const ResKernel& k) {
 }
 
 bool res_lds_fits(const ResLaunch& rl, int device, std::string* why) {
-    const ResKernel k = res_kernel(rl);
+    if (rl.stream && !res_lds_fits_instance(res_kernel(rl, true), device, why)) return false;      // (the instance with the fp32 walk: 40 static bytes more)
+    return res_lds_fits_instance(res_kernel(rl, false), device, why);
+}
+static bool res_lds_fits_instance(const ResKernel& k, int device, std::string* why) {
     hipFuncAttributes fa{};
     int cap = 0;
     char buf[192];
@@ -1275,11 +1336,88 @@ hipError_t launch_cg_resident(const LaunchCtx& c, const ResLaunch& rl, double2* 
     a.ncomp = rl.nw;
     static const int res_flags = getenv("FOS_RES_FLAGS") ? atoi(getenv("FOS_RES_FLAGS")) : (2 << 8);
     a.flags = res_flags;
-    const ResKernel k = res_kernel(rl);
+    // the fp32 walk: the streamed form on a handle without peers (its rule: rs_lowp_decide; eta's share of the stop tolerance, K = 8 for a residual that
+    // halves per iteration -- DESIGN.md 3.1).  lowp_mode 2 (tests): every sweep behind the start, no guard
+    // The rule is priced on min(tol, l eps): l eps is the floor of the projection's tolerance schedule (affinepluslinear.jl:108-112), the tightest solve
+    // the solver ever asks for.  A solve at a loose tolerance (the first outer iterations: 0.2^sqrt(i)) may not spend eta of THAT on the float copy --
+    // from the first sweep on, that moved the iterates of 40 DR steps by 8e-9 relative against the doubles, where the project holds two builds to 1e-9;
+    // at the floor, where the steady state runs, the two are the same number.
+    if (rl.stream && rl.val32 && rl.lowp_mode > 0 && !fold) {
+        constexpr double K = 8.0;
+        const double tol_lp = std::min(tol, (double)c.l * 2.220446049250313e-16);
+        a.val32 = rl.val32; a.lowp_out = rl.lowp_out; a.lowp_delta = rl.lowp_delta;
+        a.lowp_theta = (rl.lowp_mode == 2 || rl.lowp_delta == 0.0) ? INFINITY : rl.lowp_eta * tol_lp / (K * rl.lowp_delta);
+        a.lowp_budget = rl.lowp_mode == 2 ? -1.0 : 0.5 * rl.lowp_eta * tol_lp;
+    }
+    const ResKernel k = res_kernel(rl, a.val32 != nullptr);
     const hipError_t e = res_lds_optin(k);
     if (e != hipSuccess) return e;
     void* args[] = {&a};
     return hipLaunchKernel(k.fn, dim3(rl.G), dim3(k.threads), args, k.lds, c.stream);
+}
+
+// ---- set-up of the fp32 walk: val32 = fl32(val), and delta >= |A - fl32(A)|_2.  The operator is block-diagonal over units and a streamed workgroup (or the
+// wpu workgroups of a split unit) holds whole units on <= 64 columns, so |dA|_2 = max over those column ranges of |dA_u|_2 <= sqrt(|dA_u' dA_u|_inf): one
+// workgroup per range forms the <= 64 x 64 Gram matrix of its tiles' rounding errors (tile after tile, fixed order: the same bits for the same operator)
+// and leaves the square root of its largest absolute row sum in part[workgroup]; the host takes the maximum.
+__global__ __launch_bounds__(256) void rs_lowp_round_kernel(const double* __restrict__ val, float* __restrict__ val32, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) val32[i] = (float)val[i];
+}
+
+__global__ __launch_bounds__(256) void rs_lowp_delta_kernel(const BlkDesc* __restrict__ blk, const double* __restrict__ val, const ResWG* __restrict__ wg,
+                                                            double* __restrict__ part) {
+    __shared__ double s_d[64][65];             // [column of the workgroup][row of the tile] (65: the rows of one column spread over the banks)
+    __shared__ double s_row[256];
+    const int tid = threadIdx.x;
+    const ResWG me = wg[blockIdx.x];
+    if (me.idx != 0) { if (tid == 0) part[blockIdx.x] = 0.0; return; }       // (a split unit: counted once, by its first workgroup)
+    const int j = tid >> 2, k0 = (tid & 3) * 16;
+    double acc[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) acc[k] = 0.0;
+    for (int kk = 0; kk < me.wpu; ++kk) {
+        const ResWG w = wg[me.wg0 + kk];
+        for (int ti = 0; ti < w.nblk; ++ti) {
+            const BlkDesc d = blk[w.blk0 + ti];
+            const int coff = d.meta[0] - me.c0, steps = d.steps();
+            int any = 0;
+            for (int e = tid; e < 64 * 64; e += 256) {
+                const int c = e >> 6, r = e & 63, t = c - coff;
+                double dv = 0.0;
+                if (t >= 0 && t < steps) { const double v = val[d.nnz0 + 64 * (int64_t)t + r]; dv = v - (double)(float)v; }
+                s_d[c][r] = dv;
+                any |= dv != 0.0;
+            }
+            if (__syncthreads_or(any)) {       // (a tile of values that are floats already adds nothing)
+                for (int r = 0; r < 64; ++r) {
+                    const double dj = s_d[j][r];
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) acc[k] += dj * s_d[k0 + k][r];
+                }
+            }
+            __syncthreads();
+        }
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s += fabs(acc[k]);
+    s_row[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        double mx = 0.0;
+        for (int q = 0; q < 64; ++q) {
+            const double rs = (s_row[4 * q] + s_row[4 * q + 1]) + (s_row[4 * q + 2] + s_row[4 * q + 3]);
+            mx = rs > mx || rs != rs ? rs : mx;                              // (a NaN stays: no fp32 walk for such an operator)
+        }
+        part[blockIdx.x] = sqrt(mx);
+    }
+}
+
+hipError_t launch_rs_lowp_setup(hipStream_t stream, const BlkDesc* blk, const double* val, int64_t nvals, const ResWG* wg, int G, float* val32, double* part) {
+    const int grid = (int)std::min<int64_t>(4096, (nvals + 255) / 256);
+    if (grid > 0) hipLaunchKernelGGL(rs_lowp_round_kernel, dim3(grid), dim3(256), 0, stream, val, val32, nvals);
+    hipLaunchKernelGGL(rs_lowp_delta_kernel, dim3(G), dim3(256), 0, stream, blk, val, wg, part);
+    return hipGetLastError();
 }
 
 }  // namespace fos

@@ -286,6 +286,7 @@ int cg_solve(fos_solver* h, d2* x, const d2* rhs, double tol, int maxit, int64_t
     if (resident) {
         // the whole solve is ONE launch (resident.hip): nothing to enqueue ahead, nothing to predict; what follows the solve is enqueued behind it
         // (gated on DevState.done, which the launch sets when it ends) and the host reads the iteration count from the mark the launch leaves
+        FOS_TRY(resident_lowp_ensure(h));                  // (a handle whose default is another recurrence builds its float copy here, once)
         const int pe = prof_begin(h, FOS_PROF_RESIDENT, 1, h->prof_seen[FOS_PROF_RESIDENT]++);
         const hipError_t le = launch_cg_resident(c, h->op.res, x, rhs, apply_on ? apply_on : x, tol, maxit, fold ? &h->tr.peer : nullptr, seq_base);
         prof_end(h, pe);
@@ -1158,6 +1159,8 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     const PsdTuning psd_tuning = PsdTuning::from_env();
     h->psd_fuse = !(getenv("FOS_PSD_FUSE") && atoi(getenv("FOS_PSD_FUSE")) == 0);
     h->relax_ew = !(getenv("FOS_RELAX_EW") && atoi(getenv("FOS_RELAX_EW")) == 0);
+    if (const char* e = getenv("FOS_RS_LOWP")) h->rs_lowp = std::max(0, std::min(2, atoi(e)));
+    if (const char* e = getenv("FOS_RS_LOWP_ETA")) { const double eta = atof(e); if (eta > 0.0 && eta <= 1.0) h->rs_lowp_eta = eta; }
 
     // ---- operator (operator.cpp)
     h->row_sharded = (flags & FOS_CREATE_ROW_SHARDED) != 0;
@@ -1219,6 +1222,11 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     if (const char* e = getenv("FOS_CG_CHUNK")) h->cg_chunk = std::max(1, atoi(e));
 
     FOS_TRY(resident_setup(h, cus));                      // FOS_CG_RESIDENT: does the operator qualify, and the plan if so
+    {   // where the resident solve is the handle's default, its float copy is part of the set-up (and of what a caller times as set-up)
+        int32_t v = FOS_CG_REFERENCE;
+        FOS_TRY(fos_get_cg_variant(h, &v));
+        if (v == FOS_CG_RESIDENT) FOS_TRY(resident_lowp_ensure(h));
+    }
     FOS_TRY(fos_set_alg(h, FOS_ALG_GAP, 0.8, 1.8, 1.8, 0.0));
     FOS_TRY(fos_set_iterate(h, nullptr));
     FOS_HIP(hipStreamSynchronize(h->stream));
@@ -1828,6 +1836,7 @@ int fos_set_cg_variant(fos_handle h, int32_t variant) {
         return FOS_EUNSUPPORTED;
     }
     if (variant == FOS_CG_FUSED_P) FOS_TRY(refuse_fused_p_on_window_panels(h));
+    if (variant == FOS_CG_RESIDENT) { FOS_HIP(hipSetDevice(h->device)); FOS_TRY(resident_lowp_ensure(h)); }      // (asked for: its float copy is built now)
     h->cg_variant = variant;
     if (variant >= 0) h->fuse_p = variant == FOS_CG_FUSED_P;
     h->last_cg_pred = 0; h->cg_same_run = 0;

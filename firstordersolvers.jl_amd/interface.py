@@ -473,6 +473,7 @@ class HipHSDE:
         ws = (C.c_int64 * 4)()
         _lib.check(self._lib.fos_window_stats(self._h, ws))
         out.update(zip(("win_panels", "win_segments", "win_slices", "win_vals"), list(ws)))
+        out["lowp_val32_bytes"] = int(self._lowp_stats()[4])      # the float copy of the tile values (streamed resident plan, fos_resident_lowp_stats)
         return out
 
     def sync(self):
@@ -538,7 +539,15 @@ class HipHSDE:
         out = {k: int(st[i]) for i, k in enumerate(keys)}
         out["form"] = "streamed" if out["tiles_per_wave"] < 0 else "registers"        # streamed: tiles re-read every iteration (resident.hip, cg_stream_kernel)
         out["tiles_per_wave"] = abs(out["tiles_per_wave"])
+        # the streamed form's fp32 walk (foship.h fos_resident_lowp_stats): its bound of |A - fl32(A)|_2 and the last solve's record
+        lp = self._lowp_stats()
+        out.update(lowp_delta=lp[0], lowp_sweeps_last_solve=int(lp[1]), lowp_reverted_last_solve=int(lp[2]), lowp_bound_last_solve=lp[3])
         return out
+
+    def _lowp_stats(self):
+        lp = np.zeros(8)
+        _lib.check(self._lib.fos_resident_lowp_stats(self._h, _lib.dptr(lp)))
+        return [float(v) for v in lp]
 
     def debug_set(self, what, value):
         _lib.check(self._lib.fos_debug_set(self._h, int(what), int(value)))

@@ -477,6 +477,18 @@ int fos_set_cg_variant(fos_handle h, int32_t variant);
  * whose tiles exceed the register file), units (runs of columns = diagonal blocks), most tiles in one workgroup, steps per tile (32 / 64),
  * every rank qualifies (sharded handles: the vote of fos_peer_enable; else = qualifies)}. */
 int fos_resident_stats(fos_handle h, int64_t* stats8);
+/* The streamed form's fp32 walk (handles without peers; FOS_RS_LOWP=0 in the environment at fos_create: none, the solve reads doubles only).  The plan keeps
+ * a second copy of the tile values as float; a CG solve reads it in the sweeps whose residual is small enough that the rounding of A (delta >=
+ * |A - fl32(A)|_2, computed at set-up) moves the true residual of the result by at most eta * tol (eta = 0.1, FOS_RS_LOWP_ETA): from the first iteration
+ * with |r_i| <= eta tol / (8 delta) on, and back on the doubles for the rest of the solve if the running bound B = delta sum |alpha_i| |p~_i| passes
+ * eta tol / 2.  (tol here is min(the solve's tol, l eps): a solve at a loose tolerance is held to the floor of the tolerance schedule as well, so that the
+ * float copy moves no outer iterate by more than the tightest solve would.)  The stop rule, tol and the iteration caps are unchanged.  stats8 = {delta, fp32 sweeps of the last solve that entered an update, whether
+ * that solve went back to the doubles (0 / 1), its bound B, bytes of the float copy, mode (0 none, 1 by the rule, 2 FOS_RS_LOWP=2: every sweep behind the
+ * start and no guard -- tests), eta, 0}; all zero where the plan has no float copy.  The copy and delta are built at fos_create where FOS_CG_RESIDENT is the
+ * handle's default, else by fos_set_cg_variant(FOS_CG_RESIDENT) or the first such solve (all zero until then).  eta is a share of min(tol, l eps), not of a loose
+ * solve's own tolerance: a caller's solve at a tolerance above the floor reads floats only once its residual is small enough for the floor's budget.  The record is
+ * written by every solve that ran with the copy, also one that ended on a failed exchange.  Waits for the handle's stream. */
+int fos_resident_lowp_stats(fos_handle h, double* stats8);
 int fos_get_cg_variant(fos_handle h, int32_t* variant);   /* the variant the next projection runs (defaults resolved) */
 
 /* test hooks.  FOS_DEBUG_PUPDATE_DELAY: every workgroup but the first of the kernel that closes a CG iteration waits `value`

@@ -16,6 +16,7 @@ d.set_alg(pkg.DR())
 d.set_iterate(None)
 d.step(1, 220, 10 ** 12, 1e-8)
 print("cg iterations of the last solve:", d.cgiter())
+print({k: v for k, v in d.resident_stats().items() if k.startswith("lowp")})
 lib = pkg.lib.load()
 n = 4 * 16 * 64 * 16
 buf = (C.c_longlong * n)()
@@ -74,6 +75,8 @@ for w, wn in enumerate(("wg 0", "wg 1", "wg G/2", "wg G-1")):
         for k in its[:3] + its[-1:]:
             print("   it %2d: total %6.2f us | " % (k, (s[k, last] - s[k, 0]) / 100.0) + "  ".join("%s %.2f" % (nm, v) for nm, v in zip(names, ph[its.index(k)])))
         print("   mean over iterations 1..: total %.2f us | " % tot[1:].mean() + "  ".join("%s %.2f" % (nm, v) for nm, v in zip(names, ph[1:].mean(axis=0))))
+        # every round's first phase (the sweep): the streamed form's fp64 sweeps come first, its fp32 sweeps from the round the rule switches at
+        print("   %s of every round, us: " % names[0] + " ".join("%.1f" % v for v in ph[:-1, 0]))
         if who == ncomp:           # finer stamps inside the first communication wavefront: offsets from barrier A / from the arrival of everybody's words
             f = lambda a, b: np.mean([(s[k, a] - s[k, b]) / 100.0 for k in its[1:] if s[k, a] > 0 and s[k, b] > 0])
             print("   finer: after A: column sums added +%.2f, wavefront sums added +%.2f, four sums formed +%.2f, published +%.2f | after all words: totals +%.2f, +ranks %.2f, w rows +%.2f, scalars + updates +%.2f, LDS written +%.2f"
