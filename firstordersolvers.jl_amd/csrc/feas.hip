@@ -11,13 +11,13 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <vector>
 
 #include "dev_common.hpp"
 #include "fos_internal.hpp"
+#include "wrappers.hpp"
 
 namespace fos {
 
@@ -140,11 +140,7 @@ struct fos_feas : DevOwned {                      // (owns the vectors below; th
     int status = FOS_STATUS_CONTINUE;
     int checked = 0;
     double err = NAN;
-    int64_t ls_interval = 0;        // LineSearchWrapper (wrappers/linesearch.jl): every ls_interval-th iteration is a step-length search
-    double ls_log[34] = {0};        // normres, 31 test residuals, alpha_best, iteration (the layout of fos_linesearch_log)
-    LongPlanes lp;                  // LongstepWrapper (wrappers/longstep.jl): planes saved in the last nsave + 1 iterations of every interval (vectors viewed as L/2 double2)
-    int64_t gapp_iproj = 100;       // GAPP (solvers/gapproj.jl): every iproj-th iteration is a projected search
-    double gapp_log[23] = {0};      // 21 test norms, alpha_best, iteration
+    Wrappers wr;                    // LineSearchWrapper, GAPP (an algorithm of its own here: FOS_ALG_GAPP), LongstepWrapper (wrappers.hpp; the planes see the vectors as L/2 double2)
 };
 
 namespace {
@@ -171,7 +167,7 @@ LaunchCtx feas_long_ctx(const fos_feas* h) {
     return c;
 }
 inline void feas_long_save(fos_feas* h, int which, const double* y, const double* x) {
-    if (h->lp.now) long_save_plane(feas_long_ctx(h), h->lp, which, reinterpret_cast<const double2*>(y), reinterpret_cast<const double2*>(x));
+    if (h->wr.lp.now) long_save_plane(feas_long_ctx(h), h->wr.lp, which, reinterpret_cast<const double2*>(y), reinterpret_cast<const double2*>(x));
 }
 
 // prox!(y, S, x): the projection onto set `which`; y must not alias x
@@ -201,12 +197,7 @@ int feas_object(fos_feas* h, int32_t which, const void* out, int kind, const cha
 int feas_check(fos_feas* h, const double* z, int64_t i, int64_t checki, double eps, bool override_) {
     if (override_ || (checki > 0 && i % checki == 0)) {
         FEAS_K(feas_check_kernel, h->n, h->prev, z, 1, h->partials);                   // |prev - z|^2 and prev = z in one pass
-        std::vector<double> part((size_t)h->grid);
-        FOS_HIP(hipMemcpyAsync(part.data(), h->partials, sizeof(double) * h->grid, hipMemcpyDeviceToHost, h->stream));
-        FOS_HIP(hipStreamSynchronize(h->stream));
-        double s = 0.0;
-        for (double v : part) s += v;
-        h->err = std::sqrt(s);
+        FOS_TRY(norm_of_partials(h->partials, (size_t)h->grid, h->stream, &h->err));
         h->status = (h->err <= eps) ? FOS_STATUS_OPTIMAL : FOS_STATUS_CONTINUE;       // :57 (NaN <= eps is false)
         h->checked = 1;
     } else {
@@ -216,54 +207,37 @@ int feas_check(fos_feas* h, const double* z, int64_t i, int64_t checki, double e
     return FOS_OK;
 }
 
-int feas_norm_of_diff(fos_feas* h, const double* a, const double* b, double* out) {
-    FEAS_K(feas_normdiff_kernel, h->n, a, b, h->partials);
-    std::vector<double> part((size_t)h->grid);
-    FOS_HIP(hipMemcpyAsync(part.data(), h->partials, sizeof(double) * h->grid, hipMemcpyDeviceToHost, h->stream));
-    FOS_HIP(hipStreamSynchronize(h->stream));
-    double s = 0.0;
-    for (double v : part) s += v;
-    *out = std::sqrt(s);
-    return FOS_OK;
-}
+// the searches' view of the handle (wrappers.hpp).  Scratch the algorithms with a search leave free: the line search's tmp1 = y, tmp2 = t1, res = xold, tmp3 = p;
+// GAPP's tmp1 = t1, tmp2 = t2, res = xold (prox!(res, S1, .) writes it directly), tmp3 = p, tmp4 = q
+struct FeasSearch {
+    fos_feas* h;
+    double *x, *tmp1, *tmp2, *res, *tmp3, *tmp4; const double *res_from, *a12;          // (a12: GAPA relaxes with the device scalar alpha12)
+    explicit FeasSearch(fos_feas* h_) : h(h_), x(h_->x), tmp1(h_->alg == FOS_ALG_GAPP ? h_->t1 : h_->y), tmp2(h_->t2), res(h_->xold), tmp3(h_->p), tmp4(h_->q), res_from(h_->xold),
+                                        a12(h_->alg == FOS_ALG_GAPA ? h_->a12 : nullptr) {}
+    int relaxed_s1(const double* in) { FOS_TRY(feas_prox(h, 0, h->t1, in)); FEAS_K(feas_relax_kernel, h->n, h->t1, in, h->alpha1, a12); return FOS_OK; }
+    int relaxed_s2(double* out) { FOS_TRY(feas_prox(h, 1, out, h->t1)); FEAS_K(feas_relax_kernel, h->n, out, (const double*)h->t1, h->alpha2, a12); return FOS_OK; }
+    int prox_s2(double* out, const double* in) { return feas_prox(h, 1, out, in); }
+    void axpy(double* out, const double* base, double a, const double* dir) { FEAS_K(feas_axpy_kernel, h->n, out, base, a, dir); }
+    void sub(double* out, const double* a, const double* b) { FEAS_K(feas_sub_kernel, h->n, out, a, b); }
+    int normdiff(const double* a, const double* b, double* out) { FEAS_K(feas_normdiff_kernel, h->n, a, b, h->partials); return norm_of_partials(h->partials, (size_t)h->grid, h->stream, out); }
+};
 
 // LineSearchWrapper(GAP / GAPA), one search iteration      wrappers/linesearch.jl:36-75
-// scratch: y = tmp1 (the iterate the search starts from), xold = res, p = tmp3 -- unused by these two algorithms
 int feas_linesearch_iteration(fos_feas* h, int64_t i, int64_t checki, double eps) {
-    const int64_t n = h->n;
-    const double* a12 = h->alg == FOS_ALG_GAPA ? h->a12 : nullptr;
-    FEAS_K(feas_copy_kernel, n, h->y, (const double*)h->x);                             // tmp1 .= x                 :41
-    FOS_TRY(feas_prox(h, 0, h->t1, h->x));                                             // S1!(tmp2, x)              :45
-    FEAS_K(feas_relax_kernel, n, h->t1, (const double*)h->x, h->alpha1, a12);
+    FeasSearch f(h);
+    FEAS_K(feas_copy_kernel, h->n, h->y, (const double*)h->x);                         // tmp1 .= x                 :41
+    FOS_TRY(f.relaxed_s1(h->x));                                                       // S1!(tmp2, x)              :45
     FOS_TRY(feas_prox(h, 1, h->x, h->t1));                                             // S2!(x, tmp2, status)      :46
     FOS_TRY(feas_check(h, h->x, i, checki, eps, false));
-    FEAS_K(feas_relax_kernel, n, h->x, (const double*)h->t1, h->alpha2, a12);
-    FEAS_K(feas_sub_kernel, n, h->xold, (const double*)h->x, (const double*)h->y);     // res .= x .- tmp1          :49
-    FOS_TRY(feas_norm_of_diff(h, h->x, h->y, &h->ls_log[0]));                          // normres = norm(res)       :50
-    double best = INFINITY, abest = 1.0, a = 0.1;                                      // :53-55
-    for (int k = 0; k <= 30; ++k) {                                                    // :56
-        a = a * 1.8;                                                                   // :57
-        FEAS_K(feas_axpy_kernel, n, h->x, (const double*)h->y, a, (const double*)h->xold);      // x .= tmp1 .+ a.*res   :58
-        FOS_TRY(feas_prox(h, 0, h->t1, h->x));                                         // S1!(tmp2, x, nostatus)    :60
-        FEAS_K(feas_relax_kernel, n, h->t1, (const double*)h->x, h->alpha1, a12);
-        FOS_TRY(feas_prox(h, 1, h->p, h->t1));                                         // S2!(tmp3, tmp2, nostatus) :61
-        FEAS_K(feas_relax_kernel, n, h->p, (const double*)h->t1, h->alpha2, a12);
-        double tr = 0.0;
-        FOS_TRY(feas_norm_of_diff(h, h->x, h->p, &tr));                                // testres = normdiff(x, tmp3) :62
-        h->ls_log[1 + k] = tr;
-        if (tr < best) { best = tr; abest = a; }                                       // :64-67
-    }
-    FEAS_K(feas_axpy_kernel, n, h->x, (const double*)h->y, abest, (const double*)h->xold);      // x .= tmp1 .+ abest.*res :70
-    h->ls_log[32] = abest;
-    h->ls_log[33] = (double)i;
-    return FOS_OK;
+    FEAS_K(feas_relax_kernel, h->n, h->x, (const double*)h->t1, h->alpha2, f.a12);
+    return linesearch_search(f, h->wr.ls_log, i);
 }
 
-// GAPP, one iteration      solvers/gapproj.jl:29-72      scratch: xold = res, p = tmp3, q = tmp4
+// GAPP, one iteration      solvers/gapproj.jl:29-72
 int feas_gapp_iteration(fos_feas* h, int64_t i, int64_t checki, double eps) {
     const int64_t n = h->n;
     FOS_TRY(feas_prox(h, 0, h->t1, h->x));                                             // prox!(tmp1, S1, x)        :33
-    if (i % h->gapp_iproj != 0) {                                                      // the GAP step              :63-70
+    if (i % h->wr.gapp_iproj != 0) {                                                   // the GAP step              :63-70
         FEAS_K(feas_relax_kernel, n, h->t1, (const double*)h->x, h->alpha1, (const double*)nullptr);
         FOS_TRY(feas_prox(h, 1, h->t2, h->t1));
         FOS_TRY(feas_check(h, h->t2, i, checki, eps, false));
@@ -271,22 +245,10 @@ int feas_gapp_iteration(fos_feas* h, int64_t i, int64_t checki, double eps) {
         FEAS_K(feas_combine_kernel, n, h->x, (const double*)h->t2, h->alpha);
         return FOS_OK;
     }
+    FeasSearch f(h);
     FOS_TRY(feas_prox(h, 1, h->t2, h->t1));                                            // prox!(tmp2, S2, tmp1)     :39
     FOS_TRY(feas_prox(h, 0, h->xold, h->t2));                                          // prox!(res, S1, tmp2)      :40
-    FEAS_K(feas_sub_kernel, n, h->xold, (const double*)h->xold, (const double*)h->t1); // res .= res - tmp1         :41
-    double normbest = INFINITY, abest = -1.0;                                          // :44-45
-    for (int k = 0; k <= 20; ++k) {                                                    // :46
-        const double at = std::ldexp(1.0, k);                                          // 2.0^k
-        FEAS_K(feas_axpy_kernel, n, h->p, (const double*)h->t1, at, (const double*)h->xold);       // tmp3 .= tmp1 .+ at.*res
-        FOS_TRY(feas_prox(h, 1, h->q, h->p));                                          // prox!(tmp4, S2, tmp3)
-        double nt = 0.0;
-        FOS_TRY(feas_norm_of_diff(h, h->q, h->p, &nt));                                // norm(tmp4 - tmp3)
-        h->gapp_log[k] = nt;
-        if (nt < normbest) { abest = at; normbest = nt; }
-    }
-    h->gapp_log[21] = abest; h->gapp_log[22] = (double)i;
-    FEAS_K(feas_axpy_kernel, n, h->p, (const double*)h->t1, abest, (const double*)h->xold);        // tmp1 .= tmp1 .+ abest.*res   :58
-    FOS_TRY(feas_prox(h, 1, h->t2, h->p));                                             // prox!(tmp2, S2, tmp1)     :59
+    FOS_TRY(gapp_search(f, h->wr.gapp_log, i));
     FOS_TRY(feas_check(h, h->t2, i, checki, eps, false));                              // :60
     FEAS_K(feas_relax_kernel, n, h->t2, (const double*)h->p, h->alpha2, (const double*)nullptr);   // :61
     FEAS_K(feas_copy_kernel, n, h->x, (const double*)h->t2);                           // x .= tmp2                 :62
@@ -296,13 +258,8 @@ int feas_gapp_iteration(fos_feas* h, int64_t i, int64_t checki, double eps) {
 int feas_step_once(fos_feas* h, int64_t i, int64_t checki, double eps) {
     const int64_t n = h->n;
     if (h->alg == FOS_ALG_GAPP) return feas_gapp_iteration(h, i, checki, eps);
-    if (h->ls_interval > 0 && i % h->ls_interval == 0) return feas_linesearch_iteration(h, i, checki, eps);      // linesearch.jl:39
-    h->lp.now = false;
-    if (h->lp.interval > 0) {                                                           // longstep.jl:44-49
-        const int64_t savepos = (i - 1) % h->lp.interval - h->lp.interval + h->lp.nsave + 2;
-        if (savepos > 0) h->lp.savepos = savepos;
-        h->lp.now = h->lp.savepos > 0;
-    }
+    if (h->wr.ls_interval > 0 && i % h->wr.ls_interval == 0) return feas_linesearch_iteration(h, i, checki, eps);      // linesearch.jl:39
+    long_window(h->wr.lp, i);                                                          // longstep.jl:44-49
     switch (h->alg) {
     case FOS_ALG_GAP:
     case FOS_ALG_GAPA: {
@@ -350,12 +307,7 @@ int feas_step_once(fos_feas* h, int64_t i, int64_t checki, double eps) {
     }
     default: set_error("feasibility form: unknown algorithm %d", h->alg); return FOS_EINVAL;
     }
-    if (h->lp.now && h->lp.savepos == h->lp.nsave + 1) {                                // longstep.jl:53-58: projectonnormals!, x .= tmp
-        FOS_TRY(long_project_planes(feas_long_ctx(h), h->lp, reinterpret_cast<double2*>(h->x), i));
-        h->lp.savepos = -1;
-    }
-    h->lp.now = false;
-    return FOS_OK;
+    return long_window_close(feas_long_ctx(h), h->wr.lp, reinterpret_cast<double2*>(h->x), i);      // longstep.jl:53-58: projectonnormals!, x .= tmp
 }
 
 }  // namespace
@@ -642,76 +594,35 @@ int fos_feas_set_alg(fos_feas_handle h, int32_t alg, double alpha, double alpha1
     if (!h || alg < FOS_ALG_GAP || alg > FOS_ALG_DYKSTRA) { set_error("fos_feas_set_alg: unknown algorithm"); return FOS_EINVAL; }
     h->alg = alg; h->alpha = alpha; h->alpha1 = alpha1; h->alpha2 = alpha2; h->beta = beta;
     if (alg == FOS_ALG_GAPA) h->alpha1 = h->alpha2 = 2.0;              // (unused: GAPA relaxes with the device scalar alpha12)
-    h->ls_interval = 0;                                                // a fresh algorithm is unwrapped (fos_feas_set_linesearch follows)
-    h->lp.interval = 0; h->lp.savepos = 0; h->lp.now = false;          // ... (fos_feas_set_longstep follows)
+    h->wr.off();                                                       // a fresh algorithm is unwrapped (fos_feas_set_linesearch / _longstep follow)
     return FOS_OK;
 }
 
 // GAPP(alpha, alpha1, alpha2; iproj)      solvers/gapproj.jl:5-13 (Feasibility form only)
 int fos_feas_set_gapp(fos_feas_handle h, double alpha, double alpha1, double alpha2, int64_t iproj) {
     if (!h || iproj < 1) { set_error("fos_feas_set_gapp: iproj >= 1 is required"); return FOS_EINVAL; }
-    h->alg = FOS_ALG_GAPP; h->alpha = alpha; h->alpha1 = alpha1; h->alpha2 = alpha2; h->beta = 0.0; h->gapp_iproj = iproj;
-    h->ls_interval = 0;
-    h->lp.interval = 0; h->lp.savepos = 0; h->lp.now = false;          // a fresh algorithm is unwrapped (support_longstep(::GAPP) = false, gapproj.jl:83)
+    h->alg = FOS_ALG_GAPP; h->alpha = alpha; h->alpha1 = alpha1; h->alpha2 = alpha2; h->beta = 0.0;
+    h->wr.off();                                                       // a fresh algorithm is unwrapped (support_longstep(::GAPP) = false, gapproj.jl:83)
+    h->wr.gapp_iproj = iproj;
     return FOS_OK;
 }
-int fos_feas_gapp_log(fos_feas_handle h, double* out23) {
-    if (!h || !out23) { set_error("NULL argument"); return FOS_EINVAL; }
-    memcpy(out23, h->gapp_log, sizeof(h->gapp_log));
-    return FOS_OK;
-}
-
 int fos_feas_set_linesearch(fos_feas_handle h, int64_t lsinterval) {
     if (!h || lsinterval < 0) { set_error("bad argument"); return FOS_EINVAL; }
-    if (lsinterval > 0 && h->alg != FOS_ALG_GAP && h->alg != FOS_ALG_GAPA) {
-        set_error("this algorithm does not support line search (support_linesearch: GAP and GAPA only, solvers/defaults.jl:22)");
-        return FOS_EUNSUPPORTED;
-    }
-    // (a search iteration returns before the planes of a saving window are written: the two wrappers exclude each other, both ways)
-    if (lsinterval > 0 && h->lp.interval > 0) { set_error("LineSearchWrapper inside a LongstepWrapper is not supported (fos_feas_set_longstep(h, 0, 0) first)"); return FOS_EUNSUPPORTED; }
-    h->ls_interval = lsinterval;
+    FOS_TRY(wrappers_check(h->wr, WRAP_LINESEARCH, h->alg, false, lsinterval, 0));
+    h->wr.ls_interval = lsinterval;
     return FOS_OK;
 }
 // LongstepWrapper on the Feasibility form (as fos_set_longstep)
 int fos_feas_set_longstep(fos_feas_handle h, int64_t longinterval, int64_t nsave) {
     if (!h || longinterval < 0 || nsave < 0) { set_error("bad argument"); return FOS_EINVAL; }
-    if (longinterval == 0) { h->lp.interval = 0; h->lp.savepos = 0; h->lp.now = false; return FOS_OK; }
-    if (h->alg == FOS_ALG_GAPP) { set_error("Algorithm alg does not support longstep (support_longstep(::GAPP) = false, gapproj.jl:83)"); return FOS_EUNSUPPORTED; }
-    if (2 * (nsave + 1) > LONG_KMAX_ROWS) { set_error("LongstepWrapper: nsave <= %d", LONG_KMAX_ROWS / 2 - 1); return FOS_EUNSUPPORTED; }
-    if (longinterval < nsave + 1) { set_error("LongstepWrapper: longinterval must be at least nsave + 1"); return FOS_EINVAL; }
-    if (h->ls_interval > 0) { set_error("LongstepWrapper around a LineSearchWrapper is not supported"); return FOS_EUNSUPPORTED; }
+    if (longinterval == 0) { h->wr.lp.interval = 0; h->wr.lp.savepos = 0; h->wr.lp.now = false; return FOS_OK; }
+    FOS_TRY(wrappers_check(h->wr, WRAP_LONGSTEP, h->alg, false, longinterval, nsave));
     FOS_HIP(hipSetDevice(h->device));
-    const int64_t K = 2 * (nsave + 1);
-    if (!h->lp.P || h->lp.nsave != nsave) {
-        FOS_HIP(hipStreamSynchronize(h->stream));
-        for (void* old : {(void*)h->lp.P, (void*)h->lp.bpart, (void*)h->lp.dots, (void*)h->lp.nu}) {       // replaced, not piled up (feas_alloc zeroes the new ones)
-            if (!old) continue;
-            auto it = std::find(h->owned.begin(), h->owned.end(), old);
-            if (it != h->owned.end()) h->owned.erase(it);
-            (void)hipFree(old);
-        }
-        h->lp.P = nullptr; h->lp.bpart = nullptr; h->lp.dots = nullptr; h->lp.nu = nullptr;
-        double* q = nullptr;
-        FOS_TRY(h->zeros(&q, (size_t)K * h->L, h->stream)); h->lp.P = reinterpret_cast<double2*>(q);
-        FOS_TRY(h->zeros(&h->lp.bpart, (size_t)K * h->grid, h->stream));
-        FOS_TRY(h->zeros(&h->lp.dots, (size_t)h->grid * 2 * (LONG_KMAX_ROWS + 1), h->stream));
-        FOS_TRY(h->zeros(&h->lp.nu, (size_t)2 * K, h->stream));
-    }
-    h->lp.interval = longinterval; h->lp.nsave = nsave; h->lp.savepos = 0; h->lp.now = false;
-    h->lp.max_supports = getenv("FOS_LONG_MAX_SUPPORTS") ? atoll(getenv("FOS_LONG_MAX_SUPPORTS")) : 4096;
-    h->lp.log[7] = 0.0;
-    return FOS_OK;
+    return long_setup(h->wr.lp, longinterval, nsave, (size_t)h->L / 2, (size_t)h->grid, h->stream, h->owned, [h](double** out, size_t count) { return h->zeros(out, count, h->stream); });
 }
-int fos_feas_longstep_log(fos_feas_handle h, double* out8) {
-    if (!h || !out8) { set_error("NULL argument"); return FOS_EINVAL; }
-    memcpy(out8, h->lp.log, sizeof(h->lp.log));
-    return FOS_OK;
-}
-int fos_feas_linesearch_log(fos_feas_handle h, double* out34) {
-    if (!h || !out34) { set_error("NULL argument"); return FOS_EINVAL; }
-    memcpy(out34, h->ls_log, sizeof(h->ls_log));
-    return FOS_OK;
-}
+int fos_feas_linesearch_log(fos_feas_handle h, double* out34) { return wrappers_copy_log(h ? h->wr.ls_log : nullptr, 34, out34); }
+int fos_feas_gapp_log(fos_feas_handle h, double* out23) { return wrappers_copy_log(h ? h->wr.gapp_log : nullptr, 23, out23); }
+int fos_feas_longstep_log(fos_feas_handle h, double* out8) { return wrappers_copy_log(h ? h->wr.lp.log : nullptr, 8, out8); }
 
 // x = x0 (NULL: zeros(n), Feasibility.jl:58) and the state of a fresh init_algorithm!: alpha12 = 2 (gapa.jl:29), t = 1, y = xold = 0
 // (fista.jl:22-24), p = q = 0 (dykstra.jl:21-22), prev = NaN (Feasibility.jl:78)

@@ -558,11 +558,11 @@ struct LongPlanes {
     double* nu = nullptr;              // [rows][hi, lo] multipliers, device copy
     double log[8] = {0};               // last projection: iteration, active inequalities, KKT violation, |x_new - x|, rows, supports tried, [6] given up (0 / 1),
                                        // [7] projections given up since fos_set_longstep
-    int64_t max_supports = 4096;       // candidate supports a projection may try (FOS_LONG_MAX_SUPPORTS, read at fos_set_longstep)
+    int64_t max_supports = 4096;       // candidate supports a projection may try (FOS_LONG_MAX_SUPPORTS, read at long_setup)
 };
 struct LaunchCtx;
 void long_save_plane(const LaunchCtx& c, LongPlanes& lp, int which, const double2* y, const double2* x);      // addprojeq (0) / addprojineq (1) at lp.savepos
-int long_project_planes(const LaunchCtx& c, LongPlanes& lp, double2* X, int64_t i);                          // projectonnormals! + x .= tmp   (solver.cpp)
+int long_project_planes(const LaunchCtx& c, LongPlanes& lp, double2* X, int64_t i);                          // projectonnormals! + x .= tmp   (wrappers.cpp)
 void launch_long_plane(const LaunchCtx& c, double2* row, const double2* x, const double2* y, double* bpart);          // row = x - y; bpart[blocks]: partial sums of (x - y).y
 void launch_long_dots(const LaunchCtx& c, const double2* P, int K, int a, const double2* x, double* out);              // out[blocks][33][hi, lo]: row_a . row_{a+k}, k < 32; [32]: row_a . x (double-double)
 void launch_long_apply(const LaunchCtx& c, double2* x, const double2* P, int K, const double* nu);                     // x += sum_k nu[k] row_k

@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "fos_internal.hpp"
+#include "wrappers.hpp"
 
 typedef double2 d2;
 
@@ -176,20 +177,10 @@ struct fos_solver {
     int hit_max_accum = 0;
     bool firstrun2 = true;                     // HSDEMatrix.cgdata.firstrun
     int last_cg_pred = 0;
-    // LineSearchWrapper (wrappers/linesearch.jl): every ls_interval-th iteration is a 31-point step-length search
     bool shift_ready = false;                  // RHS already holds SOL - [0; X.y] (written by the step's last kernel): inside fos_step only
     bool shift_fuse = true;                    // FOS_SHIFT_FUSE=0: every projection runs its own shift pass
     bool in_step = false;
-    int64_t ls_interval = 0;
-    bool ls_now = false;                       // the iteration in flight is a line-search iteration (between step_once and step_finish)
-    // GAPP ("projected GAP", solvers/gapproj.jl): GAP whose every gapp_iproj-th iteration is a 21-point projected search
-    int64_t gapp_iproj = 0;
-    bool gapp_now = false;
-    double gapp_log[23] = {0};                 // 21 test norms, alpha_best, iteration
-    double ls_log[34] = {0};                   // last search: ||res||, the 31 test residuals, the chosen alpha, the iteration
-    // LongstepWrapper (wrappers/longstep.jl, saveplanes.jl): the last nsave + 1 iterations of every long_interval save the two half-planes of
-    // their projections; the iterate is then projected onto the saved planes
-    fos::LongPlanes lp;                             // (fos_internal.hpp)
+    fos::Wrappers wr;                          // LineSearchWrapper, GAPP, LongstepWrapper (wrappers.hpp)
     int cg_same_run = 0;                       // consecutive solves that took exactly last_cg_pred iterations
     const d2* last_checked = nullptr;          // vector the last checkstatus was evaluated on
 

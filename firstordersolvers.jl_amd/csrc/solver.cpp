@@ -557,90 +557,58 @@ int status_check(fos_solver* h, const d2* z, double eps, fos_check_result* res) 
 
 // ---- LineSearchWrapper(GAP / GAPA)                                   wrappers/linesearch.jl:36-75
 // S1!(y, x) = a1 prox_S1(x) + (1 - a1) x ,  S2!(y, x) = a2 prox_S2(x) + (1 - a2) x   (gap.jl:42-59; GAPA: a1 = a2 = alpha12, gapa.jl:61-79)
-// scratch: Y = tmp1 (the iterate the search starts from), XOLD = res, W = tmp3 -- unused by these two algorithms
 void ls_relax(fos_solver* h, const LaunchCtx& c, d2* out, const d2* y, const d2* x, int which) {
     if (h->alg == FOS_ALG_GAPA) { launch_relax_a12(c, out, y, x); return; }
     const double a = which == 1 ? h->alpha1 : h->alpha2;
     launch_axpby(c, out, a, y, 1 - a, x);
 }
-int ls_normdiff(fos_solver* h, const LaunchCtx& c, const d2* x, const d2* y, double* out) {
-    launch_normdiff(c, x, y);
-    std::vector<double> part((size_t)c.vec_blocks);
-    FOS_HIP(hipMemcpyAsync(part.data(), c.partials, sizeof(double) * part.size(), hipMemcpyDeviceToHost, h->stream));
-    FOS_HIP(hipStreamSynchronize(h->stream));
-    double s = 0.0;
-    for (double v : part) s += v;
-    *out = std::sqrt(s);
-    return FOS_OK;
-}
+// the searches' view of the handle (wrappers.hpp).  Scratch: Y = tmp1 (the point the search starts from), XOLD = res, W = tmp3 -- unused by GAP and GAPA; the
+// line search's tmp2 is T1 with prox_S2's result in T2; GAPP's tmp2 is T2, its tmp4 T1, and prox!(res, S1, .) leaves its result in SOL
+struct HsdeSearch {
+    fos_solver* h; LaunchCtx c;
+    d2 *x, *tmp1, *tmp2, *res, *tmp3, *tmp4; const d2* res_from;
+    explicit HsdeSearch(fos_solver* h_) : h(h_), c(h_->ctx()), x(h_->X), tmp1(h_->Y), tmp2(h_->T2), res(h_->XOLD), tmp3(h_->W), tmp4(h_->T1), res_from(h_->SOL) {}
+    int relaxed_s1(const d2* in) { FOS_TRY(prox_affine(h, in)); ls_relax(h, c, h->T1, h->SOL, in, 1); return FOS_OK; }
+    int relaxed_s2(d2* out) { FOS_TRY(prox_cones(h, h->T2, h->T1)); ls_relax(h, c, out, h->T2, h->T1, 2); return FOS_OK; }
+    int prox_s2(d2* out, const d2* in) { return prox_cones(h, out, in); }
+    void axpy(d2* out, const d2* base, double a, const d2* dir) { launch_axpby(c, out, 1.0, base, a, dir); }
+    void sub(d2* out, const d2* a, const d2* b) { launch_axpby(c, out, 1.0, a, -1.0, b); }
+    int normdiff(const d2* a, const d2* b, double* out) { launch_normdiff(c, a, b); return norm_of_partials(c.partials, (size_t)c.vec_blocks, h->stream, out); }
+};
 int ls_begin(fos_solver* h, const d2** check_on) {
-    LaunchCtx c = h->ctx();
+    HsdeSearch f(h);
     FOS_HIP(hipMemcpyAsync(h->Y, h->X, sizeof(d2) * h->l, hipMemcpyDeviceToDevice, h->stream));     // tmp1 .= x            :41
-    FOS_TRY(prox_affine(h, h->X));                                                                  // S1!(tmp2, x)         :45
-    ls_relax(h, c, h->T1, h->SOL, h->X, 1);
+    FOS_TRY(f.relaxed_s1(h->X));                                                                    // S1!(tmp2, x)         :45
     FOS_TRY(prox_cones(h, h->T2, h->T1));                                                           // S2!(x, tmp2): prox + checkstatus :46
     *check_on = h->T2;
     return FOS_OK;
 }
 int ls_finish(fos_solver* h, int64_t i) {
-    LaunchCtx c = h->ctx();
-    ls_relax(h, c, h->X, h->T2, h->T1, 2);                                                          //   ... and its relaxation
-    launch_axpby(c, h->XOLD, 1.0, h->X, -1.0, h->Y);                                                // res .= x .- tmp1     :49
-    FOS_TRY(ls_normdiff(h, c, h->X, h->Y, &h->ls_log[0]));                                          // normres = norm(res)  :50
-    double best = INFINITY, abest = 1.0, a = 0.1;                                                   // :53-55
-    for (int k = 0; k <= 30; ++k) {                                                                 // :56
-        a = a * 1.8;                                                                                // :57
-        launch_axpby(c, h->X, 1.0, h->Y, a, h->XOLD);                                               // x .= tmp1 .+ a.*res  :58
-        FOS_TRY(prox_affine(h, h->X));                                                              // S1!(tmp2, x, nostatus) :60
-        ls_relax(h, c, h->T1, h->SOL, h->X, 1);
-        FOS_TRY(prox_cones(h, h->T2, h->T1));                                                       // S2!(tmp3, tmp2, nostatus) :61
-        ls_relax(h, c, h->W, h->T2, h->T1, 2);
-        double tr = 0.0;
-        FOS_TRY(ls_normdiff(h, c, h->X, h->W, &tr));                                                // testres = normdiff(x, tmp3) :62
-        h->ls_log[1 + k] = tr;
-        if (tr < best) { best = tr; abest = a; }                                                    // :64-67
-    }
-    launch_axpby(c, h->X, 1.0, h->Y, abest, h->XOLD);                                               // x .= tmp1 .+ abest.*res :70
-    h->ls_log[32] = abest;
-    h->ls_log[33] = (double)i;
-    return FOS_OK;
+    HsdeSearch f(h);
+    ls_relax(h, f.c, h->X, h->T2, h->T1, 2);                                                        //   ... and its relaxation
+    return linesearch_search(f, h->wr.ls_log, i);
 }
 
 // ---- GAPP, a search iteration                                       solvers/gapproj.jl:29-62
-// scratch: Y = tmp1 = P_S1(x), XOLD = res, W = tmp3 / the new tmp1, T1 = tmp4 -- Y, XOLD, W are unused by GAP
 int gapp_begin(fos_solver* h, int64_t i, const d2** check_on) {
-    LaunchCtx c = h->ctx();
+    HsdeSearch f(h);
     FOS_TRY(prox_affine(h, h->X));                                                                  // prox!(tmp1, S1, x)        :33
     FOS_HIP(hipMemcpyAsync(h->Y, h->SOL, sizeof(d2) * h->l, hipMemcpyDeviceToDevice, h->stream));
     FOS_TRY(prox_cones(h, h->T2, h->Y));                                                            // prox!(tmp2, S2, tmp1)     :39
     FOS_TRY(prox_affine(h, h->T2));                                                                 // prox!(res, S1, tmp2)      :40
-    launch_axpby(c, h->XOLD, 1.0, h->SOL, -1.0, h->Y);                                              // res .= res - tmp1         :41
-    double normbest = INFINITY, abest = -1.0;                                                       // :44-45
-    for (int k = 0; k <= 20; ++k) {                                                                 // :46
-        const double at = std::ldexp(1.0, k);                                                       // 2.0^k
-        launch_axpby(c, h->W, 1.0, h->Y, at, h->XOLD);                                              // tmp3 .= tmp1 .+ at.*res
-        FOS_TRY(prox_cones(h, h->T1, h->W));                                                        // prox!(tmp4, S2, tmp3)
-        double nt = 0.0;
-        FOS_TRY(ls_normdiff(h, c, h->T1, h->W, &nt));                                               // norm(tmp4 - tmp3)
-        h->gapp_log[k] = nt;
-        if (nt < normbest) { abest = at; normbest = nt; }
-    }
-    h->gapp_log[21] = abest; h->gapp_log[22] = (double)i;
-    launch_axpby(c, h->W, 1.0, h->Y, abest, h->XOLD);                                               // tmp1 .= tmp1 .+ abest.*res :58
-    FOS_TRY(prox_cones(h, h->T2, h->W));                                                            // prox!(tmp2, S2, tmp1)     :59
+    FOS_TRY(gapp_search(f, h->wr.gapp_log, i));
     *check_on = h->T2;                                                                              // checkstatus(status, tmp2) :60
     return FOS_OK;
 }
 int gapp_finish(fos_solver* h) {
-    LaunchCtx c = h->ctx();
-    launch_axpby(c, h->X, h->alpha2, h->T2, 1 - h->alpha2, h->W);                                   // x .= a2 tmp2 + (1-a2) tmp1 :61-62
+    launch_axpby(h->ctx(), h->X, h->alpha2, h->T2, 1 - h->alpha2, h->W);                            // x .= a2 tmp2 + (1-a2) tmp1 :61-62
     return FOS_OK;
 }
 
 // ---- LongstepWrapper                                                 wrappers/longstep.jl:41-101, saveplanes.jl:13-35
 int step_finish_launch(fos_solver* h, const LaunchCtx& c);
 // addprojeq (which = 0) / addprojineq (which = 1): row i = (savepos - 1) (neq + nineq) + eqi (+ uneqi) + 1 with neq = nineq = 1     longstep.jl:69,88
-void long_save(fos_solver* h, const LaunchCtx& c, int which, const d2* y, const d2* x) { fos::long_save_plane(c, h->lp, which, y, x); }
+void long_save(fos_solver* h, const LaunchCtx& c, int which, const d2* y, const d2* x) { fos::long_save_plane(c, h->wr.lp, which, y, x); }
 // a saving iteration: the step of the wrapped algorithm, unfused, with the two planes taken where the reference's step calls addprojeq /
 // addprojineq (gap.jl:47,57  gapa.jl:66,76  fista.jl:36,42  dykstra.jl:30,34)
 int long_begin(fos_solver* h, int64_t i, const d2** check_on) {
@@ -675,99 +643,6 @@ int long_begin(fos_solver* h, int64_t i, const d2** check_on) {
     }
     return FOS_EINVAL;
 }
-// The projection of x onto {v : A v = b, C v >= d}, A = the first nsave + 1 saved rows, C = the others (saveplanes.jl:17-28 -- the rows are
-// saved equality, inequality, equality, ... and split here into halves: the reference's behaviour, kept).  The reference hands the n-variable
-// problem to QPDAS in BigFloat; the solution is v = x + P' nu with nu = (lambda, mu >= 0) the minimiser of the SMALL dual
-//     1/2 nu' G nu - nu' (beta - P x),  G = P P'  (K = 2 (nsave + 1) <= 32 unknowns),
-// solved on the host: the inequality multipliers by enumeration of their support (<= 2^16 candidate supports; each a K x K symmetric system
-// by eigen-decomposition, singular ones -- parallel planes -- through the pseudo-inverse); a support is accepted when its multipliers are
-// non-negative and the inequalities outside it hold.  Only G, P x and beta leave the device; x += P' nu runs there.
-// 113-bit arithmetic for the small dual QP of the LongstepWrapper (the reference solves it in BigFloat, saveplanes.jl:24)
-typedef __float128 qreal;
-static inline qreal qabs(qreal x) { return x < 0 ? -x : x; }
-static inline qreal qsqrt(qreal x) {
-    if (!(x > 0)) return 0;
-    qreal y = (qreal)sqrtl((long double)x);
-    y = (y + x / y) / 2; y = (y + x / y) / 2;
-    return y;
-}
-static void sym_eig_jacobi(int n, std::vector<qreal>& A, std::vector<qreal>& V) {      // A (n x n, row-major) -> eigenvalues on its diagonal, eigenvectors in the columns of V
-    V.assign((size_t)n * n, (qreal)0);
-    for (int i = 0; i < n; ++i) V[(size_t)i * n + i] = 1;
-    for (int sweep = 0; sweep < 80; ++sweep) {
-        qreal off = 0, diag = 0;
-        for (int i = 0; i < n; ++i) { diag += A[(size_t)i * n + i] * A[(size_t)i * n + i]; for (int j = i + 1; j < n; ++j) off += A[(size_t)i * n + j] * A[(size_t)i * n + j]; }
-        if (off <= (qreal)1e-64 * diag || off == 0) break;
-        for (int p = 0; p < n; ++p)
-            for (int q = p + 1; q < n; ++q) {
-                const qreal apq = A[(size_t)p * n + q];
-                if (apq == 0) continue;
-                const qreal theta = (A[(size_t)q * n + q] - A[(size_t)p * n + p]) / (2 * apq);
-                const qreal t = (theta >= 0 ? (qreal)1 : (qreal)-1) / (qabs(theta) + qsqrt(theta * theta + 1));
-                const qreal cs = 1 / qsqrt(t * t + 1), sn = t * cs;
-                for (int k = 0; k < n; ++k) {
-                    const qreal akp = A[(size_t)k * n + p], akq = A[(size_t)k * n + q];
-                    A[(size_t)k * n + p] = cs * akp - sn * akq; A[(size_t)k * n + q] = sn * akp + cs * akq;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const qreal apk = A[(size_t)p * n + k], aqk = A[(size_t)q * n + k];
-                    A[(size_t)p * n + k] = cs * apk - sn * aqk; A[(size_t)q * n + k] = sn * apk + cs * aqk;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const qreal vkp = V[(size_t)k * n + p], vkq = V[(size_t)k * n + q];
-                    V[(size_t)k * n + p] = cs * vkp - sn * vkq; V[(size_t)k * n + q] = sn * vkp + cs * vkq;
-                }
-            }
-    }
-}
-// nu_F = pinv(G_FF) c_F on the index set F, zero elsewhere.  Cholesky first (a few thousand 113-bit operations); a pivot below 1e-26 of the
-// trace = dependent planes -> the pseudo-inverse through the eigendecomposition (eigenvalues below that cut dropped)
-static void long_solve_support(int K, const std::vector<qreal>& G, const std::vector<qreal>& cvec, const std::vector<int>& F, std::vector<qreal>& nu) {
-    const int nf = (int)F.size();
-    nu.assign((size_t)K, (qreal)0);
-    if (nf == 0) return;
-    std::vector<qreal> A((size_t)nf * nf), V;
-    qreal tr = 0;
-    for (int i = 0; i < nf; ++i) { for (int j = 0; j < nf; ++j) A[(size_t)i * nf + j] = G[(size_t)F[i] * K + F[j]]; tr += A[(size_t)i * nf + i]; }
-    const qreal cut = (qreal)1e-26 * (tr > 0 ? tr : (qreal)1e-300);
-    {
-        std::vector<qreal> L(A);
-        bool ok = true;
-        for (int j = 0; j < nf && ok; ++j) {
-            qreal dj = L[(size_t)j * nf + j];
-            for (int k = 0; k < j; ++k) dj -= L[(size_t)j * nf + k] * L[(size_t)j * nf + k];
-            if (!(dj > cut)) { ok = false; break; }
-            const qreal ljj = qsqrt(dj);
-            L[(size_t)j * nf + j] = ljj;
-            for (int i = j + 1; i < nf; ++i) {
-                qreal v = L[(size_t)i * nf + j];
-                for (int k = 0; k < j; ++k) v -= L[(size_t)i * nf + k] * L[(size_t)j * nf + k];
-                L[(size_t)i * nf + j] = v / ljj;
-            }
-        }
-        if (ok) {
-            std::vector<qreal> y((size_t)nf);
-            for (int i = 0; i < nf; ++i) { qreal v = cvec[(size_t)F[i]]; for (int k = 0; k < i; ++k) v -= L[(size_t)i * nf + k] * y[(size_t)k]; y[(size_t)i] = v / L[(size_t)i * nf + i]; }
-            for (int i = nf - 1; i >= 0; --i) { qreal v = y[(size_t)i]; for (int k = i + 1; k < nf; ++k) v -= L[(size_t)k * nf + i] * y[(size_t)k]; y[(size_t)i] = v / L[(size_t)i * nf + i]; }
-            for (int i = 0; i < nf; ++i) nu[(size_t)F[i]] = y[(size_t)i];
-            return;
-        }
-    }
-    sym_eig_jacobi(nf, A, V);
-    for (int e = 0; e < nf; ++e) {
-        const qreal lam = A[(size_t)e * nf + e];
-        if (!(lam > cut)) continue;
-        qreal proj = 0;
-        for (int i = 0; i < nf; ++i) proj += V[(size_t)i * nf + e] * cvec[(size_t)F[i]];
-        proj /= lam;
-        for (int i = 0; i < nf; ++i) nu[(size_t)F[i]] += V[(size_t)i * nf + e] * proj;
-    }
-}
-int long_project(fos_solver* h, int64_t i) {
-    FOS_TRY(fos::long_project_planes(h->ctx(), h->lp, h->X, i));
-    h->shift_ready = false;                                                   // (the iterate changed behind the step's last kernel)
-    return FOS_OK;
-}
 int long_finish(fos_solver* h, int64_t i) {
     LaunchCtx c = h->ctx();
     switch (h->alg) {
@@ -777,10 +652,8 @@ int long_finish(fos_solver* h, int64_t i) {
         case FOS_ALG_DYKSTRA: long_save(h, c, 1, h->X, h->W); break;          // addprojineq(longstep, x, y .+ q)
     }
     FOS_TRY(step_finish_launch(h, c));
-    if (h->lp.savepos == h->lp.nsave + 1) {                               // longstep.jl:53-58
-        FOS_TRY(long_project(h, i));
-        h->lp.savepos = -1;
-    }
+    FOS_TRY(long_window_close(c, h->wr.lp, h->X, i));
+    if (h->wr.lp.savepos == -1) h->shift_ready = false;                       // (projected: the iterate changed behind the step's last kernel)
     return FOS_OK;
 }
 
@@ -809,17 +682,12 @@ int affine_then(fos_solver* h, const LaunchCtx& c, const d2* in, const PostFn& p
 int step_once(fos_solver* h, int64_t i, const d2** check_on, bool will_check, bool* finish_done) {
     LaunchCtx c = h->ctx();
     *finish_done = false;
-    h->ls_now = h->ls_interval > 0 && (i % h->ls_interval) == 0;                                    // linesearch.jl:39
-    if (h->ls_now) return ls_begin(h, check_on);
-    h->gapp_now = h->gapp_iproj > 0 && (i % h->gapp_iproj) == 0;                                     // gapproj.jl:34
-    if (h->gapp_now) return gapp_begin(h, i, check_on);
-    h->lp.now = false;
-    if (h->lp.interval > 0) {                                                                      // longstep.jl:44-49
-        const int64_t savepos = (i - 1) % h->lp.interval - h->lp.interval + h->lp.nsave + 2;
-        if (savepos > 0) h->lp.savepos = savepos;
-        h->lp.now = h->lp.savepos > 0;
-        if (h->lp.now) return long_begin(h, i, check_on);
-    }
+    Wrappers& wr = h->wr;
+    wr.ls_now = wr.ls_interval > 0 && (i % wr.ls_interval) == 0;                                    // linesearch.jl:39
+    if (wr.ls_now) return ls_begin(h, check_on);
+    wr.gapp_now = wr.gapp_iproj > 0 && (i % wr.gapp_iproj) == 0;                                    // gapproj.jl:34
+    if (wr.gapp_now) return gapp_begin(h, i, check_on);
+    if (long_window(wr.lp, i)) return long_begin(h, i, check_on);                                   // longstep.jl:44-49
     switch (h->alg) {
         case FOS_ALG_GAP:                                                // gap.jl:61-80
         case FOS_ALG_GAPA: {                                             // gapa.jl:80-105
@@ -831,7 +699,7 @@ int step_once(fos_solver* h, int64_t i, const d2** check_on, bool will_check, bo
                 const bool fuse_ew = h->relax_ew, fuse_psd = h->psd_fuse;          // (per handle: read at fos_create)
                 // GAP / DR, no status check in this step, every non-elementwise cone a PSD(64) cone with a basis from the last projection:
                 // relaxation, projection and the step's last pass are ONE launch (PsdFuse, fos_internal.hpp)
-                if (fuse_psd && !gapa && !will_check && !h->ls_interval && !h->gapp_iproj && !h->lp.interval && cone_set_can_fuse(*h->cones, cg)) {
+                if (fuse_psd && !gapa && !will_check && !h->wr.active() && cone_set_can_fuse(*h->cones, cg)) {
                     RoctxRange range("fos:relaxation + PSD projection + final pass (one launch)");
                     const bool sh = h->in_step && h->shift_fuse && !h->direct_exact();
                     PsdFuse fz{};
@@ -906,9 +774,9 @@ int step_once(fos_solver* h, int64_t i, const d2** check_on, bool will_check, bo
 // the part of the step after checkstatus
 int step_finish(fos_solver* h, int64_t i) {
     LaunchCtx c = h->ctx();
-    if (h->ls_now) { h->ls_now = false; return ls_finish(h, i); }
-    if (h->gapp_now) { h->gapp_now = false; return gapp_finish(h); }
-    if (h->lp.now) { h->lp.now = false; return long_finish(h, i); }
+    if (h->wr.ls_now) { h->wr.ls_now = false; return ls_finish(h, i); }
+    if (h->wr.gapp_now) { h->wr.gapp_now = false; return gapp_finish(h); }
+    if (h->wr.lp.now) return long_finish(h, i);
     return step_finish_launch(h, c);
 }
 int step_finish_launch(fos_solver* h, const LaunchCtx& c) {
@@ -976,117 +844,6 @@ int download_caller(fos_solver* h, double* z, const d2* src) {
 }
 
 }  // namespace
-
-namespace fos {
-int long_project_planes(const LaunchCtx& c, LongPlanes& lp, d2* X, int64_t i) {
-    const int K = (int)(2 * (lp.nsave + 1)), neq = (int)(lp.nsave + 1), nin = K - neq;
-    const int nb = c.vec_blocks;
-    const size_t W = 2 * (LONG_KMAX_ROWS + 1);                                // (hi, lo) pairs per workgroup
-    std::vector<qreal> G((size_t)K * K, (qreal)0), Px((size_t)K, (qreal)0), beta((size_t)K, (qreal)0);
-    std::vector<double> part((size_t)nb * W), bp((size_t)K * nb);
-    for (int a = 0; a < K; ++a) {
-        launch_long_dots(c, lp.P, K, a, X, lp.dots);
-        FOS_HIP(hipMemcpyAsync(part.data(), lp.dots, sizeof(double) * part.size(), hipMemcpyDeviceToHost, c.stream));
-        FOS_HIP(hipStreamSynchronize(c.stream));
-        for (int k = 0; a + k < K; ++k) {
-            qreal sacc = 0;
-            for (int b = 0; b < nb; ++b) sacc += (qreal)part[(size_t)b * W + 2 * k] + (qreal)part[(size_t)b * W + 2 * k + 1];
-            G[(size_t)a * K + a + k] = G[(size_t)(a + k) * K + a] = sacc;
-        }
-        qreal sx = 0;
-        for (int b = 0; b < nb; ++b) sx += (qreal)part[(size_t)b * W + 2 * LONG_KMAX_ROWS] + (qreal)part[(size_t)b * W + 2 * LONG_KMAX_ROWS + 1];
-        Px[(size_t)a] = sx;
-    }
-    FOS_HIP(hipMemcpyAsync(bp.data(), lp.bpart, sizeof(double) * bp.size(), hipMemcpyDeviceToHost, c.stream));
-    FOS_HIP(hipStreamSynchronize(c.stream));
-    // (the offsets b = (x - y).y are float64 sums in the reference too, longstep.jl:71-75: data of the QP, not part of its solution)
-    for (int a = 0; a < K; ++a) { double sacc = 0.0; for (int b = 0; b < nb; ++b) sacc += bp[(size_t)a * nb + b]; beta[(size_t)a] = (qreal)sacc; }
-    std::vector<qreal> cvec((size_t)K);
-    for (int a = 0; a < K; ++a) cvec[(size_t)a] = beta[(size_t)a] - Px[(size_t)a];
-    qreal scale = 0;
-    for (int a = 0; a < K; ++a) { const qreal v = qabs(cvec[(size_t)a]) + qsqrt(G[(size_t)a * K + a]); if (v > scale) scale = v; }
-    if (!(scale > 0)) scale = (qreal)1e-300;
-    std::vector<qreal> nu, best_nu((size_t)K, (qreal)0);
-    qreal best_viol = (qreal)INFINITY;
-    int best_active = 0;
-    int64_t tried = 0;
-    std::vector<int> F;
-    std::vector<qreal> gres((size_t)K);
-    // one candidate support: solve, residuals g = G nu - c, KKT violation (equality residuals, negative multipliers inside the support, violated
-    // inequalities outside it); true when it is the solution
-    auto try_support = [&](uint32_t mask) {
-        F.clear();
-        for (int a = 0; a < neq; ++a) F.push_back(a);
-        for (int j = 0; j < nin; ++j) if (mask & (1u << j)) F.push_back(neq + j);
-        long_solve_support(K, G, cvec, F, nu);
-        ++tried;
-        qreal viol = 0;
-        for (int a = 0; a < K; ++a) {
-            qreal g = -cvec[(size_t)a];                                       // (G nu - c)_a = P_a v - beta_a
-            for (int b2 = 0; b2 < K; ++b2) g += G[(size_t)a * K + b2] * nu[(size_t)b2];
-            gres[(size_t)a] = g;
-            qreal va;
-            if (a < neq) va = qabs(g);
-            else if (mask & (1u << (a - neq))) { const qreal gd = G[(size_t)a * K + a]; const qreal m2 = -nu[(size_t)a] * qsqrt(gd > 0 ? gd : (qreal)1e-300); va = qabs(g) > m2 ? qabs(g) : m2; }
-            else va = -g;
-            if (va > viol) viol = va;
-        }
-        if (viol < best_viol) { best_viol = viol; best_nu = nu; best_active = __builtin_popcount(mask); }
-        return best_viol <= (qreal)1e-12 * scale;
-    };
-    // (i) an active-set walk from the empty support: drop the most negative multiplier, else add the most violated inequality -- a handful of
-    //     solves when it ends at the solution (it is accepted by the same KKT test); (ii) otherwise the enumeration of all supports
-    bool found = false;
-    // budget of candidate supports (FOS_LONG_MAX_SUPPORTS; 0 tries none: the failure path, tests)
-    // (read once, at fos_set_longstep; a COUNT only -- a wall-clock cut-off made the iterate sequence depend on the load of the machine)
-    const int64_t LONG_MAX_SUPPORTS = lp.max_supports;
-    {
-        uint32_t mask = 0;
-        std::vector<uint32_t> seen;
-        for (int it = 0; it < 4 * nin + 4 && !found && tried < LONG_MAX_SUPPORTS; ++it) {
-            if (std::find(seen.begin(), seen.end(), mask) != seen.end()) break;
-            seen.push_back(mask);
-            if (try_support(mask)) { found = true; break; }
-            int drop = -1, add = -1;
-            qreal worst_nu = 0, worst_g = 0;
-            for (int j = 0; j < nin; ++j) {
-                const int a = neq + j;
-                if (mask & (1u << j)) { if (nu[(size_t)a] < worst_nu) { worst_nu = nu[(size_t)a]; drop = j; } }
-                else if (gres[(size_t)a] < worst_g) { worst_g = gres[(size_t)a]; add = j; }
-            }
-            if (drop >= 0) mask &= ~(1u << drop);
-            else if (add >= 0) mask |= 1u << add;
-            else break;
-        }
-    }
-    // (ii) bounded: inconsistent or dependent planes have NO support that passes the KKT test, and 2^nin solves in 113-bit arithmetic (each a
-    // Jacobi eigen-decomposition when Cholesky rejects the block) would hold fos_step for minutes -- at most LONG_MAX_SUPPORTS candidates, smallest
-    // supports first in counting order (deterministic: the same problem projects, or does not, on every run)
-    for (uint32_t mask = 0; !found && mask < (1u << nin) && tried < LONG_MAX_SUPPORTS; ++mask) found = try_support(mask);
-    lp.log[6] = found ? 0.0 : 1.0;
-    if (!found) lp.log[7] += 1.0;                              // projections given up since fos_set_longstep (the host mirrors warn when it grows)
-    if (!found) {
-        // no KKT point of the small dual within the budget: the planes do not describe a projection -- the iterate stays as the wrapped
-        // algorithm left it (the reference's QP solver throws here; a step that is not the projection must not be applied silently)
-        lp.log[0] = (double)i; lp.log[1] = (double)best_active; lp.log[2] = (double)(best_viol / scale); lp.log[3] = 0.0; lp.log[4] = (double)K; lp.log[5] = (double)tried;
-        return FOS_OK;
-    }
-    qreal step2 = 0;                                                          // |P' nu|^2 = nu' G nu
-    for (int a = 0; a < K; ++a) for (int b2 = 0; b2 < K; ++b2) step2 += best_nu[(size_t)a] * G[(size_t)a * K + b2] * best_nu[(size_t)b2];
-    std::vector<double> nu2((size_t)2 * K);                                   // multipliers as (hi, lo) pairs for the double-double update
-    for (int a = 0; a < K; ++a) { const double hi = (double)best_nu[(size_t)a]; nu2[(size_t)2 * a] = hi; nu2[(size_t)2 * a + 1] = (double)(best_nu[(size_t)a] - (qreal)hi); }
-    FOS_HIP(hipMemcpyAsync(lp.nu, nu2.data(), sizeof(double) * 2 * K, hipMemcpyHostToDevice, c.stream));
-    launch_long_apply(c, X, lp.P, K, lp.nu);                     // x .= longstep.tmp      longstep.jl:57
-    FOS_HIP(hipStreamSynchronize(c.stream));                                 // (nu2 leaves scope)
-    lp.log[0] = (double)i; lp.log[1] = (double)best_active; lp.log[2] = (double)best_viol; lp.log[3] = (double)qsqrt(step2 > 0 ? step2 : (qreal)0);
-    lp.log[4] = (double)K; lp.log[5] = (double)tried;
-    return FOS_OK;
-}
-void long_save_plane(const LaunchCtx& c, LongPlanes& lp, int which, const d2* y, const d2* x) {
-    const int64_t row = 2 * (lp.savepos - 1) + which;
-    launch_long_plane(c, lp.P + row * c.l, x, y, lp.bpart + row * c.vec_blocks);
-}
-}  // namespace fos
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -1324,9 +1081,7 @@ int fos_set_alg(fos_handle h, int alg, double alpha, double alpha1, double alpha
     if (alg < FOS_ALG_GAP || alg > FOS_ALG_DYKSTRA) { set_error("unknown algorithm %d", alg); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
     h->alg = alg; h->alpha = alpha; h->alpha1 = alpha1; h->alpha2 = alpha2; h->beta = beta;
-    h->ls_interval = 0; h->ls_now = false;                              // a fresh algorithm is unwrapped (fos_set_linesearch follows)
-    h->gapp_iproj = 0; h->gapp_now = false;                             // ... and plain (fos_set_gapp follows)
-    h->lp.interval = 0; h->lp.savepos = 0; h->lp.now = false;     // ... (fos_set_longstep follows)
+    h->wr.off();                                                        // a fresh algorithm is unwrapped (fos_set_linesearch / _gapp / _longstep follow)
     h->fista_t = 1.0;                                                   // fista.jl:24
     // fresh *Data: alpha12 = 2.0 (gapa.jl:29); y = xold = 0 (fista.jl:24); p = q = 0 (dykstra.jl:21)
     DevState z;
@@ -1413,70 +1168,31 @@ int fos_step(fos_handle h, int64_t i_first, int64_t count, int64_t checki, doubl
 // the step length along S2(S1(x)) - x; 0 switches it off.  fos_linesearch_log: what the reference prints during the last search.
 int fos_set_linesearch(fos_handle h, int64_t lsinterval) {
     if (!h || lsinterval < 0) { set_error("bad argument"); return FOS_EINVAL; }
-    if (lsinterval > 0 && h->alg != FOS_ALG_GAP && h->alg != FOS_ALG_GAPA) {
-        set_error("this algorithm does not support line search (support_linesearch: GAP and GAPA only, solvers/defaults.jl:22)");
-        return FOS_EUNSUPPORTED;
-    }
-    if (lsinterval > 0 && (h->sharded() || h->row_sharded)) {
-        // normres / normdiff (linesearch.jl:50,62) are GLOBAL norms; the search below adds this rank's partial sums only
-        set_error("LineSearchWrapper is built for single-GPU handles only (its step-length scores are global norms)");
-        return FOS_EUNSUPPORTED;
-    }
-    if (lsinterval > 0 && h->lp.interval > 0) { set_error("LineSearchWrapper inside a LongstepWrapper is not supported"); return FOS_EUNSUPPORTED; }
-    h->ls_interval = lsinterval;
+    FOS_TRY(wrappers_check(h->wr, WRAP_LINESEARCH, h->alg, h->sharded() || h->row_sharded, lsinterval, 0));
+    h->wr.ls_interval = lsinterval;
     return FOS_OK;
 }
 // GAPP(alpha, alpha1, alpha2; iproj) (solvers/gapproj.jl, README solver table): fos_set_alg(FOS_ALG_GAP, alpha, alpha1, alpha2) and then
 // fos_set_gapp(iproj > 0): iterations i with i % iproj == 0 search 21 step lengths 2^k along P_S1(P_S2(P_S1 x)) - P_S1 x.
 int fos_set_gapp(fos_handle h, int64_t iproj) {
     if (!h || iproj < 0) { set_error("bad argument"); return FOS_EINVAL; }
-    if (iproj > 0 && h->alg != FOS_ALG_GAP) { set_error("GAPP is GAP with a projected search: fos_set_alg(FOS_ALG_GAP, ...) first"); return FOS_EUNSUPPORTED; }
-    if (iproj > 0 && (h->sharded() || h->row_sharded)) { set_error("GAPP is built for single-GPU handles only (its test norms are global norms)"); return FOS_EUNSUPPORTED; }
-    if (iproj > 0 && h->ls_interval > 0) { set_error("GAPP and the LineSearchWrapper exclude each other"); return FOS_EUNSUPPORTED; }
-    if (iproj > 0 && h->lp.interval > 0) { set_error("GAPP inside a LongstepWrapper is not supported (fos_set_longstep(h, 0, 0) first)"); return FOS_EUNSUPPORTED; }
-    h->gapp_iproj = iproj;
-    return FOS_OK;
-}
-int fos_gapp_log(fos_handle h, double* out23) {
-    if (!h || !out23) { set_error("NULL argument"); return FOS_EINVAL; }
-    memcpy(out23, h->gapp_log, sizeof(h->gapp_log));
+    FOS_TRY(wrappers_check(h->wr, WRAP_GAPP, h->alg, h->sharded() || h->row_sharded, iproj, 0));
+    h->wr.gapp_iproj = iproj;
     return FOS_OK;
 }
 // LongstepWrapper(alg; longinterval, nsave) around the algorithm set last (wrappers/longstep.jl:22-40): 0 switches it off
 int fos_set_longstep(fos_handle h, int64_t longinterval, int64_t nsave) {
     if (!h || longinterval < 0 || nsave < 0) { set_error("bad argument"); return FOS_EINVAL; }
-    if (longinterval == 0) { h->lp.interval = 0; h->lp.savepos = 0; return FOS_OK; }
-    if (2 * (nsave + 1) > LONG_KMAX_ROWS) { set_error("LongstepWrapper: nsave <= %d (2 (nsave + 1) saved planes, small dual QP solved by enumeration)", LONG_KMAX_ROWS / 2 - 1); return FOS_EUNSUPPORTED; }
-    if (longinterval < nsave + 1) { set_error("LongstepWrapper: longinterval must be at least nsave + 1 (every plane is written before it is read)"); return FOS_EINVAL; }
-    if (h->sharded() || h->row_sharded) { set_error("LongstepWrapper is built for single-GPU handles only (the planes' products are global sums)"); return FOS_EUNSUPPORTED; }
-    if (h->ls_interval > 0 || h->gapp_iproj > 0) { set_error("LongstepWrapper around a LineSearchWrapper / GAPP is not supported"); return FOS_EUNSUPPORTED; }
+    if (longinterval == 0) { h->wr.lp.interval = 0; h->wr.lp.savepos = 0; return FOS_OK; }
+    FOS_TRY(wrappers_check(h->wr, WRAP_LONGSTEP, h->alg, h->sharded() || h->row_sharded, longinterval, nsave));
     FOS_HIP(hipSetDevice(h->device));
-    const int64_t K = 2 * (nsave + 1);
-    if (!h->lp.P || h->lp.nsave != nsave) {
-        FOS_HIP(hipStreamSynchronize(h->stream));
-        dev_release(h, &h->lp.P); dev_release(h, &h->lp.bpart); dev_release(h, &h->lp.dots); dev_release(h, &h->lp.nu);    // (a caller sweeping nsave must not pile buffers up)
-        // rows a saving window never wrote (fos_step entered in the middle of one) are zero planes, not uninitialised memory
-        FOS_TRY(dev_zeros(h, &h->lp.P, (size_t)K * h->l));
-        FOS_TRY(dev_zeros(h, &h->lp.bpart, (size_t)K * h->vec_blocks));
-        FOS_TRY(dev_alloc(h, &h->lp.dots, (size_t)h->vec_blocks * 2 * (LONG_KMAX_ROWS + 1)));
-        FOS_TRY(dev_alloc(h, &h->lp.nu, (size_t)2 * K));
-    }
-    h->lp.interval = longinterval; h->lp.nsave = nsave; h->lp.savepos = 0; h->lp.now = false;
-    h->lp.max_supports = getenv("FOS_LONG_MAX_SUPPORTS") ? atoll(getenv("FOS_LONG_MAX_SUPPORTS")) : 4096;      // (0 tries none: the failure path, tests)
-    h->lp.log[7] = 0.0;
-    return FOS_OK;
+    return long_setup(h->wr.lp, longinterval, nsave, (size_t)h->l, (size_t)h->vec_blocks, h->stream, h->owned, [h](double** out, size_t count) { return dev_zeros(h, out, count); });
 }
-// last projection of the LongstepWrapper: out8 = iteration, active inequalities, largest KKT violation of the small dual, |x_new - x|, rows, supports tried
-int fos_longstep_log(fos_handle h, double* out8) {
-    if (!h || !out8) { set_error("NULL argument"); return FOS_EINVAL; }
-    memcpy(out8, h->lp.log, sizeof(h->lp.log));
-    return FOS_OK;
-}
-int fos_linesearch_log(fos_handle h, double* out34) {
-    if (!h || !out34) { set_error("NULL argument"); return FOS_EINVAL; }
-    memcpy(out34, h->ls_log, sizeof(h->ls_log));
-    return FOS_OK;
-}
+// the last search / projection: fos_linesearch_log: ||res||, 31 test residuals, alpha, iteration; fos_gapp_log: 21 test norms, alpha, iteration; fos_longstep_log:
+// iteration, active inequalities, largest KKT violation of the small dual, |x_new - x|, rows, supports tried, failed, projections given up
+int fos_linesearch_log(fos_handle h, double* out34) { return wrappers_copy_log(h ? h->wr.ls_log : nullptr, 34, out34); }
+int fos_gapp_log(fos_handle h, double* out23) { return wrappers_copy_log(h ? h->wr.gapp_log : nullptr, 23, out23); }
+int fos_longstep_log(fos_handle h, double* out8) { return wrappers_copy_log(h ? h->wr.lp.log : nullptr, 8, out8); }
 
 int fos_getsol(fos_handle h, double* z_out, int32_t force_check, double eps, fos_check_result* res) {
     if (!h) { set_error("NULL handle"); return FOS_EINVAL; }

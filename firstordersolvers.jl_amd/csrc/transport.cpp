@@ -312,10 +312,15 @@ static int eq_refuse_sharding() {
     set_error("an equilibrated handle cannot be sharded: a rank knows neither the other ranks' column norms nor the global sigma, rho (create it with equil_passes = 0)");
     return FOS_EUNSUPPORTED;
 }
+// nor can a wrapped one: the searches' norms and the planes' Gram products are sums over this rank's part only (wrappers_check refuses the other order)
+static int wrappers_refuse_sharding() {
+    set_error("switch the LineSearchWrapper / GAPP / LongstepWrapper off before sharding the handle (fos_set_linesearch(h, 0), fos_set_gapp(h, 0), fos_set_longstep(h, 0, 0))");
+    return FOS_EUNSUPPORTED;
+}
 int fos_comm_init(fos_handle h, int nranks, int rank, const void* id128) {
     if (!h || nranks < 1 || rank < 0 || rank >= nranks) { set_error("bad comm arguments"); return FOS_EINVAL; }
     if (h->equilibrated()) return eq_refuse_sharding();
-    if (h->ls_interval > 0 || h->gapp_iproj > 0) { set_error("switch the LineSearchWrapper / GAPP off before sharding the handle (fos_set_linesearch(h, 0), fos_set_gapp(h, 0))"); return FOS_EUNSUPPORTED; }
+    if (h->wr.active()) return wrappers_refuse_sharding();
     FOS_TRY(rccl_load());
     FOS_HIP(hipSetDevice(h->device));
     ncclUniqueId id;
@@ -332,7 +337,7 @@ int fos_comm_init(fos_handle h, int nranks, int rank, const void* id128) {
 int fos_comm_init_host(fos_handle h, int nranks, int rank, fos_allreduce_fn fn, void* user) {
     if (!h || !fn || nranks < 1 || rank < 0 || rank >= nranks) { set_error("bad comm arguments"); return FOS_EINVAL; }
     if (h->equilibrated()) return eq_refuse_sharding();
-    if (h->ls_interval > 0 || h->gapp_iproj > 0) { set_error("switch the LineSearchWrapper / GAPP off before sharding the handle (fos_set_linesearch(h, 0), fos_set_gapp(h, 0))"); return FOS_EUNSUPPORTED; }
+    if (h->wr.active()) return wrappers_refuse_sharding();
     Transport& t = h->tr;
     if (t.comm || t.peer_on) { set_error("this handle already has a communicator"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
@@ -547,7 +552,7 @@ int fos_peer_enable(fos_handle h, int32_t on) {
     if (!h) { set_error("NULL handle"); return FOS_EINVAL; }
     if (on && !h->tr.peer.box) { set_error("fos_peer_enable before fos_peer_open"); return FOS_EINVAL; }
     if (on && h->row_sharded && !h->tr.vec.buf) { set_error("row-sharded handle: fos_peer_vec_export / fos_peer_vec_open before fos_peer_enable"); return FOS_EINVAL; }
-    if (on && (h->ls_interval > 0 || h->gapp_iproj > 0)) { set_error("switch the LineSearchWrapper / GAPP off before sharding the handle (fos_set_linesearch(h, 0), fos_set_gapp(h, 0))"); return FOS_EUNSUPPORTED; }
+    if (on && h->wr.active()) return wrappers_refuse_sharding();
     FOS_HIP(hipSetDevice(h->device));
     FOS_HIP(hipStreamSynchronize(h->stream));
     h->tr.peer_on = on != 0;

@@ -248,9 +248,35 @@ def host_equilibrate(A, b, c, K1, K2, passes=EQUILIBRATE_DEFAULT_PASSES):
     return dict(passes=int(passes), D=D, E=E, sigma=float(scal[0]), rho=float(scal[1]), gamma=float(scal[2]), A=As, b=bo, c=co)
 
 
-class HipHSDE:
+class _WrapperLogs:
+    """The last search / projection of the three wrappers, for both handles: `_log_prefix` names the form's entries (fos_ / fos_feas_)."""
+
+    def _wrapper_log(self, name, count):
+        out = np.zeros(count)
+        _lib.check(getattr(self._lib, self._log_prefix + name)(self._h, _lib.dptr(out)))
+        return out
+
+    def longstep_log(self):
+        """last projection onto the saved planes: dict(iteration, active inequalities, KKT violation of the small dual, step length, rows, supports tried)"""
+        out = self._wrapper_log("longstep_log", 8)
+        return dict(iteration=int(out[0]), active=int(out[1]), violation=float(out[2]), step=float(out[3]), rows=int(out[4]), tried=int(out[5]), failed=bool(out[6]),
+                    given_up=int(out[7]))
+
+    def gapp_log(self):
+        """(iteration, [21 test norms], alpha_best) of GAPP's last search."""
+        out = self._wrapper_log("gapp_log", 23)
+        return int(out[22]), out[0:21].copy(), float(out[21])
+
+    def linesearch_log(self):
+        """(iteration, ||res||, [31 test residuals], alpha_best) of the last search."""
+        out = self._wrapper_log("linesearch_log", 34)
+        return int(out[33]), float(out[0]), out[1:32].copy(), float(out[32])
+
+
+class HipHSDE(_WrapperLogs):
     """Owns one fos_handle: the device-resident S1 (AffinePlusLinear over HSDEMatrixQ), S2 (DualConeProduct),
     iterate and algorithm data.  == what init_algorithm!/get_sets_and_status build (FOSSolverInterface.jl:76-79)."""
+    _log_prefix = "fos_"
 
     def __init__(self, A, b, c, K1, K2, device=0, row_sharded=False, equilibrate=0):
         """row_sharded (SURVEY 8(f2)): this rank holds the rows of A of its K1 cones and all columns (sharding.shard_rows);
@@ -297,28 +323,9 @@ class HipHSDE:
         """LongstepWrapper around the current algorithm (longinterval 0: off); fos_set_longstep."""
         _lib.check(self._lib.fos_set_longstep(self._h, int(longinterval), int(nsave)))
 
-    def longstep_log(self):
-        """last projection onto the saved planes: dict(iteration, active inequalities, KKT violation of the small dual, step length, rows, supports tried)"""
-        out = np.zeros(8)
-        _lib.check(self._lib.fos_longstep_log(self._h, _lib.dptr(out)))
-        return dict(iteration=int(out[0]), active=int(out[1]), violation=float(out[2]), step=float(out[3]), rows=int(out[4]), tried=int(out[5]), failed=bool(out[6]),
-                    given_up=int(out[7]))
-
-    def gapp_log(self):
-        """(iteration, [21 test norms], alpha_best) of GAPP's last search."""
-        out = np.zeros(23)
-        _lib.check(self._lib.fos_gapp_log(self._h, _lib.dptr(out)))
-        return int(out[22]), out[0:21].copy(), float(out[21])
-
     def set_linesearch(self, lsinterval):
         """LineSearchWrapper around the current algorithm (0: off); fos_set_linesearch."""
         _lib.check(self._lib.fos_set_linesearch(self._h, int(lsinterval)))
-
-    def linesearch_log(self):
-        """(iteration, ||res||, [31 test residuals], alpha_best) of the last search."""
-        out = np.zeros(34)
-        _lib.check(self._lib.fos_linesearch_log(self._h, _lib.dptr(out)))
-        return int(out[33]), float(out[0]), out[1:32].copy(), float(out[32])
 
     def reset_affine(self):
         _lib.check(self._lib.fos_reset_affine(self._h))
@@ -1304,8 +1311,9 @@ def _csc_one_based(A):
     return i64, colptr, rowval, np.ascontiguousarray(A.data, dtype=np.float64)
 
 
-class HipFeasibility:
+class HipFeasibility(_WrapperLogs):
     """The device handle of a Feasibility problem (fos_feas_*): both sets, the algorithm's vectors and the status state."""
+    _log_prefix = "fos_feas_"
 
     def __init__(self, problem: Feasibility, device=0):
         self.n = problem.n
@@ -1450,24 +1458,6 @@ class HipFeasibility:
             _lib.check(self._lib.fos_feas_set_linesearch(self._h, alg.lsinterval))
         if isinstance(alg, LongstepWrapper):
             _lib.check(self._lib.fos_feas_set_longstep(self._h, alg.longinterval, alg.nsave))
-
-    def longstep_log(self):
-        out = np.zeros(8)
-        _lib.check(self._lib.fos_feas_longstep_log(self._h, _lib.dptr(out)))
-        return dict(iteration=int(out[0]), active=int(out[1]), violation=float(out[2]), step=float(out[3]), rows=int(out[4]), tried=int(out[5]), failed=bool(out[6]),
-                    given_up=int(out[7]))
-
-    def gapp_log(self):
-        """(iteration, [21 test norms], alpha_best) of GAPP's last search."""
-        out = np.zeros(23)
-        _lib.check(self._lib.fos_feas_gapp_log(self._h, _lib.dptr(out)))
-        return int(out[22]), out[0:21].copy(), float(out[21])
-
-    def linesearch_log(self):
-        """(iteration, ||res||, [31 test residuals], alpha_best) of the last search."""
-        out = np.zeros(34)
-        _lib.check(self._lib.fos_feas_linesearch_log(self._h, _lib.dptr(out)))
-        return int(out[33]), float(out[0]), out[1:32].copy(), float(out[32])
 
     def set_iterate(self, x0=None):
         if x0 is None:

@@ -321,6 +321,12 @@ int fos_longstep_log(fos_handle h, double* out8);
  * alpha_best, iteration of the last search (what gapproj.jl:51,57 print).  Single-GPU handles. */
 int fos_set_gapp(fos_handle h, int64_t iproj);
 int fos_gapp_log(fos_handle h, double* out23);
+/* Test-only, host (no GPU needed): the LongstepWrapper's projection of x (n doubles) onto { v : P[0:neq] v = beta[0:neq], P[neq:] v >= beta[neq:] }, P the
+ * (neq + nin) x n rows, ROW-major, neq + nin <= 32, nin <= 16.  G = P P' and P x are formed in 113-bit arithmetic from the doubles, the small dual is solved by the
+ * function the device path calls (csrc/wrappers.cpp) with a budget of max_supports candidate supports, x_out = x + P' nu is rounded once.  log8 as
+ * fos_longstep_log (iteration 0); failed = 1 (log8[6]): x_out = x. */
+int fos_host_long_project(int64_t n, int64_t neq, int64_t nin, const double* P, const double* beta, const double* x, int64_t max_supports, double* x_out,
+                          double* log8);
 
 /* getsol(alg, data, x): one more S1 prox + S2 prox (gap.jl:82-87, gapa.jl:107-112, fista.jl:50-56); advances
  * the CG call counter like the reference.  z_out (N doubles) receives `guess`.  If force_check != 0 the

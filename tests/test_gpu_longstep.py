@@ -168,3 +168,52 @@ def test_longstep_without_a_kkt_point_leaves_the_iterate(pkg, monkeypatch):
     with pytest.raises(pkg.lib.FosError):
         pkg.lib.check(d._lib.fos_set_gapp(d._h, 10))
     d.close()
+
+
+def test_longstep_is_refused_when_sharding_follows(pkg):
+    """The planes' Gram products and offsets are sums over this rank's part of the vectors only, so the LongstepWrapper and sharding exclude each other in
+    BOTH orders, like the searches (test_linesearch_is_refused_on_sharded_handles): fos_set_longstep on a sharded handle was always refused; a transport
+    opened on a handle with the wrapper on went through, and every rank then projected onto planes whose products were local sums."""
+    prob = pkg.workloads.c1_readme_nnls(seed=2)
+    d = pkg.HipHSDE(prob.A, prob.b, prob.c, prob.K1, prob.K2)
+    d.set_alg(pkg.DR())
+    d.set_longstep(20, 2)
+    with pytest.raises(pkg.lib.FosError) as ei:
+        d.comm_init_host(1, 0, lambda a: None)
+    assert ei.value.code == -4                                 # FOS_EUNSUPPORTED
+    assert "LongstepWrapper" in str(ei.value)
+    d.set_longstep(0, 0)
+    d.comm_init_host(1, 0, lambda a: None)                     # fine once the wrapper is off
+    d.close()
+
+
+def test_longstep_setup_on_the_feasibility_form(pkg, monkeypatch):
+    """The set-up both forms share, on the Feasibility form, with the assertions of test_longstep_without_a_kkt_point_leaves_the_iterate: nsave swept on one
+    handle (the plane buffers are replaced, not piled up), then a full window whose projection succeeds; under a budget of zero candidate supports the log
+    says `failed` and the iterate is the unwrapped algorithm's -- bit for bit here: the Feasibility step has no fused variant, a saving iteration runs the
+    same launches plus the two that save the planes."""
+    A, b = affine_box_instance(m=50, n=100)
+    hp = pkg.Feasibility(pkg.IndAffine(A, b), pkg.IndBox(0.0, np.inf), 100)
+    d = pkg.HipFeasibility(hp)
+    for nsave in (1, 3, 2, 5):
+        d.set_alg(pkg.LongstepWrapper(pkg.AP(), longinterval=25, nsave=nsave))
+    runs = {}
+    for budget in (None, "0"):
+        if budget is None:
+            monkeypatch.delenv("FOS_LONG_MAX_SUPPORTS", raising=False)
+        else:
+            monkeypatch.setenv("FOS_LONG_MAX_SUPPORTS", budget)
+        d.set_alg(pkg.LongstepWrapper(pkg.AP(), longinterval=25, nsave=5))          # (the budget is read at the set-up)
+        d.set_iterate(None)
+        d.step(1, 25, 10 ** 9, 1e-30)
+        runs[budget] = (d.get_iterate(), d.longstep_log())
+    d.set_alg(pkg.AP())
+    d.set_iterate(None)
+    d.step(1, 25, 10 ** 9, 1e-30)
+    plain = d.get_iterate()
+    d.close()
+    ok, failed = runs[None][1], runs["0"][1]
+    assert not ok["failed"] and ok["given_up"] == 0 and ok["iteration"] == 25 and ok["rows"] == 12 and ok["step"] > 0
+    assert np.linalg.norm(runs[None][0] - plain) > 1e-6 * np.linalg.norm(plain)           # (the projection does move the iterate)
+    assert failed["failed"] and failed["tried"] == 0 and failed["step"] == 0.0 and failed["given_up"] == 1
+    assert runs["0"][0].tobytes() == plain.tobytes()
