@@ -125,6 +125,8 @@ PROTOTYPES = {
     "fos_set_tuning": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32]),
     "fos_set_cg_variant": (C.c_int, [_h, C.c_int32]),
     "fos_get_cg_variant": (C.c_int, [_h, _i32p]),
+    "fos_host_cg_variant": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _i32p]),
+    "fos_host_cg_windows": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p]),
     "fos_resident_stats": (C.c_int, [_h, _i64p]),
     "fos_resident_lowp_stats": (C.c_int, [_h, _dp]),
     "fos_debug_set": (C.c_int, [_h, C.c_int32, C.c_int64]),

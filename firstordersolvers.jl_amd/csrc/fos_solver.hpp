@@ -1,9 +1,10 @@
-// struct fos_solver (the handle behind fos_handle) and the helpers that solver.cpp, operator.cpp, cones.cpp, direct.cpp and transport.cpp share.  Private: not part of the ABI.
+// struct fos_solver (the handle behind fos_handle) and the helpers that solver.cpp, cg.cpp, operator.cpp, cones.cpp, direct.cpp and transport.cpp share.  Private: not part of the ABI.
 #pragma once
 
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <functional>
 
 #include "fos_internal.hpp"
 #include "wrappers.hpp"
@@ -84,6 +85,25 @@ struct Operator {
     double* res_lowp_out = nullptr;
 };
 
+// ------------------------------------------------------------------------------------------------ the CG solve behind prox_affine (cg.cpp)
+struct CgState {
+    bool fuse_p = false;                       // the p update of CG rides on the next sweep (2 launches per iteration)
+    int cg_variant = -1;                       // FOS_CG_*: -1 = the handle's default (sharded: merged reduction, closing in the update)
+    int cg_chunk = 8;                          // iterations enqueued per host poll
+    int cg_blocks = 0;                         // fos::LaunchCtx::cg_blocks
+    int last_cg_pred = 0;                      // the last predicted solve's iteration count: the size of the next one's first batch
+    int cg_same_run = 0;                       // consecutive solves that took exactly last_cg_pred iterations
+    int64_t cg_total = 0;                      // CG iterations since fos_create
+    uint32_t cg_epoch = 0;                     // windows of 2048 sequence numbers used so far (cg_windows): the folded exchanges, the resident solve
+    int hit_max_accum = 0;                     // a solve since the last status check ended on its cap
+    // speculation past a CG solve: the kernels that follow it are enqueued (gated on fos::DevState.done) BEFORE the host learns the
+    // iteration count, which it then reads from a record the CG kernels write into pinned host memory (wait_cg_mark)
+    bool speculate = true;
+    fos::HostMark* mark = nullptr;             // pinned + mapped; fos::DevState.hostmark points at it
+    double* pre_sums = nullptr;                // fos::LaunchCtx::pre
+    bool pre_on = true;
+};
+
 // ------------------------------------------------------------------------------------------------ the handle
 struct fos_solver {
     int device = 0;
@@ -118,18 +138,10 @@ struct fos_solver {
     // scalars
     fos::DevState* st = nullptr;
     fos::DevState* st_host = nullptr;               // pinned
-    // speculation past a CG solve: the kernels that follow it are enqueued (gated on fos::DevState.done) BEFORE the host learns the
-    // iteration count, which it then reads from a record the CG kernels write into pinned host memory (wait_cg_mark)
-    fos::HostMark* mark = nullptr;                  // pinned + mapped; fos::DevState.hostmark points at it
-    double* pre_sums = nullptr;                // fos::LaunchCtx::pre
-    bool pre_on = true;
-    bool speculate = true;
+    CgState cg;                                // the CG solve's state and switches (cg.cpp)
     double* partials = nullptr;
     double* reduced = nullptr;                 // 16 doubles
     int vec_blocks = 0;
-    int cg_blocks = 0;
-    bool fuse_p = false;                       // the p update of CG rides on the next sweep (2 launches per iteration)
-    int cg_variant = -1;                       // FOS_CG_*: -1 = the handle's default (sharded: merged reduction, closing in the update)
 
     // algorithm (gap.jl:6-21, gapa.jl:9-25, fista.jl:6-18, dykstra.jl:5-17)
     int alg = FOS_ALG_GAP;
@@ -174,20 +186,16 @@ struct fos_solver {
     int64_t prox_i = 1;
     bool firstrun = true;
     int64_t cgiter = 0;
-    int hit_max_accum = 0;
     bool firstrun2 = true;                     // HSDEMatrix.cgdata.firstrun
-    int last_cg_pred = 0;
     bool shift_ready = false;                  // RHS already holds SOL - [0; X.y] (written by the step's last kernel): inside fos_step only
     bool shift_fuse = true;                    // FOS_SHIFT_FUSE=0: every projection runs its own shift pass
     bool in_step = false;
     fos::Wrappers wr;                          // LineSearchWrapper, GAPP, LongstepWrapper (wrappers.hpp)
-    int cg_same_run = 0;                       // consecutive solves that took exactly last_cg_pred iterations
     const d2* last_checked = nullptr;          // vector the last checkstatus was evaluated on
 
-    // sharding: how the sums cross the ranks is the transport's business (transport.cpp); what is sharded, and the solves' sequence windows, is the handle's
+    // sharding: how the sums cross the ranks is the transport's business (transport.cpp); what is sharded is the handle's, the solves' sequence windows are the CG state's
     Transport tr;
     int nranks = 1, rank = 0;
-    uint32_t cg_epoch = 0;                     // windows of 2048 sequence numbers used so far (cg_solve): the folded exchanges, the resident solve
     bool sharded() const { return tr.via() != VIA_NONE; }
     // row sharding of a non-block-diagonal A: the first n entries (and tau, kappa) of every vector are replicated,
     // the slots of the rows of A' are summed over the ranks (RCCL all-reduce of 2n doubles) between a sweep and its slot-list sums
@@ -203,10 +211,8 @@ struct fos_solver {
     bool equilibrated() const { return eq_passes > 0; }
 
     // tuning / measurement
-    int cg_chunk = 8;
     bool prof = false;
     int prof_period = 1;                       // every prof_period-th launch of a class is bracketed by events (1: all)
-    int64_t cg_total = 0;                      // CG iterations since fos_create
     int64_t direct_sweeps = 0;                 // sweeps of the block-direct projection since fos_create (profiling ordinal)
     struct ProfRec { hipEvent_t a, b; int cls; int j; };
     std::vector<ProfRec> prof_recs;            // event pairs, reused
@@ -222,10 +228,10 @@ struct fos_solver {
     fos::LaunchCtx ctx(bool mailboxes = false) const {
         fos::LaunchCtx c;
         c.stream = stream; c.S = op.dev; c.cb = cb; c.n = n; c.m = m; c.l = l; c.st = st;
-        c.partials = partials; c.reduced = reduced; c.vec_blocks = vec_blocks; c.cg_blocks = cg_blocks;
+        c.partials = partials; c.reduced = reduced; c.vec_blocks = vec_blocks; c.cg_blocks = cg.cg_blocks;
         c.peer = (tr.peer_on || mailboxes) ? &tr.peer : nullptr;
         c.def_mask = op.def_mask;
-        c.pre = pre_on ? pre_sums : nullptr;
+        c.pre = cg.pre_on ? cg.pre_sums : nullptr;
         c.between = nullptr; c.between_arg = nullptr;
         c.cus = cus;
         c.psd_refine_max_mats = (tr.peer_same_device && nranks > 1) ? std::max(1, cus / nranks) : 0;
@@ -258,6 +264,22 @@ int prof_begin_other(fos_solver* h, int post);
 void prof_end(fos_solver* h, int idx);
 int poll_state(fos_solver* h);
 int kkt_apply_full(fos_solver* h, const LaunchCtx& c, const d2* w, d2* out, bool deferred = true, bool tau_row = true);
+int upload_plain(fos_solver* h, d2* dst, const double* z);      // a caller's plain 2l-vector <-> a device vector, through h->plain; synchronise
+int download_plain(fos_solver* h, double* z, const d2* src);
+// cg.cpp: the CG state of a new handle (the operator must exist: cg_blocks reads op.dev.ndef) and its end, the solve, the CG half of fos_set_tuning
+int cg_setup(fos_solver* h);
+void cg_teardown(fos_solver* h);
+typedef std::function<int(const LaunchCtx&)> PostFn;
+// conjugategradient!(x, KKTMatrix(Q), rhs, r, p, Ap; tol, max_iters)      conjugategradients.jl:31-55
+struct CgCall {
+    d2* x; const d2* rhs; double tol; int maxit;
+    const d2* apply_on = nullptr;              // the vector the start residual's operator product is taken of (default: x)
+    const PostFn* post = nullptr;              // what follows the solve on the stream, enqueued gated behind the first batch ...
+    bool* post_ran = nullptr;                  // ... and whether that batch sufficed (else the caller runs `post` itself)
+    bool predict = true;                       // false: a solve outside the outer iteration -- first batch of cg_chunk, last_cg_pred left alone
+};
+int cg_solve(fos_solver* h, const CgCall& a, int64_t* iters);
+int cg_set_tuning(fos_solver* h, int32_t cg_chunk, int32_t fuse_p);
 // operator.cpp: the operator of a new handle (h->m, n, cus and row_sharded set), another grid for its sweep (fos_set_tuning), the resident solve's plan
 int operator_setup(fos_solver* h, const int64_t* colptr, const int64_t* rowval, const double* nzval);
 int operator_repartition(fos_solver* h, int nwg);

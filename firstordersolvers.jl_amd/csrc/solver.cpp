@@ -1,11 +1,9 @@
-// libfoship: handle life cycle, the device-resident CG driver, the GAP/GAPA/FISTA/Dykstra step loops, the status
+// libfoship: handle life cycle, the affine projection (its CG solve: cg.cpp), the GAP/GAPA/FISTA/Dykstra step loops, the status
 // check and the C ABI of include/foship.h.  Host C++ only orchestrates launches on ONE HIP stream; all data stays
 // in HBM between fos_create and fos_destroy (the only transfers are N doubles at set/get-iterate and ~100 bytes of
 // scalars per CG poll / convergence check).
 #include <dlfcn.h>
-#include <functional>
 
-#include <chrono>
 #include <cmath>
 #include <mutex>
 
@@ -176,255 +174,26 @@ int global_setup(fos_solver* h) {
     return FOS_OK;
 }
 
+int upload_plain(fos_solver* h, d2* dst, const double* z) {
+    LaunchCtx c = h->ctx();
+    FOS_HIP(hipMemcpyAsync(h->plain, z, sizeof(double) * 2 * h->l, hipMemcpyHostToDevice, h->stream));
+    launch_interleave(c, dst, h->plain);
+    FOS_HIP(hipStreamSynchronize(h->stream));
+    return FOS_OK;
+}
+int download_plain(fos_solver* h, double* z, const d2* src) {
+    LaunchCtx c = h->ctx();
+    launch_deinterleave(c, h->plain, src);
+    FOS_HIP(hipMemcpyAsync(z, h->plain, sizeof(double) * 2 * h->l, hipMemcpyDeviceToHost, h->stream));
+    FOS_HIP(hipStreamSynchronize(h->stream));
+    return FOS_OK;
+}
+
 }  // namespace fos
 
 using namespace fos;
 
 namespace {
-
-// Has CG solve number `epoch` ended within its first batch of iterations?  No stream synchronisation and nothing in the stream:
-// the kernel that ends a solve writes HostMark.seq in pinned host memory, the marked p update of a batch that runs out before
-// convergence writes HostMark.batch; the host spins on the two (and looks at the stream now and then, in case neither comes).
-int wait_cg_mark(fos_solver* h, uint32_t epoch, int32_t batch_id, bool* ended) {
-    FOS_TRY(check_launch("poll"));
-    volatile HostMark* m = h->mark;
-    // a wall-clock bound (FOS_CG_WAIT_S, default 120 s): a kernel of the solve that never ends must not hang the host either
-    static const double wait_s = getenv("FOS_CG_WAIT_S") ? atof(getenv("FOS_CG_WAIT_S")) : 120.0;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t spin = 1;; ++spin) {
-        if (__atomic_load_n(&m->seq, __ATOMIC_ACQUIRE) == epoch) { *ended = true; break; }
-        if (__atomic_load_n(&m->batch, __ATOMIC_ACQUIRE) == batch_id) { *ended = false; break; }
-        __builtin_ia32_pause();
-        if ((spin & 0xFFFFu) == 0 && hipStreamQuery(h->stream) == hipSuccess) {          // everything enqueued has run
-            if (__atomic_load_n(&m->seq, __ATOMIC_ACQUIRE) == epoch) { *ended = true; break; }
-            if (__atomic_load_n(&m->batch, __ATOMIC_ACQUIRE) == batch_id) { *ended = false; break; }
-            // no mark: a kernel of the solve gave up (a peer exchange timed out, ...) -- the ordinary state read reports why
-            FOS_TRY(poll_state(h));
-            *ended = h->st_host->done != 0;
-            return FOS_OK;
-        }
-        if ((spin & 0xFFFFFu) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > wait_s) {
-            set_error("CG solve %u: neither its end mark nor its batch mark arrived within %.0f s (a kernel of the solve does not finish)", epoch, wait_s);
-            return FOS_EHIP;
-        }
-    }
-    if (*ended) { h->st_host->done = 1; h->st_host->iter = m->iter; h->st_host->hit_max = m->hit_max; h->st_host->rr = m->rr; }
-    else h->st_host->done = 0;
-    return FOS_OK;
-}
-
-// conjugategradient!(x, KKTMatrix(Q), rhs, r, p, Ap; tol, max_iters)      conjugategradients.jl:31-55
-// Device resident: the host enqueues iterations AHEAD (every CG kernel is gated on DevState.done) and polls once per batch.
-// `apply_on` (default: x): the vector the start residual's operator product is taken of -- prox_affine passes x - (0, in.y)
-// together with rhs = in, which is rhs - M x without ever forming rhs (see there).
-// `post` (optional): what follows the solve on the stream (relaxation, cone projection, ...), taking a LaunchCtx whose `gate`
-// it must hand to every launch.  It is enqueued right behind the FIRST batch of iterations, gated on DevState.done, and the host
-// then reads the state at the end of the batch on a second stream: when the batch sufficed (the steady state) the GPU has
-// gone straight on while the host was still finding that out, and *post_ran = true.  Otherwise the gated launches were
-// no-ops, CG continues as usual and the caller runs `post` itself.
-typedef std::function<int(const LaunchCtx&)> PostFn;
-int cg_solve(fos_solver* h, d2* x, const d2* rhs, double tol, int maxit, int64_t* iters, const d2* apply_on = nullptr,
-             const PostFn* post = nullptr, bool* post_ran = nullptr) {
-    LaunchCtx c = h->ctx();
-    int next_j = 1;                          // iteration number of the next enqueued launch group (if CG still runs)
-    const bool fold = h->tr.peer_on && peer_fold_env();
-    const bool rccl = h->sharded() && !fold;  // sums cross the ranks between the kernels (reduce kernel + all-reduce, or unfolded mailboxes)
-    // which recurrence: the reference's (three launches, two reduction points per iteration) or the merged-reduction form (two
-    // launches, one reduction point); sharded handles take the latter by default and always close in the update kernel
-    int32_t variant = FOS_CG_REFERENCE;
-    FOS_TRY(fos_get_cg_variant(h, &variant));
-    const bool resident = variant == FOS_CG_RESIDENT;
-    const bool merged = variant == FOS_CG_MERGED_SWEEP || variant == FOS_CG_MERGED_UPDATE;
-    const bool close_in_update = variant == FOS_CG_MERGED_UPDATE;
-    const bool fuse_p = variant == FOS_CG_FUSED_P;
-    // single GPU, reference recurrence: the solve starts like the merged one -- sweep, ONE launch for r_0 = rhs - M v, p_1 = r_0,
-    // the tau row, the slot-spread rows and the r.r records (added by the sweep of iteration 1) -- instead of five launches
-    static const bool start_env = !(getenv("FOS_CG_FUSED_START") && atoi(getenv("FOS_CG_FUSED_START")) == 0);
-    const bool start_fused = !merged && !h->sharded() && !c.between && start_env;
-    // the solve's sequence numbers: seq_base + 1 .. seq_base + 2 maxit + 3 (the folded exchanges: 2 j + phase; the resident solve: maxit + 2 exchange
-    // rounds, the streamed form's early r.r rounds on top) in windows of 2048 -- as many as `maxit` can use, so that no record of this solve carries a
-    // number of the next one.  Counted from maxit alone: the same on every rank (all ranks make the same calls), whatever form a shard takes.  A window
-    // run never wraps through epoch 0 mod 2^21 (sequence number 0 is never sent), it starts there instead (no speculation: the mark's initial value).
-    const uint32_t nwin = (uint32_t)std::min<int64_t>((2 * (int64_t)std::max(maxit, 0) + 4 + 2047) / 2048, (int64_t)1 << 20);
-    uint32_t epoch = h->cg_epoch + 1u;                   // the solve's first window
-    if (const uint32_t off = epoch & 0x1FFFFFu; off != 0u && off + (nwin - 1u) > 0x1FFFFFu) epoch += 0x200000u - off;
-    h->cg_epoch = epoch + (nwin - 1u);
-    const uint32_t seq_base = (uint32_t)(epoch * 2048u);                // + 2 j + phase
-    auto iter_desc = [&](int j) {
-        CgIter it;
-        it.j = j; it.r = h->R; it.p_prev = h->PB[(j - 1) & 1]; it.p_cur = h->PB[j & 1];
-        it.fuse_p = fuse_p; it.rr_from_reduced = rccl ? 1 : 0; it.fold = fold ? &h->tr.peer : nullptr; it.seq_base = seq_base;
-        it.start_fused = start_fused;
-        return it;
-    };
-    auto merged_desc = [&](int j) {
-        CgmIter it;
-        it.j = j; it.x = x; it.r = h->R; it.p = h->PB[0]; it.s = h->PB[1]; it.w = h->AP;
-        it.close_in_update = close_in_update; it.from_reduced = rccl ? 1 : 0; it.fold = fold ? &h->tr.peer : nullptr; it.seq_base = seq_base;
-        return it;
-    };
-    const size_t prof_start = h->prof_used;
-    // (sharded: only with the exchanges folded into the CG kernels -- no collective call sits in the stream -- and only for GAP,
-    //  whose post-solve kernels contain no reduction; every rank takes the same decisions, so all mispredict together.
-    //  Solve number 0 mod 2^21 is the mark's initial value.)
-    const bool spec = post && h->speculate && !c.between && !fuse_p && (seq_base >> 11) != 0u &&
-                      (!h->sharded() || (fold && h->alg != FOS_ALG_GAPA));
-    const int32_t batch_id = (int32_t)(((seq_base >> 11) & 0x7FFFFFu) << 8 | 1u);
-    bool mark_last = spec;                   // the first batch ends with a marked launch
-    // merged reduction, sharded without folded mailboxes: the sweep's three sums and the update's r.r cross the ranks together,
-    // between the sweep of iteration j-1 and the update of iteration j -- ONE all-reduce of four doubles per iteration
-    auto merged_reduce = [&](int j) -> int {
-        if (c.between) FOS_TRY(c.between(c.between_arg));         // row-sharded: A'y partial sums over the ranks (n-vector)
-        if (!rccl) return FOS_OK;
-        launch_reduce1(c, c.S.nwg, 3, 1, 0);
-        LaunchCtx c2 = c;
-        c2.partials = c.partials + 3 * (size_t)PART_CAP + (size_t)((j - 1) & 1) * CGM_RR_STRIDE;
-        c2.reduced = c.reduced + 3;
-        launch_reduce1(c2, c.cg_blocks, 1, 1);
-        return allreduce(h, 4);
-    };
-    if (resident) {
-        // the whole solve is ONE launch (resident.hip): nothing to enqueue ahead, nothing to predict; what follows the solve is enqueued behind it
-        // (gated on DevState.done, which the launch sets when it ends) and the host reads the iteration count from the mark the launch leaves
-        FOS_TRY(resident_lowp_ensure(h));                  // (a handle whose default is another recurrence builds its float copy here, once)
-        const int pe = prof_begin(h, FOS_PROF_RESIDENT, 1, h->prof_seen[FOS_PROF_RESIDENT]++);
-        const hipError_t le = launch_cg_resident(c, h->op.res, x, rhs, apply_on ? apply_on : x, tol, maxit, fold ? &h->tr.peer : nullptr, seq_base);
-        prof_end(h, pe);
-        if (le != hipSuccess) { set_error("resident CG launch: %s", hipGetErrorString(le)); return FOS_EHIP; }
-        if (spec) {
-            LaunchCtx cg = c;
-            cg.gate = &h->st->done;
-            FOS_TRY((*post)(cg));
-            bool ended = false;
-            FOS_TRY(wait_cg_mark(h, (uint32_t)(seq_base >> 11), batch_id, &ended));
-            if (!ended) { set_error("resident CG solve %u ended without its mark", (unsigned)(seq_base >> 11)); return FOS_EHIP; }
-            if (post_ran) *post_ran = true;
-        } else {
-            FOS_TRY(poll_state(h));
-            if (!h->st_host->done) { set_error("resident CG solve %u did not finish", (unsigned)(seq_base >> 11)); return FOS_EHIP; }
-        }
-        *iters = h->st_host->iter;
-        h->cg_same_run = (h->st_host->iter == h->last_cg_pred) ? h->cg_same_run + 1 : 0;
-        h->last_cg_pred = h->st_host->iter;
-        h->cg_total += h->st_host->iter;
-        if (h->st_host->hit_max) h->hit_max_accum = 1;
-        return FOS_OK;
-    }
-    if (merged) {
-        // start: sweep M v, ONE launch for r = rhs - M v (+ r.r records, tau row, slot-spread rows, the solve's scalars), then
-        // w_0 = M r_0, the sweep every iteration's update starts from (it also adds g_0 = r_0.r_0 unless the first update does)
-        CgmIter it0 = merged_desc(0);
-        const d2* v = apply_on ? apply_on : x;
-        const int po = prof_begin_other(h, 0);
-        launch_cgm_apply(c, it0, v);                                       // :32  mul!(Ap, A, x)
-        if (c.between) FOS_TRY(c.between(c.between_arg));
-        if (rccl) { launch_reduce1(c, c.S.nwg, 3, 0, 0); FOS_TRY(allreduce(h, 3)); }
-        launch_cgm_start(c, it0, rhs, v, tol, maxit);                      // :33-36
-        prof_end(h, po);
-        const int pe = prof_begin(h, FOS_PROF_KKT, 0, h->cg_total);
-        launch_cgm_sweep(c, it0, close_in_update ? -1 : 0);
-        prof_end(h, pe);
-    } else if (start_fused) {
-        CgmIter it0 = merged_desc(0);
-        const d2* v = apply_on ? apply_on : x;
-        const int po = prof_begin_other(h, 0);
-        launch_cgm_apply(c, it0, v);                                       // :32  mul!(Ap, A, x)
-        launch_cgm_start(c, it0, rhs, v, tol, maxit, h->PB[1]);            // :33-36   (p_1 in buffer 1)
-        prof_end(h, po);
-    } else {
-        int fr = 0;
-        const int po = prof_begin_other(h, 0);
-        FOS_TRY(kkt_apply_full(h, c, apply_on ? apply_on : x, h->AP));    // :32  mul!(Ap, A, x)
-        launch_cg_init(c, rhs, h->AP, h->R, h->PB[1]);                     // :33-34   (p_1 in buffer 1)
-        FOS_TRY(finish_reduce(h, c, c.vec_blocks, 1, 0, &fr));
-        launch_cg_init_finalize(c, h->R, tol, maxit, fr);                  // :35-36
-        prof_end(h, po);
-    }
-    auto enqueue = [&](int count) -> int {
-        if (merged) {
-            for (int q = 0; q < count && next_j <= maxit; ++q, ++next_j) {
-                CgmIter it = merged_desc(next_j);
-                const bool last = q == count - 1 || next_j == maxit;
-                if (mark_last && last) it.batch_mark = batch_id;
-                FOS_TRY(merged_reduce(next_j));
-                // launch 1: scalars, p = r + beta p, s = w + beta s, x += alpha p, r -= alpha s, r.r partials             :39-41,:46-50
-                int pe = prof_begin(h, FOS_PROF_CGVEC, next_j, (h->cg_total + next_j - 1) % 4 == 1 ? (h->cg_total + next_j - 1) / 4 : 1);
-                launch_cgm_update(c, it, false);
-                prof_end(h, pe);
-                // launch 2: [close iteration j: r.r, stop test] sweep w = M r + partial sums                               :38,:42
-                // (closing in the sweep: the sweep behind the LAST update returns in its prologue -- recorded as iteration j+1, which
-                //  the profile drops)
-                pe = prof_begin(h, FOS_PROF_KKT, next_j + (close_in_update ? 0 : 1), h->cg_total + next_j);
-                launch_cgm_sweep(c, it, close_in_update ? -1 : next_j);
-                prof_end(h, pe);
-            }
-            if (close_in_update) {           // the last enqueued iteration is closed by a one-workgroup launch of the update kernel
-                CgmIter it = merged_desc(next_j);
-                if (mark_last) it.batch_mark = batch_id;
-                FOS_TRY(merged_reduce(next_j));
-                launch_cgm_update(c, it, true);
-            }
-            return FOS_OK;
-        }
-        for (int q = 0; q < count && next_j <= maxit; ++q, ++next_j) {
-            CgIter it = iter_desc(next_j);
-            if (mark_last && (q == count - 1 || next_j == maxit)) it.batch_mark = batch_id;
-            // launch 1: [close iteration j-1: r.r, stop test, beta; p_j on the fly] KKT sweep Ap = M p_j + partial sums   :38,:42-50
-            int pe = prof_begin(h, FOS_PROF_KKT, next_j, h->cg_total + next_j - 1);
-            launch_kkt2_cg(c, it, h->AP);
-            prof_end(h, pe);
-            int f1 = 0;
-            if (c.between) FOS_TRY(c.between(c.between_arg));         // row-sharded: A'y partial sums over the ranks (n-vector)
-            if (rccl) { launch_reduce1(c, c.S.nwg, 3, 1, 0); FOS_TRY(allreduce(h, 3)); f1 = 1; }
-            // launch 2: alpha, tau rows, slot-spread rows, x += alpha p, r -= alpha Ap, r.r partials                       :39-41
-            pe = prof_begin(h, FOS_PROF_CGVEC, next_j, (h->cg_total + next_j - 1) % 4 == 1 ? (h->cg_total + next_j - 1) / 4 : 1);   // a quarter of the sweeps' rate, other iterations
-            launch_cg_update(c, it, x, h->R, h->AP, f1);
-            if (rccl) {
-                LaunchCtx c2 = c;
-                c2.partials = c.partials + 3 * (size_t)PART_CAP;
-                launch_reduce1(c2, c.cg_blocks, 1, 1);
-                FOS_TRY(allreduce(h, 1));
-            }
-            // gather-bound operators: closing the iteration and p_{j+1} = r + beta p_j stay a launch of their own           :42-51
-            if (!fuse_p) launch_cg_pupdate(c, it, x, h->PB[(next_j + 1) & 1]);
-            prof_end(h, pe);
-        }
-        // the last update of the batch is closed by a one-workgroup launch (a following batch's sweep repeats it, same result)
-        if (fuse_p) launch_cg_stop_check(c, iter_desc(next_j));
-        return FOS_OK;
-    };
-    static const int pred_slack = getenv("FOS_CG_SLACK") ? atoi(getenv("FOS_CG_SLACK")) : 1;   // iterations enqueued beyond the last solve's count (each costs a few gated no-op launches when not needed; too few costs a poll)
-    // (the slack iteration is dropped once three solves in a row took the same number of iterations: steady state of a
-    // well-conditioned problem -- C4: 17, 17, 17, ... -- where it would be three gated no-op launches per solve)
-    const int slack = (pred_slack == 1 && h->cg_same_run >= 3) ? 0 : pred_slack;
-    int first = h->last_cg_pred > 0 ? h->last_cg_pred + slack : h->cg_chunk;
-    first = std::max(1, std::min(first, maxit));
-    FOS_TRY(enqueue(first));
-    mark_last = false;
-    if (spec) {
-        LaunchCtx cg = c;
-        cg.gate = &h->st->done;
-        FOS_TRY((*post)(cg));
-        bool ended = false;
-        FOS_TRY(wait_cg_mark(h, (uint32_t)(seq_base >> 11), batch_id, &ended));
-        if (post_ran) *post_ran = ended;
-    } else {
-        FOS_TRY(poll_state(h));
-    }
-    while (!h->st_host->done) {
-        FOS_TRY(enqueue(h->cg_chunk));
-        FOS_TRY(poll_state(h));
-    }
-    *iters = h->st_host->iter;
-    // profiling: launches enqueued past convergence were gated no-ops -- drop their event pairs
-    for (size_t k = prof_start; k < h->prof_used; ++k)
-        if (h->prof_recs[k].cls != FOS_PROF_OTHER && h->prof_recs[k].j > h->st_host->iter) h->prof_recs[k].cls = -1;
-    h->cg_same_run = (h->st_host->iter == h->last_cg_pred) ? h->cg_same_run + 1 : 0;
-    h->last_cg_pred = h->st_host->iter;
-    h->cg_total += h->st_host->iter;
-    if (h->st_host->hit_max) h->hit_max_accum = 1;
-    return FOS_OK;
-}
 
 // prox!(y, S1::AffinePlusLinear, x) with the result left in h->SOL       affinepluslinear.jl:83-126
 int prox_affine(fos_solver* h, const d2* x, const PostFn* post = nullptr, bool* post_ran = nullptr) {
@@ -458,8 +227,8 @@ int prox_affine(fos_solver* h, const d2* x, const PostFn* post = nullptr, bool* 
     h->prox_i += 1;                                                     // :114
     int64_t it = 0;
     const int64_t cap = at_floor ? 10000 : 1000;                   // (:115: 1000; the exact projection is given the default cap of conjugategradients.jl:31)
-    if (fused_rhs) FOS_TRY(cg_solve(h, h->SOL, x, tol, cap, &it, h->RHS, post, post_ran));
-    else FOS_TRY(cg_solve(h, h->SOL, h->RHS, tol, cap, &it, nullptr, post, post_ran));          // :115-117 ; y aliases xinit (:106,:122)
+    CgCall call{h->SOL, fused_rhs ? x : h->RHS, tol, (int)cap, fused_rhs ? h->RHS : nullptr, post, post_ran};
+    FOS_TRY(cg_solve(h, call, &it));                                    // :115-117 ; y aliases xinit (:106,:122)
     h->cgiter = it;                                                     // :121
     return FOS_OK;                                                      // :124 y2 .*= beta with beta = 1
 }
@@ -517,8 +286,8 @@ static int eq_status_check(fos_solver* h, const d2* z, double eps, fos_check_res
     res->norm_b = nb;
     res->norm_c = nc;
     res->cgiter = h->cgiter;
-    res->cg_maxiter_hit = h->hit_max_accum;
-    h->hit_max_accum = 0;
+    res->cg_maxiter_hit = h->cg.hit_max_accum;
+    h->cg.hit_max_accum = 0;
     res->status = status_decide(res, eps);
     return FOS_OK;
 }
@@ -549,8 +318,8 @@ int status_check(fos_solver* h, const d2* z, double eps, fos_check_result* res) 
     res->norm_b = nb;
     res->norm_c = nc;
     res->cgiter = h->cgiter;
-    res->cg_maxiter_hit = h->hit_max_accum;
-    h->hit_max_accum = 0;
+    res->cg_maxiter_hit = h->cg.hit_max_accum;
+    h->cg.hit_max_accum = 0;
     res->status = status_decide(res, eps);
     return FOS_OK;
 }
@@ -810,21 +579,6 @@ int step_finish_launch(fos_solver* h, const LaunchCtx& c) {
     return FOS_EINVAL;
 }
 
-int upload_plain(fos_solver* h, d2* dst, const double* z) {
-    LaunchCtx c = h->ctx();
-    FOS_HIP(hipMemcpyAsync(h->plain, z, sizeof(double) * 2 * h->l, hipMemcpyHostToDevice, h->stream));
-    launch_interleave(c, dst, h->plain);
-    FOS_HIP(hipStreamSynchronize(h->stream));
-    return FOS_OK;
-}
-int download_plain(fos_solver* h, double* z, const d2* src) {
-    LaunchCtx c = h->ctx();
-    launch_deinterleave(c, h->plain, src);
-    FOS_HIP(hipMemcpyAsync(z, h->plain, sizeof(double) * 2 * h->l, hipMemcpyDeviceToHost, h->stream));
-    FOS_HIP(hipStreamSynchronize(h->stream));
-    return FOS_OK;
-}
-
 // the iterate's way in and out of an equilibrated handle: the same staging with the scaling kernels (plain handles: upload_plain / download_plain)
 int upload_caller(fos_solver* h, d2* dst, const double* z) {
     if (!h->equilibrated()) return upload_plain(h, dst, z);
@@ -904,9 +658,6 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     h->m = m; h->n = n; h->l = n + m + 1; h->l_global = h->l;
     h->nnz = colptr[n] - 1;
     FOS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    FOS_HIP(hipHostMalloc((void**)&h->mark, sizeof(HostMark), hipHostMallocMapped));
-    memset(h->mark, 0, sizeof(HostMark));
-    h->speculate = !(getenv("FOS_SPECULATE") && atoi(getenv("FOS_SPECULATE")) == 0);
     h->shift_fuse = !(getenv("FOS_SHIFT_FUSE") && atoi(getenv("FOS_SHIFT_FUSE")) == 0);
 
     hipDeviceProp_t prop;
@@ -922,12 +673,6 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     // ---- operator (operator.cpp)
     h->row_sharded = (flags & FOS_CREATE_ROW_SHARDED) != 0;
     FOS_TRY(operator_setup(h, colptr, rowval, nzval));
-    // The p update of CG can ride on the next sweep (two launches per iteration, launch_kkt2_cg): built and measured -- on
-    // MI355X it is SLOWER than the separate launch at every size tried (C4: sweep 59 -> 86 us against a 10 us p update kernel;
-    // 64-block shard: 13 -> 20 us against 5 us), so it stays an option (fos_set_tuning / FOS_CG_FUSE_P)
-    h->fuse_p = false;
-    if (const char* e = getenv("FOS_CG_FUSE_P")) h->fuse_p = atoi(e) != 0;
-    if (const char* e = getenv("FOS_CG_VARIANT")) h->cg_variant = std::max(-1, std::min((int)FOS_CG_RESIDENT, atoi(e)));
 
     std::vector<double> cbv((size_t)(n + m));
     for (int64_t j = 0; j < n; ++j) { cbv[j] = c[j]; }
@@ -942,13 +687,6 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     for (d2** v : vecs) FOS_TRY(dev_zeros(h, v, l));
     FOS_TRY(dev_alloc(h, &h->plain, 2 * l));
     h->vec_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((h->l + 255) / 256, 1024));
-    h->cg_blocks = std::min(h->vec_blocks, getenv("FOS_CG_BLOCKS") ? std::max(1, atoi(getenv("FOS_CG_BLOCKS"))) : 2 * cus);
-    // the x,r update kernel also adds the slot lists of the rows spread over dual tiles (`def_lpr` lanes per row): its grid must
-    // cover them in ONE pass even when the vectors are short (dense LP C2: 15 000 such rows x 16 lanes against l = 15 001 --
-    // sized by l alone the kernel took 105 us instead of 17)
-    if (h->op.dev.ndef > 0)
-        h->cg_blocks = std::max<int>(h->cg_blocks, (int)std::min<int64_t>(1024, ((int64_t)h->op.dev.ndef * h->op.dev.def_lpr + 255) / 256));
-    h->cg_blocks = std::min(h->cg_blocks, 1024);         // (cg_close_iteration adds at most 1024 r.r records per wavefront)
 
     // ---- cones
     ConeTable table;
@@ -964,19 +702,11 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
 
     // ---- scalars
     FOS_TRY(dev_zeros(h, &h->st, 1));
-    FOS_TRY(dev_zeros(h, &h->pre_sums, 128));           // 16 producers x 3 sums x 2 self-validating words (sweep_sums3)
-    h->pre_on = !(getenv("FOS_CG_PRE") && atoi(getenv("FOS_CG_PRE")) == 0);
-    {
-        void* dp = nullptr;
-        FOS_HIP(hipHostGetDevicePointer(&dp, h->mark, 0));
-        const unsigned long long addr = (unsigned long long)(uintptr_t)dp;
-        FOS_HIP(hipMemcpy(&h->st->hostmark, &addr, sizeof(addr), hipMemcpyHostToDevice));
-    }
+    FOS_TRY(cg_setup(h));                                 // the CG solve's state, switches and grid (cg.cpp)
     FOS_HIP(hipHostMalloc((void**)&h->st_host, sizeof(DevState), hipHostMallocDefault));
     memset(h->st_host, 0, sizeof(DevState));
     FOS_TRY(dev_alloc(h, &h->partials, (size_t)6 * PART_CAP));
     FOS_TRY(dev_zeros(h, &h->reduced, 16));
-    if (const char* e = getenv("FOS_CG_CHUNK")) h->cg_chunk = std::max(1, atoi(e));
 
     FOS_TRY(resident_setup(h, cus));                      // FOS_CG_RESIDENT: does the operator qualify, and the plan if so
     {   // where the resident solve is the handle's default, its float copy is part of the set-up (and of what a caller times as set-up)
@@ -1061,7 +791,7 @@ int fos_destroy(fos_handle h) {
     for (void* p : h->pooled) uncached_release(p);
     for (void* p : h->owned) (void)hipFree(p);
     if (h->st_host) (void)hipHostFree(h->st_host);
-    if (h->mark) (void)hipHostFree(h->mark);
+    cg_teardown(h);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return FOS_OK;
@@ -1098,7 +828,7 @@ int fos_set_alg(fos_handle h, int alg, double alpha, double alpha1, double alpha
 
 int fos_reset_affine(fos_handle h) {
     if (!h) { set_error("NULL handle"); return FOS_EINVAL; }
-    h->prox_i = 1; h->firstrun = true; h->cgiter = 0; h->hit_max_accum = 0; h->last_cg_pred = 0;
+    h->prox_i = 1; h->firstrun = true; h->cgiter = 0; h->cg.hit_max_accum = 0; h->cg.last_cg_pred = 0;
     h->firstrun2 = true;
     return FOS_OK;
 }
@@ -1302,20 +1032,6 @@ int fos_kkt_apply(fos_handle h, double* y, const double* x) {
     return download_plain(h, y, h->AP);
 }
 
-int fos_cg_kkt(fos_handle h, double* x, const double* rhs, double tol, int64_t max_iters, int64_t* iters) {
-    if (!h || !x || !rhs || max_iters < 1) { set_error("bad argument"); return FOS_EINVAL; }
-    FOS_HIP(hipSetDevice(h->device));
-    FOS_TRY(upload_plain(h, h->W, x));
-    FOS_TRY(upload_plain(h, h->RHS, rhs));
-    int64_t it = 0;
-    int pred = h->last_cg_pred;
-    h->last_cg_pred = 0;
-    FOS_TRY(cg_solve(h, h->W, h->RHS, tol, (int)std::min<int64_t>(max_iters, INT32_MAX), &it));
-    h->last_cg_pred = pred;
-    if (iters) *iters = it;
-    return download_plain(h, x, h->W);
-}
-
 int fos_prox_affine(fos_handle h, double* y, const double* x) {
     if (!h || !y || !x) { set_error("NULL argument"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
@@ -1336,10 +1052,9 @@ int fos_hsdematrix_prox(fos_handle h, double* y, const double* x) {
     const double eps = 2.220446049250313e-16;
     const double tol = (double)(2 * h->l_global) * eps;                // :106
     int64_t it = 0;
-    int pred = h->last_cg_pred;
-    h->last_cg_pred = 0;
-    FOS_TRY(cg_solve(h, h->SOL2, h->RHS, tol, 1000, &it));             // :116 ; xinit .= y :119
-    h->last_cg_pred = pred;
+    CgCall call{h->SOL2, h->RHS, tol, 1000};
+    call.predict = false;
+    FOS_TRY(cg_solve(h, call, &it));                                   // :116 ; xinit .= y :119
     h->cgiter = it;
     // v = Q*u                                                          :122-124
     int fr = 0;
@@ -1378,12 +1093,6 @@ int fos_profile(fos_handle h, int32_t enable) {
 static double kkt_bytes(const fos_solver* h) {
     // B_kkt,min = 24 nnz + 4(m+n+2) + 32(m+n)
     return 24.0 * (double)h->nnz + 4.0 * (double)(h->m + h->n + 2) + 32.0 * (double)(h->m + h->n);
-}
-
-int fos_get_cg_total(fos_handle h, int64_t* total) {
-    if (!h || !total) { set_error("NULL argument"); return FOS_EINVAL; }
-    *total = h->cg_total;
-    return FOS_OK;
 }
 
 // launches / summed milliseconds per class of the bracketed launch groups since the last read; resets the records
@@ -1440,85 +1149,6 @@ int fos_bench_kkt(fos_handle h, int32_t reps, double* total_ms) {
     return FOS_OK;
 }
 
-int fos_bench_cg_chain(fos_handle h, int32_t iters, int32_t reps, int32_t use_graph, double* ms_per_iter) {
-    if (!h || iters < 1 || reps < 1 || !ms_per_iter) { set_error("bad argument"); return FOS_EINVAL; }
-    if (h->sharded()) { set_error("fos_bench_cg_chain: single-GPU handles only"); return FOS_EUNSUPPORTED; }
-    FOS_HIP(hipSetDevice(h->device));
-    LaunchCtx c = h->ctx();
-    // CG on M y = X from y = 0 with a tolerance that is never met: every enqueued iteration really runs
-    FOS_HIP(hipMemcpyAsync(h->RHS, h->X, sizeof(d2) * h->l, hipMemcpyDeviceToDevice, h->stream));
-    FOS_HIP(hipMemsetAsync(h->W, 0, sizeof(d2) * h->l, h->stream));
-    FOS_TRY(kkt_apply_full(h, c, h->W, h->AP));
-    launch_cg_init(c, h->RHS, h->AP, h->R, h->PB[1]);
-    launch_cg_init_finalize(c, h->R, -1.0, INT32_MAX, 0);
-    int variant = h->cg_variant >= 0 ? h->cg_variant : (h->fuse_p ? FOS_CG_FUSED_P : FOS_CG_REFERENCE);
-    if (variant == FOS_CG_FUSED_P && h->op.dev.npanel > 0) variant = FOS_CG_REFERENCE;      // (as fos_get_cg_variant resolves it)
-    const bool merged = variant == FOS_CG_MERGED_SWEEP || variant == FOS_CG_MERGED_UPDATE;
-    // (the producer flags of the update kernels carry the launch's sequence number: a replayed graph would present the SAME
-    //  numbers again and the consumers would not wait -- the graph runs without the producers)
-    if (use_graph) c.pre = nullptr;
-    uint32_t chain_no = 0;
-    auto chain = [&]() {
-        const uint32_t seq_base = (++chain_no) * 2048u;
-        if (merged) {
-            CgmIter it;
-            it.x = h->W; it.r = h->R; it.p = h->PB[0]; it.s = h->PB[1]; it.w = h->AP;
-            it.close_in_update = variant == FOS_CG_MERGED_UPDATE; it.from_reduced = 0; it.fold = nullptr; it.seq_base = seq_base;
-            it.j = 0;
-            launch_cgm_apply(c, it, h->W);
-            launch_cgm_start(c, it, h->RHS, h->W, -1.0, INT32_MAX);
-            launch_cgm_sweep(c, it, it.close_in_update ? -1 : 0);
-            for (int j = 1; j <= iters; ++j) {
-                it.j = j;
-                launch_cgm_update(c, it, false);
-                launch_cgm_sweep(c, it, it.close_in_update ? -1 : j);
-            }
-            return;
-        }
-        for (int j = 1; j <= iters; ++j) {
-            CgIter it;
-            it.j = j; it.r = h->R; it.p_prev = h->PB[(j - 1) & 1]; it.p_cur = h->PB[j & 1];
-            it.fuse_p = variant == FOS_CG_FUSED_P; it.rr_from_reduced = 0; it.fold = nullptr; it.seq_base = seq_base;
-            launch_kkt2_cg(c, it, h->AP);
-            launch_cg_update(c, it, h->W, h->R, h->AP, 0);
-            if (!it.fuse_p) launch_cg_pupdate(c, it, h->W, h->PB[(j + 1) & 1]);
-        }
-    };
-    hipEvent_t e0, e1;
-    FOS_HIP(hipEventCreate(&e0));
-    FOS_HIP(hipEventCreate(&e1));
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    if (use_graph) {
-        FOS_HIP(hipStreamSynchronize(h->stream));
-        FOS_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-        chain();
-        FOS_HIP(hipStreamEndCapture(h->stream, &graph));
-        FOS_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-        FOS_HIP(hipGraphLaunch(exec, h->stream));          // warm
-    } else {
-        chain();                                           // warm
-    }
-    FOS_HIP(hipEventRecord(e0, h->stream));
-    for (int rep = 0; rep < reps; ++rep) {
-        if (use_graph) FOS_HIP(hipGraphLaunch(exec, h->stream));
-        else chain();
-    }
-    FOS_HIP(hipEventRecord(e1, h->stream));
-    FOS_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    FOS_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *ms_per_iter = (double)ms / ((double)reps * iters);
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    // leave the handle as fos_reset_affine + a fresh iterate would: the CG state used above is scratch
-    FOS_TRY(check_launch("fos_bench_cg_chain"));
-    FOS_TRY(poll_state(h));
-    return FOS_OK;
-}
-
 int fos_sync(fos_handle h) {
     if (!h) { set_error("NULL handle"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
@@ -1526,64 +1156,11 @@ int fos_sync(fos_handle h) {
     return FOS_OK;
 }
 
-// FOS_CG_FUSED_P closes the previous iteration and builds p on the fly inside kkt2_kernel; the window-panel sweeps (kkt2_win_kernel) have no such
-// form -- they would apply M to the PREVIOUS p and leave the iteration unclosed -- so the variant is refused where the operator is stored that way
-static int refuse_fused_p_on_window_panels(const fos_solver* h) {
-    if (h->op.dev.npanel == 0) return FOS_OK;
-    set_error("FOS_CG_FUSED_P: the operator is stored in window panels, whose sweeps cannot build p on the fly (row-block and tile storage only)");
-    return FOS_EUNSUPPORTED;
-}
-
 int fos_set_tuning(fos_handle h, int32_t spmv_workgroups, int32_t cg_chunk, int32_t fuse_p) {
     if (!h) { set_error("NULL handle"); return FOS_EINVAL; }
     FOS_HIP(hipSetDevice(h->device));
-    if (fuse_p > 0) FOS_TRY(refuse_fused_p_on_window_panels(h));
-    if (fuse_p >= 0) { h->fuse_p = fuse_p != 0; h->cg_variant = -1; }
-    if (cg_chunk > 0) h->cg_chunk = cg_chunk;
+    FOS_TRY(cg_set_tuning(h, cg_chunk, fuse_p));
     if (spmv_workgroups > 0) FOS_TRY(operator_repartition(h, spmv_workgroups));
-    return FOS_OK;
-}
-
-// which CG recurrence the affine projection runs (FOS_CG_*; -1: the handle's default)
-int fos_set_cg_variant(fos_handle h, int32_t variant) {
-    if (!h || variant < -1 || variant > FOS_CG_RESIDENT) { set_error("unknown CG variant %d", (int)variant); return FOS_EINVAL; }
-    if (variant == FOS_CG_RESIDENT && !h->op.res_ok) {
-        set_error("FOS_CG_RESIDENT: the operator does not qualify (%s)", h->op.res_plan.why.empty() ? "no plan" : h->op.res_plan.why.c_str());
-        return FOS_EUNSUPPORTED;
-    }
-    if (variant == FOS_CG_FUSED_P) FOS_TRY(refuse_fused_p_on_window_panels(h));
-    if (variant == FOS_CG_RESIDENT) { FOS_HIP(hipSetDevice(h->device)); FOS_TRY(resident_lowp_ensure(h)); }      // (asked for: its float copy is built now)
-    h->cg_variant = variant;
-    if (variant >= 0) h->fuse_p = variant == FOS_CG_FUSED_P;
-    h->last_cg_pred = 0; h->cg_same_run = 0;
-    return FOS_OK;
-}
-
-// the variant the next affine projection will run (the default resolved: sharded handles take the merged recurrence)
-int fos_get_cg_variant(fos_handle h, int32_t* variant) {
-    if (!h || !variant) { set_error("NULL argument"); return FOS_EINVAL; }
-    const bool fold_env = peer_fold_env();
-    // default: the reference's recurrence -- except where a CG iteration is bound by its launches, not its bytes: sharded handles (one
-    // exchange per iteration instead of two) and cache-resident gather-type operators of 32 768 rows or more (C3: two launches per iteration
-    // instead of three, 370 -> 385 iterations/s; the streamed operators C2 / C4 / C5 are faster on the reference recurrence; small problems
-    // keep the reference's arithmetic).  Same Krylov iterates, same
-    // iteration counting and stop test; FOS_CG_VARIANT=0 / fos_set_cg_variant restore the reference recurrence everywhere.
-    int v = h->cg_variant >= 0 ? h->cg_variant
-            : (h->fuse_p ? FOS_CG_FUSED_P : ((h->sharded() || (h->op.dev.resident && !h->row_sharded && h->l >= 32768)) ? FOS_CG_MERGED_UPDATE : FOS_CG_REFERENCE));
-    // the resident solve: on request wherever the operator qualifies; by default on sharded handles whose sums travel through mailboxes and
-    // whose shards ALL qualify (FOS_RESIDENT_DEFAULT=0: never by default).  Sharded without mailboxes (RCCL, the caller's collective): a
-    // collective call cannot sit inside a kernel -- the launch-per-iteration form of the same recurrence runs instead.
-    const bool res_default = !(getenv("FOS_RESIDENT_DEFAULT") && atoi(getenv("FOS_RESIDENT_DEFAULT")) == 0);      // (read at every call: bench.py turns it off after a failed warm-up)
-    const bool res_usable = h->op.res_ok && !h->row_sharded && (!h->sharded() || (h->tr.peer_on && fold_env && h->op.res_all));
-    if (h->cg_variant < 0 && !h->fuse_p && h->sharded() && res_usable && res_default) v = FOS_CG_RESIDENT;
-    // one GPU: the STREAMED form where it fills at least half of the chip (C4: 66.3 us per CG iteration against 89 for three launches); operators
-    // small enough for the register form keep the reference's arithmetic by default
-    if (h->cg_variant < 0 && !h->fuse_p && !h->sharded() && res_usable && res_default && h->op.res_plan.stream && 2 * h->op.res_plan.G >= h->cus) v = FOS_CG_RESIDENT;
-    if (v == FOS_CG_RESIDENT && !res_usable) v = FOS_CG_MERGED_UPDATE;
-    if (v == FOS_CG_FUSED_P && h->op.dev.npanel > 0) v = FOS_CG_REFERENCE;      // (FOS_CG_FUSE_P is set for the whole process: window-panel handles keep three launches)
-    if (v == FOS_CG_MERGED_SWEEP && h->sharded()) v = FOS_CG_MERGED_UPDATE;
-    if (v == FOS_CG_MERGED_UPDATE && h->tr.peer_on && !fold_env) v = FOS_CG_REFERENCE;
-    *variant = v;
     return FOS_OK;
 }
 

@@ -1,6 +1,6 @@
 // libfoship, the transports: how the sums of a sharded handle cross the ranks, and the fos_comm_* / fos_peer_* / fos_exchange_bench entries of include/foship.h.
-// Their state is one member of the handle, fos_solver::tr (struct Transport, fos_solver.hpp); what is sharded (nranks, rank, row_sharded) and the solves'
-// sequence windows (cg_epoch) are the handle's.  Nothing outside this file knows RCCL, HIP IPC or the shm segment.
+// Their state is one member of the handle, fos_solver::tr (struct Transport, fos_solver.hpp); what is sharded (nranks, rank, row_sharded) is the handle's, the
+// solves' sequence windows (cg_epoch) are the CG state's (fos_solver::cg, cg.cpp).  Nothing outside this file knows RCCL, HIP IPC or the shm segment.
 //
 //   transport (ReduceVia)   scalar sums (allreduce, <= 8 doubles in h->reduced)                  row-sharded n-vector (sum_slots_over_ranks, 2n doubles)
 //   ----------------------  ---------------------------------------------------------------------  ---------------------------------------------------------

@@ -248,6 +248,28 @@ def host_equilibrate(A, b, c, K1, K2, passes=EQUILIBRATE_DEFAULT_PASSES):
     return dict(passes=int(passes), D=D, E=E, sigma=float(scal[0]), rho=float(scal[1]), gamma=float(scal[2]), A=As, b=bo, c=co)
 
 
+CG_VARIANT_NAMES = ("reference", "fused_p", "merged_sweep", "merged_update", "resident")
+# foship.h FOS_CGV_*, in bit order
+CG_VARIANT_FLAGS = ("fuse_p", "sharded", "mailboxes", "fold", "row_sharded", "qualifies", "all_qualify", "cache_resident", "window_panels", "plan_streamed",
+                    "resident_default")
+
+
+def host_cg_variant(request=None, l=0, plan_workgroups=0, cus=256, **flags):
+    """fos_host_cg_variant: the recurrence a handle with these properties would run (the rule behind cg_variant_name(), no GPU).  request: a name of
+    CG_VARIANT_NAMES or None (the default); flags: CG_VARIANT_FLAGS by keyword, False where not given."""
+    bits = sum(1 << CG_VARIANT_FLAGS.index(k) for k, on in flags.items() if on)
+    v = C.c_int32(0)
+    _lib.check(_lib.load().fos_host_cg_variant(-1 if request is None else CG_VARIANT_NAMES.index(request), bits, int(l), int(plan_workgroups), int(cus), C.byref(v)))
+    return CG_VARIANT_NAMES[v.value]
+
+
+def host_cg_windows(cg_epoch, maxit):
+    """fos_host_cg_windows: (first window, last window = the new cg_epoch) of a solve with the cap `maxit` behind `cg_epoch` (no GPU)."""
+    first, last = C.c_int64(0), C.c_int64(0)
+    _lib.check(_lib.load().fos_host_cg_windows(int(cg_epoch), int(maxit), C.byref(first), C.byref(last)))
+    return first.value, last.value
+
+
 class _WrapperLogs:
     """The last search / projection of the three wrappers, for both handles: `_log_prefix` names the form's entries (fos_ / fos_feas_)."""
 
@@ -536,7 +558,7 @@ class HipHSDE(_WrapperLogs):
     def cg_variant_name(self):
         v = C.c_int32(0)
         _lib.check(self._lib.fos_get_cg_variant(self._h, C.byref(v)))
-        return ("reference", "fused_p", "merged_sweep", "merged_update", "resident")[v.value]
+        return CG_VARIANT_NAMES[v.value]
 
     def resident_stats(self):
         """The plan of the resident CG solve (foship.h fos_resident_stats)."""

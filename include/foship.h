@@ -496,6 +496,24 @@ int fos_resident_stats(fos_handle h, int64_t* stats8);
  * written by every solve that ran with the copy, also one that ended on a failed exchange.  Waits for the handle's stream. */
 int fos_resident_lowp_stats(fos_handle h, double* stats8);
 int fos_get_cg_variant(fos_handle h, int32_t* variant);   /* the variant the next projection runs (defaults resolved) */
+/* Host-only exports of the two pure rules of the CG solve (no GPU needed; used by the CPU test-suite).
+ * fos_host_cg_variant: the rule behind fos_get_cg_variant from its inputs alone -- request: what fos_set_cg_variant / FOS_CG_VARIANT asked for (-1: the
+ * default); flags: the FOS_CGV_* below; l: rows of the KKT operator; plan_workgroups, cus: the resident plan's workgroups against the device's compute units.
+ * fos_host_cg_windows: the windows of 2048 sequence numbers a solve with the cap `maxit` reserves behind `cg_epoch` (the last window used so far, as uint32):
+ * *first_epoch the solve's first window, *new_cg_epoch its last. */
+#define FOS_CGV_FUSE_P           0x001   /* fos_set_tuning(fuse_p = 1) / FOS_CG_FUSE_P */
+#define FOS_CGV_SHARDED          0x002   /* the handle's sums cross ranks (RCCL, a host collective or mailboxes) */
+#define FOS_CGV_MAILBOXES        0x004   /* ... through peer mailboxes (fos_peer_enable) */
+#define FOS_CGV_FOLD             0x008   /* FOS_PEER_FOLD: the exchanges are folded into the CG kernels */
+#define FOS_CGV_ROW_SHARDED      0x010
+#define FOS_CGV_QUALIFIES        0x020   /* fos_resident_stats: qualifies */
+#define FOS_CGV_ALL_QUALIFY      0x040   /* ... and every rank's shard does */
+#define FOS_CGV_CACHE_RESIDENT   0x080   /* the operator's sweep runs from cache */
+#define FOS_CGV_WINDOW_PANELS    0x100   /* the operator is stored in window panels */
+#define FOS_CGV_PLAN_STREAMED    0x200   /* the resident plan is the streamed form */
+#define FOS_CGV_RESIDENT_DEFAULT 0x400   /* FOS_RESIDENT_DEFAULT is not 0 */
+int fos_host_cg_variant(int32_t request, int32_t flags, int64_t l, int32_t plan_workgroups, int32_t cus, int32_t* variant);
+int fos_host_cg_windows(int64_t cg_epoch, int64_t maxit, int64_t* first_epoch, int64_t* new_cg_epoch);
 
 /* test hooks.  FOS_DEBUG_PUPDATE_DELAY: every workgroup but the first of the kernel that closes a CG iteration waits `value`
  * ticks of the 100 MHz clock at entry (tests/test_gpu_parity.py: a late workgroup must still apply the last x update). */

@@ -29,7 +29,7 @@ pytestmark = pytest.mark.gpu
 VARIANTS = ("reference", "fused_p", "merged_sweep", "merged_update")
 OPERATORS = [(name, None) for name in cases.row_names()] + [(name, geom) for geom in ("1", "2") for name in cases.window_names()]
 OP_IDS = ["%s%s" % (name, "" if geom is None else "-win" + geom) for name, geom in OPERATORS]
-DEFAULT_CHUNK = 8                    # fos_solver::cg_chunk
+DEFAULT_CHUNK = 8                    # CgState::cg_chunk
 
 WORST = {}            # storage class -> variant -> worst |device - reference| / allowance
 STATS = {}            # operator id -> operator_stats()
