@@ -12,5 +12,5 @@ from .interface import (AP, DR, FISTA, GAP, GAPA, GAPP, Dykstra, FOSAlgorithm, F
                         LineSearchWrapper, LongstepWrapper, Solution, solve, HEADER_CG, HEADER_DIRECT,
                         ConeProduct, Feasibility, FeasibilityModel, FeasibilitySolution, HipFeasibility, IndAffine, IndBox, IndBallL2, IndBallL1, IndSimplex, IndHalfspace,
                         IndHyperslab, IndPoint, IndFree, SeparableSum, NormL1, SqrNormL2, ElasticNet, Linear, NormL2, HuberLoss, NormLinf, LeastSquares, Quadratic, solve_feasibility, direct_factor_code, DIRECT_FACTOR_NAMES,
-                        host_equilibrate, equilibrate_passes, host_cg_variant, host_cg_windows, CG_VARIANT_FLAGS, CG_VARIANT_NAMES)
+                        host_equilibrate, equilibrate_passes, host_cg_variant, host_cg_windows, host_lowp_cached, CG_VARIANT_FLAGS, CG_VARIANT_NAMES)
 from . import sharding             # noqa: F401

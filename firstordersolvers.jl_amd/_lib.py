@@ -129,6 +129,8 @@ PROTOTYPES = {
     "fos_host_cg_windows": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p]),
     "fos_resident_stats": (C.c_int, [_h, _i64p]),
     "fos_resident_lowp_stats": (C.c_int, [_h, _dp]),
+    "fos_resident_lowp_cache_stats": (C.c_int, [_h, _i64p]),
+    "fos_host_lowp_cached": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, _i32p, _i64p]),
     "fos_debug_set": (C.c_int, [_h, C.c_int32, C.c_int64]),
     "fos_set_gapp": (C.c_int, [_h, C.c_int64]),
     "fos_gapp_log": (C.c_int, [_h, _dp]),

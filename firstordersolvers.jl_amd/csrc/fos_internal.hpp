@@ -520,7 +520,22 @@ struct ResLaunch {
     // eta = the share of a solve's stop tolerance the walk may cost, mode 1: by the rule, 2: every sweep behind the start (tests), and the device
     // record of the last solve {fp32 sweeps, reverted, bound}
     const float* val32; double lowp_delta, lowp_eta; int lowp_mode; double* lowp_out;
+    int lowp_cached;                 // the sweeps read val32 with default-policy loads, not non-temporal ones (rs_lowp_cached below; resident.hip, rs_request)
 };
+// WHERE THE FLOAT COPY IS READ FROM.  A solve's fp32 sweeps read the same val32 bytes one sweep after the other, with nothing else of size in between; read
+// with loads that pass the CU's L1 by and take the default policy behind it, the sweeps are 2 us shorter.  Why is not established (the Infinity Cache serves
+// non-temporal loads too: DESIGN_LOG.md), so the budget is not a cache's size but the largest copy this was MEASURED to pay for, and little more: copies of 69,
+// 104 and 138.4 MB in the solve (profiles/stream_lowp_cache_sizes.txt, stream_lowp_cache_ab.json) and the bare walk at 138 MB; at 200 MB the bare walk reads no
+// faster than with non-temporal loads (profiles/stream_reread_ceiling.json: the file this budget was read from) and nothing between was measured.  138 MiB
+// (144.7 MB) is the largest copy a plan of 32-step tiles can have (69 tiles of 8 KB in each of 256 workgroups) and 4.5 % above the flagship's 132 MiB: that
+// margin is a guess.  A larger copy (plans of 64-step tiles alone) keeps the non-temporal loads.
+constexpr int64_t RS_LOWP_CACHE_BUDGET_BYTES = (int64_t)138 << 20;
+// the budget in force: FOS_RS_LOWP_CACHE_MB (MiB, tests) or the constant
+inline int64_t rs_lowp_cache_budget(int64_t mb_override) {
+    return mb_override < 0 ? RS_LOWP_CACHE_BUDGET_BYTES : std::min<int64_t>(mb_override, (int64_t)1 << 20) << 20;
+}
+// the rule (pure; fos_host_lowp_cached): a plan with a float copy of val32_bytes reads it with the cached policy unless FOS_RS_LOWP_CACHE=0 says no
+inline bool rs_lowp_cached(int64_t val32_bytes, bool cache_on, int64_t budget_bytes) { return cache_on && val32_bytes > 0 && val32_bytes <= budget_bytes; }
 // rounds `nvals` tile values to val32 and leaves, per workgroup of the streamed plan, its bound of |A - fl32(A)|_2 in part[G] (the maximum is delta)
 hipError_t launch_rs_lowp_setup(hipStream_t stream, const BlkDesc* blk, const double* val, int64_t nvals, const ResWG* wg, int G, float* val32, double* part);
 // x (in: the start iterate, out: the solution), r_0 = rhs - M v; fold != nullptr: the sums cross the ranks through the mailboxes

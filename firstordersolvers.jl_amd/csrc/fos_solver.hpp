@@ -134,6 +134,8 @@ struct fos_solver {
     bool relax_ew = true;                      // FOS_RELAX_EW=0: the relaxation does not project the elementwise cones in the same pass
     int rs_lowp = 1;                           // FOS_RS_LOWP: 0 the streamed CG solve reads doubles only, 1 fp32 tiles by the rule (default), 2 on every sweep behind the start (tests)
     double rs_lowp_eta = 0.1;                  // FOS_RS_LOWP_ETA: the share of min(a solve's tolerance, the schedule's floor l eps) the fp32 sweeps may cost
+    bool rs_lowp_cache = true;                 // FOS_RS_LOWP_CACHE=0: the float copy is read with non-temporal loads whatever its size (rs_lowp_cached, fos_internal.hpp)
+    int64_t rs_lowp_cache_budget = fos::RS_LOWP_CACHE_BUDGET_BYTES;      // FOS_RS_LOWP_CACHE_MB: another budget for the rule (tests)
 
     // scalars
     fos::DevState* st = nullptr;

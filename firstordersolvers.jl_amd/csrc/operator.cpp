@@ -253,6 +253,7 @@ int resident_lowp_ensure(fos_solver* h) {
     for (double v : hp) delta = (v > delta || v != v) ? v : delta;
     if (!(delta < std::numeric_limits<double>::infinity())) return FOS_OK;
     o.res.val32 = o.res_val32; o.res.lowp_out = o.res_lowp_out; o.res.lowp_delta = delta * (1.0 + 0x1p-20); o.res.lowp_mode = h->rs_lowp;
+    o.res.lowp_cached = rs_lowp_cached(4 * o.dev.nnz_padded, h->rs_lowp_cache, h->rs_lowp_cache_budget) ? 1 : 0;
     return FOS_OK;
 }
 
@@ -290,6 +291,7 @@ int resident_setup(fos_solver* h, int gmax) {
     static const double res_wait_s = getenv("FOS_RESIDENT_WAIT_S") ? atof(getenv("FOS_RESIDENT_WAIT_S")) : 5.0;
     o.res.timeout_ticks = (int64_t)(res_wait_s * 1e8);
     o.res.val32 = nullptr; o.res.lowp_out = nullptr; o.res.lowp_delta = 0.0; o.res.lowp_eta = h->rs_lowp_eta; o.res.lowp_mode = 0;
+    o.res.lowp_cached = 0;
     o.res_lowp_pending = true;                             // (resident_lowp_ensure, in front of the first resident solve on this plan)
     o.res_plan = plan; o.res_ok = true; o.res_all = !h->sharded();
     return FOS_OK;
@@ -345,6 +347,21 @@ int fos_resident_lowp_stats(fos_handle h, double* stats8) {
     FOS_HIP(hipMemcpy(rec, o.res.lowp_out, sizeof(rec), hipMemcpyDeviceToHost));
     stats8[0] = o.res.lowp_delta; stats8[1] = rec[0]; stats8[2] = rec[1]; stats8[3] = rec[2];
     stats8[4] = 4.0 * (double)o.dev.nnz_padded; stats8[5] = (double)o.res.lowp_mode; stats8[6] = o.res.lowp_eta;
+    return FOS_OK;
+}
+
+int fos_resident_lowp_cache_stats(fos_handle h, int64_t* stats2) {
+    if (!h || !stats2) { set_error("NULL argument"); return FOS_EINVAL; }
+    const Operator& o = h->op;
+    stats2[0] = o.res_ok && o.res.val32 && o.res.lowp_cached ? 1 : 0;
+    stats2[1] = h->rs_lowp_cache_budget;
+    return FOS_OK;
+}
+
+int fos_host_lowp_cached(int64_t val32_bytes, int32_t cache_switch, int64_t budget_mb, int32_t* cached, int64_t* budget_bytes) {
+    if (!cached || !budget_bytes || val32_bytes < 0) { set_error("bad argument"); return FOS_EINVAL; }
+    *budget_bytes = rs_lowp_cache_budget(budget_mb);
+    *cached = rs_lowp_cached(val32_bytes, cache_switch != 0, *budget_bytes) ? 1 : 0;
     return FOS_OK;
 }
 

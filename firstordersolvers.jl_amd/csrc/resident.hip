@@ -663,16 +663,29 @@ __device__ __forceinline__ BlkDesc rs_desc(const BlkDesc* blk, int i) {
 // the tile's first value, one address for the wavefront, and are never consumed -- a request that is there on one path and not on another leaves the
 // compiler no count of the loads in flight behind a chunk, and every chunk then waits for ALL requests (s_waitcnt vmcnt(0)): the ring held one chunk
 // (VT = float: the same chunk of val32 -- same offsets, half the bytes; the ring is then twice as deep, rs_walk)
+// HOW THE VALUES ARE LOADED: val, which no cache of the chip holds from one sweep to the next, with non-temporal loads.  val32 of a plan whose copy the
+// planner found small enough (CACHED: rs_lowp_cached, fos_internal.hpp) with loads that pass the CU's L1 by and take the default policy behind it
+// (global_load ... sc1: what a relaxed agent-scope atomic load compiles to -- still one dword per lane, still counted by the waits): the thirteen fp32
+// sweeps of a solve read the same bytes in a row, and on the flagship they run 17 - 20 us each this way against 19.5 - 22 (profiles/stream_lowp_cache_stamps.txt;
+// the Infinity Cache serves non-temporal loads too, so what is gained is not established to be its hits: DESIGN_LOG.md)
 template <class VT> __device__ __forceinline__ const VT* rs_values(const ResArgs& a);
 template <> __device__ __forceinline__ const double* rs_values<double>(const ResArgs& a) { return a.val; }
 template <> __device__ __forceinline__ const float* rs_values<float>(const ResArgs& a) { return a.val32; }
-template <class VT>
+template <class VT, bool CACHED>
 __device__ __forceinline__ void rs_request(const ResArgs& a, int blk, int grp, int lane, VT (&val)[TILE_GROUP]) {
+    static_assert(!CACHED || sizeof(VT) == sizeof(float), "the doubles are always streamed");
     const BlkDesc d = rs_desc(a.blk, blk);
     const bool live = TILE_GROUP * grp < d.steps();                  // wave-uniform
     const VT* __restrict__ vp = rs_values<VT>(a) + d.nnz0 + (live ? 64 * TILE_GROUP * grp : 0) + (live ? lane : 0);
 #pragma unroll
-    for (int t = 0; t < TILE_GROUP; ++t) val[t] = __builtin_nontemporal_load(vp + 64 * t);      // (zero-padded storage beyond the tile's rows and columns)
+    for (int t = 0; t < TILE_GROUP; ++t) {                                                      // (zero-padded storage beyond the tile's rows and columns)
+        // (DEPENDS ON THE COMPILER: a relaxed agent-scope atomic load of a float is `global_load_dword ... sc1` with no fence or invalidate around it under
+        //  the hipcc this was built with (184 of them in <32, 9, true, true>, waits vmcnt(8) .. vmcnt(31)).  Nothing in the build or the tests pins that: a
+        //  compiler that maps it otherwise changes the policy, or the waits, while every result stays the same bits -- look at the assembly and at
+        //  tools/ab_bench.sh with FOS_RS_LOWP_CACHE=0 after a compiler update)
+        if constexpr (CACHED) val[t] = __hip_atomic_load(vp + 64 * t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else val[t] = __builtin_nontemporal_load(vp + 64 * t);
+    }
 }
 
 // (RS_NTC = 6: tiles the communication wavefront may sweep itself -- it waits at barrier (A) otherwise; which tiles a wavefront walks is the plan's
@@ -705,7 +718,7 @@ __device__ __forceinline__ void rs_rows_store(const ResArgs& a, int blk_first, i
 
 // one column group of a wavefront's tiles Q, Q + 1, ...: the tiles NEST (tile Q + 1 inside tile Q's branch), so the paths of wavefronts with fewer tiles
 // leave the group and do not meet the others again inside it
-template <int Q, int NT, int D, class VT>
+template <int Q, int NT, int D, class VT, bool CACHED>
 __device__ __forceinline__ void rs_group(const ResArgs& a, int bf, int cnt, int grp, int c0, int lane, const d2* __restrict__ s_gcol, d2* __restrict__ mycol,
                                          RsRows<NT>& R, VT (&val)[D][TILE_GROUP], double (&a1)[TILE_GROUP], double (&a2)[TILE_GROUP]) {
     if constexpr (Q < NT) {
@@ -714,8 +727,8 @@ __device__ __forceinline__ void rs_group(const ResArgs& a, int bf, int cnt, int 
             const int coff = d.meta[0] - c0 + TILE_GROUP * grp;
             const bool in = TILE_GROUP * grp < d.steps();
             if (in) res_tile_plain(val[Q % D], R.rr[Q], s_gcol + coff, R.ww[Q], a1, a2);
-            if (Q + D < NT && Q + D < cnt) rs_request(a, bf + Q + D, grp, lane, val[Q % D]);
-            else rs_request(a, bf + Q % D, grp + 1, lane, val[Q % D]);
+            if (Q + D < NT && Q + D < cnt) rs_request<VT, CACHED>(a, bf + Q + D, grp, lane, val[Q % D]);
+            else rs_request<VT, CACHED>(a, bf + Q % D, grp + 1, lane, val[Q % D]);
             // the segment's last tile: the column sums of this group
             const bool last = Q + 1 == NT || Q + 1 >= cnt || rs_desc(a.blk, bf + Q + 1).meta[0] != d.meta[0];
             if (in && last) {
@@ -726,7 +739,7 @@ __device__ __forceinline__ void rs_group(const ResArgs& a, int bf, int cnt, int 
 #pragma unroll
                 for (int u = 0; u < TILE_GROUP; ++u) a1[u] = a2[u] = 0.0;
             }
-            rs_group<Q + 1, NT, D, VT>(a, bf, cnt, grp, c0, lane, s_gcol, mycol, R, val, a1, a2);
+            rs_group<Q + 1, NT, D, VT, CACHED>(a, bf, cnt, grp, c0, lane, s_gcol, mycol, R, val, a1, a2);
         }
     }
 }
@@ -747,7 +760,7 @@ __device__ __forceinline__ void rs_group(const ResArgs& a, int bf, int cnt, int 
 #ifndef RS_RING
 #define RS_RING 2
 #endif
-template <int TMAX, int NT, class VT>
+template <int TMAX, int NT, class VT, bool CACHED>
 __device__ __forceinline__ void rs_walk(const ResArgs& a, int blk_first, int cnt, int c0, int lane, const d2* __restrict__ s_gcol, d2* __restrict__ mycol,
                                         RsRows<NT>& R) {
     constexpr int RING = RS_RING * (int)(sizeof(double) / sizeof(VT));
@@ -759,7 +772,7 @@ __device__ __forceinline__ void rs_walk(const ResArgs& a, int blk_first, int cnt
     VT val[D][TILE_GROUP];
     double a1[TILE_GROUP], a2[TILE_GROUP];
 #pragma unroll
-    for (int s = 0; s < D; ++s) if (s < cnt) rs_request<VT>(a, blk_first + s, 0, lane, val[s]);
+    for (int s = 0; s < D; ++s) if (s < cnt) rs_request<VT, CACHED>(a, blk_first + s, 0, lane, val[s]);
 #pragma unroll
     for (int q = 0; q < NT; ++q) R.ww[q] = make_double2(0.0, 0.0);
 #pragma unroll
@@ -767,10 +780,10 @@ __device__ __forceinline__ void rs_walk(const ResArgs& a, int blk_first, int cnt
     for (int grp = 0; grp < ngrp; ++grp) {
         int bf = blk_first;
         asm volatile("" : "+s"(bf));           // (opaque per group: the descriptor loads stay in the loop, see above)
-        rs_group<0, NT, D, VT>(a, bf, cnt, grp, c0, lane, s_gcol, mycol, R, val, a1, a2);
+        rs_group<0, NT, D, VT, CACHED>(a, bf, cnt, grp, c0, lane, s_gcol, mycol, R, val, a1, a2);
     }
 }
-template <int TMAX, int NT, bool LOWP>
+template <int TMAX, int NT, bool LOWP, bool CACHED>
 __device__ __forceinline__ void rs_sweep(const ResArgs& a, int blk_first, int cnt, int c0, int lane, const d2* __restrict__ s_gcol, const double* s_ctl,
                                          d2* __restrict__ mycol, RsRows<NT>& R, double (&acc)[4], bool early = false,
                                          const double* __restrict__ cbh = nullptr) {
@@ -780,11 +793,13 @@ __device__ __forceinline__ void rs_sweep(const ResArgs& a, int blk_first, int cn
     acc[0] = acc[1] = acc[2] = acc[3] = 0.0;
     if (cnt > 0) {                                 // wave-uniform
         // which values this sweep reads: one decision per sweep, the same in every wavefront of the grid (wave-uniform, outside the group loop)
-        // (LOWP: the kernel instance of a plan with a float copy; the other instance is the fp64 walk alone, as it was before there was a second one)
+        // (LOWP: the kernel instance of a plan with a float copy; the other instance is the fp64 walk alone, as it was before there was a second one;
+        //  CACHED: how that instance loads the copy -- a property of the instance, so that a kernel holds one float walk and every request of it is there
+        //  on every path: rs_request)
         bool lowp = false;
         if constexpr (LOWP) lowp = __builtin_amdgcn_readfirstlane((int)(s_ctl[RC_LOWP] != 0.0)) != 0;
-        if (lowp) rs_walk<TMAX, NT, float>(a, blk_first, cnt, c0, lane, s_gcol, mycol, R);
-        else rs_walk<TMAX, NT, double>(a, blk_first, cnt, c0, lane, s_gcol, mycol, R);
+        if (lowp) rs_walk<TMAX, NT, float, CACHED>(a, blk_first, cnt, c0, lane, s_gcol, mycol, R);
+        else rs_walk<TMAX, NT, double, false>(a, blk_first, cnt, c0, lane, s_gcol, mycol, R);
         // the rows' epilogue: [c; b] from the caller's registers (cbh), or of all tiles requested together
         double cb[NT];
 #pragma unroll
@@ -930,8 +945,9 @@ __device__ __forceinline__ double rs_lowp_decide(const ResArgs& a, double* s_low
     return state == 1.0 ? 1.0 : 0.0;
 }
 
-template <int TMAX, int NT, bool LOWP>
+template <int TMAX, int NT, bool LOWP, bool CACHED = false>
 __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs a) {
+    static_assert(LOWP || !CACHED, "CACHED is how the float copy is loaded");
     __shared__ __attribute__((aligned(16))) d2 s_gcol[64];                   // the workgroup's column elements of the vector being swept (v, then r)
     __shared__ double s_red[16][4];
     __shared__ double s_ctl[RC_COUNT];
@@ -997,7 +1013,7 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
         bool early = false;
         for (int i = -1, xr = 0;; ++xr) {
             double acc[4];
-            rs_sweep<TMAX, NT, LOWP>(a, me.blk0 + t0, cnt, c0, lane, s_gcol, s_ctl, mycol, R, acc, early, HOLD_CB ? cbh : nullptr);
+            rs_sweep<TMAX, NT, LOWP, CACHED>(a, me.blk0 + t0, cnt, c0, lane, s_gcol, s_ctl, mycol, R, acc, early, HOLD_CB ? cbh : nullptr);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const double v = wave_sum(acc[k]);
@@ -1065,7 +1081,7 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
         nx += 1;
         if (c0wave) {
             double racc[4];
-            rs_sweep<TMAX, NTC, LOWP>(a, me.blk0 + t0, cnt, c0, lane, s_gcol, s_ctl, mycol, R, racc, early);
+            rs_sweep<TMAX, NTC, LOWP, CACHED>(a, me.blk0 + t0, cnt, c0, lane, s_gcol, s_ctl, mycol, R, racc, early);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const double v = wave_sum(racc[k]);
@@ -1270,18 +1286,21 @@ __global__ __launch_bounds__(64 * (RS_NCOMP + 1)) void cg_stream_kernel(ResArgs 
 
 // The kernel instance a plan launches, with its block and its dynamic LDS (res_stream_lds_bytes / res_reg_lds_bytes, fos_internal.hpp: the planner's formula)
 struct ResKernel { const void* fn; int threads; size_t lds; };
-static ResKernel res_kernel(const ResLaunch& rl, bool lowp = false) {
+// (lowp: the instance with the fp32 walk; cached: the one of them that reads the float copy past the CU's L1 with the default policy -- rs_request)
+static ResKernel res_kernel(const ResLaunch& rl, bool lowp = false, bool cached = false) {
     auto k = [](auto kern, int threads, size_t lds) { return ResKernel{reinterpret_cast<const void*>(kern), threads, lds}; };
     if (rl.stream) {
         // (the compute wavefronts' sums land in s_red[wv]: RS_NCOMP rows, the others zeroed once)
         const int thr = 64 * (RS_NCOMP + 1);
         const size_t lds = res_stream_lds_bytes(rl.tiles_wg_max);
-        if (rl.tmax > 32 && rl.nt <= 3) return lowp ? k(cg_stream_kernel<64, 3, true>, thr, lds) : k(cg_stream_kernel<64, 3, false>, thr, lds);
-        if (rl.tmax > 32) return lowp ? k(cg_stream_kernel<64, 5, true>, thr, lds) : k(cg_stream_kernel<64, 5, false>, thr, lds);
-        if (rl.nt <= 3) return lowp ? k(cg_stream_kernel<32, 3, true>, thr, lds) : k(cg_stream_kernel<32, 3, false>, thr, lds);
-        if (rl.nt <= 5) return lowp ? k(cg_stream_kernel<32, 5, true>, thr, lds) : k(cg_stream_kernel<32, 5, false>, thr, lds);
-        if (rl.nt <= 9) return lowp ? k(cg_stream_kernel<32, 9, true>, thr, lds) : k(cg_stream_kernel<32, 9, false>, thr, lds);
-        return lowp ? k(cg_stream_kernel<32, 10, true>, thr, lds) : k(cg_stream_kernel<32, 10, false>, thr, lds);
+#define RS_INSTANCE(TM, N) (!lowp ? k(cg_stream_kernel<TM, N, false>, thr, lds) : cached ? k(cg_stream_kernel<TM, N, true, true>, thr, lds) : k(cg_stream_kernel<TM, N, true>, thr, lds))
+        if (rl.tmax > 32 && rl.nt <= 3) return RS_INSTANCE(64, 3);
+        if (rl.tmax > 32) return RS_INSTANCE(64, 5);
+        if (rl.nt <= 3) return RS_INSTANCE(32, 3);
+        if (rl.nt <= 5) return RS_INSTANCE(32, 5);
+        if (rl.nt <= 9) return RS_INSTANCE(32, 9);
+        return RS_INSTANCE(32, 10);
+#undef RS_INSTANCE
     }
     const int thr = 64 * (rl.nw + rl.ncomm);
     if (rl.tmax <= 32 && rl.rpt == 1) return k(cg_resident_kernel<32, 1, 768>, thr, res_reg_lds_bytes(12, 32));
@@ -1298,7 +1317,8 @@ static hipError_t res_lds_optin(const ResKernel& k) {
 }
 
 bool res_lds_fits(const ResLaunch& rl, int device, std::string* why) {
-    if (rl.stream && !res_lds_fits_instance(res_kernel(rl, true), device, why)) return false;      // (the instance with the fp32 walk: 40 static bytes more)
+    if (rl.stream && !res_lds_fits_instance(res_kernel(rl, true), device, why)) return false;      // (the instances with the fp32 walk: 40 static bytes more)
+    if (rl.stream && !res_lds_fits_instance(res_kernel(rl, true, true), device, why)) return false;
     return res_lds_fits_instance(res_kernel(rl, false), device, why);
 }
 static bool res_lds_fits_instance(const ResKernel& k, int device, std::string* why) {
@@ -1349,7 +1369,7 @@ hipError_t launch_cg_resident(const LaunchCtx& c, const ResLaunch& rl, double2* 
         a.lowp_theta = (rl.lowp_mode == 2 || rl.lowp_delta == 0.0) ? INFINITY : rl.lowp_eta * tol_lp / (K * rl.lowp_delta);
         a.lowp_budget = rl.lowp_mode == 2 ? -1.0 : 0.5 * rl.lowp_eta * tol_lp;
     }
-    const ResKernel k = res_kernel(rl, a.val32 != nullptr);
+    const ResKernel k = res_kernel(rl, a.val32 != nullptr, a.val32 != nullptr && rl.lowp_cached != 0);
     const hipError_t e = res_lds_optin(k);
     if (e != hipSuccess) return e;
     void* args[] = {&a};

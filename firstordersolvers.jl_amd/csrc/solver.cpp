@@ -669,6 +669,8 @@ int fos_create2(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowv
     h->relax_ew = !(getenv("FOS_RELAX_EW") && atoi(getenv("FOS_RELAX_EW")) == 0);
     if (const char* e = getenv("FOS_RS_LOWP")) h->rs_lowp = std::max(0, std::min(2, atoi(e)));
     if (const char* e = getenv("FOS_RS_LOWP_ETA")) { const double eta = atof(e); if (eta > 0.0 && eta <= 1.0) h->rs_lowp_eta = eta; }
+    if (const char* e = getenv("FOS_RS_LOWP_CACHE")) h->rs_lowp_cache = atoi(e) != 0;
+    if (const char* e = getenv("FOS_RS_LOWP_CACHE_MB")) h->rs_lowp_cache_budget = rs_lowp_cache_budget(std::max<long long>(0, atoll(e)));
 
     // ---- operator (operator.cpp)
     h->row_sharded = (flags & FOS_CREATE_ROW_SHARDED) != 0;

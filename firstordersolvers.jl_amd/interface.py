@@ -263,6 +263,14 @@ def host_cg_variant(request=None, l=0, plan_workgroups=0, cus=256, **flags):
     return CG_VARIANT_NAMES[v.value]
 
 
+def host_lowp_cached(val32_bytes, cache=True, budget_mb=None):
+    """fos_host_lowp_cached: (whether a streamed plan with a float copy of `val32_bytes` reads it with the cached policy, the budget in bytes) -- the rule
+    behind resident_stats()["lowp_cached"], no GPU.  cache: FOS_RS_LOWP_CACHE; budget_mb: FOS_RS_LOWP_CACHE_MB (MiB) or None for the built-in budget."""
+    cached, budget = C.c_int32(0), C.c_int64(0)
+    _lib.check(_lib.load().fos_host_lowp_cached(int(val32_bytes), 1 if cache else 0, -1 if budget_mb is None else int(budget_mb), C.byref(cached), C.byref(budget)))
+    return bool(cached.value), budget.value
+
+
 def host_cg_windows(cg_epoch, maxit):
     """fos_host_cg_windows: (first window, last window = the new cg_epoch) of a solve with the cap `maxit` behind `cg_epoch` (no GPU)."""
     first, last = C.c_int64(0), C.c_int64(0)
@@ -571,6 +579,10 @@ class HipHSDE(_WrapperLogs):
         # the streamed form's fp32 walk (foship.h fos_resident_lowp_stats): its bound of |A - fl32(A)|_2 and the last solve's record
         lp = self._lowp_stats()
         out.update(lowp_delta=lp[0], lowp_sweeps_last_solve=int(lp[1]), lowp_reverted_last_solve=int(lp[2]), lowp_bound_last_solve=lp[3])
+        # where the float copy is read from (foship.h fos_resident_lowp_cache_stats): 1 = with the cached policy, and the budget the rule was held to
+        lc = (C.c_int64 * 2)()
+        _lib.check(self._lib.fos_resident_lowp_cache_stats(self._h, lc))
+        out.update(lowp_cached=int(lc[0]), lowp_cache_budget_bytes=int(lc[1]))
         return out
 
     def _lowp_stats(self):

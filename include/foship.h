@@ -495,6 +495,16 @@ int fos_resident_stats(fos_handle h, int64_t* stats8);
  * solve's own tolerance: a caller's solve at a tolerance above the floor reads floats only once its residual is small enough for the floor's budget.  The record is
  * written by every solve that ran with the copy, also one that ended on a failed exchange.  Waits for the handle's stream. */
 int fos_resident_lowp_stats(fos_handle h, double* stats8);
+/* How the fp32 walk loads the float copy.  The fp32 sweeps of a solve read the same bytes one sweep after the other; a copy of at most the budget
+ * (138 MiB; FOS_RS_LOWP_CACHE_MB=<MiB> at fos_create: another one, tests) is read with loads that pass the compute unit's L1 by and take the default
+ * cache policy behind it, a larger one -- and every copy under FOS_RS_LOWP_CACHE=0 at fos_create -- with the non-temporal loads the doubles are read with.
+ * Measured, the sweeps are about 2 us shorter with the former up to the flagship's 138 MB; which cache that is owed to is not established (the Infinity Cache
+ * serves both kinds of load), so "cached" in the names below says which loads are used, not where the bytes were found, and the budget is the largest size
+ * measured plus a small margin, not a cache's capacity.  The same operations on the same values either way: the results are the same bits.  stats2 = {the plan in force reads its copy with the cached policy
+ * (0 / 1; 0 where there is no copy), the budget in bytes}.  fos_host_lowp_cached: the rule alone, on the host (the CPU test-suite) -- cache_switch:
+ * FOS_RS_LOWP_CACHE, budget_mb: FOS_RS_LOWP_CACHE_MB or -1 for the built-in budget. */
+int fos_resident_lowp_cache_stats(fos_handle h, int64_t* stats2);
+int fos_host_lowp_cached(int64_t val32_bytes, int32_t cache_switch, int64_t budget_mb, int32_t* cached, int64_t* budget_bytes);
 int fos_get_cg_variant(fos_handle h, int32_t* variant);   /* the variant the next projection runs (defaults resolved) */
 /* Host-only exports of the two pure rules of the CG solve (no GPU needed; used by the CPU test-suite).
  * fos_host_cg_variant: the rule behind fos_get_cg_variant from its inputs alone -- request: what fos_set_cg_variant / FOS_CG_VARIANT asked for (-1: the
