@@ -172,7 +172,7 @@ static CgRun cg_run(fos_solver* h, const CgCall& a, int variant, uint32_t epoch)
     //  whose post-solve kernels contain no reduction; every rank takes the same decisions, so all mispredict together.
     //  Solve number 0 mod 2^21 is the mark's initial value.)
     r.spec = a.post && h->cg.speculate && !r.c.between && !r.fuse_p && (r.seq_base >> 11) != 0u &&
-             (!h->sharded() || (r.fold && h->alg != FOS_ALG_GAPA));
+             (!h->sharded() || (r.fold && h->step.alg != FOS_ALG_GAPA));
     r.batch_id = (int32_t)(((r.seq_base >> 11) & 0x7FFFFFu) << 8 | 1u);
     r.x = a.x; r.rhs = a.rhs; r.v = a.apply_on ? a.apply_on : a.x; r.tol = a.tol; r.maxit = a.maxit;
     r.next_j = 1;

@@ -112,7 +112,7 @@ static int prox_affine_direct_block(fos_solver* h, const d2* x, d2* out, bool fr
         launch_blkdir_tau(c, T, h->blk_qphg, h->blk_prm, zero_kappa ? 1 : 0, out, p1, p2, h->blk_ctx, h->blk_n, fr);
     }
     prof_end(h, po);
-    h->cgiter = 0;
+    h->step.cgiter = 0;
     return check_launch("block-direct affine projection");
 }
 
@@ -173,7 +173,7 @@ int fos::prox_affine_direct(fos_solver* h, const d2* x) {
     launch_q1(c, Q_VFROMU, h->AP, 0, 1.0, h->SOL);                     // SOL = (u+, Q u+)
     FOS_TRY(finish_reduce(h, c, c.S.npart, 1, 0, &fr, c.S.part_off));
     launch_q1_finalize(c, Q_VFROMU, h->AP, 0, 1.0, h->SOL, fr);
-    h->cgiter = 0;
+    h->step.cgiter = 0;
     return check_launch(red ? "reduced direct affine projection" : "direct affine projection");
 }
 

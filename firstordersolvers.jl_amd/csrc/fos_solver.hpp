@@ -1,4 +1,4 @@
-// struct fos_solver (the handle behind fos_handle) and the helpers that solver.cpp, cg.cpp, operator.cpp, cones.cpp, direct.cpp and transport.cpp share.  Private: not part of the ABI.
+// struct fos_solver (the handle behind fos_handle) and the helpers that solver.cpp, step.cpp, cg.cpp, operator.cpp, cones.cpp, direct.cpp and transport.cpp share.  Private: not part of the ABI.
 #pragma once
 
 #include <rccl/rccl.h>
@@ -104,6 +104,26 @@ struct CgState {
     bool pre_on = true;
 };
 
+// ------------------------------------------------------------------------------------------------ the outer iteration (step.cpp)
+struct StepState {
+    // algorithm (gap.jl:6-21, gapa.jl:9-25, fista.jl:6-18, dykstra.jl:5-17)
+    int alg = FOS_ALG_GAP;
+    double alpha = 0.8, alpha1 = 1.8, alpha2 = 1.8, beta = 0.0;
+    double fista_t = 1.0;
+    // S1 = AffinePlusLinear state (affinepluslinear.jl:58-69)
+    int64_t prox_i = 1;
+    bool firstrun = true;
+    int64_t cgiter = 0;
+    bool firstrun2 = true;                     // HSDEMatrix.cgdata.firstrun
+    bool shift_ready = false;                  // RHS already holds SOL - [0; X.y] (written by the step's last kernel): inside fos_step only
+    bool in_step = false;                      // fos_step is running (the entries that project outside it leave no shift behind)
+    // the step's switches (step_read_switches; FOS_FUSED_RHS is per process and sits beside it)
+    bool shift_fuse = true;                    // FOS_SHIFT_FUSE=0: every projection runs its own shift pass
+    bool psd_fuse = true;                      // FOS_PSD_FUSE=0: relaxation, projection and the step's last pass stay separate launches
+    bool relax_ew = true;                      // FOS_RELAX_EW=0: the relaxation does not project the elementwise cones in the same pass
+    const d2* last_checked = nullptr;          // vector the last checkstatus was evaluated on
+};
+
 // ------------------------------------------------------------------------------------------------ the handle
 struct fos_solver {
     int device = 0;
@@ -130,8 +150,6 @@ struct fos_solver {
     // cones: S2 = DualConeProduct, its table, workspaces and warm-start state (cones.cpp)
     fos::ConeSet* cones = nullptr;
     int cus = 256;                             // compute units of `device`
-    bool psd_fuse = true;                      // FOS_PSD_FUSE=0: relaxation, projection and the step's last pass stay separate launches
-    bool relax_ew = true;                      // FOS_RELAX_EW=0: the relaxation does not project the elementwise cones in the same pass
     int rs_lowp = 1;                           // FOS_RS_LOWP: 0 the streamed CG solve reads doubles only, 1 fp32 tiles by the rule (default), 2 on every sweep behind the start (tests)
     double rs_lowp_eta = 0.1;                  // FOS_RS_LOWP_ETA: the share of min(a solve's tolerance, the schedule's floor l eps) the fp32 sweeps may cost
     bool rs_lowp_cache = true;                 // FOS_RS_LOWP_CACHE=0: the float copy is read with non-temporal loads whatever its size (rs_lowp_cached, fos_internal.hpp)
@@ -144,11 +162,6 @@ struct fos_solver {
     double* partials = nullptr;
     double* reduced = nullptr;                 // 16 doubles
     int vec_blocks = 0;
-
-    // algorithm (gap.jl:6-21, gapa.jl:9-25, fista.jl:6-18, dykstra.jl:5-17)
-    int alg = FOS_ALG_GAP;
-    double alpha = 0.8, alpha1 = 1.8, alpha2 = 1.8, beta = 0.0;
-    double fista_t = 1.0;
 
     // direct = true (HSDE.jl:12-15): S1 = IndAffine([Q -I], 0), an exact projection through a one-time dense factorisation (direct.cpp).
     // direct_form says which form is ACTIVE; what is STORED (Ginv, blk_ready, red_ready) does not depend on it: a disabled handle keeps its factorisation
@@ -184,16 +197,8 @@ struct fos_solver {
     double red_minv[4] = {0, 0, 0, 0};         // inverse of the 2 x 2 border system, row-major
     double direct_setup_s = 0.0;               // wall time of the last set-up (fos_get_direct_stats)
 
-    // S1 = AffinePlusLinear state (affinepluslinear.jl:58-69)
-    int64_t prox_i = 1;
-    bool firstrun = true;
-    int64_t cgiter = 0;
-    bool firstrun2 = true;                     // HSDEMatrix.cgdata.firstrun
-    bool shift_ready = false;                  // RHS already holds SOL - [0; X.y] (written by the step's last kernel): inside fos_step only
-    bool shift_fuse = true;                    // FOS_SHIFT_FUSE=0: every projection runs its own shift pass
-    bool in_step = false;
+    StepState step;                            // the outer iteration's state and switches (step.cpp)
     fos::Wrappers wr;                          // LineSearchWrapper, GAPP, LongstepWrapper (wrappers.hpp)
-    const d2* last_checked = nullptr;          // vector the last checkstatus was evaluated on
 
     // sharding: how the sums cross the ranks is the transport's business (transport.cpp); what is sharded is the handle's, the solves' sequence windows are the CG state's
     Transport tr;
@@ -244,6 +249,9 @@ struct fos_solver {
     }
 };
 
+// does the step's last kernel also leave SOL - [0; X.y] in RHS for the next iteration's CG start?  (inside fos_step, and where S1 runs a CG solve)
+inline bool leaves_shift(const fos_solver* h) { return h->step.in_step && h->step.shift_fuse && !h->direct_exact(); }
+
 // ------------------------------------------------------------------------------------------------ shared helpers (defined in solver.cpp where no other file is named)
 namespace fos {
 // transport.cpp: the sums of a sharded handle (allreduce: `count` doubles in h->reduced, in place, in stream), the end of its transports, the two switches
@@ -268,6 +276,10 @@ int poll_state(fos_solver* h);
 int kkt_apply_full(fos_solver* h, const LaunchCtx& c, const d2* w, d2* out, bool deferred = true, bool tau_row = true);
 int upload_plain(fos_solver* h, d2* dst, const double* z);      // a caller's plain 2l-vector <-> a device vector, through h->plain; synchronise
 int download_plain(fos_solver* h, double* z, const d2* src);
+int upload_caller(fos_solver* h, d2* dst, const double* z);     // the same in the CALLER's units: an equilibrated handle scales on the way (plain handles: the two above)
+int download_caller(fos_solver* h, double* z, const d2* src);
+// step.cpp: the per-handle switches of the outer iteration, read into a new handle's state
+void step_read_switches(StepState& s);
 // cg.cpp: the CG state of a new handle (the operator must exist: cg_blocks reads op.dev.ndef) and its end, the solve, the CG half of fos_set_tuning
 int cg_setup(fos_solver* h);
 void cg_teardown(fos_solver* h);

@@ -1,5 +1,5 @@
 """
-The status check of an EQUILIBRATED handle (fos_create3, equil_passes > 0: csrc/equilibrate.hip eq_status_kernel, csrc/solver.cpp eq_status_check) held to
+The status check of an EQUILIBRATED handle (fos_create3, equil_passes > 0: csrc/equilibrate.hip eq_status_kernel, csrc/step.cpp status_check) held to
 the standard of tests/status_reference.py: an fp64 numpy restatement of what the device evaluates, and the worst-case fp64 allowance of that evaluation
 against the extended-precision reference ON THE CALLER'S A, b, c.  Shared by test_equilibrate_status_cpu.py (no GPU: the restatement within 1 x allowance,
 every decision clear of its threshold) and test_gpu_equilibrate_formats.py (the device within 2 x).
@@ -84,7 +84,7 @@ def reference(A, b, c, z):
 
 
 def _decide(res, eps):
-    """status_decide of csrc/solver.cpp (HSDEStatus.jl:53-63) on fp64 values"""
+    """status_decide of csrc/step.cpp (HSDEStatus.jl:53-63) on fp64 values"""
     with np.errstate(divide="ignore", invalid="ignore"):
         if (res["p"] <= eps * (1 + res["nb"]) and res["d"] <= eps * (1 + res["nc"])
                 and res["g"] <= eps * (1 + abs(res["ctx"] / res["tau"]) + abs(res["bty"] / res["tau"]))):

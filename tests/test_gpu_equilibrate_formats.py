@@ -1,5 +1,5 @@
 """
-The status check of an EQUILIBRATED handle (eq_status_check: the Q_PLAIN_NOTAU sweep of the scaled operator, then eq_status_kernel) on every storage
+The status check of an EQUILIBRATED handle (status_check of csrc/step.cpp: the Q_PLAIN_NOTAU sweep of the scaled operator, then eq_status_kernel) on every storage
 format of the operator, against the extended-precision reference ON THE CALLER'S DATA at twice the worst-case fp64 allowance of
 tests/equilibrate_status.py and nothing else -- the standard test_gpu_status_formats.py sets for a plain handle.
 

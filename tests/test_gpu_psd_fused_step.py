@@ -1,5 +1,5 @@
 """
-The one-launch step (relaxation + PSD(64) projection + final pass: psd64_refine_kernel with PsdFuse::on, step_once in solver.cpp) at small
+The one-launch step (relaxation + PSD(64) projection + final pass: psd64_refine_kernel with PsdFuse::on, step_once in step.cpp) at small
 shapes and on every path it has, each step checked against its own definition (tests/step_identity.py: the iterate before, the affine
 projection and the iterate after, reference cone projection by LAPACK).  fos_psd_fused_steps says whether a step took the fused launch,
 the kernel's per-matrix record (fos_psd_stats) which path each matrix took:
