@@ -1382,6 +1382,13 @@ __device__ __forceinline__ SocOut soc_decide(double t, double nx) {
 }
 
 constexpr double S45 = 0.7071067811865475;
+constexpr double SOC_SUMSQ_MIN = 0x1p-960, SOC_SUMSQ_MAX = 1.7976931348623157e308;      // a sum of squares outside [2^-960, DBL_MAX] is formed again, scaled
+
+__device__ __forceinline__ double soc_wave_max(double v) {                                // (only on the rescaling path; fmax drops a NaN)
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+    return v;
+}
 
 __global__ __launch_bounds__(VEC_THREADS) void cones_soc_kernel(d2* __restrict__ out, const d2* __restrict__ in,
                                                                 const ConeDesc* __restrict__ cones, int ncones, const int32_t* __restrict__ gate) {
@@ -1419,7 +1426,38 @@ __global__ __launch_bounds__(VEC_THREADS) void cones_soc_kernel(d2* __restrict__
         t0 = sg0 * h0.x;
         t1 = sg1 * h0.y;
     }
-    const double nx0 = sqrt(n0), nx1 = sqrt(n1);
+    double nx0 = sqrt(n0), nx1 = sqrt(n1);
+    // The reference's norm is the scaled one: a plain sum of squares is infinite once entries pass ~1e154 and zero once every square underflows.  Out of
+    // that range (one wavefront-uniform comparison on the ordinary path, false for a NaN too) the tail is walked again with every entry scaled by the power
+    // of two that brings the largest to [1, 2) -- exact, and in the same order, so a sum that was in range keeps its bits -- and the norm is scaled back.
+    if (!(fmin(n0, n1) >= SOC_SUMSQ_MIN && fmax(n0, n1) <= SOC_SUMSQ_MAX)) {
+        double m0 = fabs(x20), m1 = fabs(x21);
+        for (int k = head + lane; k < len; k += 64) {
+            const d2 v = x[k];
+            m0 = fmax(m0, fabs(v.x));
+            m1 = fmax(m1, fabs(v.y));
+        }
+        m0 = soc_wave_max(m0);
+        m1 = soc_wave_max(m1);
+        // (an all-zero part keeps its 0, a part with an infinite entry its inf or NaN)
+        const bool f0 = !(n0 >= SOC_SUMSQ_MIN && n0 <= SOC_SUMSQ_MAX) && m0 > 0.0 && m0 <= SOC_SUMSQ_MAX;
+        const bool f1 = !(n1 >= SOC_SUMSQ_MIN && n1 <= SOC_SUMSQ_MAX) && m1 > 0.0 && m1 <= SOC_SUMSQ_MAX;
+        const int e0 = f0 ? ilogb(m0) : 0, e1 = f1 ? ilogb(m1) : 0;
+        double s0 = 0.0, s1 = 0.0;
+        if (f0 || f1) for (int k = head + lane; k < len; k += 64) {     // (a part that is zero throughout, as part 2 of a Feasibility ConeProduct, ends here)
+            const d2 v = x[k];
+            const double a = scalbn(v.x, -e0), b = scalbn(v.y, -e1);
+            s0 += a * a;
+            s1 += b * b;
+        }
+        s0 = wave_sum(s0);
+        s1 = wave_sum(s1);
+        const double a = scalbn(x20, -e0), b = scalbn(x21, -e1);
+        s0 += a * a;
+        s1 += b * b;
+        if (f0) nx0 = scalbn(sqrt(s0), e0);
+        if (f1) nx1 = scalbn(sqrt(s1), e1);
+    }
     const SocOut o0 = soc_decide(t0, nx0), o1 = soc_decide(t1, nx1);
     // tail entries
     for (int k = head + lane; k < len; k += 64) {

@@ -503,16 +503,32 @@ def prox_nonpos(y, x):          # IndNonpositive
     np.minimum(x, 0.0, out=y)
 
 
+# The reference's norm is the scaled one; np.linalg.norm and np.dot form a plain sum of squares, infinite once entries pass ~1e154 and zero once every
+# square underflows.  Outside [2^-960, DBL_MAX] for the sum (only there: no other bit of this restatement changes) the norm is formed again with every entry
+# scaled by the power of two that brings the largest to [1, 2), and scaled back -- as cones_soc_kernel does.
+_SOC_NORM_MIN, _SOC_NORM_MAX = 2.0 ** -480, math.sqrt(1.7976931348623157e308)
+
+
+def _soc_scaled_norm(nx, v):
+    m = float(np.fmax.reduce(np.abs(v))) if len(v) else 0.0        # (fmax drops a NaN, as the kernel's does)
+    if not 0.0 < m <= 1.7976931348623157e308:                      # zero throughout, or an infinite entry: as it was
+        return nx
+    e = math.frexp(m)[1] - 1
+    return math.ldexp(float(np.linalg.norm(np.ldexp(v, -e))), e)
+
+
 def prox_soc(y, x):
     """IndSOC: {(t, v): ||v|| <= t}, t first.  (ProximalOperators indSOC.jl)"""
     nx = float(np.linalg.norm(x[1:]))
+    if not _SOC_NORM_MIN <= nx <= _SOC_NORM_MAX:
+        nx = _soc_scaled_norm(nx, x[1:])
     t = float(x[0])
     if t <= -nx:
         y[:] = 0.0
     elif t >= nx:
         y[:] = x
     else:
-        r = 0.5 * (1.0 + t / nx)
+        r = 0.5 * (1.0 + (t / nx if nx != 0.0 else math.nan))      # (nx = 0 gets here with t = NaN only: IEEE's NaN / 0, not Python's exception)
         y[0] = r * nx
         y[1:] = r * x[1:]
 
@@ -524,7 +540,10 @@ def prox_socrot(y, x):
     """IndRotatedSOC: {(p, q, v): ||v||^2 <= 2pq, p,q >= 0} via a pi/4 rotation onto IndSOC."""
     x1 = _S45 * x[0] + _S45 * x[1]
     x2 = _S45 * x[0] - _S45 * x[1]
-    nx = math.sqrt(x2 * x2 + float(np.dot(x[2:], x[2:])))
+    with np.errstate(over="ignore", under="ignore"):
+        nx = math.sqrt(x2 * x2 + float(np.dot(x[2:], x[2:])))
+    if not _SOC_NORM_MIN <= nx <= _SOC_NORM_MAX:
+        nx = _soc_scaled_norm(nx, np.concatenate(([x2], x[2:])))
     t = x1
     if t <= -nx:
         y[:] = 0.0
@@ -533,7 +552,7 @@ def prox_socrot(y, x):
         y[1] = x2
         y[2:] = x[2:]
     else:
-        r = 0.5 * (1.0 + t / nx)
+        r = 0.5 * (1.0 + (t / nx if nx != 0.0 else math.nan))      # (nx = 0 gets here with t = NaN only: IEEE's NaN / 0, not Python's exception)
         y[0] = r * nx
         y[1] = r * x2
         y[2:] = r * x[2:]
