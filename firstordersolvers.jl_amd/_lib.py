@@ -16,6 +16,9 @@ CONE_CODES = {"Free": 0, "Zero": 1, "NonNeg": 2, "NonPos": 3, "SOC": 4, "SOCRota
               "ExpPrimal": 7, "ExpDual": 8}
 SET_CODES = {"IndFree": 0, "IndBallL2": 1, "IndBallL1": 2, "IndSimplex": 3, "IndHalfspace": 4, "IndHyperslab": 5, "IndPoint": 6, "IndBox": 7}      # FOS_SET_*
 FN_CODES = {"NormL1": 32, "SqrNormL2": 33, "ElasticNet": 34, "Linear": 35, "NormL2": 36, "HuberLoss": 37, "NormLinf": 38}      # FOS_FN_*: further kinds of fos_feas_set_blocks
+# FOS_FN_BLK_QUADRATIC, FOS_SET_BLK_AFFINE, FOS_FN_BLK_LEAST_SQUARES: the dense blocks of fos_feas_set_blocks2, by the class whose block they are (a table of
+# its own: tests pin SET_CODES and FN_CODES to the vector kinds)
+BLK_CODES = {"Quadratic": 48, "IndAffine": 49, "LeastSquares": 50}
 LS_FORM_CODES = {"sparse_factored": 0, "normal": 1}      # FOS_LS_FORM_*
 ALG_GAP, ALG_GAPA, ALG_FISTA, ALG_DYKSTRA = 0, 1, 2, 3
 CG_REFERENCE, CG_FUSED_P, CG_MERGED_SWEEP, CG_MERGED_UPDATE, CG_RESIDENT = 0, 1, 2, 3, 4
@@ -40,6 +43,7 @@ _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
 _i32p = C.POINTER(C.c_int32)
 _h = C.c_void_p
+_dpp = C.POINTER(_dp)
 
 # name -> (restype, argtypes): every symbol include/foship.h declares
 PROTOTYPES = {
@@ -171,6 +175,10 @@ PROTOTYPES = {
     "fos_feas_set_blocks": (C.c_int, [_h, C.c_int32, C.c_int64, _i32p, _i64p, _dp, _dp]),
     "fos_feas_set_stats": (C.c_int, [_h, C.c_int32, _dp]),
     "fos_host_set_project": (C.c_int, [C.c_int32, C.c_int64, _dp, _dp, _dp, _dp, _i32p]),
+    "fos_feas_set_blocks2": (C.c_int, [_h, C.c_int32, C.c_int64, _i32p, _i64p, _dp, _dp, C.c_int64, _i64p, _i64p, _dpp, _i64p, _dpp]),
+    "fos_feas_dense_block_stats": (C.c_int, [_h, C.c_int32, _dp]),
+    "fos_feas_dense_block_get": (C.c_int, [_h, C.c_int32, C.c_int64, _dp, _dp]),
+    "fos_host_dense_block": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp]),
     "fos_feas_set_alg": (C.c_int, [_h, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double]),
     "fos_feas_set_gapp": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, C.c_int64]),
     "fos_feas_gapp_log": (C.c_int, [_h, _dp]),

@@ -4,7 +4,7 @@
 //              src/solvers/{gap,gapa,fista,dykstra}.jl (the steps: the same files the HSDE path follows).
 // The reference takes ANY two ProximalOperators objects (host callbacks); here a set is a device object behind one interface (ProxObject, fos_internal.hpp): the
 // handle owns one per slot and calls its prox.  The objects live in feas_objects.hip (dense IndAffine projector, IndBox, ConeProduct, host callback) and in the
-// back-ends' own files (affine_sparse.hip, affine_dense.hip, affine_sparse_factored.hip, nspace.hip, sets.hip).  This file keeps the algorithms, the status check,
+// back-ends' own files (affine_sparse.hip, affine_dense.hip, affine_sparse_factored.hip, nspace.hip, sets.hip with its dense blocks in dense_blocks.hip).  This file keeps the algorithms, the status check,
 // the wrappers and the ABI.  Every fos_feas_set_* entry does three things: validate, build, feas_install -- the object is built first, so that a refused call
 // leaves the set as it was, and the install frees what the slot held.  Vectors are plain n-vectors in HBM, zero padded to L.  No CPU fallback.
 #include <hip/hip_runtime.h>
@@ -588,6 +588,35 @@ int fos_feas_set_stats(fos_feas_handle h, int32_t which, double* out8) {
     FOS_TRY(feas_object(h, which, out8, FEAS_BLOCKS, "fos_feas_set_stats", "was not defined by fos_feas_set_blocks", &s));
     FOS_HIP(hipSetDevice(h->device));
     return set_blocks_stats(s, h->stream, out8);
+}
+
+// A separable sum that may hold dense Quadratic / LeastSquares / IndAffine blocks (dense_blocks.hip); nmat == 0: fos_feas_set_blocks
+int fos_feas_set_blocks2(fos_feas_handle h, int32_t which, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec,
+                         int64_t nmat, const int64_t* mat_rows, const int64_t* mat_cols, const double* const* mats, const int64_t* block_mat, const double* const* block_vec) {
+    if (!h || which < 1 || which > 2) { set_error("fos_feas_set_blocks2: NULL handle or which not in {1, 2}"); return FOS_EINVAL; }
+    if (nmat < 0) { set_error("fos_feas_set_blocks2: nmat >= 0 is required"); return FOS_EINVAL; }
+    if (nmat > 0 && !block_mat) { set_error("fos_feas_set_blocks2: block_mat is required with matrices"); return FOS_EINVAL; }
+    FOS_HIP(hipSetDevice(h->device));
+    DenseBlockArgs dense;
+    dense.nmat = nmat; dense.mat_rows = mat_rows; dense.mat_cols = mat_cols; dense.mats = mats; dense.block_mat = block_mat; dense.block_vec = block_vec;
+    ProxObject* s = nullptr;
+    FOS_TRY(set_blocks_setup2(h->n, nblocks, kind, len, scal, vec, dense, &s));
+    return feas_install(h, which, s);
+}
+int fos_feas_dense_block_stats(fos_feas_handle h, int32_t which, double* out8) {
+    const ProxObject* s = nullptr;
+    FOS_TRY(feas_object(h, which, out8, FEAS_BLOCKS, "fos_feas_dense_block_stats", "is not a separable sum with dense blocks", &s));
+    if (!set_blocks_dense(s)) { set_error("fos_feas_dense_block_stats: set %d is not a separable sum with dense blocks", (int)which); return FOS_EINVAL; }
+    dense_blocks_stats(set_blocks_dense(s), out8);
+    return FOS_OK;
+}
+int fos_feas_dense_block_get(fos_feas_handle h, int32_t which, int64_t block, double* G, double* d) {
+    const ProxObject* s = nullptr;
+    FOS_TRY(feas_object(h, which, G, FEAS_BLOCKS, "fos_feas_dense_block_get", "is not a separable sum with dense blocks", &s));
+    if (!d || !set_blocks_dense(s)) { set_error("fos_feas_dense_block_get: set %d is not a separable sum with dense blocks (or d is NULL)", (int)which); return FOS_EINVAL; }
+    FOS_HIP(hipSetDevice(h->device));
+    FOS_HIP(hipStreamSynchronize(h->stream));
+    return dense_blocks_get(set_blocks_dense(s), block, G, d);
 }
 
 int fos_feas_set_alg(fos_feas_handle h, int32_t alg, double alpha, double alpha1, double alpha2, double beta) {

@@ -906,6 +906,26 @@ int host_nspace_cg_ls(int64_t m, int64_t n, const int64_t* colptr, const int64_t
 // Separable sums of convex vector sets (sets.hip): norm balls, simplex, halfspace / hyperslab, point, free, scalar box -- contiguous blocks covering 1..n
 int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec, ProxObject** out);
 int set_blocks_stats(const ProxObject* p, hipStream_t stream, double* out8);
+// Dense Quadratic / LeastSquares / IndAffine blocks of a separable sum (dense_blocks.hip): the optional dense part of SetBlocks.  The arrays are those of
+// fos_feas_set_blocks2; block_mat == nullptr: the sum has no dense part (kinds 48..50 are then unknown kinds)
+struct DenseBlockArgs {
+    int64_t nmat = 0;
+    const int64_t *mat_rows = nullptr, *mat_cols = nullptr;
+    const double* const* mats = nullptr;
+    const int64_t* block_mat = nullptr;
+    const double* const* block_vec = nullptr;
+};
+struct DenseBlocks;
+bool dense_block_kind(int kind);
+int dense_blocks_setup(int64_t nblocks, const int32_t* kind, const int64_t* len, const int64_t* start, const double* scal, const DenseBlockArgs& a, DenseBlocks** out);
+void dense_blocks_free(DenseBlocks* p);
+int dense_blocks_launches(const DenseBlocks* p);
+void dense_blocks_prox(const DenseBlocks* p, hipStream_t stream, double* y, const double* x);
+void dense_blocks_stats(const DenseBlocks* p, double* out8);
+int dense_blocks_get(const DenseBlocks* p, int64_t block, double* G, double* d);
+int set_blocks_setup2(int64_t n, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec, const DenseBlockArgs& dense,
+                      ProxObject** out);
+const DenseBlocks* set_blocks_dense(const ProxObject* p);      // nullptr: the sum holds no dense block
 size_t psd_scratch_bytes(int kmax, int ncones);
 size_t psd_basis_doubles(int kmax, int ncones);
 

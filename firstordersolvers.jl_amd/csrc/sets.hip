@@ -27,6 +27,9 @@
 //   one reduction NormL2 and HuberLoss on |x|_2, the shape of IndBallL2
 //   threshold     NormLinf: prox = x - P_{|.|_1 <= lambda}(x) = sign(x) min(|x|, tau) with IndBallL1's tau for the radius lambda
 // A decision is 0 (apply the formula), 1 (y = x, the same bits) or 2 (y = 0).
+//
+// Dense Quadratic / LeastSquares / IndAffine blocks (kinds 48..50, fos_feas_set_blocks2) are the optional dense part of the same object: they take no part in the
+// three classes above, and dense_blocks.hip adds their one or two launches behind the ones of this file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -409,6 +412,8 @@ __global__ __launch_bounds__(SET_THREADS) void sets_grid_apply_kernel(SetBlock b
 // ------------------------------------------------------------------------------------------ host side
 struct SetBlocks : ProxObject, DevOwned {
     SetBlocks() : ProxObject(FEAS_BLOCKS) { what = "fos_feas_set_blocks"; }
+    ~SetBlocks() override { dense_blocks_free(dense); }
+    DenseBlocks* dense = nullptr;               // the dense Quadratic / LeastSquares / IndAffine blocks (dense_blocks.hip): at most two more launches
     int prox(hipStream_t stream, double* y, const double* x) override;
     int64_t n = 0;
     std::vector<SetBlock> blocks;
@@ -505,6 +510,12 @@ double host_combine(const std::vector<double>& lane, int64_t T, int K, int k) {
 }  // namespace
 
 int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec, ProxObject** out) {
+    return set_blocks_setup2(n, nblocks, kind, len, scal, vec, DenseBlockArgs{}, out);
+}
+
+// dense.block_mat != nullptr: blocks of the kinds 48..50 are dense blocks (dense_blocks.hip) and take no part in the three classes below
+int set_blocks_setup2(int64_t n, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec, const DenseBlockArgs& dense,
+                      ProxObject** out) {
     if (!out || n < 1 || nblocks < 1 || !kind || !len || !scal) { set_error("fos_feas_set_blocks: bad argument (nblocks >= 1; kind, len and scal are required)"); return FOS_EINVAL; }
     SetBlocks* p = new SetBlocks();
     p->n = n;
@@ -519,6 +530,13 @@ int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int6
             return fail(FOS_EINVAL);
         }
         SetBlock b;
+        if (dense.block_mat && dense_block_kind(kind[i])) {        // validated, with its matrix, by dense_blocks_setup below
+            b = SetBlock{};
+            b.start = pos; b.len = len[i]; b.kind = kind[i];
+            p->blocks.push_back(b);
+            pos += len[i];
+            continue;
+        }
         const int rc = set_block_make(i + 1, kind[i], pos, len[i], scal + 2 * i, vec, &b);
         if (rc != FOS_OK) return fail(rc);
         any_vec = any_vec || set_reads_vec(b.kind);
@@ -534,6 +552,13 @@ int set_blocks_setup(int64_t n, int64_t nblocks, const int32_t* kind, const int6
     if (pos != n) { set_error("fos_feas_set_blocks: the %lld blocks cover %lld of the %lld entries", (long long)nblocks, (long long)pos, (long long)n); return fail(FOS_EINVAL); }
     p->nwave = (int)wave_ids.size(); p->nwg = (int)wg_ids.size();
     p->launches += (p->nwave > 0) + (p->nwg > 0);
+    if (dense.block_mat) {
+        std::vector<int64_t> start(p->blocks.size());
+        for (size_t i = 0; i < p->blocks.size(); ++i) start[i] = p->blocks[i].start;
+        const int rc = dense_blocks_setup(nblocks, kind, len, start.data(), scal, dense, &p->dense);
+        if (rc != FOS_OK) return fail(rc);
+        p->launches += dense_blocks_launches(p->dense);
+    }
     const hipStream_t sync = nullptr;                        // (this set-up has no stream: blocking copies)
     int rc = p->upload(&p->d_blocks, p->blocks, sync);
     if (rc == FOS_OK && p->nwave > 0) rc = p->upload(&p->d_wave_ids, wave_ids, sync);
@@ -578,6 +603,7 @@ int SetBlocks::prox(hipStream_t stream, double* y, const double* x) {
             hipLaunchKernelGGL(sets_grid_apply_kernel, dim3(grid), dim3(SET_THREADS), 0, stream, b, x, vec, y, (const double*)nullptr);
         }
     }
+    if (p->dense) dense_blocks_prox(p->dense, stream, y, x);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("separable sum of sets: a kernel launch failed: %s", hipGetErrorString(e)); return FOS_EHIP; }
     return FOS_OK;
@@ -602,6 +628,8 @@ int set_blocks_stats(const ProxObject* obj, hipStream_t stream, double* out8) {
     out8[4] = p->launches; out8[5] = mx; out8[6] = THR_CAP; out8[7] = THR_C;
     return FOS_OK;
 }
+
+const DenseBlocks* set_blocks_dense(const ProxObject* obj) { return static_cast<const SetBlocks*>(obj)->dense; }
 
 }  // namespace fos
 

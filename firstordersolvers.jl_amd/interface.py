@@ -1275,15 +1275,52 @@ class SeparableSum:
     """The analogue of ProximalOperators.SlicedSeparableSum over index ranges, in the style of ConeProduct: blocks = [(set, length), ...], contiguous, in
     order, together covering 1..n.  A set is one of IndBallL2, IndBallL1, IndSimplex, IndHalfspace, IndHyperslab, IndPoint, IndFree, an IndBox with
     scalar bounds (cones stay in ConeProduct), or one of the functions NormL1, SqrNormL2, ElasticNet, Linear, NormL2, HuberLoss, NormLinf, whose block
-    is their prox; sets and functions mix freely.  A bare set or function used as S1 or S2 is the one-block case of length n."""
+    is their prox; sets and functions mix freely.  A bare set or function used as S1 or S2 is the one-block case of length n.
+    Dense blocks: a dense Quadratic(Q, q) (form=None), LeastSquares(A, b, lam) (form=None | "normal") or IndAffine(A, b) (form=None | "factored") of order
+    length == p <= 1024 is a block like any other (csrc/dense_blocks.hip: y = G x + d with G built once per distinct matrix).  Blocks built on the SAME ndarray
+    (Quadratic(Q, q_t) for many q_t) share one matrix on the device.  A sum with a dense block is packed by pack2 and set by fos_feas_set_blocks2.
+    Dense blocks are opt-in, SeparableSum(blocks, dense=True): without the keyword the three types are refused as before (form=None keeps every earlier refusal)."""
 
-    def __init__(self, blocks):
+    DENSE_MAX = 1024
+
+    @staticmethod
+    def _dense_block(S, length, k):
+        """the dense block S of `length` entries as (kind code, matrix, vector, lambda), or None when S is no Quadratic / LeastSquares / IndAffine"""
+        if isinstance(S, Quadratic):
+            name, M, v, lam, forms = "Quadratic", S.Q, S.q, 0.0, (None,)
+        elif isinstance(S, LeastSquares):
+            name, M, v, lam, forms = "LeastSquares", S.A, S.b, S.lam, (None, "normal")
+        elif isinstance(S, IndAffine):
+            name, M, v, lam, forms = "IndAffine", S.A, S.b, 0.0, (None, "factored")
+        else:
+            return None
+        if S.form not in forms:
+            raise ValueError("SeparableSum: block %d: %s(form=%r) is no dense block (form must be one of %s)" % (k, name, S.form, ", ".join(repr(f) for f in forms)))
+        if sp.issparse(M) or getattr(S, "sparse", False):
+            raise ValueError("SeparableSum: block %d: a %s block takes a dense matrix, not a sparse one" % (k, name))
+        if M.shape[1] != length:
+            raise ValueError("SeparableSum: block %d: the matrix of %s has %d columns, the block has %d entries" % (k, name, M.shape[1], length))
+        if length > SeparableSum.DENSE_MAX:
+            raise ValueError("SeparableSum: block %d: a dense %s block holds at most %d entries, not %d (use the whole-vector form)" % (k, name, SeparableSum.DENSE_MAX, length))
+        if name == "IndAffine" and M.shape[0] > length:
+            raise ValueError("SeparableSum: block %d: IndAffine needs m <= p, A is %d x %d" % (k, M.shape[0], M.shape[1]))
+        return _lib.BLK_CODES[name], M, v, lam
+
+    def __init__(self, blocks, dense=False):
         self.blocks = []
+        self.dense = False
+        if not dense:                                                   # opt-in: without it a Quadratic / LeastSquares / IndAffine is refused as it always was
+            for k, (S, _) in enumerate(blocks):
+                if isinstance(S, (Quadratic, LeastSquares, IndAffine)):
+                    raise ValueError("SeparableSum: block %d is %s: not one of the vector sets or functions of the device path (a dense one of order <= %d is a "
+                                     "block of SeparableSum(blocks, dense=True))" % (k + 1, type(S).__name__, self.DENSE_MAX))
         for S, length in blocks:
             length = int(length)
             if length < 1:
                 raise ValueError("SeparableSum: block %d has length %d < 1" % (len(self.blocks) + 1, length))
-            if isinstance(S, IndBox):
+            if self._dense_block(S, length, len(self.blocks) + 1) is not None:
+                self.dense = True
+            elif isinstance(S, IndBox):
                 if S.arrays:
                     raise ValueError("SeparableSum: block %d: an IndBox inside a SeparableSum takes scalar bounds" % (len(self.blocks) + 1))
                 if not S.lo <= S.hi:
@@ -1299,13 +1336,32 @@ class SeparableSum:
 
     def pack(self, n):
         """-> (kind[nblocks] int32, len[nblocks] int64, scal[2 nblocks], vec[n]): the arguments of fos_feas_set_blocks"""
+        if self.dense:
+            raise ValueError("SeparableSum: the sum holds a dense block: pack2 returns the arguments of fos_feas_set_blocks2")
+        return self._pack(n)[:4]
+
+    def pack2(self, n):
+        """-> (kind, len, scal, vec, mats, block_mat, block_vec): the arguments of fos_feas_set_blocks2.  mats: the distinct matrices (float64, C order), found by
+        identity of the ndarray plus kind and lambda; block_mat[nblocks] int64: the block's index into mats, -1 for a vector kind; block_vec[nblocks]: q or b, None."""
+        return self._pack(n)
+
+    def _pack(self, n):
         if self.n != n:
             raise ValueError("SeparableSum: the blocks cover %d entries, the problem has n = %d" % (self.n, n))
         kinds, lens = np.zeros(len(self.blocks), dtype=np.int32), np.zeros(len(self.blocks), dtype=np.int64)
         scal, vec = np.zeros(2 * len(self.blocks)), np.zeros(n)
+        mats, seen, block_mat, block_vec = [], {}, np.full(len(self.blocks), -1, dtype=np.int64), [None] * len(self.blocks)
         pos = 0
         for i, (S, length) in enumerate(self.blocks):
-            if isinstance(S, IndBox):
+            dense = self._dense_block(S, length, i + 1)
+            if dense is not None:
+                kinds[i], M, block_vec[i], scal[2 * i] = dense
+                key = (id(M), int(kinds[i]), float(scal[2 * i]))
+                if key not in seen:
+                    seen[key] = len(mats)
+                    mats.append(M)
+                block_mat[i] = seen[key]
+            elif isinstance(S, IndBox):
                 kinds[i], scal[2 * i], scal[2 * i + 1] = _lib.SET_CODES["IndBox"], S.lo, S.hi
             else:
                 kinds[i], (scal[2 * i], scal[2 * i + 1]), v = S._block(length)
@@ -1313,7 +1369,7 @@ class SeparableSum:
                     vec[pos:pos + length] = v
             lens[i] = length
             pos += length
-        return kinds, lens, scal, vec
+        return kinds, lens, scal, vec, mats, block_mat, block_vec
 
 
 PROX_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double))     # fos_prox_fn
@@ -1356,7 +1412,7 @@ class HipFeasibility(_WrapperLogs):
             if isinstance(S, _VectorSet):
                 S = SeparableSum([(S, self.n)])
             if isinstance(S, SeparableSum):
-                packed[which] = S.pack(self.n)
+                packed[which] = S.pack2(self.n) if S.dense else S.pack(self.n)
         self._lib = _lib.load()
         h = C.c_void_p()
         _lib.check(self._lib.fos_feas_create(self.n, device, C.byref(h)))
@@ -1365,7 +1421,7 @@ class HipFeasibility(_WrapperLogs):
         self.callback_error = None
         for which, S in ((1, problem.S1), (2, problem.S2)):
             if which in packed:                                         # before the `prox` test: these never become callbacks
-                self.set_blocks(which, *packed[which])
+                (self.set_blocks2 if len(packed[which]) > 4 else self.set_blocks)(which, *packed[which])
             else:
                 self.set_set(which, S)
 
@@ -1434,6 +1490,41 @@ class HipFeasibility(_WrapperLogs):
         vec = None if vec is None else np.ascontiguousarray(vec, dtype=np.float64)
         _lib.check(self._lib.fos_feas_set_blocks(self._h, which, len(kinds), kinds.ctypes.data_as(C.POINTER(C.c_int32)), lens.ctypes.data_as(C.POINTER(C.c_int64)),
                                                  _lib.dptr(scal), None if vec is None else _lib.dptr(vec)))
+
+    def set_blocks2(self, which, kinds, lens, scal, vec, mats, block_mat, block_vec):
+        """fos_feas_set_blocks2 with raw arrays (SeparableSum.pack2): a separable sum that may hold dense blocks replaces set `which`"""
+        kinds, lens = np.ascontiguousarray(kinds, dtype=np.int32), np.ascontiguousarray(lens, dtype=np.int64)
+        scal = np.ascontiguousarray(scal, dtype=np.float64)
+        vec = None if vec is None else np.ascontiguousarray(vec, dtype=np.float64)
+        mats = [np.ascontiguousarray(M, dtype=np.float64) for M in mats]
+        for M in mats:
+            if M.ndim != 2:
+                raise ValueError("set_blocks2: every matrix must be two-dimensional")
+        rows = np.ascontiguousarray([M.shape[0] for M in mats], dtype=np.int64)
+        cols = np.ascontiguousarray([M.shape[1] for M in mats], dtype=np.int64)
+        block_mat = np.ascontiguousarray(block_mat, dtype=np.int64)
+        vecs = [None if v is None else np.ascontiguousarray(v, dtype=np.float64) for v in block_vec]
+        if block_mat.shape[0] != len(kinds) or len(vecs) != len(kinds):
+            raise ValueError("set_blocks2: block_mat and block_vec have one entry per block")
+        dpp = C.POINTER(C.c_double)
+        mat_ptrs = (dpp * max(len(mats), 1))(*[_lib.dptr(M) for M in mats])
+        vec_ptrs = (dpp * max(len(vecs), 1))(*[C.cast(None, dpp) if v is None else _lib.dptr(v) for v in vecs])
+        i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        _lib.check(self._lib.fos_feas_set_blocks2(self._h, which, len(kinds), kinds.ctypes.data_as(C.POINTER(C.c_int32)), i64(lens), _lib.dptr(scal),
+                                                  None if vec is None else _lib.dptr(vec), len(mats), i64(rows), i64(cols), mat_ptrs, i64(block_mat), vec_ptrs))
+
+    def dense_block_stats(self, which):
+        """the counters of the dense blocks of a separable sum (fos_feas_dense_block_stats)"""
+        o = np.zeros(8)
+        _lib.check(self._lib.fos_feas_dense_block_stats(self._h, which, _lib.dptr(o)))
+        return {"dense_blocks": int(o[0]), "matrices": int(o[1]), "wave_blocks": int(o[2]), "workgroup_blocks": int(o[3]), "launches": int(o[4]),
+                "matrix_bytes": int(o[5]), "largest_order": int(o[6]), "lds_blocks": int(o[7])}
+
+    def dense_block_get(self, which, block, p):
+        """test entry: the G (p x p) and d (p) the device holds for the 0-based block `block` (fos_feas_dense_block_get)"""
+        G, d = np.zeros((p, p)), np.zeros(p)
+        _lib.check(self._lib.fos_feas_dense_block_get(self._h, which, block, _lib.dptr(G), _lib.dptr(d)))
+        return G, d
 
     def set_callback(self, which, S):
         """fos_feas_set_callback: set `which` becomes the object S, its prox(y, x) evaluated on the host"""

@@ -390,6 +390,46 @@ function feas_set_blocks!(handle::Ptr{Cvoid}, which::Integer, n::Integer, blocks
                                                (Ptr{Cvoid}, Int32, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}),
                                                handle, Int32(which), Int64(length(blocks)), kinds, lens, scal, v))
 end
+# Dense blocks of a separable sum (csrc/dense_blocks.hip, fos_feas_set_blocks2): a block of p <= 1024 entries with a dense matrix of its own, y = G x + d
+const FOS_FN_BLK_QUADRATIC = Int32(48)
+const FOS_SET_BLK_AFFINE = Int32(49)
+const FOS_FN_BLK_LEAST_SQUARES = Int32(50)
+import Libdl
+# blocks as for feas_set_blocks!, a dense block being (kind, lambda | 0.0, 0.0, q | b | nothing, length) with block_mat[i] its 1-based index into
+# mats (0 for a vector kind).  mats: Matrix{Float64} as Julia holds them; the library takes ROW-major m x p, so the transposed copy is passed.
+# (The entry takes two arrays of pointers, const double* const*: it is bound through its address, with the argument types of include/foship.h.)
+function feas_set_blocks2!(handle::Ptr{Cvoid}, which::Integer, n::Integer, blocks, mats, block_mat)
+    kinds = Int32[b[1] for b in blocks]
+    lens = Int64[b[5] for b in blocks]
+    scal = Float64[]
+    v = zeros(Float64, n)
+    dense(b) = b[1] == FOS_FN_BLK_QUADRATIC || b[1] == FOS_SET_BLK_AFFINE || b[1] == FOS_FN_BLK_LEAST_SQUARES
+    pos = 0
+    for b in blocks
+        push!(scal, b[2], b[3])
+        (dense(b) || b[4] === nothing) || (v[pos+1:pos+b[5]] .= b[4])
+        pos += b[5]
+    end
+    rowmajor = [Matrix{Float64}(transpose(M)) for M in mats]              # column-major p x m = ROW-major m x p
+    rows = Int64[size(M, 1) for M in mats]
+    cols = Int64[size(M, 2) for M in mats]
+    bvecs = [dense(b) && b[4] !== nothing ? Vector{Float64}(vec(b[4])) : nothing for b in blocks]
+    bmat = Int64[Int64(k) - 1 for k in block_mat]
+    fn = Libdl.dlsym(Libdl.dlopen(libfoship), :fos_feas_set_blocks2)
+    GC.@preserve kinds lens scal v rowmajor rows cols bvecs bmat begin
+        matp = Ptr{Cdouble}[pointer(M) for M in rowmajor]
+        vecp = Ptr{Cdouble}[w === nothing ? Ptr{Cdouble}(C_NULL) : pointer(w) for w in bvecs]
+        check(ccall(fn, Cint,
+                    (Ptr{Cvoid}, Int32, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Ptr{Cdouble}}, Ptr{Int64}, Ptr{Ptr{Cdouble}}),
+                    handle, Int32(which), Int64(length(blocks)), kinds, lens, scal, v, Int64(length(mats)), rows, cols, matp, bmat, vecp))
+    end
+end
+function feas_dense_block_stats(handle::Ptr{Cvoid}, which::Integer)
+    out = zeros(Float64, 8)
+    check(ccall((:fos_feas_dense_block_stats, libfoship), Cint, (Ptr{Cvoid}, Int32, Ptr{Cdouble}), handle, Int32(which), out))
+    return (dense_blocks = Int(out[1]), matrices = Int(out[2]), wave_blocks = Int(out[3]), workgroup_blocks = Int(out[4]), launches = Int(out[5]),
+            matrix_bytes = Int(out[6]), largest_order = Int(out[7]), lds_blocks = Int(out[8]))
+end
 function feas_set_stats(handle::Ptr{Cvoid}, which::Integer)
     out = zeros(Float64, 8)
     check(ccall((:fos_feas_set_stats, libfoship), Cint, (Ptr{Cvoid}, Int32, Ptr{Cdouble}), handle, Int32(which), out))

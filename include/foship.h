@@ -709,6 +709,33 @@ int fos_feas_set_stats(fos_feas_handle h, int32_t which, double* out8);
 /* Test-only host emulation of ONE block's projection (no GPU needed; as fos_host_chol_inverse): the threshold search and the formulas of the kernels,
  * with the partial sums of the class `len` falls in.  vec: centre / normal / point or NULL; passes (may be NULL): threshold passes used. */
 int fos_host_set_project(int32_t kind, int64_t len, const double* scal2, const double* vec, const double* x, double* y, int32_t* passes);
+/* Dense blocks of a separable sum: a block of p <= 1024 entries with a dense matrix of its own, mixed freely with the kinds above (numbered from 48; 8..31, 39..47 and
+ * 51..63 are unknown kinds).  The prox (step 1) of all three is one device formula, y = G x + d, with a symmetric apply matrix G of order p built once per DISTINCT
+ * matrix on the host in long double and rounded to fp64 once (csrc/dense_blocks.hip); the device keeps the packed lower triangle of G.  Blocks name their matrix by
+ * index: many blocks may name one matrix with different q or b, G is then built and stored once and a workgroup loads it once for a run of blocks. */
+#define FOS_FN_BLK_QUADRATIC     48  /* Quadratic(Q, q), Q p x p positive semidefinite, only the lower triangle read   y = (I + Q)^-1 (x - q)                    */
+#define FOS_SET_BLK_AFFINE       49  /* IndAffine(A, b), A m x p, 1 <= m <= p, full row rank                           y = x - A^+ (A x - b)                     */
+#define FOS_FN_BLK_LEAST_SQUARES 50  /* LeastSquares(A, b, lambda), A m x p, any m >= 1, lambda > 0, any rank          y = (I + lambda A'A)^-1 (x + lambda A'b)  */
+/* fos_feas_set_blocks with dense blocks.  mats[k]: ROW-major mat_rows[k] x mat_cols[k] (Quadratic: square, lower triangle read).
+ * block_mat[i]: index into mats for a dense kind, -1 otherwise.
+ * block_vec[i]: q (len[i] entries) or b (mat_rows entries) of a dense block, NULL = zeros; ignored for the vector kinds, which keep using vec.
+ * scal[2 i] = lambda for LeastSquares blocks.  nmat == 0 behaves exactly as fos_feas_set_blocks (block_mat and block_vec may then be NULL).
+ * FOS_EINVAL, the message naming the 1-based block ("set block k ..."), the set `which` held before staying usable: a non-finite entry; a failed pivot of I + Q
+ * (with its column); an IndAffine block whose scaled A A' fails its pivot test ("A needs full row rank") or has m > p; a matrix whose order or column count differs
+ * from the block length; a block longer than 1024 (the whole-vector forms above take those); lambda not finite or not positive; a matrix index out of range; a dense
+ * kind without a matrix or a vector kind with one.  A prox adds at most two launches to those of the vector kinds (blocks of order <= 64: one launch, several blocks
+ * to a wavefront up to order 32; blocks of order 65..1024: one launch, a 256-thread workgroup per run of up to 8 blocks of one matrix); no atomics, one order of
+ * additions: the same bits from run to run and whether a matrix is shared or not.  fos_feas_set_stats counts dense blocks in `blocks` and `launches` only. */
+int fos_feas_set_blocks2(fos_feas_handle h, int32_t which, int64_t nblocks, const int32_t* kind, const int64_t* len, const double* scal, const double* vec,
+                         int64_t nmat, const int64_t* mat_rows, const int64_t* mat_cols, const double* const* mats, const int64_t* block_mat, const double* const* block_vec);
+/* out8: dense blocks, distinct matrices, wavefront-class blocks, workgroup-class blocks, launches the dense part adds, bytes of G kept, largest order,
+ * blocks served from a matrix held in LDS.  FOS_EINVAL unless `which` is a separable sum that holds a dense block. */
+int fos_feas_dense_block_stats(fos_feas_handle h, int32_t which, double* out8);
+/* test-only: the G (p x p, expanded to the full square) and d the device holds for block `block` (0-based) */
+int fos_feas_dense_block_get(fos_feas_handle h, int32_t which, int64_t block, double* G, double* d);
+/* test-only host emulation, no GPU needed (as fos_host_set_project): the same set-up code, then y = G x + d with the kernels' summation order of the class p
+ * falls in (one order for every class).  M: m x p ROW-major (Quadratic: m = p); v: q or b (NULL: zeros).  G_out (p x p) / d_out (p) may be NULL. */
+int fos_host_dense_block(int32_t kind, int64_t m, int64_t p, const double* M, const double* v, double lambda, const double* x, double* y, double* G_out, double* d_out);
 int fos_feas_set_alg(fos_feas_handle h, int32_t alg, double alpha, double alpha1, double alpha2, double beta);
 /* GAPP ("projected GAP", src/solvers/gapproj.jl:5-81; test/testfeasibility.jl:36): GAP whose every iproj-th iteration searches 21 step
  * lengths 2^k along P_S1(P_S2(P_S1 x)) - P_S1 x.  out23 = the 21 test norms, alpha_best, iteration of the last search. */
