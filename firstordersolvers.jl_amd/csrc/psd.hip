@@ -812,7 +812,8 @@ __global__ __launch_bounds__(64) void psd64_wave_kernel(d2* __restrict__ out, co
 // (three products per iteration; the second term of N_ij is what pulls V back to orthonormal columns), until ||E||_F <= 1e-6; then
 // ONE Newton-Schulz step V <- V (I + (I - V'V) / 2) -- the part of the orthogonality defect of a pair with a tiny gap that is below
 // the rounding level of N (defect x gap < eps ||M||) is invisible to the iteration, and a defect of 1e-10 would be an error of 1e-10
-// in the projection -- and P = V max(diag d, 0) V'.  3 it + 3 products.
+// in the projection; the step is repeated while that defect is above 3e-8, which only a cluster of eigenvalues brings about -- and
+// P = V max(diag d, 0) V'.  3 it + 3 products.
 // START: the solver's iterates move smoothly, so the basis is EXTRAPOLATED from the last two, V0 = 2 V_prev - V_pp (the two
 // ping-pong buffers): in C4's steady state the first ||E||_F drops from 2e-2 to 1e-3 (outer iteration 200) ... 1e-4 (350), and
 // two or three iterations do where the plain start needs four.  If the extrapolated start does not converge (a jump of the
@@ -834,6 +835,7 @@ constexpr int RF_MAX_IT = 7;
 constexpr int RF_MAX_ROT = 12;
 constexpr double RF_THETA = 0.2;
 constexpr double RF_ACCEPT2 = 1e-12;          // ||E||_F <= 1e-6 at the last update: error of the projection < 1e-13 ||M|| (measured on the oracle)
+constexpr double RF_NS_AGAIN2 = 1e-15;        // ||I - V'V||_F^2 in front of a Newton-Schulz step above which another one follows (3/4 x 1e-15 is rounding level)
 constexpr double RF_NOISE = 16.0 * 2.220446049250313e-16;
 __host__ inline size_t psd64r_lds_bytes(int wps) {
     // one workgroup per CU: a third array for the rotation path (S = N + diag d); two per CU: that path borrows M's array and unpacks M again
@@ -1282,27 +1284,44 @@ __global__ __launch_bounds__(256, WPS) void psd64_refine_kernel(d2* __restrict__
     if (phase_limit == 16) return;
     PSD_STAMP(14);
 
-    // ---- one Newton-Schulz step: V <- V (I + (I - V'V) / 2)
+    // ---- Newton-Schulz: V <- V (I + (I - V'V) / 2), ONE step as a rule.  A step takes a defect ||I - V'V||_F = delta to 3/4 delta^2, and delta is not
+    // bounded by the last ||E||_F: inside a cluster of eigenvalues (gaps of 1e-9 ||M||) the quotients N_ij / (d_j - d_i) are not skew at the 1e-5 level, so
+    // a matrix accepted at ||E||_F <= 1e-6 was seen with delta = 2e-5, which one step leaves at 3e-10 -- an error of that size in the projection.  The
+    // defect of the step just taken is at hand (the product's own result), so the step is repeated while delta > RF_NS_AGAIN (at most twice more);
+    // delta <= 3e-8 leaves 7e-16.  In the steady state of a solve delta is about ||E||_F^2 <= 1e-12 and nothing changes, not a bit.
     {
-        v4d g[4];
+#pragma nounroll
+        for (int ns = 0; ns < 3; ++ns) {
+            v4d g[4];
 #pragma unroll
-        for (int ib = 0; ib < 4; ++ib) g[ib] = v4d{0.0, 0.0, 0.0, 0.0};
-        rf_gemm<16 * LD, 4, WPS == 2 ? 2 : 4>(g, Vl + lk + lr * LD, Vb);
+            for (int ib = 0; ib < 4; ++ib) g[ib] = v4d{0.0, 0.0, 0.0, 0.0};
+            rf_gemm<16 * LD, 4, WPS == 2 ? 2 : 4>(g, Vl + lk + lr * LD, Vb);
+            double def2 = 0.0;
 #pragma unroll
-        for (int ib = 0; ib < 4; ++ib)
+            for (int ib = 0; ib < 4; ++ib)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) g[ib][r] = ((16 * ib + 4 * r + lk == jcol) ? 0.5 : 0.0) - 0.5 * g[ib][r];
-        PSD_STAMP(15);
-        v4d vn[4];
+                for (int r = 0; r < 4; ++r) {
+                    g[ib][r] = ((16 * ib + 4 * r + lk == jcol) ? 0.5 : 0.0) - 0.5 * g[ib][r];
+                    def2 += g[ib][r] * g[ib][r];
+                }
+            def2 = wave_sum(def2);
+            if (lane == 0) red[12 + w] = def2;
+            PSD_STAMP(15);
+            v4d vn[4];
 #pragma unroll
-        for (int ib = 0; ib < 4; ++ib) vn[ib] = Vb[ib];
-        rf_gemm<16, 4 * LD, WPS == 2 ? 2 : 4>(vn, Vl + lr + lk * LD, g);
-        __syncthreads();
+            for (int ib = 0; ib < 4; ++ib) vn[ib] = Vb[ib];
+            rf_gemm<16, 4 * LD, WPS == 2 ? 2 : 4>(vn, Vl + lr + lk * LD, g);
+            __syncthreads();
+            const double delta2 = 4.0 * ((red[12] + red[13]) + (red[14] + red[15]));
 #pragma unroll
-        for (int ib = 0; ib < 4; ++ib)
+            for (int ib = 0; ib < 4; ++ib) {
+                Vb[ib] = vn[ib];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) Vl[16 * ib + 4 * r + lk + jcol * LD] = vn[ib][r];
-        __syncthreads();
+                for (int r = 0; r < 4; ++r) Vl[16 * ib + 4 * r + lk + jcol * LD] = vn[ib][r];
+            }
+            __syncthreads();
+            if (!(delta2 > RF_NS_AGAIN2)) break;
+        }
     }
     if (phase_limit == 17) return;
     PSD_STAMP(16);

@@ -315,8 +315,9 @@ def psd64_kernel(request, monkeypatch):
 
 
 def test_psd_known_answer_and_sizes(pkg, dev_ops, psd64_kernel):
-    """test/testPSD.jl:14-19 known answer through the GPU PSD kernel; random orders 1..120 (LDS path) and 150
-    (global-scratch path); degenerate spectra (+-lambda pairs, zero matrix, rank one)."""
+    """test/testPSD.jl:14-19 known answer through the GPU PSD kernel; random orders 1..64 (the Jacobi kernels of psd.hip) and 96, 120,
+    150 (the sign iteration of psd_sign.hip, which takes every order above 64); degenerate spectra (+-lambda pairs, zero matrix, rank one).
+    Matrix by matrix against extended-precision references: test_gpu_psd_edges.py."""
     r2 = math.sqrt(2)
     K1 = [("SDP", 3)]
     d, _, _ = dev_ops(sp.csc_matrix(np.eye(3, 2)), None, None, K1, [("Free", 2)])
