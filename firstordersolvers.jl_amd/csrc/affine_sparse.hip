@@ -137,13 +137,6 @@ __global__ __launch_bounds__(SA_THREADS) void sa_start_kernel(const double* __re
     }
 }
 
-int lanes_per_row(int64_t nnz, int64_t rows) {
-    const double avg = rows > 0 ? (double)nnz / (double)rows : 1.0;
-    int l = 1;
-    while (l < 64 && 2 * l <= avg) l <<= 1;                      // the largest power of two not above the average row length
-    return l;
-}
-
 }  // namespace
 
 struct SparseAffine : ProxObject, DevOwned {
@@ -152,8 +145,7 @@ struct SparseAffine : ProxObject, DevOwned {
     int prox(hipStream_t stream, double* y, const double* x) override;
     void reset(hipStream_t stream) override { (void)hipMemsetAsync(lam, 0, sizeof(double) * (size_t)m, stream); }      // a new solve starts from lambda = 0
     int64_t m = 0, n = 0, nnz = 0;
-    int32_t *rp = nullptr, *ci = nullptr, *trp = nullptr, *tci = nullptr;
-    double *va = nullptr, *tva = nullptr;
+    DevCsr A, At;
     double *b = nullptr, *lam = nullptr, *r = nullptr, *p = nullptr, *q = nullptr, *part = nullptr;
     SaState *st = nullptr, *st_host = nullptr;
     int lpr_a = 1, lpr_t = 1, grid_a = 1, grid_t = 1, grid_m = 1;
@@ -166,78 +158,45 @@ struct SparseAffine : ProxObject, DevOwned {
 namespace {
 
 template <int MODE>
-void sa_launch_rows(hipStream_t s, int lpr, int grid, int64_t nrows, const int32_t* rp, const int32_t* ci, const double* va, const double* in, double* out,
-                    const double* aux, double* lam, double* r, double* p, double* part, int nparts_prev, SaState* st, int k, int gated) {
-#define SA_CASE(L) case L: hipLaunchKernelGGL((sa_rows_kernel<L, MODE>), dim3(grid), dim3(SA_THREADS), 0, s, nrows, rp, ci, va, in, out, aux, lam, r, p, part, nparts_prev, st, k, gated); break;
+void sa_launch_rows(hipStream_t s, int lpr, int grid, int64_t nrows, const DevCsr& M, const double* in, double* out, const double* aux, double* lam, double* r,
+                    double* p, double* part, int nparts_prev, SaState* st, int k, int gated) {
+#define SA_CASE(L) case L: hipLaunchKernelGGL((sa_rows_kernel<L, MODE>), dim3(grid), dim3(SA_THREADS), 0, s, nrows, M.rp, M.ci, M.va, in, out, aux, lam, r, p, part, nparts_prev, st, k, gated); break;
     switch (lpr) { SA_CASE(1) SA_CASE(2) SA_CASE(4) SA_CASE(8) SA_CASE(16) SA_CASE(32) default: SA_CASE(64) }
 #undef SA_CASE
 }
 
 }  // namespace
 
-// The host half of every sparse IndAffine set-up (this file and affine_sparse_factored.hip).  A: m x n CSC, 1-based (Julia SparseMatrixCSC{Float64,Int64}); b[m]:
-// validated, the rows of [A | b] scaled to unit norm, A and A' as two CSR matrices.  `what` names the caller in the messages.
-int sparse_affine_rows(const char* what, int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, SparseRows* out,
-                       bool zero_rows) {
-    if (m < 1 || n < 1 || !colptr || !rowval || !nzval || !b) { set_error("%s: bad argument", what); return FOS_EINVAL; }
-    if (colptr[0] != 1) { set_error("%s: colptr must be 1-based (colptr[0] = %lld)", what, (long long)colptr[0]); return FOS_EINVAL; }
-    const int64_t nnz = colptr[n] - 1;
-    if (nnz < 1 || nnz > 2000000000LL) { set_error("%s: %lld stored entries (1 .. 2e9 supported)", what, (long long)nnz); return FOS_EINVAL; }
+// the host half of every sparse IndAffine set-up (ScaledRows: fos_internal.hpp)
+int sparse_affine_rows(const char* what, int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, bool ascending,
+                       bool zero_rows, ScaledRows* out) {
+    if (!b) { set_error("%s: bad argument", what); return FOS_EINVAL; }
+    FOS_TRY(csc_check(what, m, n, colptr, rowval, nzval, CscRules{true, ascending, CSC_BOUND_BOTH, "A"}));
     std::vector<double> rn2((size_t)m, 0.0);
-    std::vector<int32_t> rcount((size_t)m + 1, 0);
-    for (int64_t j = 0; j < n; ++j) {
-        if (colptr[j + 1] < colptr[j]) { set_error("%s: colptr decreases at column %lld", what, (long long)j + 1); return FOS_EINVAL; }
-        for (int64_t e = colptr[j] - 1; e < colptr[j + 1] - 1; ++e) {
-            const int64_t i = rowval[e] - 1;
-            const double v = nzval[e];
-            if (i < 0 || i >= m) { set_error("%s: row index %lld outside 1..%lld", what, (long long)rowval[e], (long long)m); return FOS_EINVAL; }
-            if (!(v == v) || std::fabs(v) > 1e300) { set_error("%s: A has non-finite entries", what); return FOS_EINVAL; }
-            rn2[(size_t)i] += v * v;
-            rcount[(size_t)i + 1]++;
-        }
-    }
-    std::vector<double>& scale = out->scale;
-    scale.resize((size_t)m);
-    std::vector<double>& bs = out->bs;
-    bs.resize((size_t)m);
+    for (int64_t e = 0; e < colptr[n] - 1; ++e) rn2[(size_t)(rowval[e] - 1)] += nzval[e] * nzval[e];
+    std::vector<double>&scale = out->scale, &bs = out->bs;
+    scale.resize((size_t)m); bs.resize((size_t)m);
     for (int64_t i = 0; i < m; ++i) {
         if (!(rn2[(size_t)i] > 0.0) && !zero_rows) { set_error("%s: row %lld of A is zero (A must have full row rank)", what, (long long)i + 1); return FOS_EINVAL; }
-        if (!(b[i] == b[i]) || std::fabs(b[i]) > 1e300) { set_error("%s: b has non-finite entries", what); return FOS_EINVAL; }
+        if (!csc_finite(b[i])) { set_error("%s: b has non-finite entries", what); return FOS_EINVAL; }
         scale[(size_t)i] = rn2[(size_t)i] > 0.0 ? 1.0 / std::sqrt(rn2[(size_t)i]) : 1.0;
         bs[(size_t)i] = b[i] * scale[(size_t)i];
     }
-    // A' in CSR = the CSC arrays as they are (0-based, scaled); A in CSR by a counting pass (columns ascending inside a row)
-    std::vector<int32_t>&trp = out->trp, &tci = out->tci, &rp = out->rp, &ci = out->ci;
-    std::vector<double>&tva = out->tva, &va = out->va;
-    trp.resize((size_t)n + 1); tci.resize((size_t)nnz); rp.assign((size_t)m + 1, 0); ci.resize((size_t)nnz);
-    tva.resize((size_t)nnz); va.resize((size_t)nnz);
-    for (int64_t i = 0; i < m; ++i) rp[(size_t)i + 1] = rp[(size_t)i] + rcount[(size_t)i + 1];
-    std::vector<int32_t> fill(rp.begin(), rp.end() - 1);
-    for (int64_t j = 0; j <= n; ++j) trp[(size_t)j] = (int32_t)(colptr[j] - 1);
-    for (int64_t j = 0; j < n; ++j)
-        for (int64_t e = colptr[j] - 1; e < colptr[j + 1] - 1; ++e) {
-            const int64_t i = rowval[e] - 1;
-            const double v = nzval[e] * scale[(size_t)i];
-            tci[(size_t)e] = (int32_t)i; tva[(size_t)e] = v;
-            const int32_t pos = fill[(size_t)i]++;
-            ci[(size_t)pos] = (int32_t)j; va[(size_t)pos] = v;
-        }
-    out->m = m; out->n = n; out->nnz = nnz;
+    csc_to_csr_pair(m, n, colptr, rowval, nzval, scale.data(), &out->A, &out->At);
     return FOS_OK;
 }
 
 // A: m x n CSC, 1-based; b[m].  Rows of [A | b] scaled to unit norm; A and A' to CSR (sparse_affine_rows); upload.
 int sparse_affine_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int cus, ProxObject** out) {
-    SparseRows R;
-    FOS_TRY(sparse_affine_rows("IndAffine (sparse)", m, n, colptr, rowval, nzval, b, &R));
-    const int64_t nnz = R.nnz;
+    ScaledRows R;
+    FOS_TRY(sparse_affine_rows("IndAffine (sparse)", m, n, colptr, rowval, nzval, b, false, false, &R));
+    const int64_t nnz = (int64_t)R.A.ci.size();
     SparseAffine* a = new SparseAffine();
     a->m = m; a->n = n; a->nnz = nnz;
     int rc = FOS_OK;
     auto fail = [&](int code) { delete a; return code; };
     const hipStream_t sync = nullptr;                        // (this set-up has no stream: blocking copies)
-    if ((rc = a->upload(&a->rp, R.rp, sync)) != FOS_OK || (rc = a->upload(&a->ci, R.ci, sync)) != FOS_OK || (rc = a->upload(&a->va, R.va, sync)) != FOS_OK ||
-        (rc = a->upload(&a->trp, R.trp, sync)) != FOS_OK || (rc = a->upload(&a->tci, R.tci, sync)) != FOS_OK || (rc = a->upload(&a->tva, R.tva, sync)) != FOS_OK ||
+    if ((rc = a->A.upload(*a, R.A, sync)) != FOS_OK || (rc = a->At.upload(*a, R.At, sync)) != FOS_OK ||
         (rc = a->upload(&a->b, R.bs, sync)) != FOS_OK || (rc = a->zeros(&a->lam, (size_t)m, sync)) != FOS_OK || (rc = a->zeros(&a->r, (size_t)m, sync)) != FOS_OK ||
         (rc = a->zeros(&a->p, (size_t)m, sync)) != FOS_OK || (rc = a->zeros(&a->q, (size_t)n, sync)) != FOS_OK || (rc = a->zeros(&a->part, 3 * SA_PARTS_MAX, sync)) != FOS_OK ||
         (rc = a->zeros(&a->st, 1, sync)) != FOS_OK)
@@ -262,8 +221,8 @@ int SparseAffine::prox(hipStream_t stream, double* y, const double* x) {
     a->calls++;
     for (;; ++round) {
         // y = x - A' lambda; r = p = A y - b; the scalars of the (re)start
-        sa_launch_rows<SA_Y>(stream, a->lpr_t, a->grid_t, a->n, a->trp, a->tci, a->tva, a->lam, y, x, nullptr, nullptr, nullptr, a->part, 0, a->st, 0, 0);
-        sa_launch_rows<SA_R>(stream, a->lpr_a, a->grid_a, a->m, a->rp, a->ci, a->va, y, nullptr, a->b, nullptr, a->r, a->p, a->part, 0, a->st, 0, 0);
+        sa_launch_rows<SA_Y>(stream, a->lpr_t, a->grid_t, a->n, a->At, a->lam, y, x, nullptr, nullptr, nullptr, a->part, 0, a->st, 0, 0);
+        sa_launch_rows<SA_R>(stream, a->lpr_a, a->grid_a, a->m, a->A, y, nullptr, a->b, nullptr, a->r, a->p, a->part, 0, a->st, 0, 0);
         hipLaunchKernelGGL(sa_start_kernel, dim3(1), dim3(SA_THREADS), 0, stream, (const double*)a->part, a->grid_a, a->st, TOL_FACTOR, maxit);
         FOS_HIP(hipMemcpyAsync(a->st_host, a->st, sizeof(SaState), hipMemcpyDeviceToHost, stream));
         FOS_HIP(hipStreamSynchronize(stream));
@@ -279,8 +238,8 @@ int SparseAffine::prox(hipStream_t stream, double* y, const double* x) {
         int k = 0;
         for (;;) {
             for (int q = 0; q < BATCH; ++q, ++k) {
-                sa_launch_rows<SA_Q>(stream, a->lpr_t, a->grid_t, a->n, a->trp, a->tci, a->tva, a->p, a->q, nullptr, nullptr, nullptr, nullptr, a->part, 0, a->st, k, 1);
-                sa_launch_rows<SA_UPD>(stream, a->lpr_a, a->grid_a, a->m, a->rp, a->ci, a->va, a->q, nullptr, nullptr, a->lam, a->r, a->p, a->part, a->grid_t, a->st, k, 1);
+                sa_launch_rows<SA_Q>(stream, a->lpr_t, a->grid_t, a->n, a->At, a->p, a->q, nullptr, nullptr, nullptr, nullptr, a->part, 0, a->st, k, 1);
+                sa_launch_rows<SA_UPD>(stream, a->lpr_a, a->grid_a, a->m, a->A, a->q, nullptr, nullptr, a->lam, a->r, a->p, a->part, a->grid_t, a->st, k, 1);
                 hipLaunchKernelGGL(sa_close_kernel, dim3(a->grid_m), dim3(SA_THREADS), 0, stream, a->m, (const double*)a->r, a->p, (const double*)a->part, a->grid_a, a->st, k);
             }
             FOS_HIP(hipMemcpyAsync(a->st_host, a->st, sizeof(SaState), hipMemcpyDeviceToHost, stream));

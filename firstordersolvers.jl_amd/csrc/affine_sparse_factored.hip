@@ -24,7 +24,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <string>
 #include <vector>
 
 namespace fos {
@@ -32,7 +31,6 @@ namespace fos {
 namespace {
 
 constexpr int SF_T = 256;                     // threads per workgroup: four work items
-constexpr int SF_LANE_ENTRIES = 4;            // packed rows: entries per lane of the packet's longest row, while g < 64
 constexpr double SF_BAR = 1e-7;               // the inverse of A A' is accepted at this probe residual (as affine_dense.hip)
 
 // PASS 1 (the CSR of A):  s = A[row, segment] in  ->  out[row] = s - aux[row]          (in = x or y, aux = b, out = r)
@@ -101,40 +99,6 @@ __global__ __launch_bounds__(SF_T) void sf_shift_diag_kernel(int64_t m, int64_t 
     for (int64_t i = blockIdx.x * (int64_t)SF_T + threadIdx.x; i < m; i += (int64_t)gridDim.x * SF_T) G[i + i * L] += scale[i] * scale[i] * inv_lambda;
 }
 
-int sf_lanes(int len) {                                  // the fewest lanes (a power of two, at most 64) that leave a lane at most SF_LANE_ENTRIES entries of a row
-    int g = 1;
-    while (g < 64 && g * SF_LANE_ENTRIES < len) g <<= 1;
-    return g;
-}
-
-}  // namespace
-
-// the work items of one pass, from the row pointers and SEG alone (SfItem, SfPass: fos_internal.hpp; nspace_cg.hip plans its passes with it too)
-void sf_plan_pass(int64_t nrows, const int32_t* rp, int seg, SfPass* P) {
-    P->items.clear(); P->frow.clear(); P->fptr.assign(1, 0); P->nparts = 0;
-    auto len = [&](int64_t r) { return rp[r + 1] - rp[r]; };
-    int64_t r = 0;
-    while (r < nrows) {
-        const int l0 = len(r);
-        if (l0 > seg) {
-            for (int e = rp[r]; e < rp[r + 1]; e += seg) P->items.push_back(SfItem{(int32_t)r, e, std::min(seg, rp[r + 1] - e), (int32_t)P->nparts++});
-            P->frow.push_back((int32_t)r); P->fptr.push_back((int32_t)P->nparts);
-            ++r;
-            continue;
-        }
-        int g = sf_lanes(l0), cnt = 1;
-        while (r + cnt < nrows && len(r + cnt) <= seg) {
-            const int g2 = std::max(g, sf_lanes(len(r + cnt)));
-            if ((cnt + 1) * g2 > 64) break;
-            g = g2; ++cnt;
-        }
-        P->items.push_back(SfItem{(int32_t)r, cnt, -g, -1});
-        r += cnt;
-    }
-}
-
-namespace {
-
 // FOS_SF_SEG (read at every set-up: per handle): a multiple of 64 from 64 up to the default
 int sf_segment_length(int* seg) {
     *seg = SF_SEG_DEFAULT;
@@ -150,21 +114,19 @@ int sf_segment_length(int* seg) {
     return FOS_OK;
 }
 
-// what both the device set-up and the host emulation refuse, and the scaled rows
+// what both the device set-up and the host emulation refuse; the scaled rows and the plans of the two passes (0: the CSR of A, 1: the CSR of A')
 const char* sf_name(double lambda) { return lambda > 0.0 ? "LeastSquares (sparse, factored)" : "IndAffine (sparse, factored)"; }
-int sf_rows(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int refine, SparseRows* R) {
+struct SfHost { ScaledRows R; SfPass P[2]; int seg = 0; };
+int sf_rows(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int refine, SfHost* H) {
     const char* what = sf_name(lambda);
     if (!(lambda >= 0.0) || lambda > 1e300) { set_error("LeastSquares: lambda must be finite and > 0"); return FOS_EINVAL; }
     if (m < 1 || n < 1 || m > n) { set_error("%s: bad argument (1 <= m <= n)", what); return FOS_EINVAL; }
     if (m > 46000) { set_error("%s: the inverse of A A' has order m = %lld: supported up to m = 46000", what, (long long)m); return FOS_EUNSUPPORTED; }
     if (refine < 0 || refine > 2) { set_error("%s: refine = %d (0, 1 or 2 refinement steps per projection)", what, refine); return FOS_EINVAL; }
-    FOS_TRY(sparse_affine_rows(what, m, n, colptr, rowval, nzval, b, R, lambda > 0.0));
-    for (int64_t j = 0; j < n; ++j)                                                   // (sf_gram_kernel adds a column's entries side by side)
-        for (int32_t e = R->trp[(size_t)j] + 1; e < R->trp[(size_t)j + 1]; ++e)
-            if (R->tci[(size_t)e] <= R->tci[(size_t)e - 1]) {
-                set_error("%s: the row indices of column %lld are not strictly ascending (duplicated or unsorted entries)", what, (long long)j + 1);
-                return FOS_EINVAL;
-            }
+    FOS_TRY(sparse_affine_rows(what, m, n, colptr, rowval, nzval, b, true, lambda > 0.0, &H->R));      // (ascending: sf_gram_kernel adds a column's entries side by side)
+    FOS_TRY(sf_segment_length(&H->seg));
+    sf_plan_pass(m, H->R.A.rp.data(), H->seg, &H->P[0]);
+    sf_plan_pass(n, H->R.At.rp.data(), H->seg, &H->P[1]);
     return FOS_OK;
 }
 
@@ -175,15 +137,10 @@ struct SparseFactored : ProxObject, DevOwned {
     int prox(hipStream_t stream, double* y, const double* x) override;
     int64_t m = 0, n = 0, nnz = 0, L = 0;
     int refine = 0, seg = 0;
-    int32_t *rp = nullptr, *ci = nullptr, *trp = nullptr, *tci = nullptr;
-    double *va = nullptr, *tva = nullptr;
+    DevCsr A, At;
+    DevPass pass[2];                                                    // 0: r = A v - b;  1: y = x - A'd
     double *G = nullptr, *X = nullptr, *b = nullptr;                    // G, X: L x L column-major; b: scaled
     double *r = nullptr, *d = nullptr, *e = nullptr;                    // m-space vectors (L)
-    SfItem *items1 = nullptr, *items2 = nullptr;
-    int32_t *frow1 = nullptr, *fptr1 = nullptr, *frow2 = nullptr, *fptr2 = nullptr;
-    double *part1 = nullptr, *part2 = nullptr;
-    int nitems1 = 0, nitems2 = 0, nfold1 = 0, nfold2 = 0;
-    int64_t nparts1 = 0, nparts2 = 0;
     DenseInv inv;
 };
 
@@ -195,32 +152,22 @@ int sparse_factored_setup(int64_t m, int64_t n, const int64_t* colptr, const int
         return FOS_EINVAL;
     }
     if (lambda > 0.0) refine = 0;
-    SparseRows R;
-    FOS_TRY(sf_rows(m, n, colptr, rowval, nzval, b, lambda, refine, &R));
-    int seg = 0;
-    FOS_TRY(sf_segment_length(&seg));
-    SfPass P1, P2;
-    sf_plan_pass(m, R.rp.data(), seg, &P1);
-    sf_plan_pass(n, R.trp.data(), seg, &P2);
+    SfHost H;
+    FOS_TRY(sf_rows(m, n, colptr, rowval, nzval, b, lambda, refine, &H));
+    const ScaledRows& R = H.R;
     SparseFactored* a = new SparseFactored();
     a->what = sf_name(lambda);
-    a->m = m; a->n = n; a->nnz = R.nnz; a->L = (m + 63) / 64 * 64; a->refine = refine; a->seg = seg;
-    a->nitems1 = (int)P1.items.size(); a->nitems2 = (int)P2.items.size(); a->nfold1 = (int)P1.frow.size(); a->nfold2 = (int)P2.frow.size();
-    a->nparts1 = P1.nparts; a->nparts2 = P2.nparts;
+    a->m = m; a->n = n; a->nnz = (int64_t)R.A.ci.size(); a->L = (m + 63) / 64 * 64; a->refine = refine; a->seg = H.seg;
     const size_t L = (size_t)a->L, L2 = L * L;
     auto fail = [&](int code) { (void)hipStreamSynchronize(stream); delete a; return code; };
     int rc = FOS_OK;
-    if ((rc = a->upload(&a->rp, R.rp, stream)) != FOS_OK || (rc = a->upload(&a->ci, R.ci, stream)) != FOS_OK || (rc = a->upload(&a->va, R.va, stream)) != FOS_OK ||
-        (rc = a->upload(&a->trp, R.trp, stream)) != FOS_OK || (rc = a->upload(&a->tci, R.tci, stream)) != FOS_OK || (rc = a->upload(&a->tva, R.tva, stream)) != FOS_OK ||
-        (rc = a->upload(&a->items1, P1.items, stream)) != FOS_OK || (rc = a->upload(&a->items2, P2.items, stream)) != FOS_OK ||
-        (rc = a->upload(&a->frow1, P1.frow, stream)) != FOS_OK || (rc = a->upload(&a->fptr1, P1.fptr, stream)) != FOS_OK ||
-        (rc = a->upload(&a->frow2, P2.frow, stream)) != FOS_OK || (rc = a->upload(&a->fptr2, P2.fptr, stream)) != FOS_OK ||
-        (rc = a->alloc(&a->part1, (size_t)P1.nparts)) != FOS_OK || (rc = a->alloc(&a->part2, (size_t)P2.nparts)) != FOS_OK ||
+    if ((rc = a->A.upload(*a, R.A, stream)) != FOS_OK || (rc = a->At.upload(*a, R.At, stream)) != FOS_OK ||
+        (rc = a->pass[0].upload(*a, H.P[0], stream)) != FOS_OK || (rc = a->pass[1].upload(*a, H.P[1], stream)) != FOS_OK ||
         (rc = a->zeros(&a->G, L2, stream)) != FOS_OK || (rc = a->alloc(&a->X, L2)) != FOS_OK)
         return fail(rc);
     for (double** v : {&a->b, &a->r, &a->d, &a->e}) if ((rc = a->zeros(v, L, stream)) != FOS_OK) return fail(rc);
     DEV_HIP(a, hipMemcpyAsync(a->b, R.bs.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
-    launch_sf_gram(stream, m, a->L, a->rp, a->ci, a->va, a->trp, a->tci, a->tva, a->G);
+    launch_sf_gram(stream, m, a->L, a->A.rp, a->A.ci, a->A.va, a->At.rp, a->At.ci, a->At.va, a->G);
     if (lambda > 0.0) {                                    // (a->e holds the row scales until the first projection overwrites it)
         DEV_HIP(a, hipMemcpyAsync(a->e, R.scale.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
         hipLaunchKernelGGL(sf_shift_diag_kernel, dim3((unsigned)std::min<int64_t>(256, (m + SF_T - 1) / SF_T)), dim3(SF_T), 0, stream, m, a->L, a->G, (const double*)a->e, 1.0 / lambda);
@@ -240,25 +187,19 @@ void launch_sf_gram(hipStream_t stream, int64_t m, int64_t L, const int32_t* rp,
 }
 
 namespace {
-unsigned sf_grid(int nitems) { return (unsigned)((nitems + SF_T / 64 - 1) / (SF_T / 64)); }
-// r = A v - b
-void sf_residual(const SparseFactored* a, hipStream_t s, const double* v) {
-    hipLaunchKernelGGL(sf_pass_kernel<1>, dim3(sf_grid(a->nitems1)), dim3(SF_T), 0, s, a->nitems1, (const SfItem*)a->items1, (const int32_t*)a->rp, (const int32_t*)a->ci,
-                       (const double*)a->va, v, (const double*)a->b, a->r, a->part1);
-    if (a->nfold1 > 0)
-        hipLaunchKernelGGL(sf_fold_kernel<1>, dim3((unsigned)std::min(1024, (a->nfold1 + SF_T - 1) / SF_T)), dim3(SF_T), 0, s, a->nfold1, (const int32_t*)a->frow1,
-                           (const int32_t*)a->fptr1, (const double*)a->part1, (const double*)a->b, a->r);
-}
-// y = x - A'd
-void sf_correct(const SparseFactored* a, hipStream_t s, double* y, const double* x) {
-    hipLaunchKernelGGL(sf_pass_kernel<2>, dim3(sf_grid(a->nitems2)), dim3(SF_T), 0, s, a->nitems2, (const SfItem*)a->items2, (const int32_t*)a->trp, (const int32_t*)a->tci,
-                       (const double*)a->tva, (const double*)a->d, x, y, a->part2);
-    if (a->nfold2 > 0)
-        hipLaunchKernelGGL(sf_fold_kernel<2>, dim3((unsigned)std::min(1024, (a->nfold2 + SF_T - 1) / SF_T)), dim3(SF_T), 0, s, a->nfold2, (const int32_t*)a->frow2,
-                           (const int32_t*)a->fptr2, (const double*)a->part2, x, y);
+// PASS 1: out = A in - aux (r = A v - b);  PASS 2: out = aux - A'in (y = x - A'd); the fold behind it when a row was cut
+template <int PASS>
+void sf_launch_pass(const SparseFactored* a, hipStream_t s, const double* in, const double* aux, double* out) {
+    const DevCsr& M = PASS == 1 ? a->A : a->At;
+    const DevPass& P = a->pass[PASS - 1];
+    hipLaunchKernelGGL(sf_pass_kernel<PASS>, dim3((unsigned)((P.nitems + SF_T / 64 - 1) / (SF_T / 64))), dim3(SF_T), 0, s, P.nitems, (const SfItem*)P.items,
+                       (const int32_t*)M.rp, (const int32_t*)M.ci, (const double*)M.va, in, aux, out, P.part);
+    if (P.nfold > 0)
+        hipLaunchKernelGGL(sf_fold_kernel<PASS>, dim3((unsigned)std::min(1024, (P.nfold + SF_T - 1) / SF_T)), dim3(SF_T), 0, s, P.nfold, (const int32_t*)P.frow,
+                           (const int32_t*)P.fptr, (const double*)P.part, aux, out);
 }
 int sf_launches(const SparseFactored* a) {
-    const int p1 = 1 + (a->nfold1 > 0 ? 1 : 0), p2 = 1 + (a->nfold2 > 0 ? 1 : 0);
+    const int p1 = 1 + (a->pass[0].nfold > 0 ? 1 : 0), p2 = 1 + (a->pass[1].nfold > 0 ? 1 : 0);
     return (p1 + 3 + p2) + a->refine * (p1 + 1 + p2);
 }
 }  // namespace
@@ -266,13 +207,13 @@ int sf_launches(const SparseFactored* a) {
 // y = the projection of x onto {A x = b} (device vectors of length n, y must not alias x), on `stream`: sf_launches(a) launches, nothing else
 int SparseFactored::prox(hipStream_t stream, double* y, const double* x) {
     const SparseFactored* a = this;
-    sf_residual(a, stream, x);                                                   // r = A x - b
+    sf_launch_pass<1>(a, stream, x, b, r);                                       // r = A x - b
     mspace_correct(stream, m, L, X, G, r, d, e);                                 // d = X r, corrected once
-    sf_correct(a, stream, y, x);                                                 // y = x - A'd
+    sf_launch_pass<2>(a, stream, d, x, y);                                       // y = x - A'd
     for (int k = 0; k < refine; ++k) {
-        sf_residual(a, stream, y);                                               // r = A y - b
+        sf_launch_pass<1>(a, stream, y, b, r);                                   // r = A y - b
         launch_da_symv(stream, m, L, X, r, nullptr, 1.0, d);                     // d = X r
-        sf_correct(a, stream, y, y);                                             // y -= A'd
+        sf_launch_pass<2>(a, stream, d, y, y);                                   // y -= A'd
     }
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) { set_error("IndAffine (sparse, factored): a kernel launch failed: %s", hipGetErrorString(err)); return FOS_EHIP; }
@@ -288,15 +229,16 @@ void sparse_factored_stats(const ProxObject* obj, double* out8) {
 // out8 = stored entries, padded order of A A', SEG in force, pass 1: work items, rows cut (folded); pass 2: work items, rows cut; segments of the cut rows of both passes
 void sparse_factored_plan(const ProxObject* obj, int64_t* out8) {
     const SparseFactored* a = static_cast<const SparseFactored*>(obj);
-    out8[0] = a->nnz; out8[1] = a->L; out8[2] = a->seg; out8[3] = a->nitems1; out8[4] = a->nfold1; out8[5] = a->nitems2; out8[6] = a->nfold2;
-    out8[7] = a->nparts1 + a->nparts2;
+    out8[0] = a->nnz; out8[1] = a->L; out8[2] = a->seg; out8[3] = a->pass[0].nitems; out8[4] = a->pass[0].nfold; out8[5] = a->pass[1].nitems; out8[6] = a->pass[1].nfold;
+    out8[7] = a->pass[0].nparts + a->pass[1].nparts;
 }
 
 // ---------------------------------------------------------------------------------- host emulation (tests; no GPU)
 namespace {
 // one pass in sf_pass_kernel's and sf_fold_kernel's order: out[row] = s - aux[row] (pass 1) / aux[row] - s (pass 2)
-void sf_host_pass(int pass, const SfPass& P, const std::vector<int32_t>& rp, const std::vector<int32_t>& ci, const std::vector<double>& va, const double* in,
-                  const double* aux, double* out) {
+void sf_host_pass(int pass, const SfPass& P, const HostCsr& M, const double* in, const double* aux, double* out) {
+    const std::vector<int32_t>&rp = M.rp, &ci = M.ci;
+    const std::vector<double>& va = M.va;
     std::vector<double> part((size_t)std::max<int64_t>(P.nparts, 1));
     auto group = [&](int e0, int e1, int g) {                         // the lanes' sums in entry order, then group_sum's tree over g lanes
         double lane[64] = {0.0};
@@ -328,30 +270,27 @@ int host_affine_sparse_factored(int64_t m, int64_t n, const int64_t* colptr, con
                                 const double* x, double* y) {
     if (!x || !y) { set_error("%s: bad argument", sf_name(lambda)); return FOS_EINVAL; }
     if (lambda > 0.0) refine = 0;
-    SparseRows R;
-    FOS_TRY(sf_rows(m, n, colptr, rowval, nzval, b, lambda, refine, &R));
-    int seg = 0;
-    FOS_TRY(sf_segment_length(&seg));
-    SfPass P1, P2;
-    sf_plan_pass(m, R.rp.data(), seg, &P1);
-    sf_plan_pass(n, R.trp.data(), seg, &P2);
+    SfHost H;
+    FOS_TRY(sf_rows(m, n, colptr, rowval, nzval, b, lambda, refine, &H));
+    const HostCsr &A = H.R.A, &At = H.R.At;
+    const std::vector<double>&bs = H.R.bs, &scale = H.R.scale;
     std::vector<double> G((size_t)m * (size_t)m, 0.0), X((size_t)m * (size_t)m);
     for (int64_t i = 0; i < m; ++i)
-        for (int32_t e = R.rp[(size_t)i]; e < R.rp[(size_t)i + 1]; ++e) {
-            const int32_t c = R.ci[(size_t)e];
-            for (int32_t t = R.trp[(size_t)c]; t < R.trp[(size_t)c + 1]; ++t) G[(size_t)(R.tci[(size_t)t] + i * m)] += R.va[(size_t)e] * R.tva[(size_t)t];
+        for (int32_t e = A.rp[(size_t)i]; e < A.rp[(size_t)i + 1]; ++e) {
+            const int32_t c = A.ci[(size_t)e];
+            for (int32_t t = At.rp[(size_t)c]; t < At.rp[(size_t)c + 1]; ++t) G[(size_t)(At.ci[(size_t)t] + i * m)] += A.va[(size_t)e] * At.va[(size_t)t];
         }
     if (lambda > 0.0)
-        for (int64_t i = 0; i < m; ++i) G[(size_t)(i + i * m)] += R.scale[(size_t)i] * R.scale[(size_t)i] * (1.0 / lambda);
+        for (int64_t i = 0; i < m; ++i) G[(size_t)(i + i * m)] += scale[(size_t)i] * scale[(size_t)i] * (1.0 / lambda);
     FOS_TRY(host_da_inverse(sf_name(lambda), m, G.data(), X.data()));
     std::vector<double> r((size_t)m), d((size_t)m), e((size_t)m);
-    sf_host_pass(1, P1, R.rp, R.ci, R.va, x, R.bs.data(), r.data());
+    sf_host_pass(1, H.P[0], A, x, bs.data(), r.data());
     host_mspace_correct(m, X.data(), G.data(), r.data(), d.data(), e.data());
-    sf_host_pass(2, P2, R.trp, R.tci, R.tva, d.data(), x, y);
+    sf_host_pass(2, H.P[1], At, d.data(), x, y);
     for (int k = 0; k < refine; ++k) {
-        sf_host_pass(1, P1, R.rp, R.ci, R.va, y, R.bs.data(), r.data());
+        sf_host_pass(1, H.P[0], A, y, bs.data(), r.data());
         host_da_symv(m, m, X.data(), r.data(), nullptr, 1.0, d.data());
-        sf_host_pass(2, P2, R.trp, R.tci, R.tva, d.data(), y, y);
+        sf_host_pass(2, H.P[1], At, d.data(), y, y);
     }
     return FOS_OK;
 }

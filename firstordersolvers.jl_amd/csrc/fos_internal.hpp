@@ -21,12 +21,11 @@
 #include <vector>
 
 #include "foship.h"
+#include "sparse_rows.hpp"
 
 namespace fos {
 
-// ---------------------------------------------------------------------------------- errors
-void set_error(const char* fmt, ...);
-
+// ---------------------------------------------------------------------------------- errors (set_error, FOS_TRY: sparse_rows.hpp)
 #define FOS_HIP(expr)                                                                         \
     do {                                                                                      \
         hipError_t _e = (expr);                                                               \
@@ -34,12 +33,6 @@ void set_error(const char* fmt, ...);
             ::fos::set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
             return FOS_EHIP;                                                                  \
         }                                                                                     \
-    } while (0)
-
-#define FOS_TRY(expr)                    \
-    do {                                 \
-        int _r = (expr);                 \
-        if (_r != FOS_OK) return _r;     \
     } while (0)
 
 // ---------------------------------------------------------------------------------- SpMV storage
@@ -815,6 +808,24 @@ struct DevOwned {
     }
     template <class T> int upload(T** out, const std::vector<T>& v, hipStream_t s) { return upload(out, v.data(), v.size(), s); }
 };
+// The device twins of HostCsr and SfPass (sparse_rows.hpp): owned by `o`, uploaded on `s` (nullptr: blocking)
+struct DevCsr {
+    int32_t *rp = nullptr, *ci = nullptr;
+    double* va = nullptr;
+    int upload(DevOwned& o, const HostCsr& h, hipStream_t s) { FOS_TRY(o.upload(&rp, h.rp, s)); FOS_TRY(o.upload(&ci, h.ci, s)); return o.upload(&va, h.va, s); }
+};
+struct DevPass {
+    SfItem* items = nullptr;
+    int32_t *frow = nullptr, *fptr = nullptr;
+    double* part = nullptr;                       // one slot per segment of a cut row (zeroed)
+    int nitems = 0, nfold = 0;
+    int64_t nparts = 0;
+    int upload(DevOwned& o, const SfPass& P, hipStream_t s) {
+        nitems = (int)P.items.size(); nfold = (int)P.frow.size(); nparts = P.nparts;
+        FOS_TRY(o.upload(&items, P.items, s)); FOS_TRY(o.upload(&frow, P.frow, s)); FOS_TRY(o.upload(&fptr, P.fptr, s));
+        return o.zeros(&part, (size_t)P.nparts, s);
+    }
+};
 // inside a set-up that defines fail(code) (release the half-built object, hand the code back): a HIP call of owner `a`
 #define DEV_HIP(a, expr) do { const int _r = (a)->hip(#expr, (expr)); if (_r != FOS_OK) return fail(_r); } while (0)
 
@@ -832,15 +843,13 @@ int callback_setup(const FeasEnv& env, int which, fos_prox_fn fn, void* ctx, Pro
 
 // The stats / plan functions below take the object the set-up of the same file built (the caller checked `kind`).
 // IndAffine(A, b) with a sparse A (affine_sparse.hip): exact projection by warm-started CG on the row-scaled normal equations, the true residual re-checked
-struct SparseRows {                              // host: what sparse_affine_rows leaves -- the scaled A (rp / ci / va) and A' (trp / tci / tva) in CSR, the scaled b
-    int64_t m = 0, n = 0, nnz = 0;
-    std::vector<int32_t> rp, ci, trp, tci;
-    std::vector<double> va, tva, bs;
-    std::vector<double> scale;                   // the row factors (1 for a zero row)
+struct ScaledRows {                              // host: the rows of [A | b] scaled to unit norm -- A and A' in CSR, the scaled b, the row factors (1 for a zero row)
+    HostCsr A, At;
+    std::vector<double> bs, scale;
 };
-// zero_rows: a zero row is accepted and keeps scale 1 (the sparse LeastSquares); otherwise it is FOS_EINVAL
-int sparse_affine_rows(const char* what, int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, SparseRows* out,
-                       bool zero_rows = false);
+// both sparse IndAffine forms and the sparse factored LeastSquares.  ascending: csc_check's rule; zero_rows: a zero row is accepted, otherwise it is FOS_EINVAL
+int sparse_affine_rows(const char* what, int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, bool ascending,
+                       bool zero_rows, ScaledRows* out);
 int sparse_affine_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, int cus, ProxObject** out);
 void sparse_affine_stats(const ProxObject* a, double* out8);
 // IndAffine(A, b) with a dense A, factored form (affine_dense.hip): A kept once, (A A')^-1 of order m, two passes over A per projection
@@ -861,17 +870,6 @@ void host_mspace_correct(int64_t m, const double* X, const double* G, const doub
 // lambda: 0: IndAffine(A, b), > 0: LeastSquares(A, b, lambda) (refine is then 0, zero and dependent rows are accepted)
 int sparse_factored_setup(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, int factor,
                           int refine, hipStream_t stream, ProxObject** out);
-// a work item of a segmented sparse pass (16 bytes, read wave-uniformly), one wavefront each:
-//   segment: a = row, b = first entry, c = entries (> 0), d = slot of part[] (-1: the row's only segment, never built: such rows are packed)
-//   packet:  a = first row, b = rows (<= 64 / g), c = -g (lanes per row, a power of two), d unused
-struct SfItem { int32_t a, b, c, d; };
-struct SfPass {
-    std::vector<SfItem> items;
-    std::vector<int32_t> frow, fptr;                     // cut rows and their slots of part[]: fptr[k] .. fptr[k + 1] - 1, in segment order
-    int64_t nparts = 0;
-};
-constexpr int SF_SEG_DEFAULT = 2048;          // stored entries per segment (FOS_SF_SEG: a multiple of 64 from 64 up to this)
-void sf_plan_pass(int64_t nrows, const int32_t* rp, int seg, SfPass* P);
 void launch_sf_gram(hipStream_t stream, int64_t m, int64_t L, const int32_t* rp, const int32_t* ci, const double* va, const int32_t* trp, const int32_t* tci,
                     const double* tva, double* G);
 void sparse_factored_stats(const ProxObject* a, double* out8);

@@ -238,35 +238,13 @@ int ns_check_quadratic(int64_t n, const double* Q, const double* q) {
         if (!(1.0 + Q[i * n + i] > 0.0)) { set_error("Quadratic: the pivot of column %lld of I + Q is not a positive finite number (Q is not positive semidefinite)", (long long)i); return FOS_EINVAL; }
     return FOS_OK;
 }
-// a sparse A for the normal-equations form: CSC, 1-based, row indices strictly ascending in every column (sf_gram_kernel adds a row's entries side by side).
-// cp / ri / va: A' in CSR = the CSC arrays, 0-based; rp / ci / rv: A in CSR (columns ascending)
-struct NsSparse { std::vector<int32_t> cp, ri, rp, ci; std::vector<double> va, rv; int64_t nnz = 0; };
-int ns_sparse_rows(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, NsSparse* S) {
+// a sparse A for the normal-equations form: CSC, 1-based, row indices strictly ascending in every column (sf_gram_kernel adds a row's entries side by side): validated, then A and A' in CSR
+int ns_sparse_rows(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, HostCsr* A, HostCsr* At) {
     const char* what = "LeastSquares (sparse, normal)";
-    if (m < 1 || n < 1 || !colptr || !rowval || !nzval || !b) { set_error("%s: bad argument", what); return FOS_EINVAL; }
-    if (m > 2000000000LL) { set_error("%s: m = %lld rows (up to 2e9 supported)", what, (long long)m); return FOS_EUNSUPPORTED; }
-    if (colptr[0] != 1) { set_error("%s: colptr must be 1-based (colptr[0] = %lld)", what, (long long)colptr[0]); return FOS_EINVAL; }
-    for (int64_t j = 0; j < n; ++j) if (colptr[j + 1] < colptr[j]) { set_error("%s: colptr decreases at column %lld", what, (long long)j + 1); return FOS_EINVAL; }
-    const int64_t nnz = colptr[n] - 1;
-    if (nnz > 2000000000LL) { set_error("%s: %lld stored entries (up to 2e9 supported)", what, (long long)nnz); return FOS_EINVAL; }
+    if (!b) { set_error("%s: bad argument", what); return FOS_EINVAL; }
+    FOS_TRY(csc_check(what, m, n, colptr, rowval, nzval, CscRules{false, true, CSC_BOUND_ROWS, "A"}));
     if (!ns_finite(b, m)) { set_error("%s: b has non-finite entries", what); return FOS_EINVAL; }
-    S->nnz = nnz;
-    S->cp.resize((size_t)n + 1); S->ri.resize((size_t)nnz); S->va.assign(nzval, nzval + nnz);
-    S->rp.assign((size_t)m + 1, 0); S->ci.resize((size_t)nnz); S->rv.resize((size_t)nnz);
-    for (int64_t j = 0; j <= n; ++j) S->cp[(size_t)j] = (int32_t)(colptr[j] - 1);
-    for (int64_t j = 0; j < n; ++j)
-        for (int64_t e = colptr[j] - 1; e < colptr[j + 1] - 1; ++e) {
-            const int64_t i = rowval[e] - 1;
-            if (i < 0 || i >= m) { set_error("%s: row index %lld outside 1..%lld", what, (long long)rowval[e], (long long)m); return FOS_EINVAL; }
-            if (e > colptr[j] - 1 && rowval[e] <= rowval[e - 1]) { set_error("%s: the row indices of column %lld are not strictly ascending (duplicated or unsorted entries)", what, (long long)j + 1); return FOS_EINVAL; }
-            if (!(nzval[e] == nzval[e]) || std::fabs(nzval[e]) > 1e300) { set_error("%s: A has non-finite entries", what); return FOS_EINVAL; }
-            S->ri[(size_t)e] = (int32_t)i;
-            S->rp[(size_t)i + 1] += 1;
-        }
-    for (int64_t i = 0; i < m; ++i) S->rp[(size_t)i + 1] += S->rp[(size_t)i];
-    std::vector<int32_t> fill(S->rp.begin(), S->rp.end() - 1);
-    for (int64_t j = 0; j < n; ++j)
-        for (int32_t e = S->cp[(size_t)j]; e < S->cp[(size_t)j + 1]; ++e) { const int32_t p = fill[(size_t)S->ri[(size_t)e]]++; S->ci[(size_t)p] = (int32_t)j; S->rv[(size_t)p] = S->va[(size_t)e]; }
+    csc_to_csr_pair(m, n, colptr, rowval, nzval, nullptr, A, At);
     return FOS_OK;
 }
 
@@ -401,8 +379,8 @@ int nspace_setup_ls_sparse(int64_t m, int64_t n, const int64_t* colptr, const in
     const char* what = "LeastSquares (sparse, normal)";
     FOS_TRY(ns_check_lambda(lambda));
     FOS_TRY(ns_check_common(what, n, factor));
-    NsSparse S;
-    FOS_TRY(ns_sparse_rows(m, n, colptr, rowval, nzval, b, &S));
+    HostCsr A, At;
+    FOS_TRY(ns_sparse_rows(m, n, colptr, rowval, nzval, b, &A, &At));
     NSpace* a = new NSpace();
     auto fail = [&](int code) { (void)hipStreamSynchronize(stream); delete a; return code; };
     int rc = FOS_OK;
@@ -410,18 +388,15 @@ int nspace_setup_ls_sparse(int64_t m, int64_t n, const int64_t* colptr, const in
         Scratch s;
         DenseWork w;
         if ((rc = ns_prepare(a, n, m, what, stream, s, w)) != FOS_OK) return fail(rc);
-        const size_t ne = (size_t)std::max<int64_t>(S.nnz, 1);
-        int32_t *dcp = s.alloc<int32_t>((size_t)n + 1), *dri = s.alloc<int32_t>(ne), *drp = s.alloc<int32_t>((size_t)m + 1), *dci = s.alloc<int32_t>(ne);
-        double *dva = s.alloc<double>(ne), *drv = s.alloc<double>(ne), *db = s.alloc<double>((size_t)m);
-        if (s.err != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipMalloc of the sparse set-up buffers failed: %s", what, hipGetErrorString(s.err)); return fail(FOS_ENOMEM); }
-#define NS_UP(dst, vec) if (!(vec).empty()) DEV_HIP(a, hipMemcpyAsync(dst, (vec).data(), sizeof((vec)[0]) * (vec).size(), hipMemcpyHostToDevice, stream))
-        NS_UP(dcp, S.cp); NS_UP(dri, S.ri); NS_UP(dva, S.va); NS_UP(drp, S.rp); NS_UP(dci, S.ci); NS_UP(drv, S.rv);
-#undef NS_UP
-        DEV_HIP(a, hipMemcpyAsync(db, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
+        DevOwned tmp;                                                              // A, A' and b: needed for the set-up only
+        DevCsr dA, dAt;
+        double* db = nullptr;
+        tmp.what = what;
+        if ((rc = dAt.upload(tmp, At, stream)) != FOS_OK || (rc = dA.upload(tmp, A, stream)) != FOS_OK || (rc = tmp.upload(&db, b, (size_t)m, stream)) != FOS_OK) return fail(rc);
         DEV_HIP(a, hipMemsetAsync(w.B0, 0, sizeof(double) * (size_t)a->L * (size_t)a->L, stream));
-        hipLaunchKernelGGL(ns_rowdot_csr_kernel, dim3((unsigned)std::min<int64_t>((n + 3) / 4, 4096)), dim3(NS_T), 0, stream, n, (const int32_t*)dcp, (const int32_t*)dri,
-                           (const double*)dva, (const double*)db, lambda, a->r);
-        launch_sf_gram(stream, n, a->L, dcp, dri, dva, drp, dci, drv, w.B0);       // A'A = B B', B = A': its CSR is A's CSC, the CSR of B' is A's
+        hipLaunchKernelGGL(ns_rowdot_csr_kernel, dim3((unsigned)std::min<int64_t>((n + 3) / 4, 4096)), dim3(NS_T), 0, stream, n, (const int32_t*)dAt.rp, (const int32_t*)dAt.ci,
+                           (const double*)dAt.va, (const double*)db, lambda, a->r);
+        launch_sf_gram(stream, n, a->L, dAt.rp, dAt.ci, dAt.va, dA.rp, dA.ci, dA.va, w.B0);       // A'A = B B', B = A': its CSR is A's CSC, the CSR of B' is A's
         if ((rc = ns_build(a, factor, stream, "I + lambda A'A", w, NsSource{0, w.B0, lambda})) != FOS_OK) return fail(rc);
     }
     *out = a;
@@ -672,22 +647,22 @@ int host_nspace_ls_sparse(int64_t m, int64_t n, const int64_t* colptr, const int
     FOS_TRY(ns_check_lambda(lambda));
     FOS_TRY(ns_check_common(what, n, FOS_DIRECT_FACTOR_CHOLESKY));
     if (!x || !y) { set_error("%s: bad argument", what); return FOS_EINVAL; }
-    NsSparse A;
-    FOS_TRY(ns_sparse_rows(m, n, colptr, rowval, nzval, b, &A));
+    HostCsr A, At;
+    FOS_TRY(ns_sparse_rows(m, n, colptr, rowval, nzval, b, &A, &At));
     std::vector<double> S((size_t)n * (size_t)n, 0.0), c((size_t)n);
     for (int64_t i = 0; i < n; ++i)                                               // sf_gram_kernel on B = A': column i of the result, the entries of row i of B in order
-        for (int32_t e = A.cp[(size_t)i]; e < A.cp[(size_t)i + 1]; ++e) {
-            const int32_t row = A.ri[(size_t)e];
+        for (int32_t e = At.rp[(size_t)i]; e < At.rp[(size_t)i + 1]; ++e) {
+            const int32_t row = At.ci[(size_t)e];
             for (int32_t t = A.rp[(size_t)row]; t < A.rp[(size_t)row + 1]; ++t) {
                 double& g = S[(size_t)(A.ci[(size_t)t] + i * n)];
-                g = std::fma(A.va[(size_t)e], A.rv[(size_t)t], g);                    // (fused on the device)
+                g = std::fma(At.va[(size_t)e], A.va[(size_t)t], g);                   // (fused on the device)
             }
         }
     for (int64_t j = 0; j < n; ++j) {
         double lane[64] = {0.0};
-        for (int32_t e = A.cp[(size_t)j]; e < A.cp[(size_t)j + 1]; ++e) {
-            double& l = lane[(e - A.cp[(size_t)j]) % 64];
-            l = std::fma(A.va[(size_t)e], b[A.ri[(size_t)e]], l);                    // (fused on the device)
+        for (int32_t e = At.rp[(size_t)j]; e < At.rp[(size_t)j + 1]; ++e) {
+            double& l = lane[(e - At.rp[(size_t)j]) % 64];
+            l = std::fma(At.va[(size_t)e], b[At.ci[(size_t)e]], l);                   // (fused on the device)
         }
         c[(size_t)j] = lambda * host_da_wave(lane);
     }

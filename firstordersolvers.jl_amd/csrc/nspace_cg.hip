@@ -4,10 +4,10 @@
 // The counterpart of ProximalOperators' iterative=true for both functions, which Feasibility.jl accepts as either set (src/problemforms/Feasibility/Feasibility.jl:2-6);
 // nspace.hip keeps the same matrices as a dense inverse, up to order 46 000.
 //
-//   * set-up (host): validated as nspace.hip / sparse_affine_rows do.  Quadratic: the entries i >= j of the CSC Q are mirrored into ONE full symmetric CSR of
+//   * set-up (host): validated by csc_check (sparse_rows.hpp).  Quadratic: the entries i >= j of the CSC Q are mirrored into ONE full symmetric CSR of
 //     M = I + Q (the unit diagonal included: every row has an entry), so the product only gathers.  LeastSquares: A and A' as two CSR matrices by a counting pass,
 //     WITHOUT a row scaling (the preconditioner below is the n-space diagonal, a row scaling of A would change M).  D = diag(M) > 0; c = lambda A'b on the device.
-//   * rows (sf_plan_pass of affine_sparse_factored.hip): a row longer than 2 048 entries is cut into segments, one wavefront each; the others are packed 64 / g to a
+//   * rows (sf_plan_pass of sparse_rows.hpp): a row longer than 2 048 entries is cut into segments, one wavefront each; the others are packed 64 / g to a
 //     wavefront.  A bounded grid walks the items, so a launch leaves at most NC_PARTS partial sums.  The LAST segment of a cut row to arrive (one counter per cut
 //     row, no waiting) adds the row's partials in segment order and runs the row's epilogue; its share of the launch's sums goes to a slot of its own, so every sum
 //     is formed in one fixed order whichever segment came last: a prox repeats bit for bit.
@@ -338,20 +338,17 @@ __global__ __launch_bounds__(NC_T) void nc_cold_kernel(int64_t n, NcVec v) {
 }
 
 // ------------------------------------------------------------------------------------------------ host: validation, the matrices, the plans
-struct NcCsr { std::vector<int32_t> rp, ci; std::vector<double> va; };
 // the plan of one matrix and what the device (or the emulation) needs beside it
 struct NcPlan {
     SfPass P;
     std::vector<int32_t> segk;
     int grid = 1;
-    void build(int64_t nrows, const NcCsr& A, bool lpr) {
+    void build(int64_t nrows, const HostCsr& A, bool lpr) {
         if (!lpr) sf_plan_pass(nrows, A.rp.data(), SF_SEG_DEFAULT, &P);
-        else {                                // measurement only: lanes_per_row of affine_sparse.hip -- every row the same g, the largest power of two not above the
-            P = SfPass();                     // mean row length, no row cut
+        else {                                // measurement only: lanes_per_row (sparse_rows.hpp) -- every row the same g, no row cut
+            P = SfPass();
             P.fptr.assign(1, 0);
-            const double avg = (double)A.rp[(size_t)nrows] / (double)nrows;
-            int g = 1;
-            while (g < 64 && 2 * g <= avg) g <<= 1;
+            const int g = lanes_per_row(A.rp[(size_t)nrows], nrows);
             for (int64_t r = 0; r < nrows; r += 64 / g) P.items.push_back(SfItem{(int32_t)r, (int32_t)std::min<int64_t>(64 / g, nrows - r), -g, -1});
         }
         segk.assign((size_t)P.nparts, 0);
@@ -366,7 +363,7 @@ bool nc_env_is(const char* name, const char* value) { const char* s = std::geten
 struct NcHost {                               // what a set-up leaves on the host
     int64_t n = 0, m = 0;                     // m = 0: Quadratic
     double lambda = 1.0;
-    NcCsr M, A;                               // Quadratic: M = I + Q;  LeastSquares: M = A' (n rows), A (m rows)
+    HostCsr M, A;                             // Quadratic: M = I + Q;  LeastSquares: M = A' (n rows), A (m rows)
     NcPlan pm, pa;
     std::vector<double> dinv, c, b;           // c: Quadratic only (LeastSquares forms it with a pass)
     int64_t stored = 0;
@@ -374,35 +371,18 @@ struct NcHost {                               // what a set-up leaves on the hos
     bool lpr = nc_env_is("FOS_NC_ROWS", "lpr");
 };
 int nc_grid_n(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(NC_PARTS, (n + NC_T - 1) / NC_T)); }
-bool nc_finite(double v) { return v == v && std::fabs(v) <= 1e300; }
-
-// the CSC arrays of both functions: 1-based, monotone, indices in 1..rows strictly ascending in a column, finite values
-int nc_check_csc(const char* what, int64_t rows, int64_t cols, const int64_t* colptr, const int64_t* rowval, const double* nzval) {
-    if (rows < 1 || cols < 1 || !colptr || !rowval || !nzval) { set_error("%s: bad argument", what); return FOS_EINVAL; }
-    if (rows > 2000000000LL || cols > 2000000000LL) { set_error("%s: %lld x %lld (up to 2e9 rows and columns supported)", what, (long long)rows, (long long)cols); return FOS_EUNSUPPORTED; }
-    if (colptr[0] != 1) { set_error("%s: colptr must be 1-based (colptr[0] = %lld)", what, (long long)colptr[0]); return FOS_EINVAL; }
-    for (int64_t j = 0; j < cols; ++j) if (colptr[j + 1] < colptr[j]) { set_error("%s: colptr decreases at column %lld", what, (long long)j + 1); return FOS_EINVAL; }
-    if (colptr[cols] - 1 > 2000000000LL) { set_error("%s: %lld stored entries (up to 2e9 supported)", what, (long long)(colptr[cols] - 1)); return FOS_EINVAL; }
-    for (int64_t j = 0; j < cols; ++j)
-        for (int64_t e = colptr[j] - 1; e < colptr[j + 1] - 1; ++e) {
-            if (rowval[e] < 1 || rowval[e] > rows) { set_error("%s: row index %lld outside 1..%lld", what, (long long)rowval[e], (long long)rows); return FOS_EINVAL; }
-            if (e > colptr[j] - 1 && rowval[e] <= rowval[e - 1]) { set_error("%s: the row indices of column %lld are not strictly ascending (duplicated or unsorted entries)", what, (long long)j + 1); return FOS_EINVAL; }
-            if (!nc_finite(nzval[e])) { set_error("%s: the matrix has non-finite entries", what); return FOS_EINVAL; }
-        }
-    return FOS_OK;
-}
+constexpr CscRules NC_RULES{false, true, CSC_BOUND_BOTH, "the matrix"};
 int nc_check_tol(const char* what, double tol) {
     if (!(tol >= 0.0) || tol >= 1.0) { set_error("%s: tol must be in [0, 1)", what); return FOS_EINVAL; }
     return FOS_OK;
 }
-int nc_longest(const NcCsr& A) { int l = 0; for (size_t i = 0; i + 1 < A.rp.size(); ++i) l = std::max(l, A.rp[i + 1] - A.rp[i]); return l; }
 
 int nc_host_quadratic(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* q, double tol, NcHost* H) {
     const char* what = "Quadratic (cg)";
     FOS_TRY(nc_check_tol(what, tol));
-    FOS_TRY(nc_check_csc(what, n, n, colptr, rowval, nzval));
+    FOS_TRY(csc_check(what, n, n, colptr, rowval, nzval, NC_RULES));
     if (!q) { set_error("%s: bad argument", what); return FOS_EINVAL; }
-    for (int64_t i = 0; i < n; ++i) if (!nc_finite(q[i])) { set_error("%s: q has non-finite entries", what); return FOS_EINVAL; }
+    for (int64_t i = 0; i < n; ++i) if (!csc_finite(q[i])) { set_error("%s: q has non-finite entries", what); return FOS_EINVAL; }
     H->n = n; H->m = 0; H->lambda = 1.0;
     // rows of M = I + Q from the entries i >= j: row i takes (i, j), j < i, in column order, its diagonal, then the mirrors of column i: columns ascending
     std::vector<int64_t> cnt((size_t)n + 1, 0);
@@ -414,14 +394,14 @@ int nc_host_quadratic(int64_t n, const int64_t* colptr, const int64_t* rowval, c
             else if (i == j) diag[(size_t)j] = 1.0 + nzval[e];
         }
     for (int64_t i = 0; i < n; ++i) {
-        if (!(diag[(size_t)i] > 0.0) || !nc_finite(diag[(size_t)i])) {
+        if (!(diag[(size_t)i] > 0.0) || !csc_finite(diag[(size_t)i])) {
             set_error("%s: 1 + Q[%lld, %lld] = %g is not a positive finite number (Q is not positive semidefinite)", what, (long long)i + 1, (long long)i + 1, diag[(size_t)i]);
             return FOS_EINVAL;
         }
         cnt[(size_t)i + 1] += 1 + cnt[(size_t)i];
     }
     if (cnt[(size_t)n] > 2000000000LL) { set_error("%s: I + Q has %lld stored entries (up to 2e9 supported)", what, (long long)cnt[(size_t)n]); return FOS_EINVAL; }
-    NcCsr& M = H->M;
+    HostCsr& M = H->M;
     M.rp.resize((size_t)n + 1); M.ci.resize((size_t)cnt[(size_t)n]); M.va.resize((size_t)cnt[(size_t)n]);
     for (int64_t i = 0; i <= n; ++i) M.rp[(size_t)i] = (int32_t)cnt[(size_t)i];
     std::vector<int32_t> fill(M.rp.begin(), M.rp.end() - 1);
@@ -441,37 +421,30 @@ int nc_host_quadratic(int64_t n, const int64_t* colptr, const int64_t* rowval, c
     H->dinv.resize((size_t)n); H->c.resize((size_t)n);
     for (int64_t i = 0; i < n; ++i) { H->dinv[(size_t)i] = 1.0 / diag[(size_t)i]; H->c[(size_t)i] = -q[i]; }
     H->pm.build(n, M, H->lpr);
-    H->stored = cnt[(size_t)n]; H->longest = nc_longest(M);
+    H->stored = cnt[(size_t)n]; H->longest = M.longest();
     return FOS_OK;
 }
 int nc_host_ls(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, double tol, NcHost* H) {
     const char* what = "LeastSquares (cg)";
     if (!(lambda > 0.0) || lambda > 1e300) { set_error("LeastSquares: lambda must be finite and > 0"); return FOS_EINVAL; }
     FOS_TRY(nc_check_tol(what, tol));
-    FOS_TRY(nc_check_csc(what, m, n, colptr, rowval, nzval));
+    FOS_TRY(csc_check(what, m, n, colptr, rowval, nzval, NC_RULES));
     if (!b) { set_error("%s: bad argument", what); return FOS_EINVAL; }
-    for (int64_t i = 0; i < m; ++i) if (!nc_finite(b[i])) { set_error("%s: b has non-finite entries", what); return FOS_EINVAL; }
+    for (int64_t i = 0; i < m; ++i) if (!csc_finite(b[i])) { set_error("%s: b has non-finite entries", what); return FOS_EINVAL; }
     H->n = n; H->m = m; H->lambda = lambda;
-    const int64_t nnz = colptr[n] - 1;
-    NcCsr &T = H->M, &A = H->A;                                   // A' in CSR = the CSC arrays, 0-based; A in CSR by a counting pass (columns ascending in a row)
-    T.rp.resize((size_t)n + 1); T.ci.resize((size_t)nnz); T.va.assign(nzval, nzval + nnz);
-    A.rp.assign((size_t)m + 1, 0); A.ci.resize((size_t)nnz); A.va.resize((size_t)nnz);
+    HostCsr &T = H->M, &A = H->A;                                 // T = A' (n rows)
+    csc_to_csr_pair(m, n, colptr, rowval, nzval, nullptr, &A, &T);
     H->dinv.resize((size_t)n);
-    for (int64_t j = 0; j <= n; ++j) T.rp[(size_t)j] = (int32_t)(colptr[j] - 1);
     for (int64_t j = 0; j < n; ++j) {
         double d = 0.0;
-        for (int64_t e = colptr[j] - 1; e < colptr[j + 1] - 1; ++e) { T.ci[(size_t)e] = (int32_t)(rowval[e] - 1); A.rp[(size_t)rowval[e]]++; d += nzval[e] * nzval[e]; }
+        for (int32_t e = T.rp[(size_t)j]; e < T.rp[(size_t)j + 1]; ++e) d += T.va[(size_t)e] * T.va[(size_t)e];
         const double dj = 1.0 + lambda * d;
-        if (!nc_finite(dj)) { set_error("%s: 1 + lambda |A[:, %lld]|^2 overflows", what, (long long)j + 1); return FOS_EINVAL; }
+        if (!csc_finite(dj)) { set_error("%s: 1 + lambda |A[:, %lld]|^2 overflows", what, (long long)j + 1); return FOS_EINVAL; }
         H->dinv[(size_t)j] = 1.0 / dj;
     }
-    for (int64_t i = 0; i < m; ++i) A.rp[(size_t)i + 1] += A.rp[(size_t)i];
-    std::vector<int32_t> fill(A.rp.begin(), A.rp.end() - 1);
-    for (int64_t j = 0; j < n; ++j)
-        for (int32_t e = T.rp[(size_t)j]; e < T.rp[(size_t)j + 1]; ++e) { const int32_t p = fill[(size_t)T.ci[(size_t)e]]++; A.ci[(size_t)p] = (int32_t)j; A.va[(size_t)p] = T.va[(size_t)e]; }
     H->b.assign(b, b + m);
     H->pm.build(n, T, H->lpr); H->pa.build(m, A, H->lpr);
-    H->stored = 2 * nnz; H->longest = nc_longest(T) + nc_longest(A);
+    H->stored = 2 * (int64_t)T.ci.size(); H->longest = T.longest() + A.longest();
     return FOS_OK;
 }
 
@@ -498,14 +471,15 @@ struct NSpaceCG : ProxObject, DevOwned {
 
 namespace {
 
-int nc_upload_mat(NSpaceCG* a, hipStream_t s, const NcCsr& C, const NcPlan& pl, NcMat* D) {
-    SfItem* items = nullptr; int32_t *rp = nullptr, *ci = nullptr, *fptr = nullptr, *segk = nullptr; double* va = nullptr;
-    FOS_TRY(a->upload(&items, pl.P.items, s)); FOS_TRY(a->upload(&rp, C.rp, s)); FOS_TRY(a->upload(&ci, C.ci, s)); FOS_TRY(a->upload(&va, C.va, s));
-    FOS_TRY(a->upload(&fptr, pl.P.fptr, s)); FOS_TRY(a->upload(&segk, pl.segk, s));
-    D->nitems = (int)pl.P.items.size(); D->nfold = (int)pl.P.frow.size(); D->grid = pl.grid;
-    D->items = items; D->rp = rp; D->ci = ci; D->va = va; D->fptr = fptr; D->segk = segk;
+int nc_upload_mat(NSpaceCG* a, hipStream_t s, const HostCsr& C, const NcPlan& pl, NcMat* D) {
+    DevCsr c;
+    DevPass p;                                                    // (its part[] is seg: a slot per segment)
+    int32_t* segk = nullptr;
+    FOS_TRY(p.upload(*a, pl.P, s)); FOS_TRY(c.upload(*a, C, s)); FOS_TRY(a->upload(&segk, pl.segk, s));
+    D->nitems = p.nitems; D->nfold = p.nfold; D->grid = pl.grid;
+    D->items = p.items; D->rp = c.rp; D->ci = c.ci; D->va = c.va; D->fptr = p.fptr; D->segk = segk; D->seg = p.part;
     FOS_TRY(a->zeros(&D->cnt, (size_t)D->nfold, s));
-    FOS_TRY(a->zeros(&D->seg, (size_t)pl.P.nparts, s)); FOS_TRY(a->zeros(&D->seg2, (size_t)pl.P.nparts, s));
+    FOS_TRY(a->zeros(&D->seg2, (size_t)pl.P.nparts, s));
     FOS_TRY(a->zeros(&D->fsum, (size_t)NC_NSUM * (size_t)D->nfold, s));
     return FOS_OK;
 }
@@ -513,7 +487,7 @@ template <int MODE>
 void nc_launch_pass(hipStream_t s, const NcMat& M, const NcVec& v, double* part, const NcSum& prev, NcState* st, int k, int maxit) {
     hipLaunchKernelGGL((nc_pass_kernel<MODE>), dim3(M.grid), dim3(NC_T), 0, s, M, v, part, prev, st, k, maxit);
 }
-int nc_setup(NSpaceCG* a, const NcHost& H, double tol, hipStream_t stream) {
+int nc_fill(NSpaceCG* a, const NcHost& H, double tol, hipStream_t stream) {
     a->n = H.n; a->m = H.m; a->stored = H.stored; a->tol = tol; a->grid_n = nc_grid_n(H.n);
     const size_t n = (size_t)H.n, m = (size_t)H.m;
     FOS_TRY(nc_upload_mat(a, stream, H.M, H.pm, &a->M));
@@ -537,6 +511,14 @@ int nc_setup(NSpaceCG* a, const NcHost& H, double tol, hipStream_t stream) {
     if (e != hipSuccess) { set_error("%s set-up: a kernel launch failed: %s", a->what, hipGetErrorString(e)); return FOS_EHIP; }
     return FOS_OK;
 }
+int nc_setup(const char* what, const NcHost& H, double tol, hipStream_t stream, ProxObject** out) {
+    NSpaceCG* a = new NSpaceCG();
+    a->what = what;
+    const int rc = nc_fill(a, H, tol, stream);
+    if (rc != FOS_OK) { (void)hipStreamSynchronize(stream); delete a; return rc; }
+    *out = a;
+    return FOS_OK;
+}
 
 }  // namespace
 
@@ -545,24 +527,14 @@ int nspace_cg_setup_quadratic(int64_t n, const int64_t* colptr, const int64_t* r
                               ProxObject** out) {
     NcHost H;
     FOS_TRY(nc_host_quadratic(n, colptr, rowval, nzval, q, tol, &H));
-    NSpaceCG* a = new NSpaceCG();
-    a->what = "Quadratic (cg)";
-    const int rc = nc_setup(a, H, tol, stream);
-    if (rc != FOS_OK) { (void)hipStreamSynchronize(stream); delete a; return rc; }
-    *out = a;
-    return FOS_OK;
+    return nc_setup("Quadratic (cg)", H, tol, stream, out);
 }
 // LeastSquares(A, b, lambda), A sparse m x n (CSC, 1-based), any m, n >= 1.  Synchronises `stream`.
 int nspace_cg_setup_ls(int64_t m, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double lambda, double tol,
                        hipStream_t stream, ProxObject** out) {
     NcHost H;
     FOS_TRY(nc_host_ls(m, n, colptr, rowval, nzval, b, lambda, tol, &H));
-    NSpaceCG* a = new NSpaceCG();
-    a->what = "LeastSquares (cg)";
-    const int rc = nc_setup(a, H, tol, stream);
-    if (rc != FOS_OK) { (void)hipStreamSynchronize(stream); delete a; return rc; }
-    *out = a;
-    return FOS_OK;
+    return nc_setup("LeastSquares (cg)", H, tol, stream, out);
 }
 
 // y = prox_f(x) (device vectors of at least n doubles, y must not alias x), on `stream`
@@ -663,7 +635,7 @@ double nc_host_total(const NcHostSum& q, int j) {
     return nc_host_block(th);
 }
 template <int MODE>
-void nc_host_pass(const NcCsr& C, const NcPlan& pl, const NcVec& v, double beta, bool two, NcHostSum* out) {
+void nc_host_pass(const HostCsr& C, const NcPlan& pl, const NcVec& v, double beta, bool two, NcHostSum* out) {
     constexpr int NS = nc_nsum(MODE);
     constexpr bool ABS = nc_abs(MODE);
     const int nitems = (int)pl.P.items.size(), grid = pl.grid, nfold = (int)pl.P.frow.size();

@@ -121,3 +121,49 @@ def test_error_paths(pkg):
         pkg.IndAffine(sp.csc_matrix(A), b[:-1])
     with pytest.raises(pkg.lib.FosError):
         pkg.HipFeasibility(pkg.Feasibility(pkg.IndBox(0.0, 1.0), pkg.IndBox(0.0, 1.0), n)).affine_stats(1)
+
+
+# fault of the CSC arrays (sparse_intake_cases.MUTATIONS) -> the message behind "IndAffine (sparse): "; None: accepted -- the CG form sums a duplicated
+# entry like any other and needs no order inside a column
+INTAKE = {
+    "colptr0_is_0": "colptr must be 1-based (colptr[0] = 0)", "colptr_decreases": "colptr decreases at column 2", "row_index_0": "row index 0 outside 1..3",
+    "row_index_m_plus_1": "row index 4 outside 1..3", "two_entries_swapped": None, "duplicated_entry": None, "nan": "A has non-finite entries",
+    "inf": "A has non-finite entries", "1e301": "A has non-finite entries", "zero_row": "row 2 of A is zero (A must have full row rank)",
+    "nnz_0": "0 stored entries (1 .. 2e9 supported)", "nan_in_vector": "b has non-finite entries",
+}
+
+
+def test_intake_fault_table(pkg):
+    """fos_feas_set_affine_sparse has no host twin: the fault table of test_sparse_intake_cpu.py through the entry itself, 3 x 5.  A refused call leaves the set
+    installed before it as it was (the same bytes from the same prox); the two accepted rows project as the sorted and summed matrix does."""
+    import ctypes as C
+    import sparse_intake_cases as intake
+    assert set(INTAKE) == set(intake.MUTATIONS)
+    args = intake.base("affine_factored")
+    m, n = args[:2]
+    i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+
+    def install(d, rows, cols, colptr, rowval, nzval, b):
+        keep = [np.ascontiguousarray(colptr, dtype=np.int64), np.ascontiguousarray(rowval if len(rowval) else [1], dtype=np.int64),
+                np.ascontiguousarray(nzval if len(nzval) else [0.0], dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)]
+        rc = d._lib.fos_feas_set_affine_sparse(d._h, 1, rows, i64(keep[0]), i64(keep[1]), pkg.lib.dptr(keep[2]), pkg.lib.dptr(keep[3]))
+        return rc, d._lib.fos_last_error().decode()
+
+    A0 = sp.csc_matrix((args[4], args[3] - 1, args[2] - 1), shape=(m, n))
+    d = pkg.HipFeasibility(pkg.Feasibility(pkg.IndAffine(A0, args[5]), pkg.IndBox(0.0, np.inf), n))
+    x = np.linspace(-1.0, 1.0, n)
+    d.prox(1, x)
+    before = d.prox(1, x).tobytes()                                     # (converged multipliers: the same input gives the same bits)
+    for fault, text in INTAKE.items():
+        if text is None:
+            continue
+        rc, msg = install(d, *intake.MUTATIONS[fault]("affine_factored", *args))
+        assert rc == -1 and msg == "IndAffine (sparse): " + text, (fault, rc, msg)
+        assert d.prox(1, x).tobytes() == before, fault
+    for fault in ("two_entries_swapped", "duplicated_entry"):
+        _, _, colptr, rowval, nzval, b = intake.MUTATIONS[fault]("affine_factored", *args)
+        rc, msg = install(d, m, n, colptr, rowval, nzval, b)
+        assert rc == 0, (fault, msg)
+        A = sp.csc_matrix((nzval, rowval - 1, colptr - 1), shape=(m, n)).toarray()          # (duplicates summed)
+        ref = x - A.T @ np.linalg.solve(A @ A.T, A @ x - b)
+        assert np.abs(d.prox(1, x) - ref).max() <= 1e-12 * max(1.0, np.abs(x).max()), (fault, d.affine_stats(1))
